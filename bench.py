@@ -12,17 +12,25 @@ random-init (orthogonal) weights.  One step = renormalise decoder columns, encod
 decoder GEMM, masked MSE + L1, full backward, (N>1: RCCL all-reduce of the gradients,) clip,
 RAdam.  One process per GPU; per-GPU work is fixed as N grows (weak scaling).
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the tied-weight gradient
-GEMM pair), timed with HIP events on the launch stream inside the timed region; `cpu_baseline` is
-the CPU oracle (oracle/sae_oracle.py, a port of the reference's step) timed on this box's host
-cores on a bounded sample (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, spins up, warms up, times the K steps and prints the headline
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration and the last step's losses).
+Everything else the benchmark measures runs only with --full: `roofline` for the dominant kernel (the tied-weight gradient
+GEMM pair), timed with HIP events on the launch stream inside the timed region; `cpu_baseline`, the CPU oracle
+(oracle/sae_oracle.py, a port of the reference's step) timed on the host cores on a bounded sample (rank 0, N=1 only); the
+data-sensitivity legs, the loader-fed sample, the per-kernel breakdown, and with N > 1 the exchange's timing, the step
+without exchange and the other carrier's leg.
 
-Before the W warm-up steps the same step is run untimed for --spinup seconds (default 1 s): an idle MI355X starts in a
+--dump-outputs DIR writes what the last timed step left to a caller of the step -- the parameters and the metrics -- as
+DIR/<name>.npy (float32), so that two builds can be compared output for output on identical inputs.
+
+Before the W warm-up steps the same step is run untimed for about --spinup seconds (default 1 s): an idle MI355X starts in a
 low power state and needs some tens of milliseconds of load to reach its sustained clocks; without it a 10 + 50 step
 run (45 ms) is timed on the ramp and reads ~7 % slower than any run of a second or more.  The spin-up must be the
 workload itself: a second of a bare MFMA loop (tried: more power than the step draws) leaves the chip throttled and the
 following steps 10 % SLOWER (0.66 vs 0.60 ms) -- the steady state of a training run is the one its own steps settle into.
-The timed region is still exactly K steps after W warm-up steps.
+The spin-up is a fixed number of steps (`spinup_steps` of the line), sized from the step's FLOPs at NOMINAL_STEP_TFLOPS
+with a floor of MIN_STEP_S per step, not a clock reading: the state the timed steps start from, and so what --dump-outputs writes, is the same in every run with the same
+arguments.  The timed region is still exactly K steps after W warm-up steps.
 
 N > 1: the exchange is set up before the warm-up (peer exchange -> in-engine RCCL -> host-driven, whichever passes its checks; the
 peer exchange's first warm-up steps are audited against a torch.distributed all-reduce and the replicas' checksums compared after
@@ -47,6 +55,43 @@ PEAK_FP8_TFLOPS = 5000.0    # dense MFMA fp8 (v_mfma_f32_32x32x64_f8f6f4), same 
 # what a bare v_mfma_f32_32x32x16_bf16 loop at 100 % issue sustains on random bf16 operands on this chip (power-managed
 # clock 1.68 GHz; tools/mfma_clock_probe.hip, profiles/r01_mfma_clock_probe.jsonl): reported next to the nominal peak
 MEASURED_MFMA_LOOP_TFLOPS = 1700.0
+# whole-step rate of the headline workload on an MI355X (profiles/r06_bench_default.json: 0.554 ms per 10 M d n FLOPs,
+# 1395 TFLOP/s); sizes the spin-up
+NOMINAL_STEP_TFLOPS = 1400.0
+MIN_STEP_S = 50e-6         # no step is assumed shorter than this: small shapes are launch-bound, not FLOP-bound
+DUMP_BYTES = 64_000_000    # --dump-outputs: at most this much in all, headers and row-index files included
+NPY_HEADER_BYTES = 256     # room per .npy file for its header (128 bytes for the arrays written here)
+
+
+def spinup_steps(seconds, step_flops):
+    """Steps that load the GPU for about `seconds` at NOMINAL_STEP_TFLOPS (at most one step per MIN_STEP_S), in whole
+    blocks of 20 (0 for no spin-up)."""
+    if seconds <= 0:
+        return 0
+    step_s = max(step_flops / (NOMINAL_STEP_TFLOPS * 1e12), MIN_STEP_S)
+    return 20 * math.ceil(seconds / step_s / 20)
+
+
+def dump_outputs(eng, out_dir):
+    """The last step's parameters and metrics as float32 .npy files; an array above its share of DUMP_BYTES is cut to a
+    fixed, seeded sample of its rows (the sampled row indices go next to it as <name>.rows.npy, counted in the share)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(eng.get_params())
+    arrays["metrics"] = eng.metrics()
+    share = DUMP_BYTES // len(arrays) - 2 * NPY_HEADER_BYTES      # an array's data and its row indices
+    written = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = max(1, share // (a.nbytes // a.shape[0] + 8))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(out_dir, f"{name}.rows.npy"), rows.astype(np.float64))
+            written += os.path.getsize(os.path.join(out_dir, f"{name}.rows.npy"))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written += os.path.getsize(os.path.join(out_dir, f"{name}.npy"))
+    if written > DUMP_BYTES:
+        raise RuntimeError(f"bench.py: --dump-outputs wrote {written} bytes, more than {DUMP_BYTES}")
 
 
 def to_activation_dtype(x32, dtype, guard=True):
@@ -299,11 +344,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--spinup", type=float, default=1.0, help="seconds of untimed steps before the warm-up (clock ramp)")
+    ap.add_argument("--spinup", type=float, default=1.0,
+                    help="about this many seconds of untimed steps before the warm-up (clock ramp), as a fixed step count")
     ap.add_argument("--rows", type=int, default=65536)
     ap.add_argument("--d", type=int, default=384)
     ap.add_argument("--n", type=int, default=3072)
     ap.add_argument("--x-dtype", default="bfloat16", choices=["bfloat16", "float16", "float32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline, CPU baseline, data sensitivity, loader-fed sample, "
+                         "per-kernel breakdown, N > 1 exchange timing and the other carrier")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's parameters and metrics as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pcie-sample", action="store_true", help="skip the loader-fed (PCIe-inclusive) sample of the same step")
     ap.add_argument("--cpu-steps", type=int, default=3)
@@ -388,6 +439,9 @@ def main():
     xs = [x] + [make_inputs(M, d, n, seed=1000 + rank + 7919 * j, dtype=dtype, kind=args.data, guard=not args.raw_cast)[0].cuda()
                 for j in range(1, max(args.rotate, 1))]
     total_steps, base_lr = 100000, 4e-4
+    step_flops = 10.0 * M * d * n                    # SURVEY 8d: algorithmic FLOPs per activation = 10 d n
+    if args.variant == "topk":
+        step_flops = (2.0 * d * n + 10.0 * args.k * d) * M   # SURVEY 8d: 2 d n + 10 k d per activation
 
     def attempt(mode_override=None):
         """engine + data-parallel set-up + spin-up + warm-up + the timed region.  Returns (engine, step function, seconds of the
@@ -445,19 +499,10 @@ def main():
             else:
                 eng.step(x, lr_of(i))
 
-        if args.spinup > 0:                      # clock spin-up (see the module docstring); not part of W or K
-            t_spin = time.perf_counter()
-            while True:
-                for j in range(20):
-                    one_step(j)                  # (with --rotate the spin-up rotates too; the index only chooses batch and LR)
-                torch.cuda.synchronize()
-                elapsed = time.perf_counter() - t_spin
-                if use_dist:                     # every rank must leave after the same number of (collective) steps
-                    te = torch.tensor([elapsed], device=ctrl_dev, dtype=torch.float64)
-                    dist.all_reduce(te, op=dist.ReduceOp.MAX)
-                    elapsed = float(te.item())
-                if elapsed >= args.spinup:
-                    break
+        for _ in range(0, spinup_steps(args.spinup, step_flops), 20):     # clock spin-up (see the module docstring); not part of W or K
+            for j in range(20):
+                one_step(j)                      # (with --rotate the spin-up rotates too; the index only chooses batch and LR)
+            torch.cuda.synchronize()
         # Peer exchange with real peers: the first warm-up steps are AUDITED -- this rank's gradient contribution is snapshotted
         # before the exchange, the snapshots are summed by torch.distributed (RCCL) and compared with what the engine's own
         # exchange produced (freud_amd/dp.py: Auditor).  The verdict is collective; a mismatch sends every rank to in-engine RCCL.
@@ -482,7 +527,8 @@ def main():
         # the dominant kernel is bracketed with HIP events: on every 8th step of a long run (an event pair costs a few us of idle
         # GPU between dependent kernels), on EVERY step of a short one (the driver's 20-step run: 20 samples; three interleaved
         # 20-step pairs on one box: 593.3 / 593.9 us sampled every step against 594.0 / 594.2 every second -- no measurable price)
-        eng.profile(1, period=8 if args.steps > 64 else 1)
+        if args.full:
+            eng.profile(1, period=8 if args.steps > 64 else 1)
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -525,7 +571,7 @@ def main():
     # run -- K steps after W warm-up steps, max over the ranks like the headline.  ms_per_step minus this is what the exchange costs
     # on the critical path (dp_timing.exposed_exchange_ms): the first multi-GPU run explains its own efficiency.
     plain_ms = None
-    if use_dist and os.environ.get("FREUD_BENCH_PLAIN_REF", "1") != "0":
+    if use_dist and args.full and os.environ.get("FREUD_BENCH_PLAIN_REF", "1") != "0":
         saved = (use_dist, args.dp_overlap)
         use_dist, args.dp_overlap = False, 1
         try:
@@ -553,30 +599,20 @@ def main():
         dp_fallback = first_failure or {"failed": "exchange failed during the first attempt"}
         if not healthy:
             raise SystemExit("bench.py: no data-parallel exchange completed the run")
-    times = eng.kernel_times()
+    if args.dump_outputs and rank == 0:          # the replicas of an N > 1 run are identical (checked above for the engine's carriers)
+        dump_outputs(eng, args.dump_outputs)
     metrics = eng.metrics()
-    eng.profile(0)
+    if args.full:
+        times = eng.kernel_times()
+        eng.profile(0)
 
     ms_per_step = dt / args.steps * 1e3
     value = M * world * args.steps / dt
-    dom = eng.dominant_kernel()
-    dom_ms, dom_cnt = times[dom]
-    dom_avg_ms = dom_ms / max(dom_cnt, 1)
-    # algorithmic FLOPs of the dominant kernel: fused backward = dc, dW(dec), dW(enc) GEMMs = 3 x 2*M*d*n;
-    # generic path's dw_gemm = the two weight-gradient GEMMs = 2 x 2*M*d*n
-    dom_flops = (6.0 if dom == "bwd_fused_gemm" else 4.0) * M * d * n
-    if args.variant == "topk":
-        dom_flops = 2.0 * M * d * n                  # the dense encoder GEMM
-    achieved = dom_flops / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
-    step_flops = 10.0 * M * d * n                    # SURVEY 8d: algorithmic FLOPs per activation = 10 d n
-    if args.variant == "topk":
-        step_flops = (2.0 * d * n + 10.0 * args.k * d) * M   # SURVEY 8d: 2 d n + 10 k d per activation
-    fb_ms, fb_cnt = times["fwd_bwd_total"]
     f8 = {"bf16": 0.0, "fp8": 0.4, "fp8bwd": 0.6}[args.precision] if args.variant == "l1" else 0.0
     step_peak = 1.0 / (f8 / PEAK_FP8_TFLOPS + (1.0 - f8) / PEAK_BF16_TFLOPS)
 
     breakdown, dp_timing = None, None
-    if args.breakdown or args.precision != "bf16" or use_dist:   # every rank runs the extra steps (they contain collectives); rank 0 reports
+    if args.breakdown or (args.full and (args.precision != "bf16" or use_dist)):   # every rank runs the extra steps (they contain collectives); rank 0 reports
         n_diag = 16 if use_dist else 10
         eng.profile(2)
         # harvested every second step: the engine keeps the last 64 event pairs per kernel id, and a configuration with several
@@ -628,20 +664,36 @@ def main():
         if rank != 0 or not (args.breakdown or args.precision != "bf16"):
             breakdown = None
 
-    # HBM bytes per launch of the dominant kernel: PMC counters cannot be read from inside this process, so the value
-    # measured with rocprofv3 (separate --pmc FETCH_SIZE / WRITE_SIZE passes of this same command, FETCH_SIZE doubled
-    # as MI355X_MICROARCH.md prescribes for gfx950) is kept under profiles/ and quoted when the workload matches
-    traffic, traffic_source = None, None
-    try:
-        if args.variant == "l1" and args.precision == "bf16" and (M, d, n) == (65536, 384, 3072):
-            import glob
-            latest = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_hbm_traffic.json")))[-1]   # newest round's pass
-            with open(latest) as f:
-                traffic = json.load(f).get(dom, {}).get("hbm_bytes_per_launch")
-            traffic_source = (f"profiles/{os.path.basename(latest)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                              "command (FETCH_SIZE doubled per the gfx950 correction), recorded earlier -- not measured in this run")
-    except Exception:
+    roofline = None
+    if args.full:
+        dom = eng.dominant_kernel()
+        dom_ms, dom_cnt = times[dom]
+        dom_avg_ms = dom_ms / max(dom_cnt, 1)
+        # algorithmic FLOPs of the dominant kernel: fused backward = dc, dW(dec), dW(enc) GEMMs = 3 x 2*M*d*n;
+        # generic path's dw_gemm = the two weight-gradient GEMMs = 2 x 2*M*d*n
+        dom_flops = (6.0 if dom == "bwd_fused_gemm" else 4.0) * M * d * n
+        if args.variant == "topk":
+            dom_flops = 2.0 * M * d * n                  # the dense encoder GEMM
+        achieved = dom_flops / (dom_avg_ms * 1e-3) / 1e12 if dom_avg_ms > 0 else 0.0
+        # HBM bytes per launch of the dominant kernel: PMC counters cannot be read from inside this process, so the value
+        # measured with rocprofv3 (separate --pmc FETCH_SIZE / WRITE_SIZE passes of this same command, FETCH_SIZE doubled
+        # as MI355X_MICROARCH.md prescribes for gfx950) is kept under profiles/ and quoted when the workload matches
         traffic, traffic_source = None, None
+        try:
+            if args.variant == "l1" and args.precision == "bf16" and (M, d, n) == (65536, 384, 3072):
+                import glob
+                latest = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_hbm_traffic.json")))[-1]   # newest round's pass
+                with open(latest) as f:
+                    traffic = json.load(f).get(dom, {}).get("hbm_bytes_per_launch")
+                traffic_source = (f"profiles/{os.path.basename(latest)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                  "command (FETCH_SIZE doubled per the gfx950 correction), recorded earlier -- not measured in this run")
+        except Exception:
+            traffic, traffic_source = None, None
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": traffic_source, "kernel": dom,
+                    "kernel_avg_ms": dom_avg_ms, "kernel_launches": dom_cnt,
+                    "flops_per_launch": dom_flops, "peak_measured_bare_mfma_loop": MEASURED_MFMA_LOOP_TFLOPS,
+                    "frac_of_measured": achieved / MEASURED_MFMA_LOOP_TFLOPS}
 
     # what the exchange really carries: the bf16 payload and the column ranges exist on the fused d=384 L1 path only
     fused = args.variant == "l1" and args.precision == "bf16" and (d + 127) // 128 * 128 == 384
@@ -655,7 +707,8 @@ def main():
     model_name = {384: "tiny", 512: "base", 768: "small", 1024: "medium", 1280: "large"}.get(d, f"d={d}")
     out = {
         "metric": f"SAE train activations/sec (d={d} dict {n // d}x)", "value": value, "unit": "activations/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_s": args.spinup, "ms_per_step": ms_per_step,
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "spinup_s": args.spinup,
+        "spinup_steps": spinup_steps(args.spinup, step_flops), "ms_per_step": ms_per_step,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16",
         "data": ("synthetic" if args.data == "lowrank" else f"synthetic ({args.data}; diagnostic)") + (" (raw cast; diagnostic)" if args.raw_cast else "")
                 + (f" ({len(xs)} resident batches in rotation)" if len(xs) > 1 else ""),
@@ -664,21 +717,19 @@ def main():
                                + (" (BASELINE configs[1])" if (d, n, M) == (384, 3072, 65536) else ""),
                    "rows_per_gpu": M, "d_model": d, "n_dict": n, "parallelism": f"dp{world}",
                    "dp": dp_desc, "dp_guards": audit_info},
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": traffic_source, "kernel": dom,
-                     "kernel_avg_ms": dom_avg_ms, "kernel_launches": dom_cnt,
-                     "flops_per_launch": dom_flops, "peak_measured_bare_mfma_loop": MEASURED_MFMA_LOOP_TFLOPS,
-                     "frac_of_measured": achieved / MEASURED_MFMA_LOOP_TFLOPS},
         # whole step against the MFMA roof; with fp8 GEMMs in the step the roof is FLOP-weighted (time at peak = fp8 FLOPs / fp8
         # peak + bf16 FLOPs / bf16 peak): 4 of the 10 M d n FLOPs run on e4m3 with --precision fp8, 6 with fp8bwd
         "step_mfma_frac": (step_flops / (ms_per_step * 1e-3) / 1e12) / step_peak,
         "step_mfma_peak": step_peak,
-        "fwd_bwd_ms": fb_ms / max(fb_cnt, 1),
         "loss": {"recon": float(metrics[0]), "l1": float(metrics[1]), "grad_norm": float(metrics[3])},
     }
+    if roofline:
+        out["roofline"] = roofline
+        fb_ms, fb_cnt = times["fwd_bwd_total"]
+        out["fwd_bwd_ms"] = fb_ms / max(fb_cnt, 1)
     if os.environ.get("FREUD_BENCH_LAUNCHER"):
         out["config"]["launcher"] = os.environ["FREUD_BENCH_LAUNCHER"]
-    if args.variant == "l1" and args.precision == "bf16":
+    if args.full and args.variant == "l1" and args.precision == "bf16":
         try:
             out["latent_nonzero_frac"] = latent_nonzero_frac(eng, M, n, torch.device("cuda", local_rank))
         except Exception as e:              # noqa: BLE001 -- an extra
@@ -687,14 +738,15 @@ def main():
         out["kernel_ms"] = breakdown
     if dp_timing:
         out["dp_timing"] = dp_timing
-    if args.precision != "bf16" and breakdown:
-        # the two fp8 GEMMs against the dense fp8 MFMA peak (2 M d n FLOPs each), next to the (bf16) dominant kernel above
+    if args.precision != "bf16":
         out["dtype"] = ("fp8 (e4m3 encoder/decoder GEMMs, fp32 accumulate) + bf16 backward" if args.precision == "fp8" else
                         "fp8 (e4m3 encoder/decoder/dpre GEMMs, fp32 accumulate) + bf16 weight-gradient GEMMs")
+        out["config"]["workload"] = out["config"]["workload"].replace("L1 SAE train step", "L1 SAE train step, fp8 enc/dec GEMMs")
+    if args.precision != "bf16" and breakdown:
+        # the two fp8 GEMMs against the dense fp8 MFMA peak (2 M d n FLOPs each), next to the (bf16) dominant kernel above
         out["fp8_gemms"] = {k: {"ms": breakdown[k], "tflops": 2.0 * M * d * n / (breakdown[k] * 1e-3) / 1e12,
                                 "frac_of_fp8_peak": 2.0 * M * d * n / (breakdown[k] * 1e-3) / 1e12 / PEAK_FP8_TFLOPS}
                             for k in ("enc_fwd_gemm", "dec_fwd_gemm") + (("dpre_gemm",) if args.precision == "fp8bwd" else ()) if breakdown.get(k)}
-        out["config"]["workload"] = out["config"]["workload"].replace("L1 SAE train step", "L1 SAE train step, fp8 enc/dec GEMMs")
     if args.dbg == 65 and rank == 0:     # diagnostic build: cycle shares of one fused-forward iteration + in-kernel clock
         st = eng.debug_read(5, (M // 128) * 32).reshape(-1, 8)
         st = st[st[:, 3] > 0]
@@ -781,18 +833,19 @@ def main():
         out["config"]["workload"] = (f"TopK SAE d={d} n={n} k={args.k} train step, M={M} rows/GPU/step, Adam, x {args.x_dtype} "
                                      "resident in HBM (BASELINE configs[2] shape)")
         out["loss"] = {"fvu": float(metrics[0]), "auxk": float(metrics[1]), "grad_norm": float(metrics[3]), "dead_frac": float(metrics[5])}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.variant == "l1":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.variant == "l1":
         out["cpu_baseline"] = cpu_baseline(x_cpu, W, b, args.cpu_steps, base_lr)
     elif rank == 0:
         out["cpu_baseline"] = None
     eng.close()
-    if (rank == 0 and world == 1 and not use_dist and not args.no_sensitivity and not args.no_cpu_baseline and args.variant == "l1"
+    if (rank == 0 and world == 1 and not use_dist and args.full and not args.no_sensitivity and not args.no_cpu_baseline and args.variant == "l1"
             and args.precision == "bf16" and args.dbg == 0):
         try:
             out["data_sensitivity"] = data_sensitivity(M, d, n, dtype, W, b, local_rank)
         except Exception as e:              # noqa: BLE001 -- an extra; must never cost the bench line
             out["data_sensitivity"] = {"error": str(e)[:200]}
-    if rank == 0 and world == 1 and not args.no_pcie_sample and not args.no_cpu_baseline and args.variant == "l1" and args.precision == "bf16":
+    if (rank == 0 and world == 1 and args.full and not args.no_pcie_sample and not args.no_cpu_baseline and args.variant == "l1"
+            and args.precision == "bf16"):
         try:
             out["pcie_inclusive"] = pcie_inclusive_sample(d, n)
         except Exception as e:              # noqa: BLE001 -- an extra; must never cost the bench line
@@ -801,7 +854,8 @@ def main():
     # leg on a fresh context after everything else is in `out`.  It runs under a watchdog thread: a carrier that hangs (RCCL can; the
     # engine's own exchange times out by itself) costs this leg, never the line -- rank 0 prints the line without it and every rank leaves.
     # (--force-dist runs the leg with one rank as well: the only way this code path executes on a one-GPU box with the nccl backend)
-    other = {"p2p": "rccl", "rccl": "p2p"}.get(dp_mode) if (use_dist and (world > 1 or args.force_dist) and dp_timing is not None) else None
+    other = ({"p2p": "rccl", "rccl": "p2p"}.get(dp_mode) if (args.full and use_dist and (world > 1 or args.force_dist) and dp_timing is not None)
+             else None)
     if (other and dp_fallback is None and os.environ.get("FREUD_BENCH_OTHER_CARRIER", "1") != "0"
             and (other != "rccl" or dist.get_backend() == "nccl")):
         import threading

@@ -1,5 +1,5 @@
 """The bench line contract (task statement, section "Measurement"), checked on the line committed under profiles/ (produced by
-`python bench.py` on an MI355X): required keys, types and the internal arithmetic the judge recomputes."""
+`python bench.py --full` on an MI355X, which then carried these extras in every line): required keys, types and the internal arithmetic the judge recomputes."""
 import json
 import os
 

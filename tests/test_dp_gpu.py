@@ -675,7 +675,7 @@ def test_bench_with_several_ranks_prints_one_line_with_the_guards_verdict(world)
     contributions), barrier-bracketed timed region, max over ranks, replica checksums after the run, ONE JSON line from rank 0
     whose value is the whole job's rows over that time."""
     import json
-    res = _run_bench_ranks(world, ["--steps", "6", "--warmup", "4", "--rows", "8192", "--no-cpu-baseline", "--spinup", "0"])
+    res = _run_bench_ranks(world, ["--steps", "6", "--warmup", "4", "--rows", "8192", "--full", "--no-cpu-baseline", "--spinup", "0"])
     for rc, so, se in res:
         assert rc == 0, se[-3000:]
     lines = [[l for l in so.splitlines() if l.startswith("{")] for _, so, _ in res]
@@ -723,7 +723,7 @@ def test_bench_gpus_n_without_a_launcher_spawns_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["FREUD_BENCH_SHARE_GPU"] = "1"
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "4", "--rows", "8192",
-                         "--no-cpu-baseline", "--spinup", "0"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+                         "--full", "--no-cpu-baseline", "--spinup", "0"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-3000:]
     lines = [l for l in pr.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, pr.stdout[-2000:]
@@ -747,7 +747,7 @@ def test_bench_reports_the_other_carrier_next_to_the_headline():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "FREUD_BENCH_SHARE_GPU")}
     env["MASTER_PORT"] = str(_free_port())
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "6", "--warmup", "3", "--rows", "8192",
-                         "--no-cpu-baseline", "--spinup", "0"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+                         "--full", "--no-cpu-baseline", "--spinup", "0"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert pr.returncode == 0, pr.stderr[-3000:]
     d = json.loads([l for l in pr.stdout.splitlines() if l.startswith("{")][-1])
     t = d["dp_timing"]

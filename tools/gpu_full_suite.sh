@@ -12,6 +12,6 @@ d=json.loads(open('$O/c3_auxk.json').read().strip().splitlines()[-1])
 km=d.get('kernel_ms') or {}
 print('c3_auxk', round(d['ms_per_step'],3), d.get('loss'), {k:v for k,v in km.items() if v})
 PY
-python bench.py > $O/default.json 2> $O/default.err; python -c "
+python bench.py --full > $O/default.json 2> $O/default.err; python -c "
 import json
 d=json.loads(open('$O/default.json').read().strip().splitlines()[-1]); print('default', d['ms_per_step'], d['value'], d['roofline']['frac'], d['cpu_baseline'])"

@@ -15,7 +15,7 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"      # every line records the extras a plain run leaves out (roofline, CPU baseline, exchange timing, fp8 breakdown)
 $B > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 $B --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_default_driver_style.json" 2>> "$OUT/bench_default.err"
 $B --no-cpu-baseline --force-dist > "$OUT/bench_forcedist.json" 2> "$OUT/bench_forcedist.err"

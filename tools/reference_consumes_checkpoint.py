@@ -8,7 +8,9 @@ ENGINE (tests/golden/engine_ckpt/*.pth, produced on an MI355X by tools/make_engi
     scheduler state_dicts into live reference objects (torch's own load_state_dict validates every key and shape),
     and one more reference optimizer step on them runs.
 
-Writes a log (profiles/r02_reference_consumes_checkpoint.log).  The reference's absent third-party imports are stubbed
+Writes a log (profiles/r02_reference_consumes_checkpoint.log) and what the reference produced into
+tests/golden/engine_ckpt/reference_outputs.npz (state_dict layouts, fp32 forward, resume step), the fixture
+tests/test_reference_consumes.py checks without the reference.  The reference's absent third-party imports are stubbed
 exactly as in tests/golden/make_golden.py; no reference source is copied."""
 import json
 import os
@@ -43,6 +45,7 @@ def main(log_path=None):
         lines.append(s)
 
     ok = True
+    fixture, meta = {}, {}
     for name in ("l1", "topk"):
         path = os.path.join(CK, f"{name}_step6.pth")
         model = init_sae_from_checkpoint(path, device="cpu")
@@ -66,6 +69,9 @@ def main(log_path=None):
         # fp32 reference vs bf16 engine arithmetic: 2e-2 on these tiny batches (TopK: boundary ties pick other latents)
         ok &= all(r < (2e-2 if name == "l1" else 6e-2) or (b == 0 and a == 0) for r, (a, b) in zip(rel, zip(got, m[:3])))
         ok &= lat_rel < (2e-2 if name == "l1" else 0.3)
+        fixture[f"{name}_latent"] = lat_ref.astype(np.float32)
+        meta[name] = {"model_state": {k: list(v.shape) for k, v in model.state_dict().items()},
+                      "fp32_forward": [float(v) for v in got]}
 
         # resume path: the reference's own objects, load_checkpoint, one more step
         ck = torch.load(path, map_location="cpu")
@@ -95,6 +101,12 @@ def main(log_path=None):
         log(f"[{name}] load_checkpoint OK: step {state['step']}, optimizer moments on the right parameters: {shapes_ok}, "
             f"one more reference step ran (optimizer step counter {step_now}, lr {sch.get_last_lr()[0]:.3e}, loss {loss.item():.4f})")
         ok &= shapes_ok and step_now == 4 and bool(torch.isfinite(loss))
+        meta[name].update({"param_shapes": [list(p.shape) for p in fresh.parameters()],
+                           "param_group_keys": sorted(k for k in opt.state_dict()["param_groups"][0] if k != "params"),
+                           "scheduler_keys": sorted(sch.state_dict().keys()), "resumed_step": state["step"],
+                           "optimizer_step_after": step_now, "lr_after": float(sch.get_last_lr()[0]), "loss_after_resume": float(loss)})
+    fixture["meta"] = np.array(json.dumps(meta))
+    np.savez(os.path.join(CK, "reference_outputs.npz"), **fixture)
     log("RESULT: " + ("PASS" if ok else "FAIL"))
     if log_path:
         open(log_path, "w").write("\n".join(lines) + "\n")
