@@ -34,6 +34,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "topk_sparse.h"
 #include "topk_aux.h"
 #include "eval_fp32.h"
+#include "search.h"
 
 #ifndef G2_PERSIST_STATIC
 #define G2_PERSIST_STATIC 512      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
@@ -270,6 +271,7 @@ struct sae_ctx {
   bool no_stream = false;       // this context's K = d GEMMs stay on the tile form (FREUD_GEMM_STREAM=0 / debug_flags 86 at ITS creation)
   int eval_prec = 0;            // 0 = the training kernels' arithmetic (bf16 operands, fp32 accumulate), 1 = fp32 end to end
   bool last_fwd_e32 = false;    // the last forward was an fp32 evaluation: its per-feature maxima live in e32_colmax
+  bool last_fwd_search = false; // the last call was a feature search (sae_search_files): it leaves no latent rows / metrics to read
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;
@@ -2532,6 +2534,7 @@ static int dispatch_fwd_bwd(sae_ctx* c, const void* x, int64_t M, int x_dtype, v
 static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dtype, hipStream_t s, bool backward) {
   c->last_dtype = x_dtype;
   c->last_fwd_e32 = false;
+  c->last_fwd_search = false;
   if (c->topk) {
     switch (x_dtype) {
       case SAE_DTYPE_F32: return topk_fwd_bwd<float>(c, (const float*)x, M, s, backward);
@@ -2627,6 +2630,7 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   c->last_M = M;
   c->last_M_p = round_up(M, c->row_pad);
   c->last_fwd_e32 = true;
+  c->last_fwd_search = false;
   c->metrics_fresh = false;
   return SAE_OK;
 }
@@ -2764,6 +2768,7 @@ extern "C" int sae_step(sae_ctx* c, const void* x, int64_t M, int x_dtype, doubl
 
 extern "C" int sae_read_metrics(sae_ctx* c, float out[SAE_NUM_METRICS], void* stream) {
   if (!c || !out) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
   USE_DEVICE(c);
   HIP_TRY(hipMemcpyAsync(out, c->G + c->nparams, SAE_NUM_METRICS * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -2894,6 +2899,7 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
 
 extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride) {
   if (!c || !dev_ptr || !row_stride) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
   if (c->last_fwd_e32) return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows");
@@ -2908,6 +2914,7 @@ extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride
 
 extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
   if (!c || !dev_ptr || !k) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
   if (!c->topk) return fail(SAE_ERR_INVALID, "sae_topk_indices: not a TopK context");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   *dev_ptr = c->top_idx;
@@ -2917,6 +2924,7 @@ extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
 
 extern "C" int sae_multi_topk_buffers(sae_ctx* c, void** dense_dev, int64_t* row_stride, void** idx_dev, int* k4) {
   if (!c || !dense_dev || !row_stride || !idx_dev || !k4) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
   if (!c->topk || !c->multi) return fail(SAE_ERR_INVALID, "sae_multi_topk_buffers: not a TopK context with multi_topk");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   if (!c->multi_dense_valid) {      // a training step on the sparse backward keeps the 4k selection compact: densify on demand
@@ -2986,6 +2994,7 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
 
 extern "C" int sae_latent_colmax(sae_ctx* c, float* out_host, int64_t capacity, void* stream) {
   if (!c || !out_host) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
   if (capacity < c->n) return fail(SAE_ERR_INVALID, "capacity too small");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
@@ -3039,6 +3048,163 @@ extern "C" int sae_eval_into(sae_ctx* c, const void* x, int64_t M, int x_dtype, 
                        Mr, c->n_p, c->n, rows_per_block);
     HIP_TRY(hipGetLastError());
   }
+  return SAE_OK;
+}
+
+// ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
+static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
+                                   bool absolute, uint64_t* keys, uint64_t* aux, hipStream_t s) {
+  const int chunk = 128;
+  const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)n_files, (unsigned)((Trows + chunk - 1) / chunk));
+  const int64_t pairs = n_files * ncols;
+  const unsigned fgrid = (unsigned)((pairs + 255) / 256);
+#define SEARCH_RAW(T)                                                                                                              \
+  if (absolute) {                                                                                                                 \
+    hipLaunchKernelGGL((search_colreduce_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, ld, ncols, Trows, lengths, chunk, keys, aux); \
+    hipLaunchKernelGGL(search_abs_fixup_kernel<T>, dim3(fgrid), dim3(256), 0, s, (const T*)x, ld, ncols, Trows, n_files, keys, aux); \
+  } else {                                                                                                                        \
+    hipLaunchKernelGGL((search_colreduce_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, ld, ncols, Trows, lengths, chunk, keys, nullptr); \
+  }
+  switch (x_dtype) {
+    case SAE_DTYPE_F32: SEARCH_RAW(float) break;
+    case SAE_DTYPE_F16: SEARCH_RAW(_Float16) break;
+    case SAE_DTYPE_BF16: SEARCH_RAW(bf16_t) break;
+    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  }
+#undef SEARCH_RAW
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// L1: the encoder GEMM of forward_impl (same weights preparation, same bf16 copy of x, same operands) with EpiSearch instead of
+// EpiEnc.  Where the streaming GEMM does not apply (small or odd shapes, FREUD_GEMM_STREAM=0, force_gemm128) or `unfused` is asked
+// for (the baseline of tools/bench_search.py), the latent is stored by the ordinary encoder and reduced by the column kernel.
+template <typename T>
+static int search_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, int64_t n_files, const int* lengths, uint64_t* keys, bool unfused,
+                          hipStream_t s) {
+  const int d = c->d, d_p = c->d_p, n_p = c->n_p;
+  float* b = c->P + c->nW;
+  int64_t Mp = round_up(M, 128);
+  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);    // (an even number of row blocks: the streaming GEMM's condition)
+  prep_weights_l1(c, s);
+  {
+    const int64_t chunks = Mp * (d_p / 8);
+    int grid = (int)((chunks + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+      hipLaunchKernelGGL((prep_x_kernel<T, true>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+    else
+      hipLaunchKernelGGL((prep_x_kernel<T, false>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+  }
+  HIP_TRY(hipMemsetAsync(keys, 0, (size_t)n_files * c->n * 8, s));
+  GemmArgs g{};
+  g.A0 = c->xb; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
+  g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
+  if (!unfused && Trows <= 65535 && gemm_streams<OP_ROW, OP_ROW, EpiSearch>(g)) {
+    EpiSearch e{};
+    e.bias = b; e.keys = keys; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n;
+    auto kerns = gemm256s_bf16_kernel<EpiSearch>;
+    LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
+    GemmArgs g2 = g;
+    g2.nbm = g.nbm / 2;
+    g2.nbn = g.nbn / 2;
+    ev_begin(c, KID_ENC_FWD, s);
+    hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, e);
+    ev_end(c, KID_ENC_FWD, s);
+    HIP_TRY(hipGetLastError());
+    return SAE_OK;
+  }
+  EpiEnc e{};
+  e.c = c->c; e.bias = b; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = g.nbn;
+  if (gemm_streams<OP_ROW, OP_ROW, EpiEnc>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)g.nbm * g.nbn * 4, s));
+  ev_begin(c, KID_ENC_FWD, s);
+  int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+  ev_end(c, KID_ENC_FWD, s);
+  if (rc) return rc;
+  return search_launch_colreduce(c->c, SAE_DTYPE_BF16, n_p, c->n, Trows, n_files, lengths, false, keys, nullptr, s);
+}
+
+static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
+  if (n_files <= 0 || rows_per_file <= 0) return fail(SAE_ERR_INVALID, "n_files=%lld and rows_per_file=%lld must be positive", (long long)n_files, (long long)rows_per_file);
+  if (n_files > 65535) return fail(SAE_ERR_INVALID, "n_files=%lld > 65535 in one call", (long long)n_files);
+  // (the column reduction launches one grid z-slice per 128 rows of a file: at most 65535 of them)
+  if (rows_per_file > 65535ll * 128) return fail(SAE_ERR_INVALID, "rows_per_file=%lld > %lld", (long long)rows_per_file, 65535ll * 128);
+  return SAE_OK;
+}
+
+extern "C" int sae_search_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                                int flags, uint64_t* file_keys, void* stream) {
+  if (!c || !x || !file_keys) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->fp8) return fail(SAE_ERR_INVALID, "sae_search_files: fp8 contexts are not supported (search in a bf16 context)");
+  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
+  const int64_t M = n_files * rows_per_file;
+  if (M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "n_files * rows_per_file = %lld > max_rows=%lld", (long long)M, (long long)c->cfg.max_rows);
+  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  if (flags & ~SAE_SEARCH_UNFUSED) return fail(SAE_ERR_INVALID, "unknown search flags 0x%x", flags);
+  USE_DEVICE(c);
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  int rc;
+  if (c->topk) {
+    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the selection scattered into the keys
+    const int64_t nk = n_files * c->n;
+    int fg = (int)((nk + 255) / 256);
+    if (fg > 4096) fg = 4096;
+    hipLaunchKernelGGL(search_fill_kernel, dim3(fg), dim3(256), 0, s, file_keys, nk, (uint64_t)SK_KEY_ZERO_FRAME0);
+    rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false);
+    if (rc) return rc;
+    int sg = (int)((M * c->k + 255) / 256);
+    if (sg > 4096) sg = 4096;
+    hipLaunchKernelGGL(search_topk_scatter_kernel, dim3(sg), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, Trows, lengths, c->n,
+                       file_keys);
+    HIP_TRY(hipGetLastError());
+  } else {
+    const bool unfused = (flags & SAE_SEARCH_UNFUSED) != 0;
+    switch (x_dtype) {
+      case SAE_DTYPE_F32: rc = search_l1_impl<float>(c, (const float*)x, M, Trows, n_files, lengths, file_keys, unfused, s); break;
+      case SAE_DTYPE_F16: rc = search_l1_impl<_Float16>(c, (const _Float16*)x, M, Trows, n_files, lengths, file_keys, unfused, s); break;
+      default: rc = search_l1_impl<bf16_t>(c, (const bf16_t*)x, M, Trows, n_files, lengths, file_keys, unfused, s); break;
+    }
+    if (rc) return rc;
+  }
+  c->last_fwd_search = true;
+  return SAE_OK;
+}
+
+extern "C" int sae_search_raw_files(const void* x, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths,
+                                    int absolute, uint64_t* file_keys, uint64_t* aux, void* stream) {
+  if (!x || !file_keys || (absolute && !aux)) return fail(SAE_ERR_INVALID, "null argument");
+  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
+  if (d <= 0 || d > (1 << 24)) return fail(SAE_ERR_INVALID, "d=%lld outside (0, 2^24]", (long long)d);
+  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipMemsetAsync(file_keys, 0, (size_t)(n_files * d) * 8, s));
+  if (absolute) HIP_TRY(hipMemsetAsync(aux, 0, (size_t)(n_files * d) * 8, s));
+  return search_launch_colreduce(x, x_dtype, d, (int)d, (int)rows_per_file, n_files, lengths, absolute != 0, file_keys, aux, s);
+}
+
+extern "C" int sae_search_merge(const uint64_t* file_keys, const uint64_t* aux, int64_t n_files, int64_t ncols, int64_t file0, int n_top,
+                                int flags, double min_val, double max_val, uint64_t* top_keys, int32_t* top_frames, void* stream) {
+  if (!file_keys || !top_keys || !top_frames) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_files <= 0 || ncols <= 0 || file0 < 0) return fail(SAE_ERR_INVALID, "n_files=%lld, ncols=%lld, file0=%lld", (long long)n_files, (long long)ncols, (long long)file0);
+  if (file0 + n_files >= 0xFFFFFFFFll) return fail(SAE_ERR_INVALID, "file indices beyond 2^32 - 2");
+  if (n_top < 1 || n_top > SAE_SEARCH_MAX_TOP) return fail(SAE_ERR_INVALID, "n_top=%d outside [1, %d]", n_top, SAE_SEARCH_MAX_TOP);
+  if (flags & ~(SAE_SEARCH_ABS | SAE_SEARCH_MIN | SAE_SEARCH_MAX)) return fail(SAE_ERR_INVALID, "unknown merge flags 0x%x", flags);
+  hipLaunchKernelGGL(search_merge_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, (hipStream_t)stream, file_keys, aux, n_files,
+                     ncols, file0, n_top, flags, min_val, max_val, top_keys, top_frames);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_search_file_values(const uint64_t* file_keys, const uint64_t* aux, int64_t n_files, int64_t ncols, int flags,
+                                      const int32_t* latents, int64_t n_latents, int64_t file0, int64_t out_stride, float* out, void* stream) {
+  if (!file_keys || !latents || !out) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_files <= 0 || ncols <= 0 || n_latents <= 0 || file0 < 0) return fail(SAE_ERR_INVALID, "empty or negative extent");
+  if (out_stride < file0 + n_files) return fail(SAE_ERR_INVALID, "out_stride=%lld < file0 + n_files=%lld", (long long)out_stride, (long long)(file0 + n_files));
+  const int64_t total = n_latents * n_files;
+  hipLaunchKernelGGL(search_values_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, file_keys, aux, n_files,
+                     ncols, flags, latents, n_latents, file0, out_stride, out);
+  HIP_TRY(hipGetLastError());
   return SAE_OK;
 }
 

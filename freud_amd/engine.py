@@ -117,6 +117,10 @@ def load() -> C.CDLL:
         "sae_read_metrics": (C.c_int, [vp, fptr, vp]),
         "sae_latent_colmax": (C.c_int, [vp, fptr, i64, vp]),
         "sae_debug_read": (C.c_int, [vp, C.c_int, fptr, i64]),
+        "sae_search_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
+        "sae_search_raw_files": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp]),
+        "sae_search_merge": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, dbl, dbl, vp, vp, vp]),
+        "sae_search_file_values": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i64, i64, i64, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -153,7 +157,10 @@ EXPORTED_SYMBOLS = [
     "sae_latent_buffer", "sae_topk_indices", "sae_decode", "sae_multi_topk_buffers",
     "sae_step", "sae_eval", "sae_eval_into", "sae_set_eval_precision", "sae_read_metrics", "sae_latent_colmax", "sae_debug_read", "sae_profile", "sae_profile_period", "sae_kernel_times",
     "sae_kernel_name", "sae_dominant_kernel",
+    "sae_search_files", "sae_search_raw_files", "sae_search_merge", "sae_search_file_values",
 ]
+SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
+SEARCH_MAX_TOP = 4096
 
 
 def _check(rc: int) -> None:
@@ -525,6 +532,20 @@ class SaeEngine:
 
         return torch.as_tensor(_Alias(), device=f"cuda:{self.device_id}")
 
+    # -- feature search (include/freud_sae.h: sae_search_*; freud_amd/feature_search.py) ------------------
+    def search_files(self, x, file_keys, lengths=None, unfused: bool = False, stream=None) -> None:
+        """Per-(file, latent) keys of x [n_files, T, d] (CUDA) into file_keys (int64 CUDA tensor [n_files, n_dict]); lengths: int32
+        CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
+        import torch
+        if x.dim() != 3:
+            raise EngineError(f"search_files expects x as [n_files, T, d], got {tuple(x.shape)}")
+        _check_search_out(file_keys, x.shape[0] * self.n)
+        lp = _lengths_ptr(lengths, x.shape[0])
+        B, T = int(x.shape[0]), int(x.shape[1])
+        x, ptr, _rows, dt = self._x_args(x)
+        _check(self._lib.sae_search_files(self._ctx, C.c_void_p(ptr), B, T, dt, lp, SEARCH_UNFUSED if unfused else 0,
+                                          C.c_void_p(file_keys.data_ptr()), self._stream(stream)))
+
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:
         out = np.empty(count, dtype=np.float32)
@@ -552,3 +573,67 @@ class SaeEngine:
 
     def dominant_kernel(self) -> str:
         return self._lib.sae_kernel_name(self._lib.sae_dominant_kernel(self._ctx)).decode()
+
+
+# -- feature search without a context (raw mode, merge, per-file values) ---------------------------------------------------
+def _check_search_out(t, numel: int) -> None:
+    import torch
+    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= numel):
+        raise EngineError(f"key buffers must be contiguous int64 CUDA tensors of >= {numel} elements")
+
+
+def _lengths_ptr(lengths, n_files: int):
+    import torch
+    if lengths is None:
+        return None
+    if not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == n_files):
+        raise EngineError(f"lengths must be a contiguous int32 CUDA tensor of {n_files} elements")
+    return C.c_void_p(lengths.data_ptr())
+
+
+def _stream_ptr(stream=None):
+    import torch
+    return C.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
+
+
+def search_raw_files(x, file_keys, aux=None, lengths=None, absolute: bool = False, stream=None) -> None:
+    """Raw mode (no SAE): per-(file, column) keys of x [n_files, T, d] itself; with absolute, aux gets the abs-mode side words."""
+    import torch
+    if x.dim() != 3:
+        raise EngineError(f"search_raw_files expects x as [n_files, T, d], got {tuple(x.shape)}")
+    B, T, d = (int(v) for v in x.shape)
+    _check_search_out(file_keys, B * d)
+    if absolute:
+        _check_search_out(aux, B * d)
+    x, ptr, _rows, dt = SaeEngine._x_args(x)
+    _check(load().sae_search_raw_files(C.c_void_p(ptr), B, T, d, dt, _lengths_ptr(lengths, B), int(absolute),
+                                       C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if absolute else None,
+                                       _stream_ptr(stream)))
+
+
+def search_merge(file_keys, aux, n_files: int, ncols: int, file0: int, n_top: int, flags: int, min_val: float, max_val: float,
+                 top_keys, top_frames, stream=None) -> None:
+    import torch
+    _check_search_out(file_keys, n_files * ncols)
+    if aux is not None:
+        _check_search_out(aux, n_files * ncols)
+    _check_search_out(top_keys, n_top * ncols)
+    if not (top_frames.is_cuda and top_frames.dtype == torch.int32 and top_frames.is_contiguous() and top_frames.numel() >= n_top * ncols):
+        raise EngineError(f"top_frames must be a contiguous int32 CUDA tensor of >= {n_top * ncols} elements")
+    _check(load().sae_search_merge(C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if aux is not None else None,
+                                   int(n_files), int(ncols), int(file0), int(n_top), int(flags), float(min_val), float(max_val),
+                                   C.c_void_p(top_keys.data_ptr()), C.c_void_p(top_frames.data_ptr()), _stream_ptr(stream)))
+
+
+def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:
+    import torch
+    _check_search_out(file_keys, n_files * ncols)
+    if aux is not None:
+        _check_search_out(aux, n_files * ncols)
+    if not (latents.is_cuda and latents.dtype == torch.int32 and latents.is_contiguous()):
+        raise EngineError("latents must be a contiguous int32 CUDA tensor")
+    if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous() and out.shape[0] >= latents.numel()):
+        raise EngineError(f"out must be a contiguous float32 CUDA tensor [>= {latents.numel()}, files]")
+    _check(load().sae_search_file_values(C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if aux is not None else None,
+                                         int(n_files), int(ncols), int(flags), C.c_void_p(latents.data_ptr()), int(latents.numel()),
+                                         int(file0), int(out.shape[1]), C.c_void_p(out.data_ptr()), _stream_ptr(stream)))

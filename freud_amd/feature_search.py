@@ -1,0 +1,293 @@
+"""Feature search: for EVERY latent at once, the answer of the reference's `top_activations` (src/utils/activations.py:61-132,
+served to the GUI by gui_server.py:91-99) -- the top-N files by the maximum of the latent's (trimmed) series, with that maximum
+and its time.
+
+The reference needs the SAE activations collected to disk first (collect_activations.py with sae_model: a dense fp32 [1500, n]
+row per file for L1) and then makes one full pass over that dataset PER LATENT.  Here one pass over the Whisper-activation shards
+does all latents: the engine encodes a batch of files with the training kernels and keeps only per-(file, latent) maxima (the
+L1 latent is never written: include/freud_sae.h, sae_search_files), merges them into a per-latent top-N table on the device
+(sae_search_merge) and the host reads the table back once at the end.
+
+Semantics are the reference's, including its quirks: the trim to int(duration / TIMESTEP_S) frames (here: `lengths`, since
+durations come from audio files that this project does not decode), the first maximal frame, the filter
+min_val <= value <= max_val, the stable order (value descending, file ascending; a file that ties the N-th is dropped), and in
+absolute_magnitude mode the signed value at argmax |a| filtered, |value| ranked, but the time of the SIGNED argmax returned
+(activations.py:106-121).
+
+    python -m freud_amd.feature_search --sae CKPT|none --data_path DIR --layer_name L --n_files N [--absolute]
+        [--min_val V] [--max_val V] [--lengths file.npy] --out atlas.npz
+"""
+from __future__ import annotations
+
+import argparse
+import dataclasses
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+TIMESTEP_S = 30 / 1500          # src/utils/constants.py:17
+
+
+@dataclasses.dataclass
+class FeatureAtlas:
+    """values / file_idx / frames / times: [n_latents, n_files]; empty slots have file_idx -1, frame -1, value and time NaN.
+    max_per_file: [len(max_per_file_features), number of files] (the signed value in abs mode), or None."""
+    values: np.ndarray
+    file_idx: np.ndarray
+    frames: np.ndarray
+    times: np.ndarray
+    filenames: List[str]
+    max_per_file: Optional[np.ndarray] = None
+    max_per_file_features: Optional[np.ndarray] = None
+
+    def top(self, feature_idx: int):
+        """[(filename, value, time)] of one latent, best first (the reference's pq without the series)."""
+        out = []
+        for v, f, t in zip(self.values[feature_idx], self.file_idx[feature_idx], self.times[feature_idx]):
+            if f < 0:
+                break
+            out.append((self.filenames[int(f)], float(v), float(t)))
+        return out
+
+    def to_npz(self, path: str) -> None:
+        arrays = dict(values=self.values, file_idx=self.file_idx, frames=self.frames, times=self.times,
+                      filenames=np.array(self.filenames, dtype=str))
+        if self.max_per_file is not None:
+            arrays["max_per_file"] = self.max_per_file
+            arrays["max_per_file_features"] = self.max_per_file_features
+        np.savez(path, **arrays)
+
+
+def unord(o: np.ndarray) -> np.ndarray:
+    """Inverse of search_keys.h's order-preserving float map (uint32 -> float32)."""
+    o = np.asarray(o, dtype=np.uint32)
+    u = np.where(o & np.uint32(0x80000000), o & np.uint32(0x7FFFFFFF), ~o).astype(np.uint32)
+    return u.view(np.float32)
+
+
+def decode_table(top_keys: np.ndarray, top_frames: np.ndarray):
+    """[N, n] rank keys / frames of sae_search_merge -> values [n, N] fp32, file indices [n, N] int64 (-1 empty), frames, times."""
+    r = np.ascontiguousarray(top_keys).view(np.uint64)
+    empty = r == 0
+    values = unord((r >> np.uint64(32)).astype(np.uint32))
+    files = (np.uint64(0xFFFFFFFF) - (r & np.uint64(0xFFFFFFFF))).astype(np.int64)
+    frames = top_frames.astype(np.int64)
+    values = np.where(empty, np.float32(np.nan), values).astype(np.float32)
+    files[empty] = -1
+    frames[empty] = -1
+    times = np.array([[f * TIMESTEP_S if f >= 0 else float("nan") for f in row] for row in frames.T.tolist()], dtype=np.float64)
+    return values.T.copy(), files.T.copy(), frames.T.copy(), times
+
+
+def check_lengths(lengths, n_total: int, T: int) -> Optional[np.ndarray]:
+    """Trim lengths (frames per file, in file order) -> int32 capped at T; a length below 1 is an error (the reference fails on
+    max() of an empty series)."""
+    if lengths is None:
+        return None
+    a = np.asarray(lengths)
+    if a.ndim != 1 or a.shape[0] != n_total:
+        raise ValueError(f"lengths must hold one entry per file ({n_total}), got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"lengths must be integers, got {a.dtype}")
+    if a.size and int(a.min()) < 1:
+        raise ValueError(f"lengths must be >= 1 (file {int(np.argmin(a))} has {int(a.min())}): an empty series has no maximum")
+    return np.minimum(a.astype(np.int64), T).astype(np.int32)
+
+
+def _resolve_sae(sae):
+    """None (raw mode) | checkpoint path | freud_amd.models instance | SaeEngine -> (model or None, engine or None)."""
+    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+        return None, None
+    if isinstance(sae, str):
+        from .models import init_sae_from_checkpoint
+        sae = init_sae_from_checkpoint(sae)
+    from .engine import SaeEngine
+    if isinstance(sae, SaeEngine):
+        return None, sae
+    if not hasattr(sae, "_ensure"):
+        raise TypeError(f"sae must be None, a checkpoint path, a freud_amd.models SAE or a SaeEngine, got {type(sae).__name__}")
+    return sae, None
+
+
+def default_batch_files(T: int, n: Optional[int], n_total: int) -> int:
+    """Files per batch when the caller gives none: 16, or for an L1 / TopK SAE the fewest files at which the encoder GEMM has the
+    2048 output tiles of 256 x 256 that its streaming form (gemm256s.h: engine.hip gemm_streams, 4 x G2_PERSIST_STATIC) needs, so
+    that the L1 search takes the fused epilogue (n = 3072, T = 1500: 30 files; n = 40 960: 16).  Dictionaries whose padded size is
+    no multiple of 256 never stream; above 512 files the batch stays at 16 (n < 1024) and the latent is stored and reduced."""
+    B = 16
+    if n is not None:
+        n_p = -(-n // 128) * 128
+        if n_p % 256 == 0:
+            need = -(-2048 // (n_p // 256))                  # 256-row blocks of the batch
+            b_min = ((need - 1) * 256) // T + 1              # round_up(B T, 256) / 256 >= need
+            if b_min <= 512:
+                B = max(B, b_min)
+    return max(1, min(B, n_total))
+
+
+def _keep_rng(fn):
+    """The search must not disturb the caller's global torch RNG: the loader's epoch_batches() draws the DataLoader base seed, and
+    building a model from a checkpoint runs the reference modules' random initialisations before the weights are loaded."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(*a, **k):
+        state = torch.get_rng_state()
+        try:
+            return fn(*a, **k)
+        finally:
+            torch.set_rng_state(state)
+    return wrapped
+
+
+@_keep_rng
+def search_features(sae, data_path: str, layer_name: str, n_files: int, *, absolute_magnitude: bool = False,
+                    min_val: Optional[float] = None, max_val: Optional[float] = None, lengths=None,
+                    subset_size: Optional[int] = None, batch_files: Optional[int] = None,
+                    max_per_file_features: Optional[Sequence[int]] = None) -> FeatureAtlas:
+    """top_activations for every latent of `sae` (None: every column of the activations themselves) in one pass.
+    batch_files: files per engine call (default: default_batch_files)."""
+    from . import engine as E
+    from .loader import MemoryMappedActivationDataLoader, MemoryMappedActivationsDataset
+
+    n_files = int(n_files)
+    if n_files < 1 or n_files > E.SEARCH_MAX_TOP:
+        raise ValueError(f"n_files={n_files} outside [1, {E.SEARCH_MAX_TOP}]")
+    if batch_files is not None and int(batch_files) < 1:
+        raise ValueError(f"batch_files={batch_files} must be >= 1")
+    ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
+    n_total = len(ds)
+    T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
+    lens = check_lengths(lengths, n_total, T)
+    if n_total == 0:
+        raise ValueError(f"{data_path}: no files")
+    model, eng = _resolve_sae(sae)
+    if not torch.cuda.is_available():
+        raise RuntimeError("the feature search runs on the GPU (HIP engine); there is no CPU path")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if model is not None:
+        dev = model.device
+        if model.activation_size != d:
+            raise ValueError(f"the SAE expects d_model={model.activation_size}, the shards hold d={d}")
+    if eng is not None and eng.d != d:
+        raise ValueError(f"the SAE expects d_model={eng.d}, the shards hold d={d}")
+    n_lat = None if (model is None and eng is None) else (eng.n if eng is not None else model.n_dict_components)
+    B = int(batch_files) if batch_files is not None else default_batch_files(T, n_lat, n_total)
+    B = min(B, n_total)
+    if eng is None and model is not None:
+        eng = model._ensure(-(-B * T // 256) * 256)     # (row room for an even number of 128-row blocks: the fused epilogue's GEMM)
+    elif eng is not None and B * T > eng.max_rows:
+        B = max(1, eng.max_rows // T)
+        if B * T > eng.max_rows:
+            raise ValueError(f"one file of {T} rows exceeds the engine's max_rows={eng.max_rows}")
+    raw = eng is None
+    ncols = d if raw else eng.n
+    if eng is not None and eng.precision != "bf16":
+        raise ValueError("the feature search runs in bf16 contexts only")
+    flags = (E.SEARCH_ABS if absolute_magnitude else 0) | (E.SEARCH_MIN if min_val is not None else 0) | \
+            (E.SEARCH_MAX if max_val is not None else 0)
+    feats = None
+    if max_per_file_features is not None:
+        feats = np.asarray(list(max_per_file_features), dtype=np.int64)
+        if feats.size == 0 or feats.min() < 0 or feats.max() >= ncols:
+            raise ValueError(f"max_per_file_features must be latent indices in [0, {ncols})")
+
+    with torch.cuda.device(dev):
+        keys = torch.empty(B * ncols, dtype=torch.int64, device=dev)
+        aux = torch.empty(B * ncols, dtype=torch.int64, device=dev) if (raw and absolute_magnitude) else None
+        top_keys = torch.zeros(n_files * ncols, dtype=torch.int64, device=dev)
+        top_frames = torch.zeros(n_files * ncols, dtype=torch.int32, device=dev)
+        lens_dev = torch.from_numpy(lens).to(dev) if lens is not None else None
+        feats_dev = torch.from_numpy(feats.astype(np.int32)).to(dev) if feats is not None else None
+        per_file = torch.zeros(len(feats), n_total, dtype=torch.float32, device=dev) if feats is not None else None
+        # (native delivery whatever FREUD_LOADER_DELIVER says: raw mode ranks x unrounded, the SAE search sees what encode() sees)
+        loader = MemoryMappedActivationDataLoader(data_path, layer_name, B, subset_size=subset_size,
+                                                  dl_kwargs={"shuffle": False, "drop_last": False}, device=dev,
+                                                  deliver_dtype="native")
+        file0 = 0
+        for x, _names in loader:
+            nb = int(x.shape[0])
+            lb = lens_dev[file0:file0 + nb] if lens_dev is not None else None
+            if raw:
+                E.search_raw_files(x, keys, aux, lb, absolute=absolute_magnitude)
+            else:
+                eng.search_files(x, keys, lb)
+            E.search_merge(keys, aux, nb, ncols, file0, n_files, flags, 0.0 if min_val is None else float(min_val),
+                           0.0 if max_val is None else float(max_val), top_keys, top_frames)
+            if feats is not None:
+                E.search_file_values(keys, aux, nb, ncols, flags, feats_dev, file0, per_file)
+            file0 += nb
+        if file0 != n_total:
+            raise RuntimeError(f"the loader delivered {file0} of {n_total} files")
+        tk = top_keys.view(n_files, ncols).cpu().numpy()          # the one read-back
+        tf = top_frames.view(n_files, ncols).cpu().numpy()
+        pf = per_file.cpu().numpy() if per_file is not None else None
+    values, files, frames, times = decode_table(tk, tf)
+    return FeatureAtlas(values, files, frames, times, list(ds.metadata["filenames"]), pf, feats)
+
+
+def _series(sae_model, eng, x: torch.Tensor, feature_idx: int) -> torch.Tensor:
+    """The latent's series over one file's rows [T, d] -- encode() of freud_amd.models (or x's own column in raw mode)."""
+    if sae_model is None and eng is None:
+        return x[:, feature_idx].float().cpu()
+    if sae_model is None:
+        raise TypeError("top_activations needs a freud_amd.models SAE (or None) to re-encode the winning files")
+    if sae_model._variant == "l1":
+        return sae_model.encode(x).latent[:, feature_idx].float().cpu()
+    enc = sae_model.encode(x)                       # activation_tensor_from_indexed (activations.py:41-58)
+    dense = torch.zeros(x.shape[0], dtype=torch.float32, device=enc.top_acts.device)
+    hit = enc.top_indices == feature_idx
+    dense += (enc.top_acts.float() * hit).sum(dim=1)
+    return dense.cpu()
+
+
+@_keep_rng
+def top_activations(sae, data_path: str, layer_name: str, feature_idx: int, n_files: int, max_val: Optional[float],
+                    min_val: Optional[float], absolute_magnitude: bool, return_max_per_file: bool, lengths=None):
+    """activations.py:61-132 with the reference's return shape: ([(audio_file, trimmed series, value, time)], max_per_file or None).
+    The series are re-encoded for the winning files only."""
+    from .loader import MemoryMappedActivationsDataset
+    model, eng = _resolve_sae(sae)
+    atlas = search_features(model if model is not None else eng, data_path, layer_name, n_files, absolute_magnitude=absolute_magnitude,
+                            min_val=min_val, max_val=max_val, lengths=lengths,
+                            max_per_file_features=[feature_idx] if return_max_per_file else None)
+    ds = MemoryMappedActivationsDataset(data_path, layer_name)
+    T = int(ds.tensor_shape[-2])
+    lens = check_lengths(lengths, len(ds), T)
+    dev = model.device if model is not None else torch.device("cuda", torch.cuda.current_device())
+    pq = []
+    for value, t, f in zip(atlas.values[feature_idx], atlas.times[feature_idx], atlas.file_idx[feature_idx]):
+        if f < 0:
+            break
+        x, fname = ds[int(f)]
+        L = T if lens is None else int(lens[int(f)])
+        series = _series(model, eng, x.to(dev), feature_idx)[:L]
+        pq.append((fname, series, float(value), float(t)))
+    mpf = [float(v) for v in atlas.max_per_file[0]] if return_max_per_file else None
+    return pq, mpf
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser(description="Top-N files of every latent in one pass (the reference's top_activations).")
+    ap.add_argument("--sae", required=True, help="checkpoint path, or 'none' for the activations' own columns")
+    ap.add_argument("--data_path", required=True)
+    ap.add_argument("--layer_name", required=True)
+    ap.add_argument("--n_files", type=int, required=True)
+    ap.add_argument("--absolute", action="store_true")
+    ap.add_argument("--min_val", type=float, default=None)
+    ap.add_argument("--max_val", type=float, default=None)
+    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
+    ap.add_argument("--batch_files", type=int, default=None)
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args(argv)
+    lengths = np.load(a.lengths) if a.lengths else None
+    atlas = search_features(None if a.sae.lower() == "none" else a.sae, a.data_path, a.layer_name, a.n_files,
+                            absolute_magnitude=a.absolute, min_val=a.min_val, max_val=a.max_val, lengths=lengths,
+                            batch_files=a.batch_files)
+    atlas.to_npz(a.out)
+    print(f"{a.out}: {atlas.values.shape[0]} latents x top {atlas.values.shape[1]} over {len(atlas.filenames)} files")
+
+
+if __name__ == "__main__":
+    main()

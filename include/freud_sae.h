@@ -303,6 +303,58 @@ int sae_read_metrics(sae_ctx* ctx, float out_host[SAE_NUM_METRICS], void* stream
  * Synchronises `stream`. */
 int sae_latent_colmax(sae_ctx* ctx, float* out_host, int64_t capacity_floats, void* stream);
 
+/* ---- Feature search: the reference's top_activations (utils/activations.py:61-132, served by gui_server.py:91-99) for EVERY
+ * latent in one pass over the data, instead of one pass over a collected SAE-activation dataset per latent.
+ *
+ * A search is three steps per batch of files, all asynchronous on `stream`, all buffers CALLER-OWNED device memory:
+ *   1. file keys: per (file, latent) one uint64 (freud_amd/csrc/search_keys.h): ord(value) << 32 | (0xFFFFFFFF - frame), the
+ *      maximum of the file's trimmed series and its first frame -- trimmed_activation.max() / .argmax() (activations.py:104-124);
+ *   2. sae_search_merge: the batch's keys merged into a running per-latent top-N table -- the reference's filter, append, stable
+ *      sort by value and truncation to n_files (activations.py:118-129): order (value descending, file ascending);
+ *   3. optionally sae_search_file_values: the per-file values of chosen latents (return_max_per_file, activations.py:111-117).
+ * The host reads the table back once at the end (freud_amd/feature_search.py).
+ *
+ * A batch holds n_files files of rows_per_file (T) rows each, row-major [n_files][T][d].  lengths_dev (int32 [n_files], or NULL
+ * = T): only the first min(length, T) frames of a file count (trim_activation, activations.py:19-29); a length below 1 is treated
+ * as 1 (the Python layer rejects it: the reference fails on max() of an empty series).  Shape checks fail before anything is
+ * enqueued. */
+enum { SAE_SEARCH_ABS = 1, SAE_SEARCH_MIN = 2, SAE_SEARCH_MAX = 4, SAE_SEARCH_UNFUSED = 8 };
+#define SAE_SEARCH_MAX_TOP 4096
+
+/* File keys of the context's SAE latents, file_keys_dev[n_files][n_dict].  L1: c = relu(x W + b) of sae_eval (bf16 operands, the
+ * in-place column renormalisation of encode() included), reduced in the encoder GEMM's epilogue -- the latent is never written
+ * (SAE_SEARCH_UNFUSED: stored and reduced by a second kernel; also taken where the streaming GEMM does not apply -- it needs an even
+ * number of 128-row blocks, so a max_rows with room for round_up(n_files * rows_per_file, 256) rows, and T <= 65535).  TopK: the eval
+ * forward, then its top-k selection scattered into the keys; frames where a latent is not selected count as 0
+ * (activation_tensor_from_indexed, activations.py:41-58), so a latent that never fires has value 0 at frame 0.  Both latents are
+ * >= 0, so the abs mode of the merge equals the plain one for them.  n_files * rows_per_file <= max_rows; fp8 contexts:
+ * SAE_ERR_INVALID.  Training state (parameters, moments, num_frames_since_fired) is untouched; afterwards sae_latent_buffer,
+ * sae_topk_indices, sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the next
+ * sae_eval / step (sae_decode reads the caller's latent and is unaffected). */
+int sae_search_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                     int flags, uint64_t* file_keys_dev, void* stream);
+
+/* Raw mode (no SAE: the README's single-neuron search): file keys of x itself, file_keys_dev[n_files][d], fp32 / fp16 / bf16 values
+ * as they are.  absolute != 0 (activations.py:106-113): the keys rank |a| (first frame of max |a|), and aux_dev[n_files][d] holds
+ * the signed value at that frame (high 32 bits, fp32) and the frame of the SIGNED maximum (low 32 bits) -- the time the reference
+ * returns even in abs mode (activations.py:120-121).  Runs on the current device. */
+int sae_search_raw_files(const void* x_dev, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths_dev,
+                         int absolute, uint64_t* file_keys_dev, uint64_t* aux_dev, void* stream);
+
+/* Merge the keys of files [file0, file0 + n_files) (file_keys_dev[n_files][ncols], aux_dev of a raw abs search or NULL) into the
+ * top-N table top_keys_dev / top_frames_dev, both [n_top][ncols] (latent-minor).  Table entries are rank keys
+ * ord(value) << 32 | (0xFFFFFFFF - file) (search_keys.h; 0 = empty: zero the table before the first batch) and frames.  flags:
+ * SAE_SEARCH_ABS ranks |value| and filters the signed value, SAE_SEARCH_MIN / _MAX apply min_val <= value <= max_val (in double,
+ * as the reference compares .item() floats).  1 <= n_top <= SAE_SEARCH_MAX_TOP; n_top may exceed the number of files.  One
+ * thread per latent, files in order: deterministic.  Runs on the current device. */
+int sae_search_merge(const uint64_t* file_keys_dev, const uint64_t* aux_dev, int64_t n_files, int64_t ncols, int64_t file0, int n_top,
+                     int flags, double min_val, double max_val, uint64_t* top_keys_dev, int32_t* top_frames_dev, void* stream);
+
+/* return_max_per_file: out_dev[l * out_stride + file0 + f] = the per-file value of latent latents_dev[l] (the signed value in abs
+ * mode) for the files of this batch.  out_stride >= file0 + n_files.  Runs on the current device. */
+int sae_search_file_values(const uint64_t* file_keys_dev, const uint64_t* aux_dev, int64_t n_files, int64_t ncols, int flags,
+                           const int32_t* latents_dev, int64_t n_latents, int64_t file0, int64_t out_stride, float* out_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
