@@ -35,6 +35,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "topk_aux.h"
 #include "eval_fp32.h"
 #include "search.h"
+#include "stats.h"
 
 #ifndef G2_PERSIST_STATIC
 #define G2_PERSIST_STATIC 512      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
@@ -272,6 +273,8 @@ struct sae_ctx {
   int eval_prec = 0;            // 0 = the training kernels' arithmetic (bf16 operands, fp32 accumulate), 1 = fp32 end to end
   bool last_fwd_e32 = false;    // the last forward was an fp32 evaluation: its per-feature maxima live in e32_colmax
   bool last_fwd_search = false; // the last call was a feature search (sae_search_files): it leaves no latent rows / metrics to read
+  bool last_fwd_stats = false;  // the last call was a statistics pass (sae_stats_files): the same
+  void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;
@@ -522,7 +525,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);
@@ -2535,6 +2538,7 @@ static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dt
   c->last_dtype = x_dtype;
   c->last_fwd_e32 = false;
   c->last_fwd_search = false;
+  c->last_fwd_stats = false;
   if (c->topk) {
     switch (x_dtype) {
       case SAE_DTYPE_F32: return topk_fwd_bwd<float>(c, (const float*)x, M, s, backward);
@@ -2631,6 +2635,7 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   c->last_M_p = round_up(M, c->row_pad);
   c->last_fwd_e32 = true;
   c->last_fwd_search = false;
+  c->last_fwd_stats = false;
   c->metrics_fresh = false;
   return SAE_OK;
 }
@@ -2769,6 +2774,7 @@ extern "C" int sae_step(sae_ctx* c, const void* x, int64_t M, int x_dtype, doubl
 extern "C" int sae_read_metrics(sae_ctx* c, float out[SAE_NUM_METRICS], void* stream) {
   if (!c || !out) return fail(SAE_ERR_INVALID, "null argument");
   if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
+  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   USE_DEVICE(c);
   HIP_TRY(hipMemcpyAsync(out, c->G + c->nparams, SAE_NUM_METRICS * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -2900,6 +2906,7 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
 extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride) {
   if (!c || !dev_ptr || !row_stride) return fail(SAE_ERR_INVALID, "null argument");
   if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
+  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
   if (c->last_fwd_e32) return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows");
@@ -2915,6 +2922,7 @@ extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride
 extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
   if (!c || !dev_ptr || !k) return fail(SAE_ERR_INVALID, "null argument");
   if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
+  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   if (!c->topk) return fail(SAE_ERR_INVALID, "sae_topk_indices: not a TopK context");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   *dev_ptr = c->top_idx;
@@ -2925,6 +2933,7 @@ extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
 extern "C" int sae_multi_topk_buffers(sae_ctx* c, void** dense_dev, int64_t* row_stride, void** idx_dev, int* k4) {
   if (!c || !dense_dev || !row_stride || !idx_dev || !k4) return fail(SAE_ERR_INVALID, "null argument");
   if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
+  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   if (!c->topk || !c->multi) return fail(SAE_ERR_INVALID, "sae_multi_topk_buffers: not a TopK context with multi_topk");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   if (!c->multi_dense_valid) {      // a training step on the sparse backward keeps the 4k selection compact: densify on demand
@@ -2948,6 +2957,7 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
   if (M <= 0 || M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "M=%lld outside (0, max_rows=%lld]", (long long)M, (long long)c->cfg.max_rows);
   if (ld < c->n) return fail(SAE_ERR_INVALID, "row stride %lld < n_dict %d", (long long)ld, c->n);
   if (latent_dtype != SAE_DTYPE_F32 && latent_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "latent dtype must be f32 or bf16");
+  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   USE_DEVICE(c);
   hipStream_t s = (hipStream_t)stream;
   const int d_p = c->d_p, n_p = c->n_p;
@@ -2995,6 +3005,7 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
 extern "C" int sae_latent_colmax(sae_ctx* c, float* out_host, int64_t capacity, void* stream) {
   if (!c || !out_host) return fail(SAE_ERR_INVALID, "null argument");
   if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
+  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   if (capacity < c->n) return fail(SAE_ERR_INVALID, "capacity too small");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
@@ -3205,6 +3216,152 @@ extern "C" int sae_search_file_values(const uint64_t* file_keys, const uint64_t*
   hipLaunchKernelGGL(search_values_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, file_keys, aux, n_files,
                      ncols, flags, latents, n_latents, file0, out_stride, out);
   HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- feature statistics (stats.h): per-latent firing counts, sums, maxima and the L0 histogram of one batch of files
+static int stats_ensure(sae_ctx* c) {
+  if (c->fs_slab) return SAE_OK;
+  const int64_t slab_bytes = (c->max_rows_p / STATS_RB) * (int64_t)c->n * 16;
+  const int64_t l0_bytes = c->topk ? 0 : c->max_rows_p * (int64_t)(c->n_p / 64);
+  HIP_TRY(hipMalloc(&c->fs_slab, (size_t)(slab_bytes + l0_bytes)));
+  return SAE_OK;
+}
+
+static StatsSlab stats_slab(sae_ctx* c) {
+  const int64_t words = (c->max_rows_p / STATS_RB) * (int64_t)c->n;
+  StatsSlab sl;
+  sl.cnt = (uint32_t*)c->fs_slab;
+  sl.mx = sl.cnt + words;
+  sl.sum = (float*)(sl.mx + words);
+  sl.sq = sl.sum + words;
+  return sl;
+}
+
+struct StatsOut {               // the caller's block (include/freud_sae.h, SAE_STATS_*)
+  unsigned long long *n_frames, *fire, *hist;
+  double *asum, *asq;
+  float* amax;
+};
+
+static StatsOut stats_out(void* block, int n) {
+  char* b = (char*)block;
+  StatsOut o;
+  o.n_frames = (unsigned long long*)(b + SAE_STATS_N_FRAMES(n));
+  o.fire = (unsigned long long*)(b + SAE_STATS_FIRE_COUNT(n));
+  o.asum = (double*)(b + SAE_STATS_ACT_SUM(n));
+  o.asq = (double*)(b + SAE_STATS_ACT_SQ_SUM(n));
+  o.hist = (unsigned long long*)(b + SAE_STATS_L0_HIST(n));
+  o.amax = (float*)(b + SAE_STATS_ACT_MAX(n));
+  return o;
+}
+
+template <class Src>
+static void stats_launch_l0(Src src, int64_t M, int T, const int* lengths, int n, const StatsOut& o, hipStream_t s) {
+  int grid = (int)((M + 3) / 4);
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(stats_l0_kernel<Src>, dim3(grid), dim3(256), 0, s, src, M, T, lengths, n + 1, o.hist, o.n_frames);
+}
+
+static void stats_launch_fold(sae_ctx* c, int nrb, const StatsOut& o, hipStream_t s) {
+  hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, stats_slab(c), nrb, c->n, o.fire, o.asum, o.asq,
+                     o.amax);
+}
+
+// L1: the encoder GEMM of search_l1_impl (forward_impl's weights preparation and bf16 copy of x) with EpiStats instead of EpiSearch.
+// Where the streaming GEMM does not apply, or `unfused` is asked for, the ordinary encoder stores the latent and two kernels
+// reduce it (column statistics into the slab, row counts into the histogram).
+template <typename T>
+static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, const StatsOut& o, bool unfused, hipStream_t s) {
+  const int d = c->d, d_p = c->d_p, n_p = c->n_p;
+  float* b = c->P + c->nW;
+  int64_t Mp = round_up(M, 128);
+  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);    // (an even number of row blocks: the streaming GEMM's condition)
+  prep_weights_l1(c, s);
+  {
+    const int64_t chunks = Mp * (d_p / 8);
+    int grid = (int)((chunks + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+      hipLaunchKernelGGL((prep_x_kernel<T, true>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+    else
+      hipLaunchKernelGGL((prep_x_kernel<T, false>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+  }
+  const StatsSlab sl = stats_slab(c);
+  uint8_t* l0b = (uint8_t*)c->fs_slab + (c->max_rows_p / STATS_RB) * (int64_t)c->n * 16;
+  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
+  GemmArgs g{};
+  g.A0 = c->xb; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
+  g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
+  if (!unfused && gemm_streams<OP_ROW, OP_ROW, EpiStats>(g)) {
+    EpiStats e{};
+    e.bias = b; e.slab = sl; e.l0b = l0b; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n; e.ncb = n_p / 64;
+    e.inv_T = 1.0f / (float)Trows;
+    auto kerns = gemm256s_bf16_kernel<EpiStats>;
+    LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
+    GemmArgs g2 = g;
+    g2.nbm = g.nbm / 2;
+    g2.nbn = g.nbn / 2;
+    ev_begin(c, KID_ENC_FWD, s);
+    hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, e);
+    ev_end(c, KID_ENC_FWD, s);
+    HIP_TRY(hipGetLastError());
+    stats_launch_l0(L0Bytes{l0b, n_p / 64}, M, Trows, lengths, c->n, o, s);
+  } else {
+    EpiEnc e{};
+    e.c = c->c; e.bias = b; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = g.nbn;
+    if (gemm_streams<OP_ROW, OP_ROW, EpiEnc>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)g.nbm * g.nbn * 4, s));
+    ev_begin(c, KID_ENC_FWD, s);
+    int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+    ev_end(c, KID_ENC_FWD, s);
+    if (rc) return rc;
+    const unsigned short* lat = (const unsigned short*)c->c;
+    hipLaunchKernelGGL(stats_colreduce_kernel, dim3((unsigned)((c->n + 255) / 256), (unsigned)nrb), dim3(256), 0, s, lat, (int64_t)n_p, c->n,
+                       M, Trows, lengths, sl);
+    stats_launch_l0(L0Latent{lat, n_p, c->n}, M, Trows, lengths, c->n, o, s);
+  }
+  stats_launch_fold(c, nrb, o, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                               int flags, void* stats, void* stream) {
+  if (!c || !x || !stats) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->fp8) return fail(SAE_ERR_INVALID, "sae_stats_files: fp8 contexts are not supported (run the statistics in a bf16 context)");
+  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
+  const int64_t M = n_files * rows_per_file;
+  if (M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "n_files * rows_per_file = %lld > max_rows=%lld", (long long)M, (long long)c->cfg.max_rows);
+  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  if (flags & ~SAE_STATS_UNFUSED) return fail(SAE_ERR_INVALID, "unknown stats flags 0x%x", flags);
+  if ((reinterpret_cast<uintptr_t>(stats) & 7) != 0) return fail(SAE_ERR_INVALID, "the stats block must be 8-byte aligned");
+  USE_DEVICE(c);
+  if (int rc = stats_ensure(c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  const StatsOut o = stats_out(stats, c->n);
+  int rc;
+  if (c->topk) {
+    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the statistics of the selection
+    rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false);
+    if (rc) return rc;
+    const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
+    const unsigned short* vals = (const unsigned short*)c->top_vals;
+    hipLaunchKernelGGL(stats_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
+                       c->top_idx, vals, c->k, M, Trows, lengths, c->n, stats_slab(c));
+    stats_launch_l0(L0Topk{vals, c->k}, M, Trows, lengths, c->n, o, s);
+    stats_launch_fold(c, nrb, o, s);
+    HIP_TRY(hipGetLastError());
+  } else {
+    const bool unfused = (flags & SAE_STATS_UNFUSED) != 0;
+    switch (x_dtype) {
+      case SAE_DTYPE_F32: rc = stats_l1_impl<float>(c, (const float*)x, M, Trows, lengths, o, unfused, s); break;
+      case SAE_DTYPE_F16: rc = stats_l1_impl<_Float16>(c, (const _Float16*)x, M, Trows, lengths, o, unfused, s); break;
+      default: rc = stats_l1_impl<bf16_t>(c, (const bf16_t*)x, M, Trows, lengths, o, unfused, s); break;
+    }
+    if (rc) return rc;
+  }
+  c->last_fwd_stats = true;
   return SAE_OK;
 }
 

@@ -121,6 +121,7 @@ def load() -> C.CDLL:
         "sae_search_raw_files": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp]),
         "sae_search_merge": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, dbl, dbl, vp, vp, vp]),
         "sae_search_file_values": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i64, i64, i64, vp, vp]),
+        "sae_stats_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -158,9 +159,19 @@ EXPORTED_SYMBOLS = [
     "sae_step", "sae_eval", "sae_eval_into", "sae_set_eval_precision", "sae_read_metrics", "sae_latent_colmax", "sae_debug_read", "sae_profile", "sae_profile_period", "sae_kernel_times",
     "sae_kernel_name", "sae_dominant_kernel",
     "sae_search_files", "sae_search_raw_files", "sae_search_merge", "sae_search_file_values",
+    "sae_stats_files",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
+STATS_UNFUSED = 1                                                   # include/freud_sae.h: SAE_STATS_UNFUSED
+
+
+def stats_layout(n: int) -> dict:
+    """Byte offsets of the sae_stats_files block for n latents (include/freud_sae.h: SAE_STATS_*): name -> (offset, dtype, count),
+    plus "bytes": the block's size."""
+    return {"n_frames": (0, "int64", 1), "fire_count": (8, "int64", n), "act_sum": (8 + 8 * n, "float64", n),
+            "act_sq_sum": (8 + 16 * n, "float64", n), "l0_hist": (8 + 24 * n, "int64", n + 1),
+            "act_max": (16 + 32 * n, "float32", n), "bytes": 16 + 36 * n}
 
 
 def _check(rc: int) -> None:
@@ -545,6 +556,23 @@ class SaeEngine:
         x, ptr, _rows, dt = self._x_args(x)
         _check(self._lib.sae_search_files(self._ctx, C.c_void_p(ptr), B, T, dt, lp, SEARCH_UNFUSED if unfused else 0,
                                           C.c_void_p(file_keys.data_ptr()), self._stream(stream)))
+
+    # -- feature statistics (include/freud_sae.h: sae_stats_files; freud_amd/feature_stats.py) -----------------------------
+    def stats_files(self, x, stats_block, lengths=None, unfused: bool = False, stream=None) -> None:
+        """Add the statistics of x [n_files, T, d] (CUDA) to stats_block (a zero-initialised uint8 CUDA tensor of
+        stats_layout(n)["bytes"] bytes); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward
+        getters fail until the next eval() / step()."""
+        import torch
+        if x.dim() != 3:
+            raise EngineError(f"stats_files expects x as [n_files, T, d], got {tuple(x.shape)}")
+        nbytes = stats_layout(self.n)["bytes"]
+        if not (stats_block.is_cuda and stats_block.dtype == torch.uint8 and stats_block.is_contiguous() and stats_block.numel() >= nbytes):
+            raise EngineError(f"stats_block must be a contiguous uint8 CUDA tensor of >= {nbytes} bytes")
+        lp = _lengths_ptr(lengths, x.shape[0])
+        B, T = int(x.shape[0]), int(x.shape[1])
+        x, ptr, _rows, dt = self._x_args(x)
+        _check(self._lib.sae_stats_files(self._ctx, C.c_void_p(ptr), B, T, dt, lp, STATS_UNFUSED if unfused else 0,
+                                         C.c_void_p(stats_block.data_ptr()), self._stream(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:

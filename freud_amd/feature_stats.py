@@ -1,0 +1,171 @@
+"""Feature statistics: how sparse a trained dictionary is on real data, and which latents are dead, rare or dense -- in one pass over
+the Whisper-activation shards, without collecting the SAE activations (the reference's route: collect_activations.py with
+sae_model, a dense fp32 [1500, n] row per file, then a reduction in torch).
+
+Semantics (include/freud_sae.h, sae_stats_files).  Over the files of a shard directory, the first min(L[f], T) frames of file f
+count when `lengths` is given (feature_search.check_lengths rules), all T frames otherwise.  Per frame and latent j, a_j is exactly
+the value freud_amd.models encode() returns: the bf16 L1 latent of the training kernels, or for TopK the scatter of top_acts at
+top_indices (0 elsewhere).  a_j is active iff a_j > 0 (a bf16 -0.0 is not).  Per latent: fire_count (frames where active),
+act_sum / act_sq_sum (sums of a_j and a_j^2, float64), act_max (float32, 0 if never active); per frame the number of active
+latents, as l0_hist[i] = frames with exactly i active.  l0_hist.sum() == n_frames and sum_i i l0_hist[i] == fire_count.sum().
+Two runs over the same data give bitwise identical arrays.
+
+    python -m freud_amd.feature_stats --sae CKPT --data_path DIR --layer_name L [--lengths f.npy] [--batch_files B] --out stats.npz
+"""
+from __future__ import annotations
+
+import argparse
+import dataclasses
+import json
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .feature_search import _keep_rng, _resolve_sae, check_lengths, default_batch_files
+
+_FIELDS = ("fire_count", "act_sum", "act_sq_sum", "act_max", "l0_hist")
+
+
+@dataclasses.dataclass
+class FeatureStats:
+    """Dataset statistics of an SAE's latents (see the module docstring)."""
+    n_frames: int
+    fire_count: np.ndarray      # int64 [n]
+    act_sum: np.ndarray         # float64 [n]
+    act_sq_sum: np.ndarray      # float64 [n]
+    act_max: np.ndarray         # float32 [n]
+    l0_hist: np.ndarray         # int64 [n + 1]
+
+    @property
+    def n_latents(self) -> int:
+        return int(self.fire_count.shape[0])
+
+    def frequency(self) -> np.ndarray:
+        """Fraction of counted frames on which each latent is active (float64 [n])."""
+        return self.fire_count / max(self.n_frames, 1)
+
+    def mean_when_active(self) -> np.ndarray:
+        """Mean of a_j over the frames where latent j is active; NaN where it never is."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.fire_count > 0, self.act_sum / self.fire_count, np.nan)
+
+    def dead(self) -> np.ndarray:
+        """Latents never active on the data (bool [n])."""
+        return self.fire_count == 0
+
+    def l0_mean(self) -> float:
+        """Mean number of active latents per frame."""
+        if self.n_frames == 0:
+            return float("nan")
+        return float((np.arange(self.l0_hist.shape[0], dtype=np.float64) * self.l0_hist).sum() / self.n_frames)
+
+    def density_histogram(self, bins=50):
+        """The feature-density histogram: np.histogram of log10(frequency) over the latents that are active at least once ->
+        (counts, edges, n_dead); dead latents (log10 0 = -inf) are counted apart."""
+        f = self.frequency()
+        alive = self.fire_count > 0
+        counts, edges = np.histogram(np.log10(f[alive]), bins=bins)
+        return counts, edges, int((~alive).sum())
+
+    def summary(self) -> dict:
+        return {"n_frames": int(self.n_frames), "n_latents": self.n_latents, "l0_mean": self.l0_mean(),
+                "dead": int(self.dead().sum()), "dense_over_10pct": int((self.frequency() > 0.1).sum())}
+
+    def to_npz(self, path: str) -> None:
+        np.savez(path, n_frames=np.int64(self.n_frames), **{k: getattr(self, k) for k in _FIELDS})
+
+    @classmethod
+    def from_npz(cls, path: str) -> "FeatureStats":
+        z = np.load(path)
+        return cls(int(z["n_frames"]), *(z[k] for k in _FIELDS))
+
+    @classmethod
+    def from_block(cls, block: np.ndarray, n: int) -> "FeatureStats":
+        """The arrays of an sae_stats_files block (uint8 bytes, engine.stats_layout)."""
+        from .engine import stats_layout
+        lay = stats_layout(n)
+        b = np.ascontiguousarray(block).view(np.uint8)
+
+        def get(name):
+            off, dt, cnt = lay[name]
+            return np.frombuffer(b, dtype=dt, count=cnt, offset=off).copy()
+        return cls(int(get("n_frames")[0]), get("fire_count"), get("act_sum"), get("act_sq_sum"), get("act_max"), get("l0_hist"))
+
+
+@_keep_rng
+def feature_stats(sae, data_path: str, layer_name: str, *, lengths=None, subset_size: Optional[int] = None,
+                  batch_files: Optional[int] = None, unfused: bool = False) -> FeatureStats:
+    """Statistics of every latent of `sae` (a checkpoint path, a freud_amd.models SAE or a SaeEngine; bf16 contexts) over the files
+    of a shard directory, in one pass.  batch_files: files per engine call (default: feature_search.default_batch_files, which
+    picks the fused L1 path where it can); unfused: force the stored-latent L1 path (tests, benchmarks)."""
+    from . import engine as E
+    from .loader import MemoryMappedActivationDataLoader, MemoryMappedActivationsDataset
+
+    if batch_files is not None and int(batch_files) < 1:
+        raise ValueError(f"batch_files={batch_files} must be >= 1")
+    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+        raise ValueError("feature statistics need an SAE (raw-activation statistics are not provided)")
+    ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
+    n_total = len(ds)
+    if n_total == 0:
+        raise ValueError(f"{data_path}: no files")
+    T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
+    lens = check_lengths(lengths, n_total, T)
+    model, eng = _resolve_sae(sae)
+    sae_d = eng.d if eng is not None else model.activation_size
+    if sae_d != d:
+        raise ValueError(f"the SAE expects d_model={sae_d}, the shards hold d={d}")
+    if eng is not None and eng.precision != "bf16":
+        raise ValueError("the feature statistics run in bf16 contexts only")
+    if not torch.cuda.is_available():
+        raise RuntimeError("the feature statistics run on the GPU (HIP engine); there is no CPU path")
+    n = eng.n if eng is not None else model.n_dict_components
+    B = int(batch_files) if batch_files is not None else default_batch_files(T, n, n_total)
+    B = min(B, n_total)
+    if eng is None:
+        eng = model._ensure(-(-B * T // 256) * 256)     # (row room for an even number of 128-row blocks: the fused epilogue's GEMM)
+        dev = model.device
+    else:
+        dev = torch.device("cuda", eng.device_id)
+        if B * T > eng.max_rows:
+            B = max(1, eng.max_rows // T)
+            if B * T > eng.max_rows:
+                raise ValueError(f"one file of {T} rows exceeds the engine's max_rows={eng.max_rows}")
+
+    with torch.cuda.device(dev):
+        block = torch.zeros(E.stats_layout(n)["bytes"], dtype=torch.uint8, device=dev)
+        lens_dev = torch.from_numpy(lens).to(dev) if lens is not None else None
+        # (native delivery, no shuffle: the statistics see what encode() of the shard rows sees)
+        loader = MemoryMappedActivationDataLoader(data_path, layer_name, B, subset_size=subset_size,
+                                                  dl_kwargs={"shuffle": False, "drop_last": False}, device=dev,
+                                                  deliver_dtype="native")
+        file0 = 0
+        for x, _names in loader:
+            nb = int(x.shape[0])
+            lb = lens_dev[file0:file0 + nb] if lens_dev is not None else None
+            eng.stats_files(x, block, lb, unfused=unfused)
+            file0 += nb
+        if file0 != n_total:
+            raise RuntimeError(f"the loader delivered {file0} of {n_total} files")
+        host = block.cpu().numpy()                  # the one read-back
+    return FeatureStats.from_block(host, n)
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser(description="Per-latent firing rates and the L0 histogram of an SAE over a shard directory.")
+    ap.add_argument("--sae", required=True, help="checkpoint path")
+    ap.add_argument("--data_path", required=True)
+    ap.add_argument("--layer_name", required=True)
+    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
+    ap.add_argument("--batch_files", type=int, default=None)
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args(argv)
+    lengths = np.load(a.lengths) if a.lengths else None
+    st = feature_stats(a.sae, a.data_path, a.layer_name, lengths=lengths, batch_files=a.batch_files)
+    st.to_npz(a.out)
+    print(json.dumps({"out": a.out, **st.summary()}))
+
+
+if __name__ == "__main__":
+    main()

@@ -355,6 +355,49 @@ int sae_search_merge(const uint64_t* file_keys_dev, const uint64_t* aux_dev, int
 int sae_search_file_values(const uint64_t* file_keys_dev, const uint64_t* aux_dev, int64_t n_files, int64_t ncols, int flags,
                            const int32_t* latents_dev, int64_t n_latents, int64_t file0, int64_t out_stride, float* out_dev, void* stream);
 
+/* ---- Feature statistics: how sparse the dictionary is on real data, in one pass over the data.  The SAE activations are never
+ * collected or written.
+ *
+ * Semantics.  Files are the rows [f T, f T + T) of a batch (row-major [n_files][T][d]).  With lengths_dev (int32 [n_files]) only
+ * the first min(length, T) frames of file f count (a length below 1 is treated as 1; the Python layer rejects it).  Without it
+ * all T frames count.  Per frame and latent j, the latent a_j is exactly the value freud_amd.models encode() returns:
+ *   L1:   the bf16 latent c = relu(x W + b) of the training kernels (the value sae_eval leaves in sae_latent_buffer);
+ *   TopK: the scatter of the top-k selection (top_acts at top_indices), 0 elsewhere; a multi_topk context uses its k selection.
+ * a_j is ACTIVE iff a_j > 0; a bf16 -0.0 is not active (the magnitude bits are compared).
+ *
+ * Output: a caller-owned device block of SAE_STATS_BYTES(n) bytes (8-byte aligned; n = n_dict) that holds running totals.  Zero it
+ * before the first batch; every call adds one batch.  Byte offsets:
+ *   SAE_STATS_N_FRAMES    int64                frames counted
+ *   SAE_STATS_FIRE_COUNT  int64   [n]          frames where latent j is active
+ *   SAE_STATS_ACT_SUM     float64 [n]          sum of a_j over the counted frames
+ *   SAE_STATS_ACT_SQ_SUM  float64 [n]          sum of a_j^2
+ *   SAE_STATS_L0_HIST     int64   [n + 1]      number of frames with exactly i active latents
+ *   SAE_STATS_ACT_MAX     float32 [n]          max of a_j (0 if never active)
+ * Invariants: sum(l0_hist) == n_frames, sum_i i * l0_hist[i] == sum(fire_count).
+ *
+ * Results are deterministic: two runs over the same batches give bitwise identical blocks.  Float sums are fp32 partials per
+ * block of rows (plain stores), added in a fixed order into the fp64 totals; counts and maxima are integers. */
+#define SAE_STATS_N_FRAMES(n) ((int64_t)0)
+#define SAE_STATS_FIRE_COUNT(n) ((int64_t)8)
+#define SAE_STATS_ACT_SUM(n) ((int64_t)8 + 8 * (int64_t)(n))
+#define SAE_STATS_ACT_SQ_SUM(n) ((int64_t)8 + 16 * (int64_t)(n))
+#define SAE_STATS_L0_HIST(n) ((int64_t)8 + 24 * (int64_t)(n))
+#define SAE_STATS_ACT_MAX(n) ((int64_t)16 + 32 * (int64_t)(n))
+#define SAE_STATS_BYTES(n) ((int64_t)16 + 36 * (int64_t)(n))
+enum { SAE_STATS_UNFUSED = 1 };
+
+/* Add the statistics of one batch (x_dev [n_files][rows_per_file][d], x_dtype) to stats_dev.  L1: the encoder GEMM reduces the
+ * latent in its epilogue and never writes it; where the streaming GEMM does not apply (it needs an even number of 128-row blocks,
+ * so a max_rows with room for round_up(n_files * rows_per_file, 256) rows), or with flags = SAE_STATS_UNFUSED, the latent is
+ * stored and reduced by separate kernels.  TopK: the eval forward, then the statistics of its selection.  n_files * rows_per_file
+ * <= max_rows; fp8 contexts: SAE_ERR_INVALID.  Shape and argument checks fail before anything is enqueued.  Asynchronous on
+ * `stream`; the first call allocates the context's scratch (about 16 bytes per 128 rows and latent, plus one byte per row and 64
+ * latents for L1).  Training state (parameters, moments, num_frames_since_fired) is untouched; afterwards sae_latent_buffer,
+ * sae_topk_indices, sae_decode, sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the
+ * next sae_eval / step. */
+int sae_stats_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                    int flags, void* stats_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
