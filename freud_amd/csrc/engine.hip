@@ -82,6 +82,23 @@ static int ensure_lds_attr(const void* fn, int bytes, int device) {
     if (rc_) return rc_;                                                      \
   } while (0)
 
+// workgroups of `per` items that cover n items, at most `cap` of them (the kernels behind it stride over the rest)
+static int grid_for(int64_t n, int cap, int per = 256) {
+  const int64_t g = (n + per - 1) / per;
+  return (int)(g < cap ? g : cap);
+}
+
+// the one dispatch on an activation dtype of include/freud_sae.h: f(typed pointer) -> status
+template <class F>
+static int with_x_type(int x_dtype, const void* x, F&& f) {
+  switch (x_dtype) {
+    case SAE_DTYPE_F32: return f((const float*)x);
+    case SAE_DTYPE_F16: return f((const _Float16*)x);
+    case SAE_DTYPE_BF16: return f((const bf16_t*)x);
+    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // kernel ids for profiling
 // ------------------------------------------------------------------------------------------
@@ -120,6 +137,10 @@ struct EvRing {
   hipEvent_t beg[EV_RING], end[EV_RING];
   int n = 0;  // recorded since last read
 };
+
+// What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
+// per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS };
 
 struct sae_ctx {
   sae_config cfg;
@@ -271,9 +292,7 @@ struct sae_ctx {
   bool stats_inline = true;     // fused d = 384 L1 path with the peer exchange: statistics pushed inside finalize_losses_kernel (see inline_stats)
   bool no_stream = false;       // this context's K = d GEMMs stay on the tile form (FREUD_GEMM_STREAM=0 / debug_flags 86 at ITS creation)
   int eval_prec = 0;            // 0 = the training kernels' arithmetic (bf16 operands, fp32 accumulate), 1 = fp32 end to end
-  bool last_fwd_e32 = false;    // the last forward was an fp32 evaluation: its per-feature maxima live in e32_colmax
-  bool last_fwd_search = false; // the last call was a feature search (sae_search_files): it leaves no latent rows / metrics to read
-  bool last_fwd_stats = false;  // the last call was a statistics pass (sae_stats_files): the same
+  LastCall last_call = LAST_FWD_BF16;   // what the last forward-like call left behind (no_forward_left, the getters)
   void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
@@ -307,6 +326,15 @@ static int use_device(const sae_ctx* c) {
     int rc_ = use_device(c);   \
     if (rc_) return rc_;       \
   } while (0)
+
+// the getters of the last forward refuse after a file pass (after_search = false: after a statistics pass only)
+static int no_forward_left(const sae_ctx* c, bool after_search = true) {
+  if (c->last_call == LAST_SEARCH && after_search)
+    return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_STATS)
+    return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  return SAE_OK;
+}
 
 static int dominant_kid(const sae_ctx* c) { return c->topk ? KID_TK_ENC : (c->use_fused_bwd ? KID_BWD_FUSED : KID_DW); }
 // Level 1 brackets the dominant kernel and the whole step on every PROF_PERIOD-th step only: an event record is a packet of
@@ -828,9 +856,7 @@ static void settle_weights(sae_ctx* c, hipStream_t s) {
   if (!c->wn_pending) return;
   if (c->wn_fwd_seen) {
     const int64_t n4 = c->nW / 4;
-    int grid = (int)((n4 + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(normalize_inplace_kernel, dim3(grid), dim3(256), 0, s, c->P, c->cnorm, n4, c->n_p);
+    hipLaunchKernelGGL(normalize_inplace_kernel, dim3(grid_for(n4, 2048)), dim3(256), 0, s, c->P, c->cnorm, n4, c->n_p);
   }
   c->wn_pending = c->wn_fwd_seen = false;
   c->cn_valid = false;
@@ -1139,12 +1165,7 @@ static int batch_stats_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
 }
 
 static int batch_stats_dispatch(sae_ctx* c, const void* x, int64_t M, int x_dtype, hipStream_t s) {
-  switch (x_dtype) {
-    case SAE_DTYPE_F32: return batch_stats_impl<float>(c, (const float*)x, M, s);
-    case SAE_DTYPE_F16: return batch_stats_impl<_Float16>(c, (const _Float16*)x, M, s);
-    case SAE_DTYPE_BF16: return batch_stats_impl<bf16_t>(c, (const bf16_t*)x, M, s);
-    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  }
+  return with_x_type(x_dtype, x, [&](auto* xt) { return batch_stats_impl(c, xt, M, s); });
 }
 
 extern "C" int sae_batch_stats(sae_ctx* c, const void* x, int64_t M, int x_dtype, void* stream) {
@@ -1544,19 +1565,24 @@ static bool gemm_streams(const GemmArgs& g) {
          (g.nbm / 2) * (g.nbn / 2) >= 4 * G2_PERSIST_STATIC;
 }
 
+// the streaming form itself, for a GEMM that gemm_streams() accepted (the file passes launch it with epilogues that have only the
+// streaming interface, so they cannot go through launch_gemm, whose tile-form branches would be instantiated with them)
+template <class Epi>
+static int launch_gemm_stream(const GemmArgs& g, const Epi& epi, hipStream_t s) {
+  auto kerns = gemm256s_bf16_kernel<Epi>;
+  LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
+  GemmArgs g2 = g;
+  g2.nbm = g.nbm / 2;
+  g2.nbn = g.nbn / 2;
+  hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, epi);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
 template <int AM, int BM_, class Epi>
 static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   if constexpr (G2_STREAM && epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW) {
-    if (gemm_streams<AM, BM_, Epi>(g)) {
-      auto kerns = gemm256s_bf16_kernel<Epi>;
-      LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
-      GemmArgs g2 = g;
-      g2.nbm = g.nbm / 2;
-      g2.nbn = g.nbn / 2;
-      hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, epi);
-      HIP_TRY(hipGetLastError());
-      return SAE_OK;
-    }
+    if (gemm_streams<AM, BM_, Epi>(g)) return launch_gemm_stream(g, epi, s);
   }
   if (!g_force_gemm128 && g.nbm % 2 == 0 && g.nbn % 2 == 0) {   // both output dimensions are multiples of 256
     auto kern256 = gemm256_bf16_kernel<AM, BM_, Epi>;
@@ -1640,6 +1666,43 @@ static void prep_weights_l1(sae_ctx* c, hipStream_t s) {
   }
 }
 
+// The L1 encoder's front, shared by the training forward and the file passes (search_l1_impl, stats_l1_impl).
+// x -> xb: the padded bf16 copy [Mp][d_p], counting the masked entries into c->masked; returns the number of count partials
+template <typename T>
+static int launch_prep_x(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s) {
+  const int d = c->d, d_p = c->d_p;
+  const int grid = grid_for(Mp * (d_p / 8), 2048);
+  if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+    hipLaunchKernelGGL((prep_x_kernel<T, true>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+  else
+    hipLaunchKernelGGL((prep_x_kernel<T, false>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+  return grid;
+}
+
+// x W: xb [Mp][d_p] times Wt [n_p][d_p]
+static GemmArgs enc_gemm_args(const sae_ctx* c, const bf16_t* xb, int64_t Mp) {
+  GemmArgs g{};
+  g.A0 = xb; g.B0 = c->Wt; g.lda = c->d_p; g.ldb = c->d_p;
+  g.nbm = (int)(Mp / 128); g.nbn = c->n_p / 128; g.ktiles0 = g.ktiles = c->d_p / 64; g.splits = 1;
+  return g;
+}
+
+// c = relu(x W + b), stored: the ordinary encoder.  (T, the caller's activation type, is not used: as a template with a deduced
+// return type the helper is instantiated inside its first caller, forward_impl<float>, so the encoder's GEMM kernels keep their
+// place in the code object and two builds stay comparable byte for byte)
+template <typename T>
+static auto launch_encoder(sae_ctx* c, const GemmArgs& g, int64_t M, hipStream_t s) {
+  EpiEnc e{};
+  e.c = c->c; e.bias = c->P + c->nW; e.l1_part = c->l1_part; e.M = M; e.n_p = c->n_p; e.nbn = g.nbn;
+  // (streaming form: one L1 partial per WORKGROUP in l1_part[0 .. grid); finalize_losses sums the whole per-tile range, so the
+  // rest of it is zeroed -- 4 bytes per 128x128 tile)
+  if (gemm_streams<OP_ROW, OP_ROW, EpiEnc>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)g.nbm * g.nbn * 4, s));
+  ev_begin(c, KID_ENC_FWD, s);
+  const int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+  ev_end(c, KID_ENC_FWD, s);
+  return rc;
+}
+
 template <typename T> static constexpr bool x_dtype_is_bf16() { return false; }
 template <> constexpr bool x_dtype_is_bf16<bf16_t>() { return true; }
 
@@ -1662,13 +1725,7 @@ static int forward_impl(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream
                        (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   c->xb_cur = alias_x ? reinterpret_cast<const bf16_t*>(x) : c->xb;
   if (!alias_x) {
-    const int64_t chunks = Mp * (d_p / 8);
-    int grid = (int)((chunks + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
-      hipLaunchKernelGGL((prep_x_kernel<T, true>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
-    else
-      hipLaunchKernelGGL((prep_x_kernel<T, false>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
+    const int grid = launch_prep_x(c, x, M, Mp, s);
     if (!c->use_fused_fwd) {
       const double* gs = (need_backward && c->dp_world > 0) ? c->stats : nullptr;
       if (gs && c->dist) HIP_TRY(hipStreamWaitEvent(s, c->ev_stats, 0));     // the summed statistics have arrived
@@ -1680,9 +1737,7 @@ static int forward_impl(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream
     hipLaunchKernelGGL(fp8_x_stats_kernel, dim3(sgrid), dim3(256), 0, s, c->xb, Mp, d_p, c->x8_part);
     hipLaunchKernelGGL(fp8_scales_kernel, dim3(1), dim3(256), 0, s, c->x8_part, sgrid, b, c->n, c->scal8);
     const int64_t n8 = Mp * (d_p / 8);
-    int qgrid = (int)((n8 + 255) / 256);
-    if (qgrid > 2048) qgrid = 2048;
-    hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(qgrid), dim3(256), 0, s, c->xb, c->x8, n8, c->scal8);
+    hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->xb, c->x8, n8, c->scal8);
   }
   ev_end(c, KID_PREP_X, s);
 
@@ -1759,20 +1814,8 @@ static int forward_impl(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream
     }
     return SAE_OK;
   }
-  {  // c = relu(x W + b)
-    GemmArgs g{};
-    g.A0 = c->xb_cur; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
-    g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
-    EpiEnc e{};
-    e.c = c->c; e.bias = b; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = g.nbn;
-    // (streaming form: one L1 partial per WORKGROUP in l1_part[0 .. grid); finalize_losses sums the whole per-tile range, so the
-    // rest of it is zeroed -- 4 bytes per 128x128 tile)
-    if (gemm_streams<OP_ROW, OP_ROW, EpiEnc>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)g.nbm * g.nbn * 4, s));
-    ev_begin(c, KID_ENC_FWD, s);
-    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-    ev_end(c, KID_ENC_FWD, s);
-    if (rc) return rc;
-  }
+  rc = launch_encoder<T>(c, enc_gemm_args(c, c->xb_cur, Mp), M, s);       // c = relu(x W + b)
+  if (rc) return rc;
   {  // x_hat = c W^T, residual, dx_hat
     GemmArgs g{};
     g.A0 = c->c; g.B0 = c->Wb; g.lda = n_p; g.ldb = n_p;
@@ -1872,9 +1915,7 @@ static int fwd_bwd_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool b
         hipLaunchKernelGGL(fp8_x_stats_kernel, dim3(sgrid), dim3(256), 0, s, c->dxh, Mp, d_p, c->x8_part);
         hipLaunchKernelGGL(fp8_g_scale_kernel, dim3(1), dim3(256), 0, s, c->x8_part, sgrid, c->scal8);
         const int64_t n8 = Mp * (d_p / 8);
-        int qgrid = (int)((n8 + 255) / 256);
-        if (qgrid > 2048) qgrid = 2048;
-        hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(qgrid), dim3(256), 0, s, c->dxh, c->dxh8, n8, c->scal8, (int)S8_SG);
+        hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->dxh, c->dxh8, n8, c->scal8, (int)S8_SG);
         Gemm8Args g{};
         g.A = c->dxh8; g.B = c->W8t; g.lda = d_p; g.ldb = d_p;
         g.nbm = (int)(Mp / 256); g.nbn = n_p / 256; g.ktiles = d_p / 128;
@@ -2032,8 +2073,7 @@ static int fwd_bwd_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool b
       c->gn_valid = true;
     } else if (c->use_fused_bwd) {   // one pass: slabs + db partials -> grads, plus the local gradient sum of squares
       const int64_t nW4 = c->nW / 4, n4 = c->nparams / 4;
-      int blocks = (int)((n4 + 255) / 256);
-      if (blocks > 1024) blocks = 1024;
+      const int blocks = grid_for(n4, 1024);
       LossFinalize fin{};
       if (fold_finalize) {
         fin.l1_part = c->l1_part; fin.sq_part = c->sq_part; fin.cnt_part = c->cnt_part; fin.n_parts = (int)(Mp / 128);
@@ -2130,16 +2170,13 @@ static int topk_fwd_bwd(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool b
 
   {
     const int64_t n8 = c->nW / 8;
-    int grid = (int)((n8 + 255) / 256);
-    if (grid > 4096) grid = 4096;
+    const int grid = grid_for(n8, 4096);
     if (!c->wb_valid) {        // (a training step's optimizer already wrote the bf16 copies of the weights it updated)
       hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, s, We, c->We_b, n8);
       hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, s, Wd, c->Wd_b, n8);
     }
     if (auxc) hipLaunchKernelGGL(aux_gather_rows_kernel, dim3(n_p / 4), dim3(256), 0, s, c->Wd_b, c->dead_cols, c->tkd, c->Wdd_b, d_p);
-    const int64_t chunks = Mp * (d_p / 8);
-    int g2 = (int)((chunks + 255) / 256);
-    if (g2 > 4096) g2 = 4096;
+    const int g2 = grid_for(Mp * (d_p / 8), 4096);
     if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
       hipLaunchKernelGGL((topk_prep_x_kernel<T, true>), dim3(g2), dim3(256), 0, s, x, bd, c->xs, M, d, Mp, d_p);
     else
@@ -2536,23 +2573,9 @@ static int dispatch_fwd_bwd(sae_ctx* c, const void* x, int64_t M, int x_dtype, v
 
 static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dtype, hipStream_t s, bool backward) {
   c->last_dtype = x_dtype;
-  c->last_fwd_e32 = false;
-  c->last_fwd_search = false;
-  c->last_fwd_stats = false;
-  if (c->topk) {
-    switch (x_dtype) {
-      case SAE_DTYPE_F32: return topk_fwd_bwd<float>(c, (const float*)x, M, s, backward);
-      case SAE_DTYPE_F16: return topk_fwd_bwd<_Float16>(c, (const _Float16*)x, M, s, backward);
-      case SAE_DTYPE_BF16: return topk_fwd_bwd<bf16_t>(c, (const bf16_t*)x, M, s, backward);
-      default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-    }
-  }
-  switch (x_dtype) {
-    case SAE_DTYPE_F32: return fwd_bwd_impl<float>(c, (const float*)x, M, s, backward);
-    case SAE_DTYPE_F16: return fwd_bwd_impl<_Float16>(c, (const _Float16*)x, M, s, backward);
-    case SAE_DTYPE_BF16: return fwd_bwd_impl<bf16_t>(c, (const bf16_t*)x, M, s, backward);
-    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  }
+  c->last_call = LAST_FWD_BF16;
+  if (c->topk) return with_x_type(x_dtype, x, [&](auto* xt) { return topk_fwd_bwd(c, xt, M, s, backward); });
+  return with_x_type(x_dtype, x, [&](auto* xt) { return fwd_bwd_impl(c, xt, M, s, backward); });
 }
 
 // ---- fp32 evaluation forward (eval_fp32.h): validate() of the reference on device='cpu' runs without autocast
@@ -2587,8 +2610,7 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   if (rc) return rc;
   // partial-sum layout of e32_part (doubles): [0, E32_L1_PARTS) latent sums | 4 x E32_RES_BLOCKS residual sums | ... multi-TopK residual | total variance
   double *l1_part = c->e32_part, *res_part = c->e32_part + E32_L1_PARTS, *res2_part = res_part + 4 * E32_RES_BLOCKS, *tv_part = res2_part + 4 * E32_RES_BLOCKS;
-  int grid_x = (int)((M * d_p + 255) / 256);
-  if (grid_x > 2048) grid_x = 2048;
+  const int grid_x = grid_for(M * d_p, 2048);
   HIP_TRY(hipMemsetAsync(c->e32_colmax, 0, (size_t)n_p * 4, s));
   E32Final f{};
   f.M = M; f.d = d; f.alpha = (float)c->cfg.recon_alpha; f.topk = c->topk ? 1 : 0;
@@ -2633,9 +2655,7 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   HIP_TRY(hipGetLastError());
   c->last_M = M;
   c->last_M_p = round_up(M, c->row_pad);
-  c->last_fwd_e32 = true;
-  c->last_fwd_search = false;
-  c->last_fwd_stats = false;
+  c->last_call = LAST_FWD_E32;
   c->metrics_fresh = false;
   return SAE_OK;
 }
@@ -2646,12 +2666,7 @@ static int eval_fp32_dispatch(sae_ctx* c, const void* x, int64_t M, int x_dtype,
   USE_DEVICE(c);
   hipStream_t s = (hipStream_t)stream;
   c->last_dtype = x_dtype;
-  switch (x_dtype) {
-    case SAE_DTYPE_F32: return eval_fp32_impl<float>(c, (const float*)x, M, s);
-    case SAE_DTYPE_F16: return eval_fp32_impl<_Float16>(c, (const _Float16*)x, M, s);
-    case SAE_DTYPE_BF16: return eval_fp32_impl<bf16_t>(c, (const bf16_t*)x, M, s);
-    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  }
+  return with_x_type(x_dtype, x, [&](auto* xt) { return eval_fp32_impl(c, xt, M, s); });
 }
 
 extern "C" int sae_set_eval_precision(sae_ctx* c, int precision) {
@@ -2701,8 +2716,7 @@ extern "C" int sae_optimizer_step(sae_ctx* c, double lr, double grad_scale, void
   }
   ev_begin(c, KID_OPT, s);
   const int64_t n4 = c->nparams / 4;  // nW and n_p are multiples of 128
-  int gblocks = (int)((n4 + 255) / 256);
-  if (gblocks > 1024) gblocks = 1024;
+  int gblocks = grid_for(n4, 1024);
   // the reduction kernel already left the local sum of squares; it is only valid when nothing (no all-reduce, no
   // rescaling) touched the gradient buffer in between, i.e. for the single-GPU sae_step path
   if (c->grads_in_bf16) {     // data parallel, bf16 payload: the summed gradient comes back to fp32 in the same pass
@@ -2714,8 +2728,7 @@ extern "C" int sae_optimizer_step(sae_ctx* c, double lr, double grad_scale, void
     hipLaunchKernelGGL(gnorm_partial_kernel, dim3(gblocks), dim3(256), 0, s, c->G, n4, a.grad_scale, c->gn_part);
   }
   c->gn_valid = false;
-  int oblocks = (int)((n4 + 255) / 256);
-  if (oblocks > 2048) oblocks = 2048;
+  const int oblocks = grid_for(n4, 2048);
   if (!c->topk && !c->fp8 && c->d_p <= 384 && c->cfg.debug_flags != 79 && c->cfg.debug_flags != 80) {
     // L1, small d: the update that also prepares the next forward's weights (column norms, bf16 copies)
     const int norm_on_load = (c->wn_pending && c->wn_fwd_seen) ? 1 : 0;
@@ -2773,8 +2786,7 @@ extern "C" int sae_step(sae_ctx* c, const void* x, int64_t M, int x_dtype, doubl
 
 extern "C" int sae_read_metrics(sae_ctx* c, float out[SAE_NUM_METRICS], void* stream) {
   if (!c || !out) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
-  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  if (int rc = no_forward_left(c)) return rc;
   USE_DEVICE(c);
   HIP_TRY(hipMemcpyAsync(out, c->G + c->nparams, SAE_NUM_METRICS * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
@@ -2905,11 +2917,10 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
 
 extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride) {
   if (!c || !dev_ptr || !row_stride) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
-  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  if (int rc = no_forward_left(c)) return rc;
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
-  if (c->last_fwd_e32) return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows");
+  if (c->last_call == LAST_FWD_E32) return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows");
   {
     int rc_d = ensure_dense(c);
     if (rc_d) return rc_d;
@@ -2921,8 +2932,7 @@ extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride
 
 extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
   if (!c || !dev_ptr || !k) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
-  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  if (int rc = no_forward_left(c)) return rc;
   if (!c->topk) return fail(SAE_ERR_INVALID, "sae_topk_indices: not a TopK context");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   *dev_ptr = c->top_idx;
@@ -2932,8 +2942,7 @@ extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
 
 extern "C" int sae_multi_topk_buffers(sae_ctx* c, void** dense_dev, int64_t* row_stride, void** idx_dev, int* k4) {
   if (!c || !dense_dev || !row_stride || !idx_dev || !k4) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
-  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  if (int rc = no_forward_left(c)) return rc;
   if (!c->topk || !c->multi) return fail(SAE_ERR_INVALID, "sae_multi_topk_buffers: not a TopK context with multi_topk");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   if (!c->multi_dense_valid) {      // a training step on the sparse backward keeps the 4k selection compact: densify on demand
@@ -2957,15 +2966,14 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
   if (M <= 0 || M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "M=%lld outside (0, max_rows=%lld]", (long long)M, (long long)c->cfg.max_rows);
   if (ld < c->n) return fail(SAE_ERR_INVALID, "row stride %lld < n_dict %d", (long long)ld, c->n);
   if (latent_dtype != SAE_DTYPE_F32 && latent_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "latent dtype must be f32 or bf16");
-  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  // (asymmetry kept as it is: sae_decode refuses after a statistics pass but not after a feature search; the other getters refuse after both)
+  if (int rc = no_forward_left(c, /*after_search=*/false)) return rc;
   USE_DEVICE(c);
   hipStream_t s = (hipStream_t)stream;
   const int d_p = c->d_p, n_p = c->n_p;
   const int64_t Mp = round_up(M, c->row_pad);
   bf16_t* lat = c->dpre;                       // [M_p][n_p] scratch that no forward output lives in
-  const int64_t total = Mp * (int64_t)n_p;
-  int grid = (int)((total + 255) / 256);
-  if (grid > 4096) grid = 4096;
+  const int grid = grid_for(Mp * (int64_t)n_p, 4096);
   if (latent_dtype == SAE_DTYPE_F32)
     hipLaunchKernelGGL(pad_latent_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)latent, ld, M, c->n, lat, Mp, n_p);
   else
@@ -2976,12 +2984,11 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
   EpiStoreF32 e{};
   e.out = x_hat; e.M = M; e.d = c->d;
   int rc;
+  const int64_t n8 = c->nW / 8;
+  const int cg = grid_for(n8, 2048);
   if (c->topk) {
     // W_dec [n_p][d_p] fp32 -> bf16 (K = n is the slow dimension of this operand: transposed-read mode)
     float* Wd = c->P + c->nW + c->n_p;
-    const int64_t n8 = c->nW / 8;
-    int cg = (int)((n8 + 255) / 256);
-    if (cg > 2048) cg = 2048;
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(cg), dim3(256), 0, s, Wd, c->Wd_b, n8);
     g.B0 = c->Wd_b; g.ldb = d_p;
     e.bias = c->P + 2 * c->nW + c->n_p;
@@ -2989,9 +2996,6 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
   } else {
     // current W [d_p][n_p] as is (decode() does not renormalise); the copy is refreshed by the next forward anyway
     settle_weights(c, s);
-    const int64_t n8 = c->nW / 8;
-    int cg = (int)((n8 + 255) / 256);
-    if (cg > 2048) cg = 2048;
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(cg), dim3(256), 0, s, c->P, c->Wb, n8);
     g.B0 = c->Wb; g.ldb = n_p;
     e.bias = nullptr;
@@ -3004,12 +3008,11 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
 
 extern "C" int sae_latent_colmax(sae_ctx* c, float* out_host, int64_t capacity, void* stream) {
   if (!c || !out_host) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->last_fwd_search) return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
-  if (c->last_fwd_stats) return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  if (int rc = no_forward_left(c)) return rc;
   if (capacity < c->n) return fail(SAE_ERR_INVALID, "capacity too small");
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
-  if (c->last_fwd_e32) {
+  if (c->last_call == LAST_FWD_E32) {
     HIP_TRY(hipMemcpyAsync(out_host, c->e32_colmax, (size_t)c->n * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return SAE_OK;
@@ -3043,7 +3046,7 @@ extern "C" int sae_eval_into(sae_ctx* c, const void* x, int64_t M, int x_dtype, 
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipMemcpyAsync(metrics_out, c->G + c->nparams, SAE_NUM_METRICS * 4, hipMemcpyDeviceToDevice, s));
-  if (colmax_out && c->last_fwd_e32) {      // the fp32 forward left the per-feature maxima (bit patterns of non-negative floats)
+  if (colmax_out && c->last_call == LAST_FWD_E32) {      // the fp32 forward left the per-feature maxima (bit patterns of non-negative floats)
     HIP_TRY(hipMemcpyAsync(colmax_out, c->e32_colmax, (size_t)c->n * 4, hipMemcpyDeviceToDevice, s));
     return SAE_OK;
   }
@@ -3069,71 +3072,28 @@ static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int n
   const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)n_files, (unsigned)((Trows + chunk - 1) / chunk));
   const int64_t pairs = n_files * ncols;
   const unsigned fgrid = (unsigned)((pairs + 255) / 256);
-#define SEARCH_RAW(T)                                                                                                              \
-  if (absolute) {                                                                                                                 \
-    hipLaunchKernelGGL((search_colreduce_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, ld, ncols, Trows, lengths, chunk, keys, aux); \
-    hipLaunchKernelGGL(search_abs_fixup_kernel<T>, dim3(fgrid), dim3(256), 0, s, (const T*)x, ld, ncols, Trows, n_files, keys, aux); \
-  } else {                                                                                                                        \
-    hipLaunchKernelGGL((search_colreduce_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, ld, ncols, Trows, lengths, chunk, keys, nullptr); \
-  }
-  switch (x_dtype) {
-    case SAE_DTYPE_F32: SEARCH_RAW(float) break;
-    case SAE_DTYPE_F16: SEARCH_RAW(_Float16) break;
-    case SAE_DTYPE_BF16: SEARCH_RAW(bf16_t) break;
-    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  }
-#undef SEARCH_RAW
+  int rc = with_x_type(x_dtype, x, [&](auto* xt) {
+    using T = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+    if (absolute) {
+      hipLaunchKernelGGL((search_colreduce_kernel<T, true>), grid, dim3(256), 0, s, xt, ld, ncols, Trows, lengths, chunk, keys, aux);
+      hipLaunchKernelGGL(search_abs_fixup_kernel<T>, dim3(fgrid), dim3(256), 0, s, xt, ld, ncols, Trows, n_files, keys, aux);
+    } else {
+      hipLaunchKernelGGL((search_colreduce_kernel<T, false>), grid, dim3(256), 0, s, xt, ld, ncols, Trows, lengths, chunk, keys, nullptr);
+    }
+    return (int)SAE_OK;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }
 
-// L1: the encoder GEMM of forward_impl (same weights preparation, same bf16 copy of x, same operands) with EpiSearch instead of
-// EpiEnc.  Where the streaming GEMM does not apply (small or odd shapes, FREUD_GEMM_STREAM=0, force_gemm128) or `unfused` is asked
-// for (the baseline of tools/bench_search.py), the latent is stored by the ordinary encoder and reduced by the column kernel.
-template <typename T>
-static int search_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, int64_t n_files, const int* lengths, uint64_t* keys, bool unfused,
-                          hipStream_t s) {
-  const int d = c->d, d_p = c->d_p, n_p = c->n_p;
-  float* b = c->P + c->nW;
-  int64_t Mp = round_up(M, 128);
-  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);    // (an even number of row blocks: the streaming GEMM's condition)
-  prep_weights_l1(c, s);
-  {
-    const int64_t chunks = Mp * (d_p / 8);
-    int grid = (int)((chunks + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
-      hipLaunchKernelGGL((prep_x_kernel<T, true>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
-    else
-      hipLaunchKernelGGL((prep_x_kernel<T, false>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
-  }
-  HIP_TRY(hipMemsetAsync(keys, 0, (size_t)n_files * c->n * 8, s));
-  GemmArgs g{};
-  g.A0 = c->xb; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
-  g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
-  if (!unfused && Trows <= 65535 && gemm_streams<OP_ROW, OP_ROW, EpiSearch>(g)) {
-    EpiSearch e{};
-    e.bias = b; e.keys = keys; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n;
-    auto kerns = gemm256s_bf16_kernel<EpiSearch>;
-    LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
-    GemmArgs g2 = g;
-    g2.nbm = g.nbm / 2;
-    g2.nbn = g.nbn / 2;
-    ev_begin(c, KID_ENC_FWD, s);
-    hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, e);
-    ev_end(c, KID_ENC_FWD, s);
-    HIP_TRY(hipGetLastError());
-    return SAE_OK;
-  }
-  EpiEnc e{};
-  e.c = c->c; e.bias = b; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = g.nbn;
-  if (gemm_streams<OP_ROW, OP_ROW, EpiEnc>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)g.nbm * g.nbn * 4, s));
-  ev_begin(c, KID_ENC_FWD, s);
-  int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-  ev_end(c, KID_ENC_FWD, s);
-  if (rc) return rc;
-  return search_launch_colreduce(c->c, SAE_DTYPE_BF16, n_p, c->n, Trows, n_files, lengths, false, keys, nullptr, s);
-}
+// ---- what sae_search_files and sae_stats_files share: one batch of files encoded with the training kernels
+struct FilePassKind {           // the words of an entry point's messages and the flags it knows
+  const char *fn, *fp8_advice, *flags_noun;
+  int flags_mask;
+};
+static const FilePassKind kSearchPass = {"sae_search_files", "search in a bf16 context", "search", SAE_SEARCH_UNFUSED};
+static const FilePassKind kStatsPass = {"sae_stats_files", "run the statistics in a bf16 context", "stats", SAE_STATS_UNFUSED};
 
 static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
   if (n_files <= 0 || rows_per_file <= 0) return fail(SAE_ERR_INVALID, "n_files=%lld and rows_per_file=%lld must be positive", (long long)n_files, (long long)rows_per_file);
@@ -3143,42 +3103,76 @@ static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
   return SAE_OK;
 }
 
+// the front door of both entry points: argument checks (nothing is enqueued when one fails), then the context's device
+static int file_pass_begin(const FilePassKind& kind, sae_ctx* c, const void* x, const void* out, int64_t n_files, int64_t rows_per_file,
+                           int x_dtype, int flags, int64_t* M) {
+  if (!c || !x || !out) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->fp8) return fail(SAE_ERR_INVALID, "%s: fp8 contexts are not supported (%s)", kind.fn, kind.fp8_advice);
+  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
+  *M = n_files * rows_per_file;
+  if (*M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "n_files * rows_per_file = %lld > max_rows=%lld", (long long)*M, (long long)c->cfg.max_rows);
+  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  if (flags & ~kind.flags_mask) return fail(SAE_ERR_INVALID, "unknown %s flags 0x%x", kind.flags_noun, flags);
+  USE_DEVICE(c);
+  return SAE_OK;
+}
+
+// L1: forward_impl's weights preparation and bf16 copy of x, then the GEMM arguments of its encoder -- for the epilogue the pass
+// brings (EpiSearch, EpiStats) where the GEMM streams, for launch_encoder and a reduction of the stored latent where it does not
+template <typename T>
+static GemmArgs file_pass_l1_front(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
+  int64_t Mp = round_up(M, 128);
+  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);    // (an even number of row blocks: the streaming GEMM's condition)
+  prep_weights_l1(c, s);
+  launch_prep_x(c, x, M, Mp, s);
+  return enc_gemm_args(c, c->xb, Mp);
+}
+
+// the pass's own epilogue in the streaming GEMM, inside the encoder's event bracket
+template <class Epi>
+static int file_pass_l1_fused(sae_ctx* c, const GemmArgs& g, const Epi& e, hipStream_t s) {
+  ev_begin(c, KID_ENC_FWD, s);
+  const int rc = launch_gemm_stream(g, e, s);
+  ev_end(c, KID_ENC_FWD, s);
+  return rc;
+}
+
+// L1 search: where the streaming GEMM does not apply (small or odd shapes, FREUD_GEMM_STREAM=0, force_gemm128) or `unfused` is asked
+// for (the baseline of tools/bench_search.py), the latent is stored by the ordinary encoder and reduced by the column kernel.
+template <typename T>
+static int search_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, int64_t n_files, const int* lengths, uint64_t* keys, bool unfused,
+                          hipStream_t s) {
+  const GemmArgs g = file_pass_l1_front(c, x, M, s);
+  HIP_TRY(hipMemsetAsync(keys, 0, (size_t)n_files * c->n * 8, s));
+  if (!unfused && Trows <= 65535 && gemm_streams<OP_ROW, OP_ROW, EpiSearch>(g)) {
+    EpiSearch e{};
+    e.bias = c->P + c->nW; e.keys = keys; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n;
+    return file_pass_l1_fused(c, g, e, s);
+  }
+  if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
+  return search_launch_colreduce(c->c, SAE_DTYPE_BF16, c->n_p, c->n, Trows, n_files, lengths, false, keys, nullptr, s);
+}
+
 extern "C" int sae_search_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
                                 int flags, uint64_t* file_keys, void* stream) {
-  if (!c || !x || !file_keys) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->fp8) return fail(SAE_ERR_INVALID, "sae_search_files: fp8 contexts are not supported (search in a bf16 context)");
-  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
-  const int64_t M = n_files * rows_per_file;
-  if (M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "n_files * rows_per_file = %lld > max_rows=%lld", (long long)M, (long long)c->cfg.max_rows);
-  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  if (flags & ~SAE_SEARCH_UNFUSED) return fail(SAE_ERR_INVALID, "unknown search flags 0x%x", flags);
-  USE_DEVICE(c);
+  int64_t M;
+  if (int rc = file_pass_begin(kSearchPass, c, x, file_keys, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
-  int rc;
   if (c->topk) {
     // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the selection scattered into the keys
     const int64_t nk = n_files * c->n;
-    int fg = (int)((nk + 255) / 256);
-    if (fg > 4096) fg = 4096;
-    hipLaunchKernelGGL(search_fill_kernel, dim3(fg), dim3(256), 0, s, file_keys, nk, (uint64_t)SK_KEY_ZERO_FRAME0);
-    rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false);
-    if (rc) return rc;
-    int sg = (int)((M * c->k + 255) / 256);
-    if (sg > 4096) sg = 4096;
-    hipLaunchKernelGGL(search_topk_scatter_kernel, dim3(sg), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, Trows, lengths, c->n,
-                       file_keys);
+    hipLaunchKernelGGL(search_fill_kernel, dim3(grid_for(nk, 4096)), dim3(256), 0, s, file_keys, nk, (uint64_t)SK_KEY_ZERO_FRAME0);
+    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+    hipLaunchKernelGGL(search_topk_scatter_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, Trows,
+                       lengths, c->n, file_keys);
     HIP_TRY(hipGetLastError());
   } else {
     const bool unfused = (flags & SAE_SEARCH_UNFUSED) != 0;
-    switch (x_dtype) {
-      case SAE_DTYPE_F32: rc = search_l1_impl<float>(c, (const float*)x, M, Trows, n_files, lengths, file_keys, unfused, s); break;
-      case SAE_DTYPE_F16: rc = search_l1_impl<_Float16>(c, (const _Float16*)x, M, Trows, n_files, lengths, file_keys, unfused, s); break;
-      default: rc = search_l1_impl<bf16_t>(c, (const bf16_t*)x, M, Trows, n_files, lengths, file_keys, unfused, s); break;
-    }
-    if (rc) return rc;
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return search_l1_impl(c, xt, M, Trows, n_files, lengths, file_keys, unfused, s); }))
+      return rc;
   }
-  c->last_fwd_search = true;
+  c->last_call = LAST_SEARCH;
   return SAE_OK;
 }
 
@@ -3220,16 +3214,19 @@ extern "C" int sae_search_file_values(const uint64_t* file_keys, const uint64_t*
 }
 
 // ---- feature statistics (stats.h): per-latent firing counts, sums, maxima and the L0 histogram of one batch of files
+// fs_slab: the slab [max_rows_p / STATS_RB][n] x 4 words of 4 bytes, then (L1) one L0 byte per row and 64 latents
+static int64_t stats_slab_words(const sae_ctx* c) { return (c->max_rows_p / STATS_RB) * (int64_t)c->n; }
+static uint8_t* stats_l0_bytes(const sae_ctx* c) { return (uint8_t*)c->fs_slab + stats_slab_words(c) * 16; }
+
 static int stats_ensure(sae_ctx* c) {
   if (c->fs_slab) return SAE_OK;
-  const int64_t slab_bytes = (c->max_rows_p / STATS_RB) * (int64_t)c->n * 16;
   const int64_t l0_bytes = c->topk ? 0 : c->max_rows_p * (int64_t)(c->n_p / 64);
-  HIP_TRY(hipMalloc(&c->fs_slab, (size_t)(slab_bytes + l0_bytes)));
+  HIP_TRY(hipMalloc(&c->fs_slab, (size_t)(stats_slab_words(c) * 16 + l0_bytes)));
   return SAE_OK;
 }
 
 static StatsSlab stats_slab(sae_ctx* c) {
-  const int64_t words = (c->max_rows_p / STATS_RB) * (int64_t)c->n;
+  const int64_t words = stats_slab_words(c);
   StatsSlab sl;
   sl.cnt = (uint32_t*)c->fs_slab;
   sl.mx = sl.cnt + words;
@@ -3258,9 +3255,7 @@ static StatsOut stats_out(void* block, int n) {
 
 template <class Src>
 static void stats_launch_l0(Src src, int64_t M, int T, const int* lengths, int n, const StatsOut& o, hipStream_t s) {
-  int grid = (int)((M + 3) / 4);
-  if (grid > 1024) grid = 1024;
-  hipLaunchKernelGGL(stats_l0_kernel<Src>, dim3(grid), dim3(256), 0, s, src, M, T, lengths, n + 1, o.hist, o.n_frames);
+  hipLaunchKernelGGL(stats_l0_kernel<Src>, dim3(grid_for(M, 1024, 4)), dim3(256), 0, s, src, M, T, lengths, n + 1, o.hist, o.n_frames);
 }
 
 static void stats_launch_fold(sae_ctx* c, int nrb, const StatsOut& o, hipStream_t s) {
@@ -3268,53 +3263,23 @@ static void stats_launch_fold(sae_ctx* c, int nrb, const StatsOut& o, hipStream_
                      o.amax);
 }
 
-// L1: the encoder GEMM of search_l1_impl (forward_impl's weights preparation and bf16 copy of x) with EpiStats instead of EpiSearch.
-// Where the streaming GEMM does not apply, or `unfused` is asked for, the ordinary encoder stores the latent and two kernels
-// reduce it (column statistics into the slab, row counts into the histogram).
+// L1 statistics: where the streaming GEMM does not apply, or `unfused` is asked for, the ordinary encoder stores the latent and two
+// kernels reduce it (column statistics into the slab, row counts into the histogram).
 template <typename T>
 static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, const StatsOut& o, bool unfused, hipStream_t s) {
-  const int d = c->d, d_p = c->d_p, n_p = c->n_p;
-  float* b = c->P + c->nW;
-  int64_t Mp = round_up(M, 128);
-  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);    // (an even number of row blocks: the streaming GEMM's condition)
-  prep_weights_l1(c, s);
-  {
-    const int64_t chunks = Mp * (d_p / 8);
-    int grid = (int)((chunks + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
-      hipLaunchKernelGGL((prep_x_kernel<T, true>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
-    else
-      hipLaunchKernelGGL((prep_x_kernel<T, false>), dim3(grid), dim3(256), 0, s, x, c->xb, c->masked, M, d, Mp, d_p);
-  }
+  const int n_p = c->n_p;
+  const GemmArgs g = file_pass_l1_front(c, x, M, s);
   const StatsSlab sl = stats_slab(c);
-  uint8_t* l0b = (uint8_t*)c->fs_slab + (c->max_rows_p / STATS_RB) * (int64_t)c->n * 16;
   const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
-  GemmArgs g{};
-  g.A0 = c->xb; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
-  g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
   if (!unfused && gemm_streams<OP_ROW, OP_ROW, EpiStats>(g)) {
+    uint8_t* l0b = stats_l0_bytes(c);
     EpiStats e{};
-    e.bias = b; e.slab = sl; e.l0b = l0b; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n; e.ncb = n_p / 64;
+    e.bias = c->P + c->nW; e.slab = sl; e.l0b = l0b; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n; e.ncb = n_p / 64;
     e.inv_T = 1.0f / (float)Trows;
-    auto kerns = gemm256s_bf16_kernel<EpiStats>;
-    LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
-    GemmArgs g2 = g;
-    g2.nbm = g.nbm / 2;
-    g2.nbn = g.nbn / 2;
-    ev_begin(c, KID_ENC_FWD, s);
-    hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, e);
-    ev_end(c, KID_ENC_FWD, s);
-    HIP_TRY(hipGetLastError());
+    if (int rc = file_pass_l1_fused(c, g, e, s)) return rc;
     stats_launch_l0(L0Bytes{l0b, n_p / 64}, M, Trows, lengths, c->n, o, s);
   } else {
-    EpiEnc e{};
-    e.c = c->c; e.bias = b; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = g.nbn;
-    if (gemm_streams<OP_ROW, OP_ROW, EpiEnc>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)g.nbm * g.nbn * 4, s));
-    ev_begin(c, KID_ENC_FWD, s);
-    int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-    ev_end(c, KID_ENC_FWD, s);
-    if (rc) return rc;
+    if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
     const unsigned short* lat = (const unsigned short*)c->c;
     hipLaunchKernelGGL(stats_colreduce_kernel, dim3((unsigned)((c->n + 255) / 256), (unsigned)nrb), dim3(256), 0, s, lat, (int64_t)n_p, c->n,
                        M, Trows, lengths, sl);
@@ -3327,24 +3292,16 @@ static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int
 
 extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
                                int flags, void* stats, void* stream) {
-  if (!c || !x || !stats) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->fp8) return fail(SAE_ERR_INVALID, "sae_stats_files: fp8 contexts are not supported (run the statistics in a bf16 context)");
-  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
-  const int64_t M = n_files * rows_per_file;
-  if (M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "n_files * rows_per_file = %lld > max_rows=%lld", (long long)M, (long long)c->cfg.max_rows);
-  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  if (flags & ~SAE_STATS_UNFUSED) return fail(SAE_ERR_INVALID, "unknown stats flags 0x%x", flags);
+  int64_t M;
+  if (int rc = file_pass_begin(kStatsPass, c, x, stats, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   if ((reinterpret_cast<uintptr_t>(stats) & 7) != 0) return fail(SAE_ERR_INVALID, "the stats block must be 8-byte aligned");
-  USE_DEVICE(c);
   if (int rc = stats_ensure(c)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   const StatsOut o = stats_out(stats, c->n);
-  int rc;
   if (c->topk) {
     // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the statistics of the selection
-    rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false);
-    if (rc) return rc;
+    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
     const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
     const unsigned short* vals = (const unsigned short*)c->top_vals;
     hipLaunchKernelGGL(stats_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
@@ -3354,14 +3311,9 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
     HIP_TRY(hipGetLastError());
   } else {
     const bool unfused = (flags & SAE_STATS_UNFUSED) != 0;
-    switch (x_dtype) {
-      case SAE_DTYPE_F32: rc = stats_l1_impl<float>(c, (const float*)x, M, Trows, lengths, o, unfused, s); break;
-      case SAE_DTYPE_F16: rc = stats_l1_impl<_Float16>(c, (const _Float16*)x, M, Trows, lengths, o, unfused, s); break;
-      default: rc = stats_l1_impl<bf16_t>(c, (const bf16_t*)x, M, Trows, lengths, o, unfused, s); break;
-    }
-    if (rc) return rc;
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return stats_l1_impl(c, xt, M, Trows, lengths, o, unfused, s); })) return rc;
   }
-  c->last_fwd_stats = true;
+  c->last_call = LAST_STATS;
   return SAE_OK;
 }
 

@@ -312,16 +312,10 @@ class SaeEngine:
         if self.variant == "topk" and x.dim() == 3 and getattr(self, "_rows_per_file", None) != x.shape[1]:
             self.set_topk_options(getattr(self, "_dead_threshold", 1e300), x.shape[1])
 
-    @staticmethod
-    def _stream(stream=None):
-        import torch
-        s = stream if stream is not None else torch.cuda.current_stream()
-        return C.c_void_p(s.cuda_stream)
-
     def forward_backward(self, x, stream=None) -> None:
         self._note_shape(x)
         x, ptr, rows, dt = self._x_args(x)
-        _check(self._lib.sae_forward_backward(self._ctx, C.c_void_p(ptr), rows, dt, self._stream(stream)))
+        _check(self._lib.sae_forward_backward(self._ctx, C.c_void_p(ptr), rows, dt, _stream_ptr(stream)))
         err, self._cb_error = getattr(self, "_cb_error", None), None
         if err is not None:
             raise err
@@ -331,7 +325,7 @@ class SaeEngine:
         """This rank's statistics of batch x (what the losses normalise by) into the statistics buffer."""
         self._note_shape(x)
         x, ptr, rows, dt = self._x_args(x)
-        _check(self._lib.sae_batch_stats(self._ctx, C.c_void_p(ptr), rows, dt, self._stream(stream)))
+        _check(self._lib.sae_batch_stats(self._ctx, C.c_void_p(ptr), rows, dt, _stream_ptr(stream)))
 
     def stats_tensor(self):
         """The statistics of the last batch_stats() as a float64 torch CUDA tensor aliasing the engine's buffer:
@@ -422,17 +416,17 @@ class SaeEngine:
         return tuple(int(v) for v in out)
 
     def optimizer_step(self, lr: float, grad_scale: float = 1.0, stream=None) -> None:
-        _check(self._lib.sae_optimizer_step(self._ctx, float(lr), float(grad_scale), self._stream(stream)))
+        _check(self._lib.sae_optimizer_step(self._ctx, float(lr), float(grad_scale), _stream_ptr(stream)))
 
     def step(self, x, lr: float, stream=None) -> None:
         self._note_shape(x)
         x, ptr, rows, dt = self._x_args(x)
-        _check(self._lib.sae_step(self._ctx, C.c_void_p(ptr), rows, dt, float(lr), self._stream(stream)))
+        _check(self._lib.sae_step(self._ctx, C.c_void_p(ptr), rows, dt, float(lr), _stream_ptr(stream)))
 
     def eval(self, x, stream=None) -> None:
         self._note_shape(x)
         x, ptr, rows, dt = self._x_args(x)
-        _check(self._lib.sae_eval(self._ctx, C.c_void_p(ptr), rows, dt, self._stream(stream)))
+        _check(self._lib.sae_eval(self._ctx, C.c_void_p(ptr), rows, dt, _stream_ptr(stream)))
 
     def set_eval_precision(self, precision: str) -> None:
         """"bf16" (default): eval() / eval_into() run the training kernels' arithmetic (CPU autocast's).  "fp32": fp32 end to end --
@@ -453,7 +447,7 @@ class SaeEngine:
             assert colmax_row.is_cuda and colmax_row.is_contiguous() and colmax_row.numel() >= self.n
             cm = C.c_void_p(colmax_row.data_ptr())
         _check(self._lib.sae_eval_into(self._ctx, C.c_void_p(ptr), rows, dt, C.c_void_p(metrics_row.data_ptr()), cm,
-                                       self._stream(stream)))
+                                       _stream_ptr(stream)))
 
     # -- inference ---------------------------------------------------------
     def latent_buffer(self):
@@ -495,17 +489,17 @@ class SaeEngine:
         assert latent.dim() == 2 and latent.stride(1) == 1
         dt = {torch.float32: DTYPE["float32"], torch.bfloat16: DTYPE["bfloat16"]}[latent.dtype]
         _check(self._lib.sae_decode(self._ctx, C.c_void_p(latent.data_ptr()), dt, int(latent.stride(0)), int(latent.shape[0]),
-                                    C.c_void_p(out.data_ptr()), self._stream(stream)))
+                                    C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
 
     def metrics(self, stream=None) -> np.ndarray:
         out = np.zeros(NUM_METRICS, dtype=np.float32)
-        _check(self._lib.sae_read_metrics(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), self._stream(stream)))
+        _check(self._lib.sae_read_metrics(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), _stream_ptr(stream)))
         return out
 
     def latent_colmax(self, stream=None) -> np.ndarray:
         """max over rows of |latent| per dictionary feature for the last forward (validate())."""
         out = np.empty(self.n, dtype=np.float32)
-        _check(self._lib.sae_latent_colmax(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), self.n, self._stream(stream)))
+        _check(self._lib.sae_latent_colmax(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), self.n, _stream_ptr(stream)))
         return out
 
     def grad_buffer(self):
@@ -547,15 +541,10 @@ class SaeEngine:
     def search_files(self, x, file_keys, lengths=None, unfused: bool = False, stream=None) -> None:
         """Per-(file, latent) keys of x [n_files, T, d] (CUDA) into file_keys (int64 CUDA tensor [n_files, n_dict]); lengths: int32
         CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
-        import torch
-        if x.dim() != 3:
-            raise EngineError(f"search_files expects x as [n_files, T, d], got {tuple(x.shape)}")
-        _check_search_out(file_keys, x.shape[0] * self.n)
-        lp = _lengths_ptr(lengths, x.shape[0])
-        B, T = int(x.shape[0]), int(x.shape[1])
-        x, ptr, _rows, dt = self._x_args(x)
-        _check(self._lib.sae_search_files(self._ctx, C.c_void_p(ptr), B, T, dt, lp, SEARCH_UNFUSED if unfused else 0,
-                                          C.c_void_p(file_keys.data_ptr()), self._stream(stream)))
+        x, xp, B, T, _d, dt, lp = _files_args(x, "search_files", lengths)
+        _check_search_out(file_keys, B * self.n)
+        _check(self._lib.sae_search_files(self._ctx, xp, B, T, dt, lp, SEARCH_UNFUSED if unfused else 0,
+                                          C.c_void_p(file_keys.data_ptr()), _stream_ptr(stream)))
 
     # -- feature statistics (include/freud_sae.h: sae_stats_files; freud_amd/feature_stats.py) -----------------------------
     def stats_files(self, x, stats_block, lengths=None, unfused: bool = False, stream=None) -> None:
@@ -563,16 +552,12 @@ class SaeEngine:
         stats_layout(n)["bytes"] bytes); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward
         getters fail until the next eval() / step()."""
         import torch
-        if x.dim() != 3:
-            raise EngineError(f"stats_files expects x as [n_files, T, d], got {tuple(x.shape)}")
+        x, xp, B, T, _d, dt, lp = _files_args(x, "stats_files", lengths)
         nbytes = stats_layout(self.n)["bytes"]
         if not (stats_block.is_cuda and stats_block.dtype == torch.uint8 and stats_block.is_contiguous() and stats_block.numel() >= nbytes):
             raise EngineError(f"stats_block must be a contiguous uint8 CUDA tensor of >= {nbytes} bytes")
-        lp = _lengths_ptr(lengths, x.shape[0])
-        B, T = int(x.shape[0]), int(x.shape[1])
-        x, ptr, _rows, dt = self._x_args(x)
-        _check(self._lib.sae_stats_files(self._ctx, C.c_void_p(ptr), B, T, dt, lp, STATS_UNFUSED if unfused else 0,
-                                         C.c_void_p(stats_block.data_ptr()), self._stream(stream)))
+        _check(self._lib.sae_stats_files(self._ctx, xp, B, T, dt, lp, STATS_UNFUSED if unfused else 0,
+                                         C.c_void_p(stats_block.data_ptr()), _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:
@@ -624,19 +609,25 @@ def _stream_ptr(stream=None):
     return C.c_void_p((stream if stream is not None else torch.cuda.current_stream()).cuda_stream)
 
 
+def _files_args(x, who: str, lengths):
+    """The shared front of search_files / stats_files / search_raw_files: x [n_files, T, d] and the files' lengths ->
+    (x kept alive, its pointer, n_files, T, d, dtype code, lengths pointer or None)."""
+    if x.dim() != 3:
+        raise EngineError(f"{who} expects x as [n_files, T, d], got {tuple(x.shape)}")
+    B, T, d = (int(v) for v in x.shape)
+    lp = _lengths_ptr(lengths, B)
+    x, ptr, _rows, dt = SaeEngine._x_args(x)
+    return x, C.c_void_p(ptr), B, T, d, dt, lp
+
+
 def search_raw_files(x, file_keys, aux=None, lengths=None, absolute: bool = False, stream=None) -> None:
     """Raw mode (no SAE): per-(file, column) keys of x [n_files, T, d] itself; with absolute, aux gets the abs-mode side words."""
-    import torch
-    if x.dim() != 3:
-        raise EngineError(f"search_raw_files expects x as [n_files, T, d], got {tuple(x.shape)}")
-    B, T, d = (int(v) for v in x.shape)
+    x, xp, B, T, d, dt, lp = _files_args(x, "search_raw_files", lengths)
     _check_search_out(file_keys, B * d)
     if absolute:
         _check_search_out(aux, B * d)
-    x, ptr, _rows, dt = SaeEngine._x_args(x)
-    _check(load().sae_search_raw_files(C.c_void_p(ptr), B, T, d, dt, _lengths_ptr(lengths, B), int(absolute),
-                                       C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if absolute else None,
-                                       _stream_ptr(stream)))
+    _check(load().sae_search_raw_files(xp, B, T, d, dt, lp, int(absolute), C.c_void_p(file_keys.data_ptr()),
+                                       C.c_void_p(aux.data_ptr()) if absolute else None, _stream_ptr(stream)))
 
 
 def search_merge(file_keys, aux, n_files: int, ncols: int, file0: int, n_top: int, flags: int, min_val: float, max_val: float,

@@ -26,6 +26,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from .file_pass import FilePass, check_lengths, default_batch_files, keep_rng, resolve_sae     # noqa: F401 (re-exported)
+
 TIMESTEP_S = 30 / 1500          # src/utils/constants.py:17
 
 
@@ -80,68 +82,7 @@ def decode_table(top_keys: np.ndarray, top_frames: np.ndarray):
     return values.T.copy(), files.T.copy(), frames.T.copy(), times
 
 
-def check_lengths(lengths, n_total: int, T: int) -> Optional[np.ndarray]:
-    """Trim lengths (frames per file, in file order) -> int32 capped at T; a length below 1 is an error (the reference fails on
-    max() of an empty series)."""
-    if lengths is None:
-        return None
-    a = np.asarray(lengths)
-    if a.ndim != 1 or a.shape[0] != n_total:
-        raise ValueError(f"lengths must hold one entry per file ({n_total}), got shape {a.shape}")
-    if not np.issubdtype(a.dtype, np.integer):
-        raise ValueError(f"lengths must be integers, got {a.dtype}")
-    if a.size and int(a.min()) < 1:
-        raise ValueError(f"lengths must be >= 1 (file {int(np.argmin(a))} has {int(a.min())}): an empty series has no maximum")
-    return np.minimum(a.astype(np.int64), T).astype(np.int32)
-
-
-def _resolve_sae(sae):
-    """None (raw mode) | checkpoint path | freud_amd.models instance | SaeEngine -> (model or None, engine or None)."""
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
-        return None, None
-    if isinstance(sae, str):
-        from .models import init_sae_from_checkpoint
-        sae = init_sae_from_checkpoint(sae)
-    from .engine import SaeEngine
-    if isinstance(sae, SaeEngine):
-        return None, sae
-    if not hasattr(sae, "_ensure"):
-        raise TypeError(f"sae must be None, a checkpoint path, a freud_amd.models SAE or a SaeEngine, got {type(sae).__name__}")
-    return sae, None
-
-
-def default_batch_files(T: int, n: Optional[int], n_total: int) -> int:
-    """Files per batch when the caller gives none: 16, or for an L1 / TopK SAE the fewest files at which the encoder GEMM has the
-    2048 output tiles of 256 x 256 that its streaming form (gemm256s.h: engine.hip gemm_streams, 4 x G2_PERSIST_STATIC) needs, so
-    that the L1 search takes the fused epilogue (n = 3072, T = 1500: 30 files; n = 40 960: 16).  Dictionaries whose padded size is
-    no multiple of 256 never stream; above 512 files the batch stays at 16 (n < 1024) and the latent is stored and reduced."""
-    B = 16
-    if n is not None:
-        n_p = -(-n // 128) * 128
-        if n_p % 256 == 0:
-            need = -(-2048 // (n_p // 256))                  # 256-row blocks of the batch
-            b_min = ((need - 1) * 256) // T + 1              # round_up(B T, 256) / 256 >= need
-            if b_min <= 512:
-                B = max(B, b_min)
-    return max(1, min(B, n_total))
-
-
-def _keep_rng(fn):
-    """The search must not disturb the caller's global torch RNG: the loader's epoch_batches() draws the DataLoader base seed, and
-    building a model from a checkpoint runs the reference modules' random initialisations before the weights are loaded."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapped(*a, **k):
-        state = torch.get_rng_state()
-        try:
-            return fn(*a, **k)
-        finally:
-            torch.set_rng_state(state)
-    return wrapped
-
-
-@_keep_rng
+@keep_rng
 def search_features(sae, data_path: str, layer_name: str, n_files: int, *, absolute_magnitude: bool = False,
                     min_val: Optional[float] = None, max_val: Optional[float] = None, lengths=None,
                     subset_size: Optional[int] = None, batch_files: Optional[int] = None,
@@ -149,42 +90,14 @@ def search_features(sae, data_path: str, layer_name: str, n_files: int, *, absol
     """top_activations for every latent of `sae` (None: every column of the activations themselves) in one pass.
     batch_files: files per engine call (default: default_batch_files)."""
     from . import engine as E
-    from .loader import MemoryMappedActivationDataLoader, MemoryMappedActivationsDataset
 
     n_files = int(n_files)
     if n_files < 1 or n_files > E.SEARCH_MAX_TOP:
         raise ValueError(f"n_files={n_files} outside [1, {E.SEARCH_MAX_TOP}]")
-    if batch_files is not None and int(batch_files) < 1:
-        raise ValueError(f"batch_files={batch_files} must be >= 1")
-    ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
-    n_total = len(ds)
-    T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
-    lens = check_lengths(lengths, n_total, T)
-    if n_total == 0:
-        raise ValueError(f"{data_path}: no files")
-    model, eng = _resolve_sae(sae)
-    if not torch.cuda.is_available():
-        raise RuntimeError("the feature search runs on the GPU (HIP engine); there is no CPU path")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if model is not None:
-        dev = model.device
-        if model.activation_size != d:
-            raise ValueError(f"the SAE expects d_model={model.activation_size}, the shards hold d={d}")
-    if eng is not None and eng.d != d:
-        raise ValueError(f"the SAE expects d_model={eng.d}, the shards hold d={d}")
-    n_lat = None if (model is None and eng is None) else (eng.n if eng is not None else model.n_dict_components)
-    B = int(batch_files) if batch_files is not None else default_batch_files(T, n_lat, n_total)
-    B = min(B, n_total)
-    if eng is None and model is not None:
-        eng = model._ensure(-(-B * T // 256) * 256)     # (row room for an even number of 128-row blocks: the fused epilogue's GEMM)
-    elif eng is not None and B * T > eng.max_rows:
-        B = max(1, eng.max_rows // T)
-        if B * T > eng.max_rows:
-            raise ValueError(f"one file of {T} rows exceeds the engine's max_rows={eng.max_rows}")
+    fp = FilePass(sae, data_path, layer_name, what="feature search", lengths=lengths, subset_size=subset_size, batch_files=batch_files)
+    eng, dev, n_total = fp.eng, fp.device, fp.n_total
     raw = eng is None
-    ncols = d if raw else eng.n
-    if eng is not None and eng.precision != "bf16":
-        raise ValueError("the feature search runs in bf16 contexts only")
+    ncols = fp.d if raw else eng.n
     flags = (E.SEARCH_ABS if absolute_magnitude else 0) | (E.SEARCH_MIN if min_val is not None else 0) | \
             (E.SEARCH_MAX if max_val is not None else 0)
     feats = None
@@ -194,21 +107,13 @@ def search_features(sae, data_path: str, layer_name: str, n_files: int, *, absol
             raise ValueError(f"max_per_file_features must be latent indices in [0, {ncols})")
 
     with torch.cuda.device(dev):
-        keys = torch.empty(B * ncols, dtype=torch.int64, device=dev)
-        aux = torch.empty(B * ncols, dtype=torch.int64, device=dev) if (raw and absolute_magnitude) else None
+        keys = torch.empty(fp.batch_files * ncols, dtype=torch.int64, device=dev)
+        aux = torch.empty(fp.batch_files * ncols, dtype=torch.int64, device=dev) if (raw and absolute_magnitude) else None
         top_keys = torch.zeros(n_files * ncols, dtype=torch.int64, device=dev)
         top_frames = torch.zeros(n_files * ncols, dtype=torch.int32, device=dev)
-        lens_dev = torch.from_numpy(lens).to(dev) if lens is not None else None
         feats_dev = torch.from_numpy(feats.astype(np.int32)).to(dev) if feats is not None else None
         per_file = torch.zeros(len(feats), n_total, dtype=torch.float32, device=dev) if feats is not None else None
-        # (native delivery whatever FREUD_LOADER_DELIVER says: raw mode ranks x unrounded, the SAE search sees what encode() sees)
-        loader = MemoryMappedActivationDataLoader(data_path, layer_name, B, subset_size=subset_size,
-                                                  dl_kwargs={"shuffle": False, "drop_last": False}, device=dev,
-                                                  deliver_dtype="native")
-        file0 = 0
-        for x, _names in loader:
-            nb = int(x.shape[0])
-            lb = lens_dev[file0:file0 + nb] if lens_dev is not None else None
+        for x, file0, nb, lb in fp:
             if raw:
                 E.search_raw_files(x, keys, aux, lb, absolute=absolute_magnitude)
             else:
@@ -217,14 +122,11 @@ def search_features(sae, data_path: str, layer_name: str, n_files: int, *, absol
                            0.0 if max_val is None else float(max_val), top_keys, top_frames)
             if feats is not None:
                 E.search_file_values(keys, aux, nb, ncols, flags, feats_dev, file0, per_file)
-            file0 += nb
-        if file0 != n_total:
-            raise RuntimeError(f"the loader delivered {file0} of {n_total} files")
         tk = top_keys.view(n_files, ncols).cpu().numpy()          # the one read-back
         tf = top_frames.view(n_files, ncols).cpu().numpy()
         pf = per_file.cpu().numpy() if per_file is not None else None
     values, files, frames, times = decode_table(tk, tf)
-    return FeatureAtlas(values, files, frames, times, list(ds.metadata["filenames"]), pf, feats)
+    return FeatureAtlas(values, files, frames, times, fp.filenames, pf, feats)
 
 
 def _series(sae_model, eng, x: torch.Tensor, feature_idx: int) -> torch.Tensor:
@@ -242,13 +144,13 @@ def _series(sae_model, eng, x: torch.Tensor, feature_idx: int) -> torch.Tensor:
     return dense.cpu()
 
 
-@_keep_rng
+@keep_rng
 def top_activations(sae, data_path: str, layer_name: str, feature_idx: int, n_files: int, max_val: Optional[float],
                     min_val: Optional[float], absolute_magnitude: bool, return_max_per_file: bool, lengths=None):
     """activations.py:61-132 with the reference's return shape: ([(audio_file, trimmed series, value, time)], max_per_file or None).
     The series are re-encoded for the winning files only."""
     from .loader import MemoryMappedActivationsDataset
-    model, eng = _resolve_sae(sae)
+    model, eng = resolve_sae(sae)
     atlas = search_features(model if model is not None else eng, data_path, layer_name, n_files, absolute_magnitude=absolute_magnitude,
                             min_val=min_val, max_val=max_val, lengths=lengths,
                             max_per_file_features=[feature_idx] if return_max_per_file else None)

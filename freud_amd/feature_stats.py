@@ -3,7 +3,7 @@ the Whisper-activation shards, without collecting the SAE activations (the refer
 sae_model, a dense fp32 [1500, n] row per file, then a reduction in torch).
 
 Semantics (include/freud_sae.h, sae_stats_files).  Over the files of a shard directory, the first min(L[f], T) frames of file f
-count when `lengths` is given (feature_search.check_lengths rules), all T frames otherwise.  Per frame and latent j, a_j is exactly
+count when `lengths` is given (file_pass.check_lengths rules), all T frames otherwise.  Per frame and latent j, a_j is exactly
 the value freud_amd.models encode() returns: the bf16 L1 latent of the training kernels, or for TopK the scatter of top_acts at
 top_indices (0 elsewhere).  a_j is active iff a_j > 0 (a bf16 -0.0 is not).  Per latent: fire_count (frames where active),
 act_sum / act_sq_sum (sums of a_j and a_j^2, float64), act_max (float32, 0 if never active); per frame the number of active
@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .feature_search import _keep_rng, _resolve_sae, check_lengths, default_batch_files
+from .file_pass import FilePass, keep_rng
 
 _FIELDS = ("fire_count", "act_sum", "act_sq_sum", "act_max", "l0_hist")
 
@@ -93,61 +93,23 @@ class FeatureStats:
         return cls(int(get("n_frames")[0]), get("fire_count"), get("act_sum"), get("act_sq_sum"), get("act_max"), get("l0_hist"))
 
 
-@_keep_rng
+@keep_rng
 def feature_stats(sae, data_path: str, layer_name: str, *, lengths=None, subset_size: Optional[int] = None,
                   batch_files: Optional[int] = None, unfused: bool = False) -> FeatureStats:
     """Statistics of every latent of `sae` (a checkpoint path, a freud_amd.models SAE or a SaeEngine; bf16 contexts) over the files
-    of a shard directory, in one pass.  batch_files: files per engine call (default: feature_search.default_batch_files, which
+    of a shard directory, in one pass.  batch_files: files per engine call (default: file_pass.default_batch_files, which
     picks the fused L1 path where it can); unfused: force the stored-latent L1 path (tests, benchmarks)."""
     from . import engine as E
-    from .loader import MemoryMappedActivationDataLoader, MemoryMappedActivationsDataset
 
-    if batch_files is not None and int(batch_files) < 1:
-        raise ValueError(f"batch_files={batch_files} must be >= 1")
     if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
         raise ValueError("feature statistics need an SAE (raw-activation statistics are not provided)")
-    ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
-    n_total = len(ds)
-    if n_total == 0:
-        raise ValueError(f"{data_path}: no files")
-    T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
-    lens = check_lengths(lengths, n_total, T)
-    model, eng = _resolve_sae(sae)
-    sae_d = eng.d if eng is not None else model.activation_size
-    if sae_d != d:
-        raise ValueError(f"the SAE expects d_model={sae_d}, the shards hold d={d}")
-    if eng is not None and eng.precision != "bf16":
-        raise ValueError("the feature statistics run in bf16 contexts only")
-    if not torch.cuda.is_available():
-        raise RuntimeError("the feature statistics run on the GPU (HIP engine); there is no CPU path")
-    n = eng.n if eng is not None else model.n_dict_components
-    B = int(batch_files) if batch_files is not None else default_batch_files(T, n, n_total)
-    B = min(B, n_total)
-    if eng is None:
-        eng = model._ensure(-(-B * T // 256) * 256)     # (row room for an even number of 128-row blocks: the fused epilogue's GEMM)
-        dev = model.device
-    else:
-        dev = torch.device("cuda", eng.device_id)
-        if B * T > eng.max_rows:
-            B = max(1, eng.max_rows // T)
-            if B * T > eng.max_rows:
-                raise ValueError(f"one file of {T} rows exceeds the engine's max_rows={eng.max_rows}")
-
-    with torch.cuda.device(dev):
-        block = torch.zeros(E.stats_layout(n)["bytes"], dtype=torch.uint8, device=dev)
-        lens_dev = torch.from_numpy(lens).to(dev) if lens is not None else None
-        # (native delivery, no shuffle: the statistics see what encode() of the shard rows sees)
-        loader = MemoryMappedActivationDataLoader(data_path, layer_name, B, subset_size=subset_size,
-                                                  dl_kwargs={"shuffle": False, "drop_last": False}, device=dev,
-                                                  deliver_dtype="native")
-        file0 = 0
-        for x, _names in loader:
-            nb = int(x.shape[0])
-            lb = lens_dev[file0:file0 + nb] if lens_dev is not None else None
-            eng.stats_files(x, block, lb, unfused=unfused)
-            file0 += nb
-        if file0 != n_total:
-            raise RuntimeError(f"the loader delivered {file0} of {n_total} files")
+    fp = FilePass(sae, data_path, layer_name, what="feature statistics", lengths=lengths, subset_size=subset_size,
+                  batch_files=batch_files)
+    n = fp.eng.n
+    with torch.cuda.device(fp.device):
+        block = torch.zeros(E.stats_layout(n)["bytes"], dtype=torch.uint8, device=fp.device)
+        for x, _file0, _nb, lb in fp:
+            fp.eng.stats_files(x, block, lb, unfused=unfused)
         host = block.cpu().numpy()                  # the one read-back
     return FeatureStats.from_block(host, n)
 

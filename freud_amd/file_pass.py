@@ -1,0 +1,142 @@
+"""One GPU pass over a shard directory in batches of files: what the feature search (feature_search.py) and the feature statistics
+(feature_stats.py) share.  Both encode batches of files with the training kernels and keep a reduction instead of the latent; this
+module owns the argument rules, the choice of the batch size and the walk over the shard loader."""
+from __future__ import annotations
+
+import functools
+from typing import Optional
+
+import numpy as np
+import torch
+
+
+def check_lengths(lengths, n_total: int, T: int) -> Optional[np.ndarray]:
+    """Trim lengths (frames per file, in file order) -> int32 capped at T; a length below 1 is an error (the reference fails on
+    max() of an empty series)."""
+    if lengths is None:
+        return None
+    a = np.asarray(lengths)
+    if a.ndim != 1 or a.shape[0] != n_total:
+        raise ValueError(f"lengths must hold one entry per file ({n_total}), got shape {a.shape}")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"lengths must be integers, got {a.dtype}")
+    if a.size and int(a.min()) < 1:
+        raise ValueError(f"lengths must be >= 1 (file {int(np.argmin(a))} has {int(a.min())}): an empty series has no maximum")
+    return np.minimum(a.astype(np.int64), T).astype(np.int32)
+
+
+def resolve_sae(sae):
+    """None (raw mode) | checkpoint path | freud_amd.models instance | SaeEngine -> (model or None, engine or None)."""
+    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+        return None, None
+    if isinstance(sae, str):
+        from .models import init_sae_from_checkpoint
+        sae = init_sae_from_checkpoint(sae)
+    from .engine import SaeEngine
+    if isinstance(sae, SaeEngine):
+        return None, sae
+    if not hasattr(sae, "_ensure"):
+        raise TypeError(f"sae must be None, a checkpoint path, a freud_amd.models SAE or a SaeEngine, got {type(sae).__name__}")
+    return sae, None
+
+
+def default_batch_files(T: int, n: Optional[int], n_total: int) -> int:
+    """Files per batch when the caller gives none: 16, or for an L1 / TopK SAE the fewest files at which the encoder GEMM has the
+    2048 output tiles of 256 x 256 that its streaming form (gemm256s.h: engine.hip gemm_streams, 4 x G2_PERSIST_STATIC) needs, so
+    that an L1 pass takes the fused epilogue (n = 3072, T = 1500: 30 files; n = 40 960: 16).  Dictionaries whose padded size is
+    no multiple of 256 never stream; above 512 files the batch stays at 16 (n < 1024) and the latent is stored and reduced."""
+    B = 16
+    if n is not None:
+        n_p = -(-n // 128) * 128
+        if n_p % 256 == 0:
+            need = -(-2048 // (n_p // 256))                  # 256-row blocks of the batch
+            b_min = ((need - 1) * 256) // T + 1              # round_up(B T, 256) / 256 >= need
+            if b_min <= 512:
+                B = max(B, b_min)
+    return max(1, min(B, n_total))
+
+
+def keep_rng(fn):
+    """A pass must not disturb the caller's global torch RNG: the loader's epoch_batches() draws the DataLoader base seed, and
+    building a model from a checkpoint runs the reference modules' random initialisations before the weights are loaded."""
+    @functools.wraps(fn)
+    def wrapped(*a, **k):
+        state = torch.get_rng_state()
+        try:
+            return fn(*a, **k)
+        finally:
+            torch.set_rng_state(state)
+    return wrapped
+
+
+class FilePass:
+    """The set-up of one pass, then its batches.  `sae`: see resolve_sae (None: raw mode, no engine); `what` is the noun of the
+    error messages ("feature search", "feature statistics").  Every check that needs no device comes before the one that does.
+
+    Attributes: model, eng (None in raw mode), device, T, d, n_total, batch_files, filenames.  Iterating yields
+    (x [nb, T, d] on `device` in the shards' dtype, file0, nb, lengths[file0:file0 + nb] on `device` or None) in file order."""
+
+    def __init__(self, sae, data_path: str, layer_name: str, *, what: str, lengths=None, subset_size: Optional[int] = None,
+                 batch_files: Optional[int] = None):
+        from .loader import MemoryMappedActivationsDataset
+
+        if batch_files is not None and int(batch_files) < 1:
+            raise ValueError(f"batch_files={batch_files} must be >= 1")
+        ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
+        n_total = len(ds)
+        if n_total == 0:
+            raise ValueError(f"{data_path}: no files")
+        T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
+        self._lens = check_lengths(lengths, n_total, T)
+        model, eng = resolve_sae(sae)
+        runs = f"the {what} run{'' if what.endswith('s') else 's'}"
+
+        def bf16_only(e):
+            if e.precision != "bf16":
+                raise ValueError(f"{runs} in bf16 contexts only")
+
+        n = None
+        if eng is not None or model is not None:
+            sae_d, n = (eng.d, eng.n) if eng is not None else (model.activation_size, model.n_dict_components)
+            if sae_d != d:
+                raise ValueError(f"the SAE expects d_model={sae_d}, the shards hold d={d}")
+        if eng is not None:
+            bf16_only(eng)
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{runs} on the GPU (HIP engine); there is no CPU path")
+        B = int(batch_files) if batch_files is not None else default_batch_files(T, n, n_total)
+        B = min(B, n_total)
+        if model is not None:
+            eng = model._ensure(-(-B * T // 256) * 256)     # (row room for an even number of 128-row blocks: the fused epilogue's GEMM)
+            bf16_only(eng)
+            dev = model.device
+        elif eng is not None:
+            dev = torch.device("cuda", eng.device_id)
+            if B * T > eng.max_rows:
+                B = max(1, eng.max_rows // T)
+                if B * T > eng.max_rows:
+                    raise ValueError(f"one file of {T} rows exceeds the engine's max_rows={eng.max_rows}")
+        else:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.model, self.eng, self.device = model, eng, dev
+        self.T, self.d, self.n_total, self.batch_files = T, d, n_total, B
+        self.filenames = list(ds.metadata["filenames"])
+        self._loader_args = (data_path, layer_name, subset_size)
+
+    def __iter__(self):
+        from .loader import MemoryMappedActivationDataLoader
+
+        data_path, layer_name, subset_size = self._loader_args
+        lens_dev = torch.from_numpy(self._lens).to(self.device) if self._lens is not None else None
+        # (native delivery whatever FREUD_LOADER_DELIVER says, no shuffle: raw mode sees x unrounded, an SAE what encode() of the
+        # shard rows sees)
+        loader = MemoryMappedActivationDataLoader(data_path, layer_name, self.batch_files, subset_size=subset_size,
+                                                  dl_kwargs={"shuffle": False, "drop_last": False}, device=self.device,
+                                                  deliver_dtype="native")
+        file0 = 0
+        for x, _names in loader:
+            nb = int(x.shape[0])
+            yield x, file0, nb, (lens_dev[file0:file0 + nb] if lens_dev is not None else None)
+            file0 += nb
+        if file0 != self.n_total:
+            raise RuntimeError(f"the loader delivered {file0} of {self.n_total} files")

@@ -24,30 +24,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from freud_amd import engine as E                                    # noqa: E402
 from freud_amd import feature_search as FS                           # noqa: E402
 from freud_amd.loader import write_shards                            # noqa: E402
+from bench_pass_common import best_alternating, enc_gemm_ms, l1_engine, timed   # noqa: E402
 
 T = 1500
 N_TOP = 16
 
 
-def timed(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def shape(d, n, B, iters, loader_files):
-    g = torch.Generator().manual_seed(0)
-    eng = E.SaeEngine("l1", d, n, -(-B * T // 256) * 256)      # (room for an even number of 128-row blocks: the fused path)
-    W = torch.empty(d, n)
-    torch.nn.init.orthogonal_(W, generator=g)
-    eng.set_params({"decoder.weight": W.numpy(), "encoder_bias": (0.01 * torch.randn(n, generator=g)).numpy()})
-    x = torch.randn(B, T, d, generator=g).cuda()
+    eng, x = l1_engine(d, n, B, T)
     keys = torch.empty(B * n, dtype=torch.int64, device="cuda")
     top = torch.zeros(N_TOP * n, dtype=torch.int64, device="cuda")
     frames = torch.zeros(N_TOP * n, dtype=torch.int32, device="cuda")
@@ -56,22 +40,10 @@ def shape(d, n, B, iters, loader_files):
         eng.search_files(x, keys, unfused=unfused)
         E.search_merge(keys, None, B, n, 0, N_TOP, 0, 0.0, 0.0, top, frames)
 
-    # alternating rounds, best round of each: the clock of a power-managed chip ramps during the first milliseconds
-    fused_ms = unfused_ms = float("inf")
-    for _ in range(5):
-        fused_ms = min(fused_ms, timed(lambda: run(False), iters))
-        unfused_ms = min(unfused_ms, timed(lambda: run(True), iters))
+    fused_ms, unfused_ms = best_alternating([lambda: run(False), lambda: run(True)], iters)
     merge_ms = timed(lambda: E.search_merge(keys, None, B, n, 0, N_TOP, 0, 0.0, 0.0, top, frames), iters)
-    eng.profile(2)
-    for _ in range(iters):
-        eng.search_files(x, keys, unfused=True)
-    kt = eng.kernel_times()
-    enc_ms = kt["enc_fwd_gemm"][0] / max(1, kt["enc_fwd_gemm"][1])
-    for _ in range(iters):
-        eng.search_files(x, keys)
-    kt = eng.kernel_times()
-    search_gemm_ms = kt["enc_fwd_gemm"][0] / max(1, kt["enc_fwd_gemm"][1])
-    eng.profile(0)
+    enc_ms, search_gemm_ms = enc_gemm_ms(eng, [lambda: eng.search_files(x, keys, unfused=True), lambda: eng.search_files(x, keys)],
+                                         iters)
     flop = 2.0 * T * d * n * B
     out = {f"d{d}_n{n}": {
         "files_per_batch": B,

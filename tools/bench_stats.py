@@ -19,46 +19,17 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from freud_amd import engine as E                                    # noqa: E402
+from bench_pass_common import best_alternating, enc_gemm_ms, l1_engine, timed   # noqa: E402
 
 T = 1500
 
 
-def timed(fn, iters):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def l1_shape(d, n, B, iters):
-    g = torch.Generator().manual_seed(0)
-    eng = E.SaeEngine("l1", d, n, -(-B * T // 256) * 256)      # (room for an even number of 128-row blocks: the fused path)
-    W = torch.empty(d, n)
-    torch.nn.init.orthogonal_(W, generator=g)
-    eng.set_params({"decoder.weight": W.numpy(), "encoder_bias": (0.01 * torch.randn(n, generator=g)).numpy()})
-    x = torch.randn(B, T, d, generator=g).cuda()
+    eng, x = l1_engine(d, n, B, T)
     block = torch.zeros(E.stats_layout(n)["bytes"], dtype=torch.uint8, device="cuda")
-
-    # alternating rounds, best round of each: the clock of a power-managed chip ramps during the first milliseconds
-    fused_ms = unfused_ms = float("inf")
-    for _ in range(5):
-        fused_ms = min(fused_ms, timed(lambda: eng.stats_files(x, block), iters))
-        unfused_ms = min(unfused_ms, timed(lambda: eng.stats_files(x, block, unfused=True), iters))
-    eng.profile(2)
-    for _ in range(iters):
-        eng.stats_files(x, block, unfused=True)
-    kt = eng.kernel_times()
-    enc_ms = kt["enc_fwd_gemm"][0] / max(1, kt["enc_fwd_gemm"][1])
-    for _ in range(iters):
-        eng.stats_files(x, block)
-    kt = eng.kernel_times()
-    stats_gemm_ms = kt["enc_fwd_gemm"][0] / max(1, kt["enc_fwd_gemm"][1])
-    eng.profile(0)
+    fused, unfused = (lambda: eng.stats_files(x, block)), (lambda: eng.stats_files(x, block, unfused=True))
+    fused_ms, unfused_ms = best_alternating([fused, unfused], iters)
+    enc_ms, stats_gemm_ms = enc_gemm_ms(eng, [unfused, fused], iters)
     eng.close()
     return {f"d{d}_n{n}": {"files_per_batch": B, "stats_ms": fused_ms, "unfused_ms": unfused_ms, "enc_gemm_ms": enc_ms,
                            "stats_gemm_ms": stats_gemm_ms, "stats_vs_enc_gemm": fused_ms / enc_ms,
