@@ -88,35 +88,18 @@ __device__ __forceinline__ bf16x8 tr_frag_perm(const char* img, int col0, int s,
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// Pair p of the next step's 7 DMA pairs is issued in gap BF_DMA_A * p + BF_DMA_B (macros so that tools/build_variant.sh
-// can sweep them).  Same-box sweeps of the backward at C2: with the default cache policy on the latent (cycles per step)
-// 3p+1 3360, 5p+1 3325, 2p+1 3565, p+1 3814 (back-to-back pieces cost more each), 8p+1 3860 and 3p+24 4044 (the last
-// pieces land after the hand-over barrier), one wave per gap (staggered) 3710; with the non-temporal latent reads (ms)
-// 4p+1 0.2871 (shipped), 4p+2 0.2874, 3p+2 0.2886, 3p+1 0.2895, 5p+1 0.2925, 2p+1 0.299, 6p+1 0.314, p+1 0.312, 8p+2 0.355.
-#ifndef BF_DMA_A_
-#define BF_DMA_A_ 4
-#define BF_DMA_B_ 1
-#endif
-constexpr int BF_DMA_A = BF_DMA_A_, BF_DMA_B = BF_DMA_B_;
+// The 14 LDS-DMA pieces of the next step are issued one per second gap (1, 3, ..., 27).  Same-box sweeps of the backward at C2 with the
+// pieces as 7 pairs, pair p in gap A p + B (cycles per step): 3p+1 3360, 5p+1 3325, 2p+1 3565, p+1 3814 (back-to-back pieces cost more
+// each), 8p+1 3860 and 3p+24 4044 (the last pieces land after the hand-over barrier); single pieces against the best pairs (4p+1):
+// 2620 -> 2581 cycles per step.
 // Round 6: the step loop unrolled over the two LDS stages (the stage a step reads is a compile-time constant).  With `cur` a run-time
 // variable every step computed its stage bases again -- by the disassembly 39 scalar instructions in ONE block at the loop head (two
 // stage offsets by multiplication, three 64-bit row pointers from the step number, fourteen LDS destinations of the DMA pieces) and 26
 // v_add_u32 (stage base + lane offset in front of the LDS reads whose immediate field cannot hold an offset into the second stage) --
 // ~65 of the ~300 instructions a wave issues per step, on the ONE issue port a single wave per SIMD has, most of them with the matrix
 // pipe idle.  Now: a second set of lane offsets for the second stage (18 registers), the row pointers advanced by their stride, the
-// LDS destination formed by the `s_add_u32 m0, ...` that writes M0 anyway.  -DBF_STATIC_STAGES=0 = round 5's loop.
-#ifndef BF_STATIC_STAGES
-#define BF_STATIC_STAGES 1
-#endif
-#ifndef BF_GATE_AHEAD
-#define BF_GATE_AHEAD 1      // the ReLU gate's compare one MFMA gap ahead of its select (see the gate below); 0 = both in one gap
-#endif
-#ifndef BF_DMA_SINGLE
-#define BF_DMA_SINGLE 1      // round 6: the 14 LDS-DMA pieces of a step one per second gap (1, 3, ..., 27) instead of 7 pairs in gaps 1, 5, ..., 25: 2620 -> 2581 cycles per step
-#endif
-#ifndef BF_RING
-#define BF_RING 12           // fragment ring (divides 72); the prefetch distance is BF_RING - 1 MFMAs
-#endif
+// LDS destination formed by the `s_add_u32 m0, ...` that writes M0 anyway.
+constexpr int BF_RING = 12;      // fragment ring (divides 72); the prefetch distance is BF_RING - 1 MFMAs
 
 // two LDS-DMA pieces whose LDS destinations are base + l0 / base + l1: the addition IS the write of M0
 __device__ __forceinline__ void glds16_x2_add(const void* sbase0, const void* sbase1, unsigned voff0, unsigned voff1, unsigned base,
@@ -128,7 +111,7 @@ __device__ __forceinline__ void glds16_x2_add(const void* sbase0, const void* sb
       : "s"(sbase0), "s"(sbase1), "v"(voff0), "v"(voff1), "s"(base), "s"(l0), "s"(l1)
       : "memory", "m0", "scc");
 }
-// single pieces of the same (BF_DMA_SINGLE)
+// single pieces of the same
 __device__ __forceinline__ void glds16_add(const void* sbase, unsigned voff, unsigned base, unsigned l0) {
   asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" : : "s"(sbase), "v"(voff), "s"(base), "s"(l0) : "memory", "m0", "scc");
 }
@@ -200,7 +183,7 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
   const int srow = lane >> 4;                         // row within the 4-row group
   const int pc = lane & 15;                           // physical 16-B chunk the lane's data lands in
   unsigned voff_d[6], voff_c[2];                      // per-lane source byte offsets relative to the step's first row
-  unsigned loff_d[6], loff_c[2];                      // wave-uniform LDS byte offsets inside a stage
+  unsigned loff_d[6];                                 // wave-uniform LDS byte offsets inside a stage
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     const int inst = w + 4 * i, sub = inst >> 3, row = 4 * (inst & 7) + srow;
@@ -213,11 +196,9 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     const int inst = w + 4 * i, row = 4 * inst + srow;
     const int ch = pc ^ (((row & 3) << 2) | ((row >> 2) & 3));
     voff_c[i] = (unsigned)(row * (a.n_p * 2) + ch * 16);
-    loff_c[i] = (unsigned)__builtin_amdgcn_readfirstlane(2 * BF_DXH_BYTES + inst * 1024);
   }
   typedef __attribute__((address_space(3))) char* lptr_t;
   const unsigned smem_base = (unsigned)(uintptr_t)(lptr_t)smem;
-#if BF_STATIC_STAGES
   // LDS layout of this form: [dx_hat stage 0 | dx_hat stage 1 | x stage 0 | x stage 1 | c stage 0 | c stage 1] (24 + 24 + 24 + 24 + 8 + 8
   // KiB) instead of two contiguous stages: the 16-bit immediate offset of an LDS read then reaches BOTH stages of an image family from
   // one set of lane offsets (row reads and transposed reads of dx_hat: 0 ... 48 KiB; x: 48 ... 96 KiB from a second set of eight; c: from
@@ -236,27 +217,15 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
       if ((k & 1) == 0) glds16_add(pd, voff_d[k >> 1], stage_base_d[stage], loff_d[k >> 1]);
       else glds16_add(px, voff_d[k >> 1], stage_base_d[stage], loff_x[k >> 1]);
     } else {
+      // the latent is read exactly once: non-temporal policy, so that it does not displace the dx_hat / x tiles the
+      // 24 column-tile workgroups of a row range share in L2 (same-box A/B: backward -4 %, -9...15 % together with the
+      // forward's non-temporal latent stores)
       glds16_add_nt(pcl, voff_c[k - 12], stage_base_c[stage], loff_cs[k - 12]);
     }
   };
   auto dma_pair_at = [&](int p, const bf16_t* pd, const bf16_t* px, const bf16_t* pcl, int stage) {
     if (p < 6) glds16_x2_add(pd, px, voff_d[p], voff_d[p], stage_base_d[stage], loff_d[p], loff_x[p]);
     else glds16_x2_add_nt(pcl, pcl, voff_c[0], voff_c[1], stage_base_c[stage], loff_cs[0], loff_cs[1]);
-  };
-#endif
-  // piece pair p (0..6) of the step whose first row is row0, into stage `stage`
-  auto dma_pair = [&](int p, int64_t row0, int stage) {
-    const unsigned buf = smem_base + stage * BF_STAGE_BYTES;
-    if (p < 6) {
-      glds16_x2(a.dxh + row0 * BF_D, a.xb + row0 * BF_D, voff_d[p], voff_d[p], buf + loff_d[p],
-                buf + BF_DXH_BYTES + loff_d[p]);
-    } else {
-      const bf16_t* gc = a.c + row0 * a.n_p + n0;
-      // the latent is read exactly once: non-temporal policy, so that it does not displace the dx_hat / x tiles the
-      // 24 column-tile workgroups of a row range share in L2 (same-box A/B: backward -4 %, -9...15 % together with the
-      // forward's non-temporal latent stores)
-      glds16_x2_nt(gc, gc, voff_c[0], voff_c[1], buf + loff_c[0], buf + loff_c[1]);
-    }
   };
 
   // ---- loop-invariant per-lane LDS read offsets (everything else folds into instruction immediates)
@@ -285,7 +254,6 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     const int col = 32 * w + 16 * g + 4 * p;
     return dual_off(4 * ah + q + 8, col >> 3) + (col & 7) * 2;
   }();
-#if BF_STATIC_STAGES
   // lane offsets of the x images (transposed reads) and of the c images in the layout above; opaque, or they are folded back into
   // `toff + constant` and rebuilt by a v_add_u32 in front of every read
   int toffX[8], coffC0 = coff0 + 4 * BF_DXH_BYTES, coffC1 = coff1 + 4 * BF_DXH_BYTES;
@@ -295,7 +263,6 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     asm volatile("" : "+v"(toffX[i]));
   }
   asm volatile("" : "+v"(coffC0), "+v"(coffC1));
-#endif
   typedef __attribute__((ext_vector_type(8))) short s16x8;
   auto tr_pair = [&](const char* p0, const char* p1) -> bf16x8 {
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, p0));
@@ -309,22 +276,11 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
   // stage, so no step starts with an exposed LDS round trip.  RING divides 72, which keeps every ring slot static.
   constexpr int RING = BF_RING, DIST = RING - 1;
   static_assert(72 % RING == 0, "ring slots must be static across steps");
-  auto load_frag = [&](const char* img_d, int i) -> bf16x8 {
-    // A-operand fragment of MFMA i (0..71) of the step whose stage image starts at img_d:
+  auto load_frag_s = [&](auto stage_tag, int i) -> bf16x8 {
+    // A-operand fragment of MFMA i (0..71) of the step in stage ST (a constant) of the interleaved layout:
     //   i in [ 0,24): dc += dx_hat(rows; ds_read_b128)      . W^T fragment i (registers)
     //   i in [24,48): dW[dt] += dx_hat^T (transposed reads) . c fragment s      (dt = (i-24)/2, s = i&1)
     //   i in [48,72): dW[dt] += x^T (transposed reads)      . dpre fragment s   (dpre made from dc in gaps 30..45)
-    if (i < 24) {
-      return *reinterpret_cast<const bf16x8*>(img_d + (i >> 3) * 8192 + roff[i & 7]);
-    } else {
-      const char* img = i < 48 ? img_d : img_d + BF_DXH_BYTES;
-      const int tt = i < 48 ? i - 24 : i - 48, dt = tt >> 1, sk = tt & 1;
-      const char* b = img + (dt >> 2) * 8192 + sk * 4096;
-      return tr_pair(b + toff[2 * (dt & 3)], b + toff[2 * (dt & 3) + 1]);
-    }
-  };
-#if BF_STATIC_STAGES
-  auto load_frag_s = [&](auto stage_tag, int i) -> bf16x8 {      // load_frag of stage ST (a constant) in the interleaved layout
     constexpr int ST = decltype(stage_tag)::value;
     if (i < 24) {
       return *reinterpret_cast<const bf16x8*>(smem + ST * BF_DXH_BYTES + (i >> 3) * 8192 + roff[i & 7]);
@@ -339,7 +295,6 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     const char* b = smem + ST * BF_C_BYTES + half * 4096;
     return tr_pair(b + coffC0, b + coffC1);
   };
-#endif
   // dc starts at (1/M)/scale: the L1 term sign(c)/M of d loss / d c, so the gate needs no add.  The dc chain is issued
   // as VGPR-form MFMAs (inline asm): the gate reads dc with plain VALU, and hipcc no longer parks a dW accumulator in
   // VGPRs to make room for it (that cost 48 v_accvgpr moves per step).
@@ -394,14 +349,9 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
   db_acc = 0.f;
   if (step_begin < step_end) {
-#if BF_STATIC_STAGES
     const int64_t r0 = (int64_t)step_begin * BF_BM;
 #pragma unroll
     for (int p = 0; p < 7; ++p) dma_pair_at(p, a.dxh + r0 * BF_D, a.xb + r0 * BF_D, a.c + r0 * a.n_p + n0, 0);
-#else
-#pragma unroll
-    for (int p = 0; p < 7; ++p) dma_pair(p, (int64_t)step_begin * BF_BM, 0);
-#endif
   }
   // make hipcc retire the W^T fragment loads HERE: otherwise it places its vmcnt waits for them inside the loop,
   // where they would also wait for the (untracked) LDS-DMA of the next step and serialise copy and compute
@@ -409,19 +359,11 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
   for (int kk = 0; kk < 24; ++kk) asm volatile("" : "+v"(wfrag[kk]));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-#if BF_STATIC_STAGES
 #pragma unroll
   for (int i = 0; i <= DIST; ++i) ring[i] = load_frag_s(std::integral_constant<int, 0>{}, i);     // includes gap 0 of the first step
   cf[0] = load_c_s(std::integral_constant<int, 0>{}, 0);
   cf[1] = load_c_s(std::integral_constant<int, 0>{}, 1);
-#else
-#pragma unroll
-  for (int i = 0; i <= DIST; ++i) ring[i] = load_frag(smem, i);     // includes gap 0 of the first step
-  cf[0] = tr_pair(smem + 2 * BF_DXH_BYTES + coff0, smem + 2 * BF_DXH_BYTES + coff1);
-  cf[1] = tr_pair(smem + 2 * BF_DXH_BYTES + 4096 + coff0, smem + 2 * BF_DXH_BYTES + 4096 + coff1);
-#endif
   if (a.clk) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
-#if BF_STATIC_STAGES
   // rows fetched during a step: those of the step after it (the last step re-copies its own rows into the idle stage instead of
   // branching around the DMA) -- as running pointers, advanced by one step's stride while a later step exists
   const int64_t nrow_first = (int64_t)(step_begin + 1 < step_end ? step_begin + 1 : step_begin) * BF_BM;
@@ -435,47 +377,10 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     using NxtT = std::integral_constant<int, CUR ^ 1>;
     f32x16 dc;
     bool gate_cur = false, gate_next = false;
-#else
-  int cur = 0;
-  for (int step = step_begin; step < step_end; ++step) {
-    // the last step re-copies its own rows into the idle stage instead of branching around the DMA
-    const int64_t next_row0 = (int64_t)(step + 1 < step_end ? step + 1 : step) * BF_BM;
-    const char* img_d = smem + cur * BF_STAGE_BYTES;
-    const char* nxt_d = smem + (cur ^ 1) * BF_STAGE_BYTES;
-    f32x16 dc;
-    bool gate_cur = false, gate_next = false;
-#endif
 
 #pragma unroll
     for (int i = 0; i < 72; ++i) {
       const bf16x8 fa = ring[i % RING];
-#ifdef BF_PROXY16
-      // TIMING PROXY ONLY (tools/build_variant.sh proxy16 -DBF_PROXY16; results are WRONG): every 32x32x16 MFMA replaced by two
-      // 16x16x32 MFMAs on the same operand registers and a quarter each of the same accumulator -- the same FLOPs, the same LDS
-      // and register traffic, the other MFMA shape: what clock / time would a 16x16x32 backward get under the chip's power limit?
-      typedef __attribute__((ext_vector_type(4))) float f32x4_;
-#define BF_TWO16(C, A, Bv, ODD)                                                                                   \
-  do {                                                                                                             \
-    f32x4_ q0_ = (ODD) ? __builtin_shufflevector(C, C, 4, 5, 6, 7) : __builtin_shufflevector(C, C, 0, 1, 2, 3);      \
-    f32x4_ q1_ = (ODD) ? __builtin_shufflevector(C, C, 12, 13, 14, 15) : __builtin_shufflevector(C, C, 8, 9, 10, 11); \
-    q0_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, Bv, q0_, 0, 0, 0);                                            \
-    q1_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, Bv, q1_, 0, 0, 0);                                            \
-    if (ODD) { C[4] = q0_[0]; C[5] = q0_[1]; C[6] = q0_[2]; C[7] = q0_[3]; C[12] = q1_[0]; C[13] = q1_[1]; C[14] = q1_[2]; C[15] = q1_[3]; } \
-    else { C[0] = q0_[0]; C[1] = q0_[1]; C[2] = q0_[2]; C[3] = q0_[3]; C[8] = q1_[0]; C[9] = q1_[1]; C[10] = q1_[2]; C[11] = q1_[3]; }       \
-  } while (0)
-      if (i == 0) {
-        dc = cinit;
-#pragma unroll
-        for (int z = 8; z < 16; ++z) dc[z] = cinit[z] * (1.0f + 1e-6f * (float)z);      // (keeps the two half-chains distinct: no CSE)
-        BF_TWO16(dc, fa, wfrag[0], false);
-      } else if (i < 24) {
-        BF_TWO16(dc, fa, wfrag[i], (i & 1) != 0);
-      } else if (i < 48) {
-        BF_TWO16(acc[(i - 24) >> 1], fa, cf[i & 1], (i & 1) != 0);
-      } else {
-        BF_TWO16(acc[(i - 48) >> 1], fa, pf[i & 1], (i & 1) != 0);
-      }
-#else
       if (i == 0) {
         asm("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(dc) : "v"(fa), "v"(wfrag[0]), "v"(cinit));
       } else if (i < 24) {
@@ -485,11 +390,9 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
       } else {
         acc[(i - 48) >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, pf[i & 1], acc[(i - 48) >> 1], 0, 0, 0);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
       // ---- gap g = i + 1 (issues while MFMA i occupies the matrix pipe); gap 72 is gap 0 of the next step
       const int g = i + 1;
-#if BF_STATIC_STAGES
       if (g == 72 - DIST) {
         // every read of this stage has been issued and returned, this wave's DMA pieces of the next step have landed
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -499,26 +402,7 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
       if (g == 72 - DIST + 1) cf[1] = load_c_s(NxtT{}, 1);
       if (g + DIST < 72) ring[(g + DIST) % RING] = load_frag_s(CurT{}, g + DIST);
       else ring[(g + DIST) % RING] = load_frag_s(NxtT{}, g + DIST - 72);
-#if BF_DMA_SINGLE
-      if (g >= 1 && (g - 1) % 2 == 0 && (g - 1) / 2 < 14) dma_one_at((g - 1) / 2, nd, nx, nc, CUR ^ 1);      // experiment: one piece per second gap
-#else
-      if (g >= BF_DMA_B && (g - BF_DMA_B) % BF_DMA_A == 0 && (g - BF_DMA_B) / BF_DMA_A < 7)
-        dma_pair_at((g - BF_DMA_B) / BF_DMA_A, nd, nx, nc, CUR ^ 1);
-#endif
-#else
-      if (g == 72 - DIST) {
-        // every read of this stage has been issued and returned, this wave's DMA pieces of the next step have landed
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();              // ... and everybody's
-        cf[0] = tr_pair(nxt_d + 2 * BF_DXH_BYTES + coff0, nxt_d + 2 * BF_DXH_BYTES + coff1);
-      }
-      if (g == 72 - DIST + 1) cf[1] = tr_pair(nxt_d + 2 * BF_DXH_BYTES + 4096 + coff0, nxt_d + 2 * BF_DXH_BYTES + 4096 + coff1);
-      if (g + DIST < 72) ring[(g + DIST) % RING] = load_frag(img_d, g + DIST);
-      else ring[(g + DIST) % RING] = load_frag(nxt_d, g + DIST - 72);
-      if (g >= BF_DMA_B && (g - BF_DMA_B) % BF_DMA_A == 0 && (g - BF_DMA_B) / BF_DMA_A < 7)
-        dma_pair((g - BF_DMA_B) / BF_DMA_A, next_row0, cur ^ 1);
-#endif
-#if BF_GATE_AHEAD
+      if (g >= 1 && (g - 1) % 2 == 0 && (g - 1) / 2 < 14) dma_one_at((g - 1) / 2, nd, nx, nc, CUR ^ 1);      // one piece per second gap
       // Round 6: the gate's COMPARE one gap ahead of its select.  `v_cmp` writes a scalar register and gfx950 wants two wait states before
       // a vector instruction reads it; with compare and select in the same gap (nothing else may move in between: the gaps are fenced)
       // hipcc filled them with `s_nop 1` -- sixteen per step on the wave's one issue port.  One gap apart the distance is there for free.
@@ -533,17 +417,8 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
         pf[s2][j] = (bf16_t)gv;
       }
       if (g >= 29 && g < 45) gate_cur = gate_next;
-#else
-      if (g >= 30 && g < 46) {      // one dpre element per gap: dc register e, gated by c at the same (row, col)
-        const int e = g - 30, s2 = e >> 3, j = e & 7;
-        const float gv = ((float)cf[s2][j] > 0.f) ? dc[e] : 0.f;    // (1/M term rides in the accumulator) bf16 once, when packed
-        db_acc += gv;
-        pf[s2][j] = (bf16_t)gv;
-      }
-#endif
       __builtin_amdgcn_sched_barrier(0);
     }
-#if BF_STATIC_STAGES
     if (step + 2 < step_end) {      // (wave-uniform: scalar pointer arithmetic)
       nd += BF_BM * BF_D;
       nx += BF_BM * BF_D;
@@ -560,10 +435,6 @@ __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) 
     }
     if (step < step_end) step_body(std::integral_constant<int, 0>{}, step);
   }
-#else
-    cur ^= 1;
-  }
-#endif
   if (a.clk) {
     clk_loop += __builtin_amdgcn_s_memtime() - clk_t0;
     clk_real += __builtin_amdgcn_s_memrealtime() - clk_r0;

@@ -37,9 +37,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "search.h"
 #include "stats.h"
 
-#ifndef G2_PERSIST_STATIC
-#define G2_PERSIST_STATIC 512      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
-#endif
+constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
 
 // ------------------------------------------------------------------------------------------
 // error handling
@@ -1558,9 +1556,9 @@ extern "C" int sae_dist_poll(sae_ctx* c) {
 // thousands of static output tiles) -- callers that size a per-workgroup output of the functor ask first
 template <int AM, int BM_, class Epi>
 static bool gemm_streams(const GemmArgs& g) {
-  if constexpr (!(G2_STREAM && epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW)) return false;
+  if constexpr (!(epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW)) return false;
   if (g_no_stream || g_force_gemm128 || g.nbm % 2 != 0 || g.nbn % 2 != 0) return false;
-  if (G2S_STATIC && g.ktiles % 2 != 0) return false;       // (the static-stage K loop walks the K tiles in pairs: gemm256s.h)
+  if (g.ktiles % 2 != 0) return false;                     // (the static-stage K loop walks the K tiles in pairs: gemm256s.h)
   return !g.dyn && g.splits == 1 && g.tail_tiles == 0 && g.ktiles == g.ktiles0 && g.ktiles >= 2 && g.seg1_gate == nullptr && g.lda == g.ldb &&
          (g.nbm / 2) * (g.nbn / 2) >= 4 * G2_PERSIST_STATIC;
 }
@@ -1581,12 +1579,12 @@ static int launch_gemm_stream(const GemmArgs& g, const Epi& epi, hipStream_t s) 
 
 template <int AM, int BM_, class Epi>
 static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
-  if constexpr (G2_STREAM && epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW) {
+  if constexpr (epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW) {
     if (gemm_streams<AM, BM_, Epi>(g)) return launch_gemm_stream(g, epi, s);
   }
   if (!g_force_gemm128 && g.nbm % 2 == 0 && g.nbn % 2 == 0) {   // both output dimensions are multiples of 256
     auto kern256 = gemm256_bf16_kernel<AM, BM_, Epi>;
-    constexpr bool a3 = G2_A3 && epi_deep_a_ring<Epi>::value;     // (gemm256.h: three A slots + two B slots)
+    constexpr bool a3 = epi_deep_a_ring<Epi>::value;     // (gemm256.h: three A slots + two B slots)
     constexpr int lds256 = a3 ? G2_A3_LDS_BYTES : (epi_rounds_first<Epi>::value && G2_BF16_LDS_BYTES > G2_LDS_BYTES) ? G2_BF16_LDS_BYTES : G2_LDS_BYTES;
     static_assert(G2_A3_LDS_BYTES >= G2_BF16_LDS_BYTES && G2_A3_LDS_BYTES >= G2_LDS_BYTES, "the epilogues reuse the ring's LDS");
     LDS_ATTR(kern256, lds256, g_device);
@@ -1625,13 +1623,13 @@ static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
 
 template <class Epi>
 static bool gemm8_streams(const Gemm8Args& g) {
-  if constexpr (!(G2_STREAM && epi_stream<Epi>::value)) return false;
+  if constexpr (!epi_stream<Epi>::value) return false;
   return !g_no_stream && g.ktiles >= 2 && g.lda == g.ldb && g.nbm * g.nbn >= 4 * G2_PERSIST_STATIC;
 }
 
 template <class Epi>
 static int launch_gemm8(const Gemm8Args& g, const Epi& epi, hipStream_t s) {
-  if constexpr (G2_STREAM && epi_stream<Epi>::value) {
+  if constexpr (epi_stream<Epi>::value) {
     if (gemm8_streams<Epi>(g)) {
       auto kerns = gemm256s_fp8_kernel<Epi>;
       LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);

@@ -31,33 +31,6 @@
 
 // STAMP: diagnostic build (bench.py --dbg 65): s_memtime / s_memrealtime around the tile loop per wave into a.stamps[wg][wave][8]
 // ([3] iterations, [4] loop cycles, [5] loop time in 10 ns ticks, [6] prologue cycles, [7] whole-kernel cycles).
-#ifndef FF2_KO
-#define FF2_KO 0
-#endif
-#ifndef FF2_EPI_PACKED
-#define FF2_EPI_PACKED 1     // 1 = the packed residual arithmetic of the no-mask path (v_pk_add / v_pk_fma on pairs)
-#endif
-#ifndef FF2_L1_SUNK
-#define FF2_L1_SUNK 0        // 1 = round 5's plain `l1_it += cv` (A/B: tools/build_variant.sh l1sunk -DFF2_L1_SUNK=1)
-#endif
-#ifndef FF2_EEDD
-#define FF2_EEDD 0
-#endif
-#ifndef FF2_SPLIT_ELEM
-#define FF2_SPLIT_ELEM 1     // round 6: a pair's latent arithmetic over four gaps, three vector instructions each (see the slot loop): -4.6 % loop cycles
-#endif
-#ifndef FF2_DMA_SPREAD
-#define FF2_DMA_SPREAD 1     // round 6: the six LDS-DMA pieces one per gap, four gaps apart (see the slot loop): loop 1969 -> 1892 cycles
-#endif
-#ifndef FF2_PAIR_ROUND
-#define FF2_PAIR_ROUND 1     // round 6: the rounding of S to bf16 (CPU autocast's GEMM output) for TWO elements by one v_cvt_pk_bf16_f32, brought back
-#endif                       // to fp32 by a shift / a mask: 3 vector instructions per pair instead of 4, the same bits (0 = one cvt + shift per element)
-#ifndef FF2_PAIR_FRAGS
-#define FF2_PAIR_FRAGS 1     // round 6: encoder fragments requested two at a time, every fourth slot: the second MFMA of a pair needs no s_waitcnt of
-#endif                       // its own (LDS reads return in order) -- 12 waits per iteration less on the wave's one issue port (0 = one per even slot)
-#ifndef FF2_PACKED
-#define FF2_PACKED 0         // 1 = the packed form below: 91 instead of 111 vector instructions per iteration and NOT faster (profiles/r05_ab_fwd_packed_valu.txt)
-#endif
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 template <typename T, bool PAD, bool STAMP = false>
@@ -74,21 +47,14 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   unsigned long long clk_k0 = 0, clk_t0 = 0, clk_r0 = 0, clk_t1 = 0;
   if (STAMP) clk_k0 = __builtin_amdgcn_s_memtime();
 
-#ifndef FF2_PRESCAN
-#define FF2_PRESCAN 1
-#endif
-#ifndef FF2_SCAN_EARLY
-#define FF2_SCAN_EARLY 1     // the -1.0 scan of x used in place: 1 = here in the prologue, as the fragments arrive (under the memory latency);
-#endif                       // 0 = while the staging image is filled (first form of round 5: +1.3 k cycles in the epilogue)
+  // the -1.0 scan of x used in place runs here in the prologue, as the fragments arrive (under the memory latency); while the staging image
+  // is filled (first form of round 5) it cost +1.3 k cycles in the epilogue
   typedef __attribute__((ext_vector_type(2))) unsigned short us2_t;
   constexpr unsigned MASK_BITS2 = std::is_same<T, bf16_t>::value ? 0xBF80BF80u : 0xBC00BC00u;     // -1.0 twice, bf16 / fp16
-  constexpr bool SCAN_EARLY = FF2_PRESCAN && FF2_SCAN_EARLY && !PAD && std::is_same<T, bf16_t>::value;
+  constexpr bool SCAN_EARLY = !PAD && std::is_same<T, bf16_t>::value;
   bool wany_early = false;     // (wave-uniform) some 16-bit word of this wave's 32 x 384 block of a.xb reads -1.0
 
   bf16x8 xfrag[24];
-#ifdef FF2_BIAS_V1
-  if (t < 2 * FF_BN) bias_s[t] = a.bias[t];
-#endif
   // ---- LDS-DMA plan of a W^T tile (as in fwd_fused.h)
   unsigned voff_t[6], loff_t[6];
 #pragma unroll
@@ -115,27 +81,15 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   for (int q = 0; q < 3; ++q)                       // prologue: W^T tiles 0, 1, 2 into slots 0, 1, 2
 #pragma unroll
     for (int p = 0; p < 3; ++p) dma_pair(p, q <= last ? q : last, q);
-#ifndef FF2_BIAS_V1
   // The first two tiles' biases by LDS-DMA like every later pair's (round 5).  As `bias_s[t] = a.bias[t]` this was a load, an
   // `s_waitcnt vmcnt(0)` and an LDS write in wave 0 -- behind that wave's 24 x loads: it sat out a whole memory latency before it issued
-  // its share of the W^T tiles, and the other three waves waited for it at the barrier (the disassembly showed it; -DFF2_BIAS_V1 = that form).
+  // its share of the W^T tiles, and the other three waves waited for it at the barrier (the disassembly showed it).
   static_assert(2 * FF_BN == 64, "one 4-byte piece per lane of wave 0");
   if (w == 0) glds4(a.bias, (unsigned)(lane * 4), (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_base + FF_FIXED_LDS)));
-#endif
   {
-#ifdef FF2_KO_XSAME      // knock-out (results wrong): every workgroup reads block 0's x -- the prologue with x served by the L2 instead of HBM
-    const bf16_t* xp = a.xb + (int64_t)(32 * w + arow) * FF_D + 8 * ah;
-#else
     const bf16_t* xp = a.xb + mrow * FF_D + 8 * ah;
-#endif
-#ifdef FF2_KO_XLOAD      // knock-out (results wrong): the same 24 KB per wave as fully coalesced 16-byte loads -- does the access pattern cost?
-    const bf16_t* xc = a.xb + m0 * FF_D + lane * 8;
-#pragma unroll
-    for (int kk = 0; kk < 24; ++kk) xfrag[kk] = *reinterpret_cast<const bf16x8*>(xc + 512 * kk);
-#else
 #pragma unroll
     for (int kk = 0; kk < 24; ++kk) xfrag[kk] = *reinterpret_cast<const bf16x8*>(xp + 16 * kk);
-#endif
   }
   // ring slot 3 and the staging image are read (times zero / as zeros) by the first iteration's decoder phase
   for (int i = t; i < FF_WT_BYTES / 16; i += 256) reinterpret_cast<u32x4*>(smem + 3 * FF_WT_BYTES)[i] = u32x4{0u, 0u, 0u, 0u};
@@ -197,12 +151,8 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   // a 2-way conflict on every c^T fragment read, and the 8-byte drain reads (4 rows per 32 lanes) hit rows r and r + 2 on the
   // same chunks.  SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE read 0.18.  With f, the 16 rows of either group give 16
   // distinct (row parity, chunk) pairs, 8 consecutive rows still give 8 distinct chunks, and rows r, r + 2 of a drain piece read
-  // chunks of different parity.  -DFF2_SWZ_V1 restores the old image for A/B runs.
-#ifdef FF2_SWZ_V1
-  auto swz = [](int row) { return row & 7; };
-#else
+  // chunks of different parity.
   auto swz = [](int row) { return (row & 7) ^ ((row >> 1) & 1) ^ ((row >> 4) & 1); };
-#endif
   int boff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) boff[i] = arow * 128 + (((4 * (i >> 1) + 2 * (i & 1) + ah) ^ swz(arow)) << 4);
@@ -216,11 +166,7 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
     doff1 = drow_l * 128 + (((4 * tl + 2 * s + 1) ^ swz(drow_l)) << 4) + 8 * u;
   }
   // pieces 2 and 3 hold rows 16..31 of the row block: bit 4 of the row flips the chunk's low bit = bit 4 of the byte offset
-#ifdef FF2_SWZ_V1
-  auto dpiece = [](int off, int) { return off; };
-#else
   auto dpiece = [](int off, int p) { return (p & 2) ? (off ^ 16) : off; };
-#endif
   bf16_t* cdrain = a.c + (m0 + drow_l) * a.n_p + dch * 8;
 
   float l1_acc = 0.f;
@@ -306,7 +252,6 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
     const int64_t dst_rstride = j >= 2 ? (int64_t)a.n_p : 0;
     f32x4 bq[4];
     float l1_it = 0.f;
-    f32x2_t l1_pk = {0.f, 0.f}, pr = {0.f, 0.f};
     unsigned se_u = 0u;
     float se_t0 = 0.f, se_t1 = 0.f;
     bf16x8 cw;
@@ -315,29 +260,18 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
     // 48 MFMA slots: EVEN slot i = decoder MFMA i / 2 of tile j-1 (m = 12 ks + 3 mb + dtl: accumulators rotate), ODD slot i =
     // encoder MFMA i / 2 of tile j+1 (a chain through one accumulator: interleaved with the decoder its dependent issue is
     // never back to back).  Fragments are requested >= 6 slots ahead.
-    // (FF2_PACKED: static_for -- the slot index as a template constant: `#pragma unroll` gives up silently above LLVM's size
-    // threshold, and with the packed form's few added lines the loop stayed rolled and indexed every register array dynamically,
-    // 1.8 KB of scratch per lane.  The shipped element-wise form keeps round 4's pragma loop: bit-identical code.)
-#if FF2_PACKED || defined(FF2_WAITSTAMP) || !FF2_L1_SUNK
-#define FF2_STATIC_LOOP 1
+    // (static_for -- the slot index as a template constant: `#pragma unroll` gives up silently above LLVM's size threshold; a
+    // few added lines once left the loop rolled, every register array indexed dynamically, 1.8 KB of scratch per lane.)
     static_for<0, 48>([&](auto slot_tag) {
       constexpr int i = decltype(slot_tag)::value;
-#else
-#define FF2_STATIC_LOOP 0
-#pragma unroll
-    for (int i = 0; i < 48; ++i) {
-#endif
       // ---- fragment prefetch
-#if FF2_PAIR_FRAGS
       // encoder fragments k = i/2 + 3 and i/2 + 4 together, every fourth slot (consumed at slots i + 7 and i + 9; the ring holds 8)
-      // -- the LATER one first: the wait in front of the earlier MFMA (its fragment is the younger request) then covers both
+      // -- the LATER one first: the wait in front of the earlier MFMA (its fragment is the younger request) then covers both: the second
+      // MFMA of a pair needs no s_waitcnt of its own (LDS reads return in order), 12 waits per iteration less on the wave's one issue port
       if ((i & 3) == 0 && i <= 40) {
         if (i / 2 + 4 <= 23) ring[(i / 2 + 4) % RING] = enc_frag(SLOT_E, i / 2 + 4);
         ring[(i / 2 + 3) % RING] = enc_frag(SLOT_E, i / 2 + 3);
       }
-#else
-      if ((i & 1) == 0 && i <= 40) ring[(i / 2 + 3) % RING] = enc_frag(SLOT_E, i / 2 + 3);         // encoder k = i/2 + 3 (slot i + 7)
-#endif
       if (i == 42 || i == 44 || i == 46) ring[(i - 42) / 2] = enc_frag(SLOT_EN, (i - 42) / 2);      // k = 0..2 of the NEXT iteration
       if (i == 15 || i == 16 || i == 17) Afr[i - 12] = dec_a(SLOT_D, i - 12);                       // k-step 1 (decoder MFMAs 12..23)
       if (i == 45 || i == 46 || i == 47) Afr[i - 45] = dec_a(SLOT_DN, i - 45);                      // k-step 0 of the next phase
@@ -370,7 +304,6 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
 #endif
         __builtin_amdgcn_sched_barrier(0);
       }
-#if FF2_DMA_SPREAD
       // Round 6: the six LDS-DMA pieces of tile j+3 ONE per gap and four gaps apart -- two right behind this iteration's hand-over, four
       // in the first gaps of the NEXT iteration (that body issues its predecessor's pieces 2..5: slot and source of phase PH - 1) --
       // instead of three pairs in gaps 41 / 43 / 45.  A piece issued right behind another waits for the address path (the backward's
@@ -378,50 +311,23 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
       // 32-cycle MFMA.  The slot is free for all of them (every wave has passed the hand-over behind which tile j-1 was last read);
       // they land a thousand cycles before the next hand-over's vmcnt wait, which still counts them (they are older than the latent
       // store it lets pass).  First iteration: the early pieces re-copy tile 2 into slot 2 (as the prologue did); after the last one
-      // the pieces not issued are redundant copies of the last tile.
+      // the pieces not issued are redundant copies of the last tile.  Loop 1969 -> 1892 cycles.
       if (i == 41 || i == 45) dma_one((i - 41) / 4, jt, SLOT_DMA);
       if (i == 1 || i == 5 || i == 9 || i == 13) dma_one(2 + (i - 1) / 4, j + 2 <= last ? j + 2 : last, (PH + 2) & 3);
-#else
-      if (i == 41 || i == 43 || i == 45) dma_pair((i - 41) / 2, jt, SLOT_DMA);
-#endif
       if ((PH & 1) == 0 && i == 46 && w == 0) {
         const int jb = j + 2 <= a.ntiles - 2 ? j + 2 : a.ntiles - 2;
         glds4(a.bias + (int64_t)jb * FF_BN, (unsigned)(lane * 4),
               (unsigned)__builtin_amdgcn_readfirstlane((int)(smem_base + FF_FIXED_LDS + ((j + 2) & (FF_BIAS_RING_TILES - 1)) * FF_BN * 4)));
       }
-#if FF2_PACKED
-      // latent elements in PAIRS (round 5): pair p = elements 2 p, 2 p + 1 of S at the gaps 4 + 4 p (both rounded to bf16 by ONE
-      // v_cvt_pk_bf16_f32, then back to fp32: two shifts) and 6 + 4 p (bias by one v_pk_add_f32, two max, the L1 sum by one
-      // v_pk_add_f32, the pair's bf16 by one v_cvt_pk).  The loop is bound by the vector instructions it issues between its MFMAs
-      // (113 per iteration by the disassembly: 32 adds, 24 conversions, 16 shifts, 16 max, 16 AGPR reads); this form issues 24 fewer.
-      // Same values per element; the L1 partial sums associate differently (two chains instead of one).
-      if (i >= 4 && i <= 32 && (i & 3) == 0) {
-        const int e = (i - 4) >> 1;                      // S register e <-> column n = (e&3) + 8 (e>>2) + 4 h
-        const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{S[e], S[e + 1]}, bf16x2));
-        pr = f32x2_t{__uint_as_float(u << 16), __uint_as_float(u & 0xFFFF0000u)};
-      }
-      if (i >= 6 && i <= 34 && (i & 3) == 2) {
-        const int e = (i - 6) >> 1;
-        // rounded to bf16 BEFORE the fp32 bias add (CPU autocast).  (inline asm: hipcc scalarises this one packed add into two
-        // v_add_f32 although both operands sit in aligned register pairs)
-        f32x2_t sv;
-        const f32x2_t bp = {bq[e >> 2][e & 3], bq[e >> 2][(e & 3) + 1]};
-        asm("v_pk_add_f32 %0, %1, %2" : "=v"(sv) : "v"(pr), "v"(bp));
-        // ReLU on the BITS (signed integer max with 0: negative floats, -0.0 included, are negative integers): fmaxf on the
-        // output of the asm above costs a second, canonicalising v_max per element
-        sv = f32x2_t{__int_as_float(max(__float_as_int(sv[0]), 0)), __int_as_float(max(__float_as_int(sv[1]), 0))};
-        if (PAD) sv = row_ok ? sv : f32x2_t{0.f, 0.f};
-        l1_pk += sv;
-        cw[e & 7] = (bf16_t)sv[0];
-        cw[(e & 7) + 1] = (bf16_t)sv[1];
-        if ((e & 7) == 6)      // the eight values of k-step e >> 3: one 16-byte chunk of this lane's row
-          *reinterpret_cast<bf16x8*>(cst + PB_W * 16384 + wrow + boff[2 * HF_W + (e >> 3)]) = cw;
-      }
-#elif FF2_SPLIT_ELEM
       // Round 6: the latent arithmetic of a PAIR of elements spread over FOUR consecutive gaps, three vector instructions each, instead of
       // six in each of two even gaps and none in the odd ones.  One wave per SIMD issues in order: a gap with six vector instructions,
       // a fragment read and a wait is ~44 cycles of issue behind a 32-cycle MFMA, and the light gap next to it cannot give the time back.
-      // Same operations on the same values in the same order (the L1 additions stay e = 0, 1, 2, ...).
+      // Same operations on the same values in the same order (the L1 additions stay e = 0, 1, 2, ...): -4.6 % loop cycles.
+      // Both elements are rounded to bf16 (CPU autocast's GEMM output) by ONE v_cvt_pk_bf16_f32 and brought back to fp32 by a shift / a
+      // mask: 3 vector instructions per pair instead of 4, the same bits.
+      // The L1 additions are opaque instructions: written as `l1_it += cv`, LLVM SANK the sixteen additions of three of the four unrolled
+      // bodies to the loop latch -- 51 dependent v_add_f32 back to back at the back edge with no MFMA between them (~200 cycles per four
+      // iterations with the matrix pipe idle).  As asm the additions stay in their MFMA gap; same operands, same order, same sum.
       if (i >= 4 && i <= 35) {
         const int p = (i - 4) >> 2, ph = (i - 4) & 3, e0 = 2 * p;       // pair p = elements e0, e0 + 1 (S register e <-> column n = (e&3) + 8 (e>>2) + 4 h)
         if (ph == 0) {
@@ -443,34 +349,6 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
             *reinterpret_cast<bf16x8*>(cst + PB_W * 16384 + wrow + boff[2 * HF_W + (e0 >> 3)]) = cw;
         }
       }
-#else
-      // latent element e at gap 4 + 2 e
-      if (i >= 4 && i <= 34 && (i & 1) == 0) {
-        const int e = (i - 4) >> 1;                      // S register e <-> column n = (e&3) + 8 (e>>2) + 4 h
-#if FF2_PAIR_ROUND
-        if ((e & 1) == 0) {      // both elements of the pair rounded by ONE conversion (round to nearest even, like bf16_round)
-          const unsigned u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{S[e], S[e + 1]}, bf16x2));
-          pr = f32x2_t{__uint_as_float(u << 16), __uint_as_float(u & 0xFFFF0000u)};
-        }
-        float cv = fmaxf(pr[e & 1] + bq[e >> 2][e & 3], 0.f);           // rounded to bf16 BEFORE the fp32 bias add (CPU autocast)
-#else
-        float cv = fmaxf(bf16_round(S[e]) + bq[e >> 2][e & 3], 0.f);    // rounded to bf16 BEFORE the fp32 bias add (CPU autocast)
-#endif
-        if (PAD) cv = row_ok ? cv : 0.f;
-#if FF2_L1_SUNK
-        l1_it += cv;
-#else
-        // Round 6 (the disassembly): written as `l1_it += cv`, LLVM SANK the sixteen additions of three of the four unrolled bodies to
-        // the loop latch -- the values stay live in sixteen registers each and 51 dependent v_add_f32 run back to back at the back edge
-        // with no MFMA between them (~200 cycles per four iterations with the matrix pipe idle).  As an opaque instruction the addition
-        // stays in its MFMA gap; same operands, same order, same sum.
-        asm volatile("v_add_f32 %0, %0, %1" : "+v"(l1_it) : "v"(cv));
-#endif
-        cw[e & 7] = (bf16_t)cv;
-        if ((e & 7) == 7)      // the eight values of k-step e >> 3: one 16-byte chunk of this lane's row
-          *reinterpret_cast<bf16x8*>(cst + PB_W * 16384 + wrow + boff[2 * HF_W + (e >> 3)]) = cw;
-      }
-#endif
       // two full-line pieces of the finished pair per iteration: LDS reads in one gap, global store 8 gaps later
       if (i == 29 || i == 33) {
         const int p = 2 * (PH & 1) + (i == 33);
@@ -483,13 +361,7 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
         __builtin_nontemporal_store(dr[i == 42], reinterpret_cast<u32x4*>(dst_pair + (int64_t)(8 * p) * dst_rstride));
       }
       __builtin_amdgcn_sched_barrier(0);
-#if FF2_EEDD
-      // (experiment, round 6: the two MFMAs of slots 4 q + 2 and 4 q + 3 exchanged -- D E E D D E E D ... -- so that every second encoder MFMA
-      // follows its predecessor in the accumulation chain directly; same operands, same chain order, bit-identical)
-      if ((i & 3) == 0 || (i & 3) == 3) {
-#else
       if ((i & 1) == 0) {
-#endif
         const int m = i / 2, ks = m / 12, mb = (m % 12) / 3, dtl = m % 3;
         acc[4 * dtl + mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Afr[3 * ks + dtl], Bq[(4 * ks + mb) & 3], acc[4 * dtl + mb], 0, 0, 0);
       } else if (i == 1) {
@@ -501,12 +373,8 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
         Snxt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ring[(i / 2) % RING], xfrag[i / 2], Snxt, 0, 0, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-#if FF2_STATIC_LOOP
     });
-#else
-    }
-#endif
-    l1_acc += l1_it + (l1_pk[0] + l1_pk[1]);
+    l1_acc += l1_it + 0.0f;      // (the + 0.0f is an instruction of its own: -0.0 would become +0.0; kept so that the compiled code stays as it was)
   };
   if (STAMP) { clk_t0 = __builtin_amdgcn_s_memtime(); clk_r0 = __builtin_amdgcn_s_memrealtime(); }
   for (int j4 = 0; j4 < a.ntiles; j4 += 4) {            // ntiles is a multiple of 4 (n_p is a multiple of 128)
@@ -549,15 +417,10 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   // Everything but this wave's four youngest vector-memory operations -- the latent stores just above -- must be done: the LDS-DMA
   // pieces of the loop's last iterations still write ring slots that the epilogue's staging image overlays.  (Round 4 waited for
   // vmcnt(0) here and again inside __syncthreads: a drain of those stores with the matrix pipe idle.)
-#ifndef FF2_TAIL_V1
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-#else
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-#endif
 
   unsigned long long clk_e0 = 0, clk_e1 = 0, clk_e2 = 0;
   if (STAMP) clk_e0 = __builtin_amdgcn_s_memtime();      // final half iteration + drain of the last latent pair done
@@ -574,10 +437,7 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   static_assert(128 * FF_DXH_PITCH <= FF_FIXED_LDS, "the dx_hat staging must fit the idle LDS");
   char* stg = smem;                                              // [128 rows][784 B]
   constexpr bool X_VIA_LDS = !PAD && sizeof(T) == 2;
-#ifndef FF2_X_FROM_FRAGS
-#define FF2_X_FROM_FRAGS 1     // tools/build_variant.sh A/B switch: 0 = round 4's reload of x from global memory
-#endif
-  constexpr bool X_FROM_FRAGS = FF2_X_FROM_FRAGS && X_VIA_LDS && std::is_same<T, bf16_t>::value;
+  constexpr bool X_FROM_FRAGS = X_VIA_LDS && std::is_same<T, bf16_t>::value;
   // Round 5 (found by knock-outs, profiles/r05_fwd_residual_knockouts.txt): the residual arithmetic below took 15.8 k cycles per workgroup
   // with the -1.0 test in it and 8.4 k without -- not for the test's instructions (keeping them in the vector unit changed nothing) but for
   // the BRANCH behind it: `if (any lane met a -1.0)` per group of 16 elements ends a basic block, so each of the 12 groups waited for its own
@@ -585,7 +445,7 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   // test moves to where x is staged -- every 16-bit x of the block passes through some lane's registers there exactly once: x ^ bits(-1.0) is
   // zero for a masked entry, a packed unsigned minimum carries it -- one flag per wave rides on the staging barrier, and the block takes
   // either the arithmetic with no test and no branch (one basic block), or, if any of its 128 x 384 entries is masked, the per-group form.
-  // Same additions in the same order either way.  (-DFF2_PRESCAN=0 = the per-group test always.)
+  // Same additions in the same order either way.
   unsigned* mflag = reinterpret_cast<unsigned*>(smem + FF_FIXED_LDS + 64);                         // bias ring: idle since the tile loop
   bool blk_masked = true;
   if (X_FROM_FRAGS && vec_ok && reinterpret_cast<const void*>(a.x) == reinterpret_cast<const void*>(a.xb)) {
@@ -597,18 +457,17 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
 #pragma unroll
     for (int kk = 0; kk < 24; ++kk) {
       *reinterpret_cast<bf16x8*>(srow_w + 32 * kk) = xfrag[kk];
-      if (FF2_PRESCAN && !SCAN_EARLY) {
+      if (!SCAN_EARLY) {
         const u32x4 xw = __builtin_bit_cast(u32x4, xfrag[kk]);
 #pragma unroll
         for (int c = 0; c < 4; ++c) mz = __builtin_elementwise_min(mz, __builtin_bit_cast(us2_t, xw[c] ^ MASK_BITS2));
       }
     }
-    if (FF2_PRESCAN) {
-      const bool wany = SCAN_EARLY ? wany_early : __builtin_amdgcn_ballot_w64((mz[0] == 0) | (mz[1] == 0)) != 0ull;
-      if (lane == 0) mflag[w] = wany ? 1u : 0u;
-    }
+    const bool wany = SCAN_EARLY ? wany_early : __builtin_amdgcn_ballot_w64((mz[0] == 0) | (mz[1] == 0)) != 0ull;
+    if (lane == 0) mflag[w] = wany ? 1u : 0u;
     __syncthreads();
-    if (FF2_PRESCAN) { const u32x4 f = *reinterpret_cast<const u32x4*>(mflag); blk_masked = (f[0] | f[1] | f[2] | f[3]) != 0u; }
+    const u32x4 f = *reinterpret_cast<const u32x4*>(mflag);
+    blk_masked = (f[0] | f[1] | f[2] | f[3]) != 0u;
   } else
   if (X_VIA_LDS && vec_ok) {     // the wave's 32 x rows are one contiguous 24 KiB block: 24 coalesced 16-byte loads per lane
     const char* xblk = reinterpret_cast<const char*>(reinterpret_cast<const T*>(a.x) + m0 * FF_D);
@@ -622,18 +481,15 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
       for (int pc = 0; pc < 4; ++pc) {
         const int off = (p0 + pc) * 1024 + lane * 16, r = off / (FF_D * 2), cb = off - r * (FF_D * 2);
         *reinterpret_cast<u32x4*>(stg + (32 * w + r) * FF_DXH_PITCH + cb) = xr[pc];
-        if (FF2_PRESCAN) {
 #pragma unroll
-          for (int c = 0; c < 4; ++c) mz = __builtin_elementwise_min(mz, __builtin_bit_cast(us2_t, xr[pc][c] ^ MASK_BITS2));
-        }
+        for (int c = 0; c < 4; ++c) mz = __builtin_elementwise_min(mz, __builtin_bit_cast(us2_t, xr[pc][c] ^ MASK_BITS2));
       }
     }
-    if (FF2_PRESCAN) {
-      const bool wany = __builtin_amdgcn_ballot_w64((mz[0] == 0) | (mz[1] == 0)) != 0ull;
-      if (lane == 0) mflag[w] = wany ? 1u : 0u;
-    }
+    const bool wany = __builtin_amdgcn_ballot_w64((mz[0] == 0) | (mz[1] == 0)) != 0ull;
+    if (lane == 0) mflag[w] = wany ? 1u : 0u;
     __syncthreads();
-    if (FF2_PRESCAN) { const u32x4 f = *reinterpret_cast<const u32x4*>(mflag); blk_masked = (f[0] | f[1] | f[2] | f[3]) != 0u; }
+    const u32x4 f = *reinterpret_cast<const u32x4*>(mflag);
+    blk_masked = (f[0] | f[1] | f[2] | f[3]) != 0u;
   }
   if (STAMP) clk_e1 = __builtin_amdgcn_s_memtime();      // x staged (and published)
   // (vec_ok is a run-time, block-uniform flag: tested inside the loops it ends a basic block per group of 16 elements -- every group waits
@@ -675,18 +531,14 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
         for (int k = 0; k < 4; ++k)
           xv[k] = PIPE ? xq[g & 1][k]
                        : (X_VIA_LDS ? *reinterpret_cast<const Tx4*>(srow + (dbase + 8 * k) * 2) : *reinterpret_cast<const Tx4*>(xrow + dbase + 8 * k));
-#ifndef FF2_EPI_V1
         if (!PAD) {
           // The lean form (round 4; round 5: which of its two halves runs is decided per BLOCK while x is staged, see X_FROM_FRAGS above).
           // Without masked entries: e = bf16(x_hat) - x, plain += e e (one fma), dx_hat = bf16(2 e) -- 6 vector instructions per element
-          // instead of round 3's 13 (-DFF2_EPI_V1).  With: the same plus four selects / adds per element.  Both keep plain and the masked
+          // instead of round 3's 13.  With: the same plus four selects / adds per element.  Both keep plain and the masked
           // entries' squared error (msq) and leave the masked MSE numerator as plain - msq.
-          // (FF2_KO: knock-outs of this phase for the stamp builds of round 5 -- results become wrong: 1 = no squared-error chain,
-          //  2 = no stores of dx_hat into the staging image, 4 = no -1.0 test, 8 = x taken as zero instead of read from LDS)
           if constexpr (NOTEST && X_VIA_LDS) {      // the block holds no masked entry (scanned while x was staged): no test, no branch
-#if FF2_EPI_PACKED
             if constexpr (std::is_same<T, bf16_t>::value) {
-              // The same in PAIRS (switch, measured in round 5: profiles/r05_fwd_epilogue.txt): one v_cvt_pk rounds both accumulators, two
+              // The same in PAIRS (measured in round 5: profiles/r05_fwd_epilogue.txt): one v_cvt_pk rounds both accumulators, two
               // shifts each bring x_hat and x to fp32, e = x_hat - x, plain += e e and 2 e as ONE packed instruction each (inline asm:
               // hipcc scalarises them), one v_cvt_pk for the output.  The squared-error sum runs in two chains (even / odd elements):
               // fp32 round-off against the element-wise form.
@@ -713,25 +565,23 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
               for (int k = 0; k < 4; ++k) *reinterpret_cast<uint2*>(srow + (dbase + 8 * k) * 2) = ow[k];
               continue;
             }
-#endif
             bf16x4 o[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
-                const float xf = (FF2_KO & 8) ? 0.0f : (float)xv[k][q];
+                const float xf = (float)xv[k][q];
                 const float e = bf16_round(acc[4 * dtl + mb][4 * k + q]) - xf;
-                if (!(FF2_KO & 1)) plain = __builtin_fmaf(e, e, plain);
+                plain = __builtin_fmaf(e, e, plain);
                 o[k][q] = (bf16_t)(e + e);
               }
 #pragma unroll
             for (int k = 0; k < 4; ++k) *reinterpret_cast<bf16x4*>(srow + (dbase + 8 * k) * 2) = o[k];
             continue;
           }
-#ifndef FF2_MASK_BRANCHY
           // A block WITH masked entries (real padding; or 16-bit data that did not come through the loader's guard, host_convert.c:5-7,
           // and hits -1.0 by rounding: N(0,1) rounded to bf16 does so in 0.14 % of its entries, i.e. in three of four 16 x 64 groups):
-          // selects, no branch -- four more instructions per element than the form above.  Round 4's form (-DFF2_MASK_BRANCHY) asked the
+          // selects, no branch -- four more instructions per element than the form above.  Round 4's form asked the
           // wave per group of 16 whether any lane met a -1.0 and then took the entries out one by one under exec masks: right when that is
           // rare, 17.7 k cycles for this phase on the bench's own data before its generator got the loader's guard.
           bf16x4 o[4];
@@ -740,52 +590,20 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
           for (int k = 0; k < 4; ++k)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const float xf = (FF2_KO & 8) ? 0.0f : (float)xv[k][q];
+              const float xf = (float)xv[k][q];
               const float e = bf16_round(acc[4 * dtl + mb][4 * k + q]) - xf;
-              const bool mk = !(FF2_KO & 4) && (xf == -1.0f);
+              const bool mk = xf == -1.0f;
               const float em = mk ? e : 0.0f, ek = mk ? 0.0f : e;
-              if (!(FF2_KO & 1)) plain = __builtin_fmaf(e, e, plain);
+              plain = __builtin_fmaf(e, e, plain);
               msq = __builtin_fmaf(em, em, msq);
               nm_i += mk ? 1u : 0u;
               o[k][q] = (bf16_t)(ek + ek);
             }
           nmask += (float)nm_i;
-#else
-          bool any_m = false;
-          bf16x4 o[4];
-          float e[16];
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const float xf = (FF2_KO & 8) ? 0.0f : (float)xv[k][q];
-              e[4 * k + q] = bf16_round(acc[4 * dtl + mb][4 * k + q]) - xf;
-              if (!(FF2_KO & 1)) plain = __builtin_fmaf(e[4 * k + q], e[4 * k + q], plain);
-              if (!(FF2_KO & 4)) any_m |= (xf == -1.0f);
-              o[k][q] = (bf16_t)(e[4 * k + q] + e[4 * k + q]);
-            }
-          if (__builtin_amdgcn_ballot_w64(any_m) != 0ull) {        // wave-uniform, almost never taken
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-              for (int q = 0; q < 4; ++q)
-                if ((float)xv[k][q] == -1.0f) {
-                  nmask += 1.0f;
-                  msq = __builtin_fmaf(e[4 * k + q], e[4 * k + q], msq);
-                  o[k][q] = (bf16_t)0.0f;
-                }
-          }
-#endif
-          if (FF2_KO & 2) {        // (keep the values alive without the LDS stores)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) asm volatile("" :: "v"(o[k]));
-            continue;
-          }
 #pragma unroll
           for (int k = 0; k < 4; ++k) *reinterpret_cast<bf16x4*>(srow + (dbase + 8 * k) * 2) = o[k];
           continue;
         }
-#endif
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           bf16x4 o;
@@ -825,7 +643,7 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
     }
   }
   };
-  if (X_VIA_LDS && FF2_PRESCAN && vec_ok && !blk_masked) residual(std::true_type{}); else residual(std::false_type{});
+  if (X_VIA_LDS && vec_ok && !blk_masked) residual(std::true_type{}); else residual(std::false_type{});
   if (STAMP) clk_e2 = __builtin_amdgcn_s_memtime();      // residual arithmetic done, dx_hat in the staging image (not yet published)
   __syncthreads();
   {   // the wave's 32 rows of dx_hat are one contiguous 24 KiB block: 24 fully coalesced 16-byte stores per lane
@@ -837,14 +655,11 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
     }
   }
   plain += plain2[0] + plain2[1];
-#ifndef FF2_TAIL_V1
   // Round 5: the four block sums in ONE exchange -- wave sums, one LDS-only barrier, thread 0 adds the four waves' values in
   // block_sum_256's order (bit-identical) -- through the bias ring (idle since the tile loop; the staging image above is still being
   // read by the dx_hat stores).  Round 4's tail stood behind a __syncthreads (= a drain of the 24 dx_hat stores per lane) and took four
-  // block sums of two more such barriers each: the stamps count the epilogue's cycles one for one (-DFF2_TAIL_V1 = that form).
-#ifndef FF2_EPI_V1
+  // block sums of two more such barriers each: the stamps count the epilogue's cycles one for one.
   if (!PAD && vec_ok) sq = plain - msq;          // (vec_ok is block-uniform)
-#endif
   float* red = reinterpret_cast<float*>(smem + FF_FIXED_LDS);
   {
     const float v0 = wave_sum(l1_acc), v1 = wave_sum(sq), v2 = wave_sum(plain), v3 = wave_sum(nmask);
@@ -855,17 +670,6 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
   const float sqs = ((red[1] + red[5]) + red[9]) + red[13];
   const float pls = ((red[2] + red[6]) + red[10]) + red[14];
   const float nms = ((red[3] + red[7]) + red[11]) + red[15];
-#else
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);
-  const float l1s = block_sum_256(l1_acc, red);
-#ifndef FF2_EPI_V1
-  if (!PAD && vec_ok) sq = plain - msq;          // (vec_ok is block-uniform)
-#endif
-  const float sqs = block_sum_256(sq, red + 8);
-  const float pls = block_sum_256(plain, red + 16);
-  const float nms = block_sum_256(nmask, red + 24);
-#endif
   if (STAMP && lane == 0) {
     unsigned long long* o = a.stamps + ((int64_t)wg * 4 + w) * 8;
     const unsigned long long te = __builtin_amdgcn_s_memtime();

@@ -12,7 +12,7 @@
 //   Epilogue: the tile leaves as four 128x128 sub-tiles through fp32 LDS, two at a time, one per 256-thread half,
 //   through the same functors as gemm.h (their block reductions are 256-thread-group local).
 //   Round 6: when both operands have the same layout the K loop runs on v_mfma_f32_16x16x32_bf16 instead -- 8x4 tiles of 16x16 per wave, 64
-//   MFMAs of 16 cycles per K tile, one piece of side work per MFMA (G2_M16: row x row, the decoder; G2_M16K: k-major x k-major through the
+//   MFMAs of 16 cycles per K tile, one piece of side work per MFMA (M16: row x row, the decoder; M16K: k-major x k-major through the
 //   half ring, the weight gradient) -- with the same images, swizzles, rings and epilogues, bit-identical output; the mixed forms keep 32x32x16.
 #pragma once
 #include "gemm.h"
@@ -57,7 +57,7 @@ __device__ __forceinline__ int g2h_piece(int w, int h, int q) { return (w >> 2) 
 // ---- accumulators -> the epilogues' LDS images, for both K-loop forms ------------------------------------------------------------
 // 32x32x16 loop: acc[i][j] = one 32x32 tile as f32x16.  The K loops feed the MFMA with the operands swapped -- D^T = B A^T -- so a lane holds
 // output row 32 i + lane % 32 and, per group of four accumulator registers, FOUR CONSECUTIVE COLUMNS 32 j + 8 g + 4 (lane / 32).
-// 16x16x32 loop (G2_M16): acc[i16][j16] = one 16x16 tile as f32x4 -- lane (r16 = lane % 16, q = lane / 16) holds columns 16 j16 + 4 q .. + 3
+// 16x16x32 loop (M16): acc[i16][j16] = one 16x16 tile as f32x4 -- lane (r16 = lane % 16, q = lane / 16) holds columns 16 j16 + 4 q .. + 3
 // of row 16 i16 + r16.  Either way a lane writes 4 consecutive columns per store; the functor-side reads do not change.
 typedef __attribute__((ext_vector_type(4))) float g2_f32x4;
 __device__ __forceinline__ void g2_put_f32(const f32x16 (&acc)[4][2], float* dst0, int lane) {
@@ -201,13 +201,10 @@ __device__ __forceinline__ void g2_epilogue_bf16(Acc& acc, char* smem, int bm, i
 // half the store instructions of a store-issue-bound tail (MI355X_MICROARCH.md: 8-byte accesses run at 0.54-0.70 x the 16-byte
 // rate).  A thread owns columns 8 (tl % 16) .. + 7 of rows tl / 16 + 16 it (it = 0..7) of each 128-column pass; Epi::prefetch
 // keeps its 4-column granularity (two per call of apply8), batches of NB / 2 calls keep the prefetched registers the same.
-#ifndef G2_WIDE8
-#define G2_WIDE8 1           // tools/build_variant.sh A/B switch: 0 = every functor through the 4-column form
-#endif
 template <class E, class = void>
 struct epi_wide8 { static constexpr bool value = false; };
 template <class E>
-struct epi_wide8<E, std::void_t<decltype(E::WIDE8)>> { static constexpr bool value = G2_WIDE8 && E::WIDE8; };
+struct epi_wide8<E, std::void_t<decltype(E::WIDE8)>> { static constexpr bool value = E::WIDE8; };
 
 template <bool FINAL_BARRIER, class Epi, class Acc>
 __device__ __forceinline__ void g2_epilogue_bf16_w8(Acc& acc, char* smem, int bm, int bn, int split, Epi& epi) {
@@ -261,22 +258,6 @@ template <class E>
 struct epi_deep_a_ring<E, std::void_t<decltype(E::DEEP_A_RING)>> { static constexpr bool value = E::DEEP_A_RING; };
 constexpr int G2_A3_LDS_BYTES = 5 * G2_OPER_BYTES;      // 3 A slots + 2 B slots = 160 KiB: the whole LDS of a CU
 
-#ifndef G2_A3
-#define G2_A3 1              // tools/kbench A/B switch: 0 = no three-deep A ring (Epi::DEEP_A_RING ignored)
-#endif
-#ifndef G2_M16
-#define G2_M16 1             // tools/kbench A/B switch: 0 = the row x row K loop on v_mfma_f32_32x32x16_bf16 like the other operand modes
-#endif
-#ifndef G2_RUNPTR
-#define G2_RUNPTR 1          // tools/kbench A/B switch: 0 = the 16x16x32 loops form tile kt + 2's source pointers anew per K tile
-#endif
-#ifndef G2_M16K
-#define G2_M16K 1            // tools/kbench A/B switch: 0 = the k-major x k-major K loop (weight gradient, half ring) on v_mfma_f32_32x32x16_bf16
-#endif
-#ifndef G2_HALF_KMAJOR
-#define G2_HALF_KMAJOR 1     // tools/kbench A/B switch: 0 = the k-major GEMMs hand their stages over whole, like the others
-#endif
-
 // One 256x256 output tile (workgroup-level id `blk` of nblk).  g.nbm / g.nbn count 256-wide tiles here.
 template <int AMODE, int BMODE, bool PERSIST, class Epi>
 __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* smem, int blk, int nbm, int nbn, int ktiles0,
@@ -310,14 +291,6 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
   int bm, bn;
   tile_coords(id, nbm, nbn, bm, bn, g.group_m > 0 ? g.group_m : GEMM_GROUP_M);
 
-#ifdef G2X_PHASE
-  // experiment: half of the FIRST round's workgroups start late by G2X_PHASE x 8128 cycles, so that the CUs' epilogue bursts
-  // (all of them otherwise write their 128 KiB tiles at the same moment) fall under the other half's K loops
-  if ((int)blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {
-#pragma unroll 1
-    for (int i = 0; i < G2X_PHASE; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
 #ifdef G2X_STAMP
   unsigned long long st0 = __builtin_readcyclecounter(), st1 = 0, st2 = 0;
 #endif
@@ -331,9 +304,9 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
   // Row-major x row-major (the decoder and every other GEMM whose operands both have K contiguous): the K loop runs on
   // v_mfma_f32_16x16x32_bf16 -- 64 MFMAs of 16 cycles per K tile instead of 32 of 32, with the fragment reads and DMA pieces spread one per
   // MFMA as in the streaming form (gemm256s.h, where the shape is described): same images, same swizzle, same ring, bit-identical output.
-  constexpr bool M16 = G2_M16 && AMODE == OP_ROW && BMODE == OP_ROW;
+  constexpr bool M16 = AMODE == OP_ROW && BMODE == OP_ROW;
   g2_f32x4 acc16[8][4];
-  if constexpr (M16 || (G2_M16K && G2_HALF_KMAJOR && AMODE == OP_KMAJOR && BMODE == OP_KMAJOR)) {
+  if constexpr (M16 || (AMODE == OP_KMAJOR && BMODE == OP_KMAJOR)) {
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -374,7 +347,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
   // A tile t + 2 is requested at the START of tile t (into the slot tile t - 1 left at its hand-over): two tiles of lead;
   // B tile t + 2 right after hand-over t, as before.  With two whole stages a wave waited ~770 cycles per K tile for its
   // own pieces at this shape (tools/kbench -DG2X_WAITSTAMP).
-  constexpr bool A3 = G2_A3 && epi_deep_a_ring<Epi>::value;
+  constexpr bool A3 = epi_deep_a_ring<Epi>::value;
   auto issue_aa = [&](int kt, int slot, int qp) {
     const unsigned dst = smem_base + slot * G2_OPER_BYTES + piece0 + 2 * qp * 1024;
     glds16_x2(a_ptr(kt), a_ptr(kt), voff_a[2 * qp], voff_a[2 * qp + 1], dst, dst + 1024);
@@ -387,7 +360,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
   // two stages are handed over in k HALVES -- a ring of four 32 KiB slots, three half tiles (1.5 K tiles) of lead for every
   // piece instead of one tile.  With whole-stage hand-over a wave waited ~410 cycles per K tile for its own pieces
   // (tools/kbench -DG2X_WAITSTAMP); with halves ~20, and the GEMM is 5-7 % faster with bit-identical output.
-  constexpr bool HALF = !A3 && G2_HALF_KMAJOR && AMODE == OP_KMAJOR && BMODE == OP_KMAJOR;
+  constexpr bool HALF = !A3 && AMODE == OP_KMAJOR && BMODE == OP_KMAJOR;
   if constexpr (HALF) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -401,7 +374,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
   // swizzle (chunk ^ ((row & 3) << 2 | (row >> 2 & 3))) the block enters as an XOR of address bits 5-7 and the second read is the first's
   // address ^ 16, + 1024: two lane offsets per operand serve every read; the half is an immediate (8192 h).  Conflict-free: the two groups of a
   // 32-lane service half sit 8 rows apart, their swizzles differ in chunk bit 1, each covers eight distinct 16-byte chunks.
-  constexpr bool M16K = G2_M16K && HALF;
+  constexpr bool M16K = HALF;
   unsigned ka0 = 0, ka1 = 0, kb0 = 0, kb1 = 0;
   if constexpr (M16K) {
     const int G = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
@@ -439,7 +412,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
   // (16x16x32 loops) the source tile origins of K tile min(kt + 2, last) as RUNNING pointers: a_ptr() / b_ptr() are a segment select and a
   // 64-bit multiply by the leading dimension each -- 43 scalar instructions in one MFMA gap per K tile, at the same moment in both waves of a
   // SIMD (they leave the same barrier): here a compare, a select and a 64-bit add
-  constexpr bool RUN2 = G2_RUNPTR && ((M16 && A3) || M16K);
+  constexpr bool RUN2 = (M16 && A3) || M16K;
   const bf16_t* pa2 = nullptr;
   const bf16_t* pb2 = nullptr;
   const bf16_t* pa2_seg1 = nullptr;
@@ -490,14 +463,10 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
       for (int q = 0; q < 4; ++q) issue(clampk(kt_begin + 1), 1, q);
     }
   }
-#ifdef G2X_PROLOGUE_WAIT_ALL
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
   // only tile 0 has to be there (this wave's 8 older DMA instructions); tile 1 keeps landing under tile 0's MFMAs and is
   // waited for at the first hand-over barrier, like every later tile
   if constexpr (HALF) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");   // the first HALF of tile 0 (4 of this wave's 16 DMA instructions)
   else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#endif
   __syncthreads();
   // (M16) fragments of the 16x16x32 MFMA: 16 rows x 32 k -- lane (r16 = lane % 16, q = lane / 16) reads the 16-byte chunk q + 4 ks of row
   // r16 of its row block; the chunk swizzle (chunk ^ (row >> 1 & 7)) does not depend on the block.  A fragments in a ring of four (block
@@ -620,22 +589,7 @@ __device__ __forceinline__ void gemm256_tile(const GemmArgs& g, Epi& epi, char* 
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-#ifdef G2_PROXY16
-        // TIMING PROXY ONLY (kbench -DG2_PROXY16; results WRONG): each 32x32x16 MFMA as two 16x16x32 on the same operand registers and a
-        // quarter each of the accumulator -- what would the tile-form K loops (weight gradient, decoder) gain from the other shape?
-        {
-          typedef __attribute__((ext_vector_type(4))) float f32x4_;
-          f32x16& C = acc[m >> 1][m & 1];
-          f32x4_ q0 = (kk & 1) ? f32x4_{C[4], C[5], C[6], C[7]} : f32x4_{C[0], C[1], C[2], C[3]};
-          f32x4_ q1 = (kk & 1) ? f32x4_{C[12], C[13], C[14], C[15]} : f32x4_{C[8], C[9], C[10], C[11]};
-          q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], q0, 0, 0, 0);
-          q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], q1, 0, 0, 0);
-          if (kk & 1) { C[4] = q0[0]; C[5] = q0[1]; C[6] = q0[2]; C[7] = q0[3]; C[12] = q1[0]; C[13] = q1[1]; C[14] = q1[2]; C[15] = q1[3]; }
-          else { C[0] = q0[0]; C[1] = q0[1]; C[2] = q0[2]; C[3] = q0[3]; C[8] = q1[0]; C[9] = q1[1]; C[10] = q1[2]; C[11] = q1[3]; }
-        }
-#else
         acc[m >> 1][m & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], acc[m >> 1][m & 1], 0, 0, 0);   // D^T = B A^T
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (HALF) {
           // half u = (kt, kk / 2).  Even K step: the fragments of the odd one.  Odd K step: hand-over H_u -- half u + 1 has

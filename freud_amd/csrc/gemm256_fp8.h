@@ -21,10 +21,6 @@
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
-#ifndef G8_SPREAD
-#define G8_SPREAD 1          // tools/build_variant.sh A/B switch: 0 = the K loops' side work clustered in front of each 8-MFMA group (rounds 2-5)
-#endif
-
 struct Gemm8Args {
   const unsigned char* A;   // [rows_a][lda] fp8, K contiguous
   const unsigned char* B;   // [rows_b][ldb] fp8, K contiguous
@@ -84,7 +80,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_fp8_kernel(Gemm8Args g, Epi ep
   };
   // A3 (Epi::DEEP_A_RING, the decoder: K = n_dict, the fp8 latent streams from HBM): three A slots at LDS 0, two B slots
   // behind them; A tile kt + 2 is requested at the START of tile kt, B tile kt + 2 after hand-over kt -- gemm256.h.
-  constexpr bool A3 = G2_A3 && epi_deep_a_ring<Epi>::value;
+  constexpr bool A3 = epi_deep_a_ring<Epi>::value;
   auto issue_aa = [&](int kt, int slot, int qp) {
     const unsigned dst = smem_base + slot * G2_OPER_BYTES + piece0 + 2 * qp * 1024;
     const unsigned char* src = a_base + (int64_t)kt * 128;
@@ -119,7 +115,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_fp8_kernel(Gemm8Args g, Epi ep
   for (int j = 0; j < 2; ++j) fb[0][j] = g8_frag(smem + (A3 ? 3 : 1) * G2_OPER_BYTES, 64 * wn + 32 * j, 0, lane);
 
   int cur = 0, aslot = 0;
-#if G8_SPREAD
   // source origins of K tiles min(kt + 1, last) and min(kt + 2, last), carried (an add per K tile instead of a clamp + multiply per DMA call)
   const unsigned char* r1a = a_base + (int64_t)clampk(1) * 128;
   const unsigned char* r1b = b_base + (int64_t)clampk(1) * 128;
@@ -137,7 +132,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_fp8_kernel(Gemm8Args g, Epi ep
     const unsigned dst = smem_base + (3 + slot) * G2_OPER_BYTES + piece0 + 2 * qp * 1024;
     glds16_x2(src, src, voff_b[2 * qp], voff_b[2 * qp + 1], dst, dst + 1024);
   };
-#endif
   for (int kt = 0; kt < g.ktiles; ++kt) {
     const int anext = aslot == 2 ? 0 : aslot + 1, aprev = anext == 2 ? 0 : anext + 1;
     const char* sa = A3 ? smem + aslot * G2_OPER_BYTES : smem + cur * G2_STAGE_BYTES;
@@ -150,7 +144,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_fp8_kernel(Gemm8Args g, Epi ep
       const char* xa = s == 0 ? sa : na;
       const char* xb = s == 0 ? sb : nb;
       const int xs = s == 0 ? 1 : 0;
-#if G8_SPREAD
       // Side work one piece per MFMA gap (round 6: clustered in front of the group -- two DMA calls with their address arithmetic, the hand-over
       // and two fragment reads, ~45 instructions -- it sat in BOTH waves of a SIMD at the same moment, right behind the barrier they share, and a
       // 64-cycle MFMA covers 16 issue slots, not 45).  MFMA m = 2 i + j; behind it: m odd -> A fragment i of the next step (its registers are
@@ -179,47 +172,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_fp8_kernel(Gemm8Args g, Epi ep
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-#else
-      if (s == 0) {            // second half of tile kt+1's pieces (its first half left right after the last hand-over)
-        if constexpr (A3) {    // ... A3: A tile kt+2 into the slot tile kt-1 left
-          issue_aa(clampk(kt + 2), aprev, 0);
-          issue_aa(clampk(kt + 2), aprev, 1);
-        } else {
-          issue(clampk(kt + 1), cur ^ 1, 2);
-          issue(clampk(kt + 1), cur ^ 1, 3);
-        }
-      } else {
-        if constexpr (A3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // all but A tile kt+2 (this wave's 4 youngest DMA instructions)
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile kt+1 have landed
-        __syncthreads();                                    // ... and everybody's; every read of this stage has returned
-        if constexpr (A3) {
-          issue_bb(clampk(kt + 2), cur, 0);
-          issue_bb(clampk(kt + 2), cur, 1);
-        } else {
-          issue(clampk(kt + 2), cur, 0);
-          issue(clampk(kt + 2), cur, 1);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) fb[xs][j] = g8_frag(xb, 64 * wn + 32 * j, xs, lane);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb[s][j], fa[i], acc[i][j], 0, 0, 0, 0, 0, 0);   // D^T = B A^T (g2_epilogue)
-        fa[i] = g8_frag(xa, 128 * wm + 32 * i, xs, lane);     // its registers are free: next step's fragment i
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
     }
-#if G8_SPREAD
     {
       const int64_t step = kt + 3 <= kt_last ? 128 : 0;
       r1a = r2a; r1b = r2b;
       r2a += step; r2b += step;
     }
-#endif
     cur ^= 1;
     aslot = anext;
   }
@@ -235,7 +193,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_fp8_kernel(Gemm8Args g, Epi ep
 
 template <class Epi>
 constexpr int g8_lds_bytes() {
-  return G2_A3 && epi_deep_a_ring<Epi>::value ? G2_A3_LDS_BYTES
+  return epi_deep_a_ring<Epi>::value ? G2_A3_LDS_BYTES
          : epi_rounds_first<Epi>::value && G2_BF16_LDS_BYTES > G2_LDS_BYTES ? G2_BF16_LDS_BYTES : G2_LDS_BYTES;
 }
 
@@ -281,13 +239,11 @@ __global__ __launch_bounds__(512, 2) void gemm256s_fp8_kernel(Gemm8Args g, Epi e
     for (int j = 0; j < 2; ++j) fb[0][j] = g8_frag(smem + G2_OPER_BYTES, 64 * wn + 32 * j, 0, lane);
     f32x16 acc[4][2];        // (started from a zero MFMA source by the first K step of every tile: gemm256s.h)
     int cur = 0;
-#if G8_SPREAD
     // origins of the stream's K tiles kt + 1 and kt + 2 (carried: a select and an add per K tile instead of two per DMA group)
     const unsigned char* q1a = a_cur + 128;
     const unsigned char* q1b = b_cur + 128;
     const unsigned char* q2a = a_cur + 256;
     const unsigned char* q2b = b_cur + 256;
-#endif
     for (;;) {
       const int nblk = blk + gridDim.x;
       const bool more = nblk < ntiles;
@@ -297,9 +253,7 @@ __global__ __launch_bounds__(512, 2) void gemm256s_fp8_kernel(Gemm8Args g, Epi e
       const unsigned char* b_nxt = more ? g.B + (int64_t)(bn2 * G2_BN) * g.ldb : b_cur + (int64_t)(nk - 2) * 128;
       auto pa = [&](int j) { return j < nk ? a_cur + (int64_t)j * 128 : a_nxt + (int64_t)(j - nk) * 128; };
       auto pb = [&](int j) { return j < nk ? b_cur + (int64_t)j * 128 : b_nxt + (int64_t)(j - nk) * 128; };
-#if G8_SPREAD
       if (nk == 2) { q2a = a_nxt; q2b = b_nxt; }      // (two K tiles per output tile: stream tile 2 is the NEXT output tile's first, known only now)
-#endif
       const int row_w = bm * G2_BM + 128 * wm, col_l = bn * G2_BN + 64 * wn + c8;
       typename Epi::SPre pre0[4];
       auto ktile = [&](auto first_tag, int kt) {
@@ -313,7 +267,6 @@ __global__ __launch_bounds__(512, 2) void gemm256s_fp8_kernel(Gemm8Args g, Epi e
           const char* xa = s == 0 ? sa : na;
           const char* xb = s == 0 ? sb : nb;
           const int xs = s == 0 ? 1 : 0;
-#if G8_SPREAD
           // (one piece of side work per MFMA gap and carried source origins: see gemm256_fp8_kernel and gemm256s.h)
 #pragma unroll
           for (int m = 0; m < 8; ++m) {
@@ -347,70 +300,13 @@ __global__ __launch_bounds__(512, 2) void gemm256s_fp8_kernel(Gemm8Args g, Epi e
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-#else
-          if (s == 0) {
-            issue(pa(kt + 1), pb(kt + 1), cur ^ 1, 2);
-            issue(pa(kt + 1), pb(kt + 1), cur ^ 1, 3);
-          } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            issue(pa(kt + 2), pb(kt + 2), cur, 0);
-            issue(pa(kt + 2), pb(kt + 2), cur, 1);
-          }
-#pragma unroll
-          for (int j = 0; j < 2; ++j) fb[xs][j] = g8_frag(xb, 64 * wn + 32 * j, xs, lane);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-#ifdef G8S_PROXY16
-              // TIMING PROXY ONLY (tools/build_variant.sh g8sproxy16 -DG8S_PROXY16; results WRONG): each 32x32x64 MFMA as two 16x16x128 on
-              // the same operand registers and a quarter each of the accumulator -- would the smaller shape lift the clock for e4m3 too?
-              {
-                typedef __attribute__((ext_vector_type(4))) float f32x4_;
-                f32x16& C = acc[i][j];
-                f32x4_ q0 = s ? f32x4_{C[4], C[5], C[6], C[7]} : f32x4_{C[0], C[1], C[2], C[3]};
-                f32x4_ q1 = s ? f32x4_{C[12], C[13], C[14], C[15]} : f32x4_{C[8], C[9], C[10], C[11]};
-                q0 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[s][j], fa[i], q0, 0, 0, 0, 0, 0, 0);
-                q1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[s][j], fa[i], q1, 0, 0, 0, 0, 0, 0);
-                if (s) { C[4] = q0[0]; C[5] = q0[1]; C[6] = q0[2]; C[7] = q0[3]; C[12] = q1[0]; C[13] = q1[1]; C[14] = q1[2]; C[15] = q1[3]; }
-                else { C[0] = q0[0]; C[1] = q0[1]; C[2] = q0[2]; C[3] = q0[3]; C[8] = q1[0]; C[9] = q1[1]; C[10] = q1[2]; C[11] = q1[3]; }
-              }
-              if constexpr (false) {
-                if (s == 0) {
-                } else {
-                }
-              } else if constexpr (false) {
-              }
-#else
-              if constexpr (FIRST) {
-                if (s == 0) {
-                  f32x16 zero;
-#pragma unroll
-                  for (int e = 0; e < 16; ++e) zero[e] = 0.f;
-                  acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb[s][j], fa[i], zero, 0, 0, 0, 0, 0, 0);
-                } else {
-                  acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb[s][j], fa[i], acc[i][j], 0, 0, 0, 0, 0, 0);
-                }
-              } else {
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fb[s][j], fa[i], acc[i][j], 0, 0, 0, 0, 0, 0);
-              }
-#endif
-            }
-            fa[i] = g8_frag(xa, 128 * wm + 32 * i, xs, lane);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-#endif
         }
-#if G8_SPREAD
         {   // the stream's tile kt + 3: this output tile's, or the first of the next one's (gemm256s.h)
           const bool wrap = kt + 3 == nk;
           q1a = q2a; q1b = q2b;
           q2a = wrap ? a_nxt : q2a + 128;
           q2b = wrap ? b_nxt : q2b + 128;
         }
-#endif
         cur ^= 1;
       };
       ktile(std::true_type{}, 0);

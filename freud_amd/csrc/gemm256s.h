@@ -39,22 +39,11 @@ struct epi_stream { static constexpr bool value = false; };
 template <class E>
 struct epi_stream<E, std::void_t<decltype(E::STREAM)>> { static constexpr bool value = E::STREAM; };
 
-#ifndef G2S_PRIO
-#define G2S_PRIO 0           // tools/kbench experiment (see the K loop)
-#endif
-#ifndef G2S_STATIC
-#define G2S_STATIC 1         // round 6: the K loop unrolled over the two LDS stages (compile-time stage; K tiles per output tile must be EVEN:
-#endif                       // the host launches the streaming form only then).  0 = round 5's loop with a run-time stage
-#ifndef G2S_RUNPTR
-#define G2S_RUNPTR 1          // the 16x16x32 loop carries the source origins of the stream's K tiles kt + 1 / kt + 2 instead of forming them (a select and
-                              // a 64-bit add per operand and DMA gap, twice per K tile, in both waves of a SIMD at once)
-#endif
-#ifndef G2S_M16
-#define G2S_M16 (G2S_STATIC)  // round 6: the K loop on v_mfma_f32_16x16x32_bf16 (needs the static-stage form).  The chip is power-managed and holds a higher
-#endif                        // clock on this shape: stand-alone, random operands, K = 1280: 5.50 -> 4.97 ms as a timing proxy (profiles/r06_kbench_proxy16.txt)
-#ifndef G2_STREAM
-#define G2_STREAM 1          // tools/build_variant.sh A/B switch: 0 = the K = d GEMMs through gemm256.h's persistent tile form
-#endif
+// The K loop (round 6) is unrolled over the two LDS stages (compile-time stage; K tiles per output tile must be EVEN: the host launches the
+// streaming form only then) and runs on v_mfma_f32_16x16x32_bf16: the chip is power-managed and holds a higher clock on this shape --
+// stand-alone, random operands, K = 1280: 5.50 -> 4.97 ms as a timing proxy (profiles/r06_kbench_proxy16.txt).  It carries the source
+// origins of the stream's K tiles kt + 1 / kt + 2 instead of forming them (a select and a 64-bit add per operand and DMA gap, twice per
+// K tile, in both waves of a SIMD at once).
 
 // The wave's 128x64 accumulator block -> functor, through the wave's own 4 KiB of LDS (see the header).
 //   write: lane (r = lane % 32, h = lane / 32) holds, per (j, g), columns 32 j + 8 g + 4 h .. + 3 of row 32 i + r: 8-byte half
@@ -104,45 +93,12 @@ __device__ __forceinline__ void g2s_epilogue(f32x16 (&acc)[4][2], char* eb, int 
 
 // The same for functors that need the fp32 accumulators (static constexpr bool STREAM_F32: the TopK encoder adds its bias BEFORE the
 // single rounding to bf16, topkautoencoder.py:75 under autocast): one 32x32 MFMA tile (4 KiB of fp32) at a time.
-//   write: lane (r, h), g = 0..3: columns 8 g + 4 h .. + 3 of row r = 16-byte chunk 2 g + h, stored at chunk (2 g + h) ^ f(r),
+//   image: columns 8 g + 4 h .. + 3 (g = 0..3, h = 0, 1) of row r = 16-byte chunk 2 g + h, stored at chunk (2 g + h) ^ f(r),
 //          f(r) = (r & 7) ^ (r >> 2 & 1) (a permutation of 0..7 over 8 consecutive rows: the 8-lane groups of ds_write_b128 are
 //          conflict-free; the 16-lane groups of the reads below -- rows {0,3,5,6} / {1,2,4,7} + 8 k, every second chunk -- too);
 //   read:  lane (rq = lane / 4, cp = lane % 4), q = 0, 1: row rq + 16 q, columns 8 cp .. + 7 = chunks 2 cp and 2 cp + 1.
 // The functor sees s_apply(e = 4 i + 2 j + q, row, col, v0, v1) with col = the lane's 8 columns of the 32-column block j.
-template <class Epi>
-__device__ __forceinline__ void g2s_epilogue_f32(f32x16 (&acc)[4][2], char* eb, int row_w, int col_w, Epi& epi) {
-  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, rq = lane >> 2, cp = lane & 3;
-  auto fsw = [](int row) { return (row & 7) ^ ((row >> 2) & 1); };
-  char* wbase = eb + r * 128;
-  const int wsw = fsw(r);
-  const char* rbase = eb + rq * 128;
-  const int rsw = fsw(rq);           // (row rq + 16: the same low bits)
-  auto write_block = [&](int b) {
-    const int i = b >> 1, j = b & 1;
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<f32x4*>(wbase + (((2 * g + h) ^ wsw) << 4)) =
-          f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-  };
-  write_block(0);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    f32x4 raw[2][2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      raw[q][0] = *reinterpret_cast<const f32x4*>(rbase + q * 2048 + (((2 * cp) ^ rsw) << 4));
-      raw[q][1] = *reinterpret_cast<const f32x4*>(rbase + q * 2048 + (((2 * cp + 1) ^ rsw) << 4));
-    }
-    if (b + 1 < 8) write_block(b + 1);
-    const int i = b >> 1, j = b & 1;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      epi.s_apply(4 * i + 2 * j + q, row_w + 32 * i + 16 * q + rq, col_w + 32 * j + 8 * cp, raw[q][0], raw[q][1]);
-  }
-  epi.s_tile_end(row_w, col_w);
-}
-
-// ---- the same two epilogues for the accumulators of the 16x16x32 K loop (G2S_M16): acc[i16][j16] = one 16x16 tile as f32x4 -- lane
+// ---- the two epilogues for the accumulators of the 16x16x32 K loop: acc[i16][j16] = one 16x16 tile as f32x4 -- lane
 // (r16 = lane % 16, q = lane / 16) holds columns 16 j16 + 4 q .. + 3 of row 16 i16 + r16 (operands swapped as in the 32x32 loop: a lane
 // owns consecutive COLUMNS).  The LDS images the functor-side reads expect are the same; only who writes which 8 (16) bytes changes:
 //   bf16 form: row rr = 16 (i16 & 1) + r16 of the 32-row block, 16-byte chunk 2 j16 + (q >> 1), 8-byte half q & 1;
@@ -251,7 +207,6 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
     typedef __attribute__((address_space(3))) char* lptr_t;
     const unsigned smem_base = (unsigned)(uintptr_t)(lptr_t)smem;
     const unsigned piece0 = (unsigned)__builtin_amdgcn_readfirstlane(4 * w * 1024);
-#if G2S_STATIC
     // Round 6 (the same finding as in bwd_fused.h): with the stage a run-time variable every K tile rebuilt its LDS addresses -- 32 vector
     // additions (stage base + lane offset in front of the fragment reads, whose 16-bit immediate cannot reach the second stage) and ~35
     // scalar instructions (stage bases, DMA destinations) per wave, 2 waves per SIMD.  LDS layout of this form: [A stage 0 | A stage 1 |
@@ -261,6 +216,8 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
       const unsigned dst = smem_base + stage * G2_OPER_BYTES + piece0 + q * 1024;
       glds16_x2(pa, pb, voff[q], voff[q], dst, dst + 2 * G2_OPER_BYTES);
     };
+    // (Lane offsets of the 32x32x16 loop this kernel ran on before round 6.  Nothing reads them any more, but the opaque statement keeps
+    // their 17 instructions in the kernel's prologue: they stay until a change that may alter the compiled kernels takes them out.)
     int offA[4], offB[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
@@ -268,13 +225,10 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
       const int o = r * 128 + ((c ^ ((r >> 1) & 7)) << 4);            // frag_read<OP_ROW>'s offset for base32 = 0
       offA[ks] = o + (128 * wm) * 128;
       offB[ks] = o + (64 * wn) * 128 + 2 * G2_OPER_BYTES;
-      asm volatile("" : "+v"(offA[ks]), "+v"(offB[ks]));             // opaque: kept as registers, not re-derived per read
+      asm volatile("" : "+v"(offA[ks]), "+v"(offB[ks]));
     }
-    auto fragA = [&](int stage, int i, int ks) { return *reinterpret_cast<const bf16x8*>(smem + stage * G2_OPER_BYTES + (32 * i) * 128 + offA[ks]); };
-    auto fragB = [&](int stage, int j, int ks) { return *reinterpret_cast<const bf16x8*>(smem + stage * G2_OPER_BYTES + (32 * j) * 128 + offB[ks]); };
-#if G2S_M16
     // fragments of v_mfma_f32_16x16x32_bf16: 16 rows x 32 k -- lane (r16 = lane % 16, q = lane / 16) reads the 16-byte chunk q + 4 ks of row
-    // r16 of its row block.  The images and their chunk swizzle (chunk ^ (row >> 1 & 7)) are the 32x32 loop's; tools/lds_bank_check.py-style
+    // r16 of its row block.  The images and their chunk swizzle (chunk ^ (row >> 1 & 7)) are those of frag_read<OP_ROW> (gemm.h); tools/lds_bank_check.py-style
     // count for the four 16-lane service groups of ds_read_b128: rows {0-3, 12-15} with chunk c and rows 4-11 with chunk c + 1 hit 16
     // distinct (row parity, chunk) slots for c = 0 and c = 4 -- conflict-free as it stands.
     int offA16[2], offB16[2];
@@ -284,17 +238,10 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
       const int o = r16 * 128 + ((c ^ ((r16 >> 1) & 7)) << 4);
       offA16[ks] = o + (128 * wm) * 128;
       offB16[ks] = o + (64 * wn) * 128 + 2 * G2_OPER_BYTES;
-      asm volatile("" : "+v"(offA16[ks]), "+v"(offB16[ks]));
+      asm volatile("" : "+v"(offA16[ks]), "+v"(offB16[ks]));         // opaque: kept as registers, not re-derived per read
     }
     auto fragA16 = [&](int stage, int i16, int ks) { return *reinterpret_cast<const bf16x8*>(smem + stage * G2_OPER_BYTES + (16 * i16) * 128 + offA16[ks]); };
     auto fragB16 = [&](int stage, int j16, int ks) { return *reinterpret_cast<const bf16x8*>(smem + stage * G2_OPER_BYTES + (16 * j16) * 128 + offB16[ks]); };
-#endif
-#else
-    auto issue = [&](const bf16_t* pa, const bf16_t* pb, int stage, int q) {
-      const unsigned dst = smem_base + stage * G2_STAGE_BYTES + piece0 + q * 1024;
-      glds16_x2(pa, pb, voff[q], voff[q], dst, dst + G2_OPER_BYTES);
-    };
-#endif
     char* eb = smem + 2 * G2_STAGE_BYTES + w * 4096;
     const int rr = lane >> 3, c8 = 8 * (lane & 7);
 
@@ -305,8 +252,6 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
     for (int q = 0; q < 4; ++q) issue(a_cur + GEMM_BK, b_cur + GEMM_BK, 1, q);
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __syncthreads();
-    bf16x8 fa[2][4], fb[2][2];
-#if G2S_M16
     // A fragments: a ring of four (row block t = 8 ks + i16 of the K tile in slot t % 4, requested three row blocks ahead); B fragments:
     // the four column blocks of a K step, double-buffered by K step
     bf16x8 fa16[4], fb16[2][4];
@@ -315,33 +260,18 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
     for (int t3 = 0; t3 < 3; ++t3) fa16[t3] = fragA16(0, t3, 0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) fb16[0][j] = fragB16(0, j, 0);
-#elif G2S_STATIC
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[0][i] = fragA(0, i, 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) fb[0][j] = fragB(0, j, 0);
-#else
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[0][i] = frag_read<OP_ROW>(smem, 128 * wm + 32 * i, 0, lane);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) fb[0][j] = frag_read<OP_ROW>(smem + G2_OPER_BYTES, 64 * wn + 32 * j, 0, lane);
-#endif
 
     // (no zeroing: the first K step of every tile multiplies into a ZERO source -- an inline constant of the MFMA -- instead of into
     // the accumulators: 128 vector moves per wave and tile less in an epilogue that is bound by its vector instructions)
-    f32x16 acc[4][2];
-    int cur = 0;
 #ifdef G2X_STAMP
     unsigned long long st_loop = 0, st_epi = 0, st_tiles = 0;
     const unsigned long long st_k0 = __builtin_readcyclecounter();
 #endif
-#if G2S_M16 && G2S_RUNPTR
     // origins of the stream's K tiles kt + 1 and kt + 2 (nk == 2: tile 2 is the next output tile's first -- set at the top of the tile loop)
     const bf16_t* q1a = a_cur + GEMM_BK;
     const bf16_t* q1b = b_cur + GEMM_BK;
     const bf16_t* q2a = a_cur + 2 * GEMM_BK;
     const bf16_t* q2b = b_cur + 2 * GEMM_BK;
-#endif
     for (;;) {
       // the tile behind this one in the workgroup's walk (none: the stream ends by re-copying this tile's last K tile, harmless)
       const int nblk = blk + gridDim.x;
@@ -350,21 +280,15 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
       if (more) tile_coords(xcd_remap(nblk, ntiles), nbm, nbn, bm2, bn2, group_m);
       const bf16_t* a_nxt = more ? g.A0 + (int64_t)(bm2 * G2_BM) * g.lda : a_cur + (int64_t)(nk - 2) * GEMM_BK;
       const bf16_t* b_nxt = more ? g.B0 + (int64_t)(bn2 * G2_BN) * g.ldb : b_cur + (int64_t)(nk - 2) * GEMM_BK;
-      // K tile j of the stream as seen from this tile: j < nk this tile's, j >= nk the next tile's j - nk
-      auto pa = [&](int j) { return j < nk ? a_cur + (int64_t)j * GEMM_BK : a_nxt + (int64_t)(j - nk) * GEMM_BK; };
-      auto pb = [&](int j) { return j < nk ? b_cur + (int64_t)j * GEMM_BK : b_nxt + (int64_t)(j - nk) * GEMM_BK; };
-#if G2S_M16 && G2S_RUNPTR
       if (nk == 2) { q2a = a_nxt; q2b = b_nxt; }      // (two K tiles per output tile: stream tile 2 is the NEXT output tile's first, known only now)
-#endif
       const int row_w = bm * G2_BM + 128 * wm, col_l = bn * G2_BN + 64 * wn + c8;
       typename Epi::SPre pre0[4];
 #ifdef G2X_STAMP
       const unsigned long long st0 = __builtin_readcyclecounter();
 #endif
 
-      // one K tile of the stream; FIRST: the tile's K tile 0 (its first K step starts the accumulators from zero)
-#if G2S_M16
-      // one K tile on the 16x16x32 shape: 64 MFMAs n = 4 t + j (t = 8 ks + i16: K step and 16-row block, j: 16-column block), one piece of
+      // one K tile of the stream; FIRST: the tile's K tile 0 (its first K step starts the accumulators from zero).
+      // On the 16x16x32 shape: 64 MFMAs n = 4 t + j (t = 8 ks + i16: K step and 16-row block, j: 16-column block), one piece of
       // other work behind each -- the A fragment of row block t + 3 at j == 0 (blocks 13-15 request the NEXT tile's blocks 0-2 from the
       // other stage: after the hand-over), K step 1's B fragments at n = 5..17, the second half of tile kt+1's DMA pieces at n = 1 / 10,
       // the hand-over at n = 50 (every read of this stage is issued by then: row block 15 was requested at n = 48), behind it the first half
@@ -400,188 +324,42 @@ __global__ __launch_bounds__(512, 2) void gemm256s_bf16_kernel(GemmArgs g, Epi e
             else fa16[tt & 3] = fragA16(CUR ^ 1, tt - 16, 0);
           }
           if constexpr (n == 5 || n == 9 || n == 13 || n == 17) fb16[1][(n - 5) >> 2] = fragB16(CUR, (n - 5) >> 2, 1);
-#if G2S_RUNPTR
           if constexpr (n == 1) issue(q1a, q1b, CUR ^ 1, 2);
           if constexpr (n == 10) issue(q1a, q1b, CUR ^ 1, 3);
-#else
-          if constexpr (n == 1) issue(pa(kt + 1), pb(kt + 1), CUR ^ 1, 2);
-          if constexpr (n == 10) issue(pa(kt + 1), pb(kt + 1), CUR ^ 1, 3);
-#endif
           if constexpr (n == 50) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
           }
-#if G2S_RUNPTR
           if constexpr (n == 51) issue(q2a, q2b, CUR, 0);
-#else
-          if constexpr (n == 51) issue(pa(kt + 2), pb(kt + 2), CUR, 0);
-#endif
           if constexpr (n == 53 || n == 54 || n == 57 || n == 58) fb16[0][n == 53 ? 0 : n == 54 ? 1 : n == 57 ? 2 : 3] = fragB16(CUR ^ 1, n == 53 ? 0 : n == 54 ? 1 : n == 57 ? 2 : 3, 0);
-#if G2S_RUNPTR
           if constexpr (n == 59) issue(q2a, q2b, CUR, 1);
-#else
-          if constexpr (n == 59) issue(pa(kt + 2), pb(kt + 2), CUR, 1);
-#endif
           __builtin_amdgcn_sched_barrier(0);
         });
-#if G2S_RUNPTR
         {   // the stream's tile kt + 3: this output tile's, or the first of the next one's (its second and third follow by + GEMM_BK)
           const bool wrap = kt + 3 == nk;
           q1a = q2a; q1b = q2b;
           q2a = wrap ? a_nxt : q2a + GEMM_BK;
           q2b = wrap ? b_nxt : q2b + GEMM_BK;
         }
-#endif
       };
-#endif
-#if G2S_STATIC
-      auto ktile = [&](auto first_tag, auto cur_tag, int kt) {
-        constexpr bool FIRST = decltype(first_tag)::value;
-        constexpr int cur = decltype(cur_tag)::value;        // (shadows the run-time `cur`, which this form does not use)
-        constexpr int sa = cur, sb = cur, na = cur ^ 1, nb = cur ^ 1;      // "images" are stage numbers here
-        auto ldfrag = [&](int ia, int ib, int ks, int f) {
-          if (f < 4) fa[ks & 1][f] = fragA(ia, f, ks);
-          else fb[ks & 1][f - 4] = fragB(ib, f - 4, ks);
-        };
-#else
-      auto ktile = [&](auto first_tag, int kt) {
-        constexpr bool FIRST = decltype(first_tag)::value;
-        const char* sa = smem + cur * G2_STAGE_BYTES;
-        const char* sb = sa + G2_OPER_BYTES;
-        const char* na = smem + (cur ^ 1) * G2_STAGE_BYTES;
-        const char* nb = na + G2_OPER_BYTES;
-        auto ldfrag = [&](const char* ia, const char* ib, int ks, int f) {
-          if (f < 4) fa[ks & 1][f] = frag_read<OP_ROW>(ia, 128 * wm + 32 * f, ks, lane);
-          else fb[ks & 1][f - 4] = frag_read<OP_ROW>(ib, 64 * wn + 32 * (f - 4), ks, lane);
-        };
-#endif
-        if (!FIRST && kt == nk - 1) {      // the functor's loads for this tile: a memory latency under the last K tile's MFMAs
-#if G2S_PRIO
-          // experiment: waves 0-3 run the last K tile's MFMAs ahead of their SIMD partners (waves 4-7), so that each half's
-          // epilogue -- vector instructions, LDS, stores -- falls beside the other half's matrix work instead of beside its epilogue
-          if (w < 4) __builtin_amdgcn_s_setprio(3);
-#endif
-          if constexpr (epi_stream_f32<Epi>::value) {
-            epi.s_tile(row_w, bn * G2_BN + 64 * wn + 8 * (lane & 3));
-          } else {
-            epi.s_tile(row_w, col_l);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) pre0[q] = epi.s_prefetch(row_w + 8 * q + rr, col_l);
-          }
-        }
-        // (the schedule of gemm256.h's K loop: one piece of other work behind each MFMA)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-          for (int m = 0; m < 8; ++m) {
-#ifdef G2S_PROXY16
-            // TIMING PROXY ONLY (tools/build_variant.sh g2sproxy16 -DG2S_PROXY16; results are WRONG): every 32x32x16 MFMA replaced by two
-            // 16x16x32 MFMAs on the same operand registers and a quarter each of the same accumulator -- the same FLOPs, LDS and register
-            // traffic, the other MFMA shape: what would a 16x16x32 K loop get under the chip's power limit with two waves per SIMD?
-            {
-              typedef __attribute__((ext_vector_type(4))) float f32x4_;
-              f32x16& C = acc[m >> 1][m & 1];
-              f32x4_ q0 = (kk & 1) ? f32x4_{C[4], C[5], C[6], C[7]} : f32x4_{C[0], C[1], C[2], C[3]};
-              f32x4_ q1 = (kk & 1) ? f32x4_{C[12], C[13], C[14], C[15]} : f32x4_{C[8], C[9], C[10], C[11]};
-              if (FIRST && kk == 0) { q0 = f32x4_{0.f, 0.f, 0.f, 0.f}; q1 = q0; }
-              q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], q0, 0, 0, 0);
-              q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], q1, 0, 0, 0);
-              if (kk & 1) { C[4] = q0[0]; C[5] = q0[1]; C[6] = q0[2]; C[7] = q0[3]; C[12] = q1[0]; C[13] = q1[1]; C[14] = q1[2]; C[15] = q1[3]; }
-              else { C[0] = q0[0]; C[1] = q0[1]; C[2] = q0[2]; C[3] = q0[3]; C[8] = q1[0]; C[9] = q1[1]; C[10] = q1[2]; C[11] = q1[3]; }
-            }
-            if constexpr (false) {
-              if (kk == 0) {
-              } else {
-              }
-            }
-#else
-            if constexpr (FIRST) {
-              if (kk == 0) {
-                f32x16 zero;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) zero[e] = 0.f;
-                acc[m >> 1][m & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[0][m & 1], fa[0][m >> 1], zero, 0, 0, 0);
-              } else {
-                acc[m >> 1][m & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], acc[m >> 1][m & 1], 0, 0, 0);
-              }
-            } else {
-              acc[m >> 1][m & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[kk & 1][m & 1], fa[kk & 1][m >> 1], acc[m >> 1][m & 1], 0, 0, 0);   // D^T = B A^T
-            }
-#endif
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk == 0) {            // second half of stream tile kt+1's pieces + the fragments of K step 1
-              if (m == 0) issue(pa(kt + 1), pb(kt + 1), cur ^ 1, 2);
-              else if (m == 3) issue(pa(kt + 1), pb(kt + 1), cur ^ 1, 3);
-              else ldfrag(sa, sb, 1, m < 3 ? m - 1 : m - 2);
-            } else if (kk < 3) {
-              if (m < 6) ldfrag(sa, sb, kk + 1, m);
-            } else {                  // hand-over, first half of stream tile kt+2's pieces, stream tile kt+1's first fragments
-              if (m == 1) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-              } else if (m == 2) {
-                issue(pa(kt + 2), pb(kt + 2), cur, 0);
-              } else if (m == 3) {
-                ldfrag(na, nb, 0, 0);
-                ldfrag(na, nb, 0, 1);
-              } else if (m == 4) {
-                ldfrag(na, nb, 0, 2);
-                ldfrag(na, nb, 0, 3);
-              } else if (m == 5) {
-                ldfrag(na, nb, 0, 4);
-                ldfrag(na, nb, 0, 5);
-              } else if (m == 6) {
-                issue(pa(kt + 2), pb(kt + 2), cur, 1);
-              }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-#if !G2S_STATIC
-        cur ^= 1;
-#endif
-      };
-#if G2S_STATIC
       {   // nk is even (host-side condition of this form): every output tile starts in stage 0
         using S0 = std::integral_constant<int, 0>;
         using S1 = std::integral_constant<int, 1>;
-#if G2S_M16
         ktile16(std::true_type{}, S0{}, 0);
         ktile16(std::false_type{}, S1{}, 1);
         for (int kt = 2; kt < nk; kt += 2) {
           ktile16(std::false_type{}, S0{}, kt);
           ktile16(std::false_type{}, S1{}, kt + 1);
         }
-#else
-        ktile(std::true_type{}, S0{}, 0);
-        ktile(std::false_type{}, S1{}, 1);
-        for (int kt = 2; kt < nk; kt += 2) {
-          ktile(std::false_type{}, S0{}, kt);
-          ktile(std::false_type{}, S1{}, kt + 1);
-        }
-#endif
       }
-#else
-      ktile(std::true_type{}, 0);
-      for (int kt = 1; kt < nk; ++kt) ktile(std::false_type{}, kt);
-#endif
-#if G2S_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
 #ifdef G2X_STAMP
       const unsigned long long st1 = __builtin_readcyclecounter();
 #endif
 
       const bool partial = row_w + 128 > epi.s_rows();       // (wave-uniform) rows beyond M in this wave's block: the masking form
-#if G2S_M16
       if constexpr (epi_stream_f32<Epi>::value) g2s_epilogue16_f32(acc16, eb, row_w, bn * G2_BN + 64 * wn, epi);
       else if (partial) g2s_epilogue16<true>(acc16, eb, row_w, col_l, pre0, epi);
       else g2s_epilogue16<false>(acc16, eb, row_w, col_l, pre0, epi);
-#else
-      if constexpr (epi_stream_f32<Epi>::value) g2s_epilogue_f32(acc, eb, row_w, bn * G2_BN + 64 * wn, epi);
-      else if (partial) g2s_epilogue<true>(acc, eb, row_w, col_l, pre0, epi);
-      else g2s_epilogue<false>(acc, eb, row_w, col_l, pre0, epi);
-#endif
 #ifdef G2X_STAMP
       st_loop += st1 - st0; st_epi += __builtin_readcyclecounter() - st1; ++st_tiles;
 #endif

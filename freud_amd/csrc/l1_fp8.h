@@ -256,13 +256,11 @@ struct EpiEnc8 {
       if (PARTIAL && row >= M) sv[k] = f32x2{0.f, 0.f};
       l1p += sv[k];
     }
-    // (timing experiment of round 5, `-DFP8_SKIP_BF16`: no bf16 copy of the latent -- the upper bound of what a single latent store buys:
-    // encoder 7.38 -> 6.64 ms at C5, profiles/r05_fp8_single_store_bound.txt; as a run-time flag it cost this kernel 6 spill instructions)
-#ifndef FP8_SKIP_BF16
+    // (without this bf16 copy of the latent -- the upper bound of what a single latent store buys -- the encoder went 7.38 -> 6.64 ms at C5,
+    // profiles/r05_fp8_single_store_bound.txt)
     const bf16x8 o = {(bf16_t)sv[0][0], (bf16_t)sv[0][1], (bf16_t)sv[1][0], (bf16_t)sv[1][1],
                       (bf16_t)sv[2][0], (bf16_t)sv[2][1], (bf16_t)sv[3][0], (bf16_t)sv[3][1]};
     EPI_STORE(reinterpret_cast<bf16x8*>(c + (int64_t)row * n_p + col), o);
-#endif
     typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
     const f32x2 q0 = sv[0] * scp, q1 = sv[1] * scp, q2 = sv[2] * scp, q3 = sv[3] * scp;
     const u32x2 q = {pack4_fp8(q0[0], q0[1], q1[0], q1[1]), pack4_fp8(q2[0], q2[1], q3[0], q3[1])};

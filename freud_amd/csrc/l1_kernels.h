@@ -151,17 +151,10 @@ __global__ __launch_bounds__(256) void finalize_count_kernel(const unsigned int*
 // Store of a large output that is next read only after it has left every cache (the [M x n] latent / pre / dpre
 // streams): non-temporal, so that it does not evict the operand tiles the co-resident workgroups share (same-box A/B at
 // d=1280 n=40960: encoder GEMM 7.1 -> 6.4 ms, dpre 7.85 -> 7.55; TopK encoder at d=768 3.03 -> 2.55 ms)
-#ifndef EPI_BATCH_HEAVY
-#define EPI_BATCH_HEAVY 8      // prefetch batch of the functors with a large Pre (gemm.h: epi_prefetch_batch)
-#endif
+constexpr int EPI_BATCH_HEAVY = 8;      // prefetch batch of the functors with a large Pre (gemm.h: epi_prefetch_batch)
 #define EPI_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
 // ... and the matching read of such a stream inside an epilogue (dpre GEMM reading the latent: 7.6 -> 7.1 ms)
 #define EPI_LOAD(ptr) __builtin_nontemporal_load(ptr)
-#ifdef EPI_KO_SKIP_STORE
-#define EPI_ENC_STORE(ptr, val) asm volatile("" :: "v"(val))      // knock-out build: the encoder's latent is computed and dropped
-#else
-#define EPI_ENC_STORE(ptr, val) EPI_STORE(ptr, val)
-#endif
 
 // GEMM epilogues (row-major over the fp32 tile, 4 consecutive columns per call).  Two phases per thread and tile:
 // prefetch(row, col) -> Pre issues every global LOAD the element needs (all of a thread's 16 prefetches are in flight
@@ -175,8 +168,6 @@ struct EpiEnc {
   float* l1_part;       // [tiles]
   int64_t M;
   int n_p, nbn;
-  // (the timing experiment "no latent store" -- round 2's `bench.py --dbg 70` -- is a BUILD switch since round 5: -DEPI_KO_SKIP_STORE.  As a
-  // run-time member it put a branch around the store of every s_apply call, i.e. a basic-block boundary per 8 latents in the epilogue.)
   float l1;
   int tile_id;
   __device__ void tile_begin(int row0, int col0, int) {
@@ -195,7 +186,7 @@ struct EpiEnc {
       l1 += cv;
       o[j] = (bf16_t)cv;
     }
-    EPI_ENC_STORE(reinterpret_cast<bf16x4*>(c + (int64_t)row * n_p + col), o);
+    EPI_STORE(reinterpret_cast<bf16x4*>(c + (int64_t)row * n_p + col), o);
   }
   static constexpr bool WIDE8 = true;                 // gemm256.h: eight columns per thread, 16-byte latent stores
   __device__ void apply8(int row, int col, f32x4 v0, f32x4 v1, const Pre& p0, const Pre& p1) {
@@ -208,7 +199,7 @@ struct EpiEnc {
       o[j] = (bf16_t)c0;
       o[4 + j] = (bf16_t)c1;
     }
-    EPI_ENC_STORE(reinterpret_cast<bf16x8*>(c + (int64_t)row * n_p + col), o);
+    EPI_STORE(reinterpret_cast<bf16x8*>(c + (int64_t)row * n_p + col), o);
   }
   __device__ void tile_end(float* scratch) {
     const float s = block_sum_256_lds(l1, scratch);
@@ -240,7 +231,7 @@ struct EpiEnc {
     }
     const bf16x8 o = {(bf16_t)sv[0][0], (bf16_t)sv[0][1], (bf16_t)sv[1][0], (bf16_t)sv[1][1],
                       (bf16_t)sv[2][0], (bf16_t)sv[2][1], (bf16_t)sv[3][0], (bf16_t)sv[3][1]};
-    EPI_ENC_STORE(reinterpret_cast<bf16x8*>(c + (int64_t)row * n_p + col), o);
+    EPI_STORE(reinterpret_cast<bf16x8*>(c + (int64_t)row * n_p + col), o);
   }
   __device__ void s_tile_end(int, int) {}
   __device__ void s_end(float* scratch) {
@@ -382,11 +373,7 @@ struct EpiDpre {
 #pragma unroll
     for (int k = 0; k < 4; ++k) scp[k] = f32x2{0.f, 0.f};
   }
-#ifdef DPRE_KO_GATE      // TIMING EXPERIMENT ONLY (results WRONG): no read of the latent -- what would a 1-bit gate mask from the encoder buy this GEMM at most?
-  __device__ SPre s_prefetch(int row, int col) const { return SPre{u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u}}; }
-#else
   __device__ SPre s_prefetch(int row, int col) const { return SPre{EPI_LOAD(reinterpret_cast<const u32x4*>(c + (int64_t)row * n_p + col))}; }
-#endif
   // the gate c > 0 on the bf16 BITS: the upper element of a pair is positive iff the dword, as a signed integer, exceeds 0xFFFF; the
   // lower one iff the dword shifted left by 16 is positive (-0.0, which a max(x, 0) may leave, is negative as an integer)
   template <bool PARTIAL>
@@ -1024,13 +1011,9 @@ __global__ __launch_bounds__(OPTC_THREADS) void optimizer_l1_cols_kernel(float* 
   // Column block of this workgroup, XCD-major (round 5): a workgroup touches 64-byte pieces of fp32 rows (16 columns) and 32-byte pieces of the
   // bf16 copy, i.e. half / a quarter of a 128-byte line, and workgroup b runs on XCD b % 8 -- with column block = blockIdx the other half of
   // every line was fetched (and written back) by ANOTHER XCD's L2.  Now XCD x owns the contiguous column blocks [x ncb / 8, (x + 1) ncb / 8)
-  // and neighbours in a line are dispatched 8 block indices apart, i.e. together.  (-DOPTC_NO_XCD_MAP = the old numbering; n_p is a
+  // and neighbours in a line are dispatched 8 block indices apart, i.e. together.  (n_p is a
   // multiple of 128, so ncb is a multiple of 8.)
-#ifndef OPTC_NO_XCD_MAP
   const int cblk = bias_block ? 0 : ((int)blockIdx.x & 7) * (ncb >> 3) + ((int)blockIdx.x >> 3);
-#else
-  const int cblk = blockIdx.x;
-#endif
   const int col0 = cblk * OPTC_COLS;
   const int tx = t % OPTC_TPR, ty = t / OPTC_TPR;      // update / Wb mapping: columns 4 tx .. 4 tx + 3, rows ty + 128 i
   // the loads of the update first: they do not depend on the clip coefficient

@@ -466,9 +466,7 @@ __device__ __forceinline__ int topk_count_ge(const u32x4 (&keys)[MAXV], unsigned
 // byte offset of the transposed copy of vec_bits behind the table (dead_compact_kernel; n_p <= 32768)
 __host__ __device__ __forceinline__ int vec_bits_t_offset(int n_p) { return ((n_p / 8 + 15) / 16) * 16; }
 constexpr int VEC_BITS_T_BYTES = 256 * 16;
-#ifndef SEL_OCC
-#define SEL_OCC 3        // waves per SIMD the compact AuxK select is compiled for
-#endif
+constexpr int SEL_OCC = 3;        // waves per SIMD the compact AuxK select is compiled for
 template <int MAXV, bool COMPACT = false>
 __global__ __launch_bounds__(256, (COMPACT && MAXV <= 12) ? SEL_OCC : 1) void topk_select_reg_kernel(const bf16_t* pre, bf16_t* dense,      // (NOT restrict: the copy + select form of the compact AuxK selection runs in place, pre == dense)
                                                                int* __restrict__ top_idx, float* __restrict__ did_fire,
@@ -762,7 +760,6 @@ __global__ __launch_bounds__(256, (COMPACT && MAXV <= 12) ? SEL_OCC : 1) void to
           SEL_FLUSH();
           return;
         }
-#ifndef SEL_BINSEARCH
         // Round 4: the k-th largest candidate by a two-level RADIX select instead of a binary search over the 32-bit word (up to 32
         // probes, a block barrier each).  Level 1: histogram over the key's upper 8 bits (sign-free bf16: the exponent) -- an LDS add
         // per candidate, one block scan over the reversed bins finds the bin B1 that holds the k-th largest and how many of its
@@ -830,7 +827,6 @@ __global__ __launch_bounds__(256, (COMPACT && MAXV <= 12) ? SEL_OCC : 1) void to
           SEL_FLUSH();
           return;
         }
-#endif
         unsigned int lo = 1u, hi = 0xFFFFFFFFu;             // largest T with #(candidates >= T) >= k; C >= k, candidates > 0
         int probe = 0;
         while (lo < hi) {
@@ -1059,12 +1055,8 @@ __global__ __launch_bounds__(256) void topk_select_tiles_kernel(const bf16_t* __
   const int64_t row = blockIdx.x;
   const int ntiles = n_p / TSEL_TILE;
   // The row's leader wave runs the descent below and ranks the first 64 candidates at the end.  (Rotating the leader with a hash
-  // of the row -- in case wave 0 of every workgroup shared a SIMD -- was 4 % SLOWER: 358 against 344 us, -DTSEL_ROTATE_LEADER.)
-#ifdef TSEL_ROTATE_LEADER
-  const int lead = (int)(((blockIdx.x >> 3) * 0x9E3779B1u) >> 30);
-#else
+  // of the row -- in case wave 0 of every workgroup shared a SIMD -- was 4 % SLOWER: 358 against 344 us.)
   constexpr int lead = 0;
-#endif
   int* ti = top_idx + row * kcap;
   unsigned short* tv = vals + row * kcap;
   if (t == 0) flag[row] = 0;
@@ -1154,7 +1146,6 @@ __global__ __launch_bounds__(256) void topk_select_tiles_kernel(const bf16_t* __
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
   TSEL_MARK();                                      // [3] candidate tiles in registers
-#ifndef TSEL_SCAN_COMPACT
   // compaction: one ballot per dword and one per 16-bit half with a hit (about one value in a hundred of the candidate tiles
   // reaches L, but a wave's 512 values per vector nearly always hold some, so nearly every branch below is taken)
   int wcount = 0;
@@ -1183,51 +1174,6 @@ __global__ __launch_bounds__(256) void topk_select_tiles_kernel(const bf16_t* __
       }
     }
   }
-#else
-  // Tried in round 4 (-DTSEL_SCAN_COMPACT), NOT faster (kernel 391 against 379 us, profiles/r04_tile_select_builds.txt) although
-  // its stamps show 27 % fewer cycles in this phase: compaction in two passes over the registers: (1) every lane counts its own values >= L (packed compare: bit 15 / 31 of
-  // (w | 0x8000'8000) - L'L per 16-bit half), ONE wave-wide exclusive scan of the counts (DPP) gives the lane its first slot in
-  // the wave's segment; (2) the few lanes with hits (a lane's eight values of a vector hold one with probability ~8 %) walk the
-  // set bits of their hit mask and store the keys.
-  // hit mask of a vector: bit q = the low half of dword q (column 2 q), bit 16 + q = its high half (column 2 q + 1)
-  auto hit_mask = [&](const u32x4& w) -> unsigned int {
-    const unsigned int h0 = ((w[0] | 0x80008000u) - lp) & 0x80008000u, h1 = ((w[1] | 0x80008000u) - lp) & 0x80008000u;
-    const unsigned int h2 = ((w[2] | 0x80008000u) - lp) & 0x80008000u, h3 = ((w[3] | 0x80008000u) - lp) & 0x80008000u;
-    return (h0 >> 15) | (h1 >> 14) | (h2 >> 13) | (h3 >> 12);
-  };
-  int cnt = 0;
-#pragma unroll
-  for (int v = 0; v < TSEL_VEC; ++v)
-    if (v * 256 < nv) cnt += __popc(hit_mask(wv_[v]));
-  int incl = cnt;
-  incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, false);      // row_shr:1 (lanes without a source add 0)
-  incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, false);      // row_shr:2
-  incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, false);      // row_shr:4
-  incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, false);      // row_shr:8: inclusive within the row of 16
-  incl += __builtin_amdgcn_update_dpp(0, incl, 0x142, 0xA, 0xF, false);      // row_bcast15: rows 1, 3 += lane 15 of the row before
-  incl += __builtin_amdgcn_update_dpp(0, incl, 0x143, 0xC, 0xF, false);      // row_bcast31: rows 2, 3 += lane 31
-  const int wcount = __builtin_amdgcn_readlane(incl, 63);
-  int pos = incl - cnt;
-#pragma unroll
-  for (int v = 0; v < TSEL_VEC; ++v) {
-    if (v * 256 >= nv) continue;
-    const u32x4 w = wv_[v];
-    unsigned int u = hit_mask(w);
-    if (u != 0u) {
-      const int vi = v * 256 + t;
-      const int col0 = (int)tlist[vi / VPT] * TSEL_TILE + (vi % VPT) * 8;
-      while (u != 0u) {
-        const int b = __ffs(u) - 1;
-        u &= u - 1u;
-        const int q = b & 3, h = b >> 4;
-        const unsigned int dw = q == 0 ? w[0] : (q == 1 ? w[1] : (q == 2 ? w[2] : w[3]));
-        const unsigned int key = (dw >> (16 * h)) & 0xFFFFu;
-        if (pos < SEG) seg[pos] = (key << 17) | (0x1FFFFu - (unsigned int)(col0 + 2 * q + h));
-        ++pos;
-      }
-    }
-  }
-#endif
   TSEL_MARK();                                      // [4] candidates appended
   if (lane == 0) wave_cnt[wv] = wcount;
   topk_pad_segment<SEG>(seg, wcount, lane);
@@ -1286,10 +1232,8 @@ __global__ __launch_bounds__(256) void topk_densify_kernel(const bf16_t* __restr
 // [l*cpl, (l+1)*cpl), so every gathered W_dec row is read as one contiguous, fully coalesced line by the wave.
 // NPAIR > 0: d_p == 128 * NPAIR is a compile-time constant, so a lane's 4 * NPAIR bytes of a W_dec row are fetched with
 // unconditional (mergeable into dwordx2/x4) loads and two gathered rows are kept in flight; NPAIR == 0: any d_p <= 1536.
-#ifndef TKD_ROWS
-#define TKD_ROWS 2        // gathered W_dec rows in flight per wave and trip of topk_decode_kernel (C3, one box: 2 -> 801 us, 4 -> 821,
+constexpr int TKD_ROWS = 2;        // gathered W_dec rows in flight per wave and trip of topk_decode_kernel (C3, one box: 2 -> 801 us, 4 -> 821,
                           // 8 -> 903: the gather is bound by what misses the L2s, not by its round trips)
-#endif
 template <typename T, int NPAIR = 0>
 __global__ __launch_bounds__(256) void topk_decode_kernel(const T* __restrict__ x, const bf16_t* __restrict__ vals,
                                                            const int* __restrict__ idx, int kcap, const bf16_t* __restrict__ Wd,

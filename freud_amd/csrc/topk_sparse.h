@@ -27,10 +27,7 @@
 #include "topk_kernels.h"
 
 constexpr int CSC_SUB = 64;           // rows a wave holds in registers at a time
-#ifndef CSC_ROWS_N
-#define CSC_ROWS_N 128
-#endif
-constexpr int CSC_ROWS = CSC_ROWS_N;  // rows per counting block (one wave, CSC_ROWS / CSC_SUB rounds; round 3: 64 -- twice the count / offset
+constexpr int CSC_ROWS = 128;         // rows per counting block (one wave, CSC_ROWS / CSC_SUB rounds; round 3: 64 -- twice the count / offset
                                       // tables, 150 MB of them at C3)
 static_assert(CSC_ROWS % CSC_SUB == 0 && CSC_ROWS * 3 < 65536, "u16 counters per (block, latent)");
 constexpr int CSC_MAX_NP = 32768;     // latents per counting segment (u16 LDS counters: 64 KiB per wave)
@@ -186,12 +183,8 @@ __global__ __launch_bounds__(64) void csc_fill_kernel(SparsePasses ps, const int
   // blocks share a 128-byte line), and workgroups go to the XCDs round robin: with block = blockIdx.x the neighbours were written
   // through eight different L2s, every store a partial line on its way to HBM.  XCD x now takes the blocks [x nb/8, (x+1) nb/8):
   // neighbours meet in ONE L2 within microseconds and leave as whole lines.
-#ifdef CSCF_NO_XCD_REMAP
-  const int blk = blockIdx.x;
-#else
   const int nb8 = gridDim.x >> 3;
   const int blk = (int)blockIdx.x < 8 * nb8 ? (int)(blockIdx.x & 7) * nb8 + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-#endif
   const int64_t r0 = (int64_t)blk * CSC_ROWS;
   const int seg0 = blockIdx.y * CSC_FILL_NP, seg1 = min(seg0 + CSC_FILL_NP, n_p), segn = seg1 - seg0;    // (n_p: a multiple of 128)
 #ifdef CSCF_STAMP
@@ -275,14 +268,10 @@ __global__ __launch_bounds__(64) void csc_fill_kernel(SparsePasses ps, const int
 #endif
 }
 
-#ifndef SB_E
-#define SB_E 4          // entries in flight per wave and trip of sparse_bwd_kernel (even)
-#endif
+constexpr int SB_E = 4;          // entries in flight per wave and trip of sparse_bwd_kernel (even)
 // ---- 5. gradient work items -----------------------------------------------------------------------------------------------
 // item -> (latent j = item_latent[item], chunk item - item_start[j]); partial sums to part[item][2][d_p] and pbe[item].
-#ifndef SB_WAVES
-#define SB_WAVES 4      // waves (work items) per workgroup of sparse_bwd_kernel
-#endif
+constexpr int SB_WAVES = 4;      // waves (work items) per workgroup of sparse_bwd_kernel
 template <int NPAIR>
 __global__ __launch_bounds__(64 * SB_WAVES) void sparse_bwd_kernel(SparsePasses ps, const bf16_t* __restrict__ xs, const bf16_t* __restrict__ Wd,
                                                          const CscEntry* __restrict__ entries, const unsigned int* __restrict__ start,

@@ -196,7 +196,7 @@ def test_fused_forward_tail_wait_counts_exactly_its_four_latent_stores(disasm, k
     assert dma, "no LDS-DMA in the fused forward?"
     last = dma[-1]
     waits = [k for k in range(last + 1, len(ins)) if ins[k].startswith("s_waitcnt") and "vmcnt(4)" in ins[k]]
-    assert waits, "the counted tail wait (vmcnt(4)) is gone: FF2_TAIL_V1's full drain, or a changed drain loop -- re-derive the count"
+    assert waits, "the counted tail wait (vmcnt(4)) is gone: a full drain (vmcnt(0)), or a changed drain loop -- re-derive the count"
     w = waits[0]
     between = ins[last + 1:w]
     vm = [i for i in between if i.startswith(("global_", "buffer_", "flat_", "scratch_"))]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Effective clock of the fused kernels from rocprofv3 counter CSVs (tools/gpu_r04_clock.sh).
+"""Effective clock of the fused kernels from rocprofv3 counter CSVs.
 
   python tools/parse_clock.py gpurun_out/r04_clock
 
