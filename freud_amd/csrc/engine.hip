@@ -35,6 +35,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "topk_aux.h"
 #include "eval_fp32.h"
 #include "search.h"
+#include "file_top.h"
 #include "stats.h"
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
@@ -3207,6 +3208,22 @@ extern "C" int sae_search_file_values(const uint64_t* file_keys, const uint64_t*
   const int64_t total = n_latents * n_files;
   hipLaunchKernelGGL(search_values_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, file_keys, aux, n_files,
                      ncols, flags, latents, n_latents, file0, out_stride, out);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- file features (file_top.h): the top-N latents of every file of a batch, selected from its file keys
+static_assert(SAE_FILE_TOP_POSITIVE == FT_POSITIVE && SAE_FILE_TOP_MAX == FT_MAX_TOP, "freud_sae.h and file_top.h disagree");
+
+extern "C" int sae_file_top_features(const uint64_t* file_keys, int64_t n_files, int64_t ncols, int n_top, int flags, int32_t* top_latents,
+                                     uint64_t* top_keys, void* stream) {
+  if (!file_keys || !top_latents || !top_keys) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_files < 1 || ncols < 1) return fail(SAE_ERR_INVALID, "n_files=%lld, ncols=%lld", (long long)n_files, (long long)ncols);
+  if (n_files > 0x7FFFFFFFll || ncols > FT_MAX_COLS) return fail(SAE_ERR_INVALID, "n_files=%lld > 2^31 - 1 or ncols=%lld > 2^24", (long long)n_files, (long long)ncols);
+  if (n_top < 1 || n_top > SAE_FILE_TOP_MAX) return fail(SAE_ERR_INVALID, "n_top=%d outside [1, %d]", n_top, SAE_FILE_TOP_MAX);
+  if (flags & ~SAE_FILE_TOP_POSITIVE) return fail(SAE_ERR_INVALID, "unknown file-top flags 0x%x", flags);
+  hipLaunchKernelGGL(file_top_kernel, dim3((unsigned)n_files), dim3(FT_THREADS), 0, (hipStream_t)stream, file_keys, ncols, n_top, flags,
+                     top_latents, top_keys);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

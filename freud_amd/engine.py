@@ -121,6 +121,7 @@ def load() -> C.CDLL:
         "sae_search_raw_files": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp]),
         "sae_search_merge": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, dbl, dbl, vp, vp, vp]),
         "sae_search_file_values": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i64, i64, i64, vp, vp]),
+        "sae_file_top_features": (C.c_int, [vp, i64, i64, C.c_int, C.c_int, vp, vp, vp]),
         "sae_stats_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
@@ -160,9 +161,12 @@ EXPORTED_SYMBOLS = [
     "sae_kernel_name", "sae_dominant_kernel",
     "sae_search_files", "sae_search_raw_files", "sae_search_merge", "sae_search_file_values",
     "sae_stats_files",
+    "sae_file_top_features",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
+FILE_TOP_POSITIVE = 1                                               # include/freud_sae.h: SAE_FILE_TOP_POSITIVE
+FILE_TOP_MAX = 1024                                                 # include/freud_sae.h: SAE_FILE_TOP_MAX
 STATS_UNFUSED = 1                                                   # include/freud_sae.h: SAE_STATS_UNFUSED
 
 
@@ -642,6 +646,19 @@ def search_merge(file_keys, aux, n_files: int, ncols: int, file0: int, n_top: in
     _check(load().sae_search_merge(C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if aux is not None else None,
                                    int(n_files), int(ncols), int(file0), int(n_top), int(flags), float(min_val), float(max_val),
                                    C.c_void_p(top_keys.data_ptr()), C.c_void_p(top_frames.data_ptr()), _stream_ptr(stream)))
+
+
+def file_top_features(file_keys, n_files: int, ncols: int, n_top: int, flags: int, top_latents, top_keys, stream=None) -> None:
+    """Per file the n_top best latents of file_keys [n_files, ncols] (as search_files / search_raw_files leave them) into
+    top_latents (int32, -1 = empty) and top_keys (int64 holding the uint64 file keys, 0 = empty), both [n_files, n_top]."""
+    import torch
+    _check_search_out(file_keys, n_files * ncols)
+    _check_search_out(top_keys, n_files * n_top)
+    if not (top_latents.is_cuda and top_latents.dtype == torch.int32 and top_latents.is_contiguous()
+            and top_latents.numel() >= n_files * n_top):
+        raise EngineError(f"top_latents must be a contiguous int32 CUDA tensor of >= {n_files * n_top} elements")
+    _check(load().sae_file_top_features(C.c_void_p(file_keys.data_ptr()), int(n_files), int(ncols), int(n_top), int(flags),
+                                        C.c_void_p(top_latents.data_ptr()), C.c_void_p(top_keys.data_ptr()), _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:

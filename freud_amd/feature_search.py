@@ -129,8 +129,12 @@ def search_features(sae, data_path: str, layer_name: str, n_files: int, *, absol
     return FeatureAtlas(values, files, frames, times, fp.filenames, pf, feats)
 
 
-def _series(sae_model, eng, x: torch.Tensor, feature_idx: int) -> torch.Tensor:
-    """The latent's series over one file's rows [T, d] -- encode() of freud_amd.models (or x's own column in raw mode)."""
+def _series(sae_model, eng, x: torch.Tensor, feature_idx) -> torch.Tensor:
+    """The latent's series over one file's rows [T, d] -- encode() of freud_amd.models (or x's own column in raw mode).
+    feature_idx: one index -> [T]; a sequence of indices -> [T, len] from ONE encode() (file_features.py)."""
+    many = not isinstance(feature_idx, (int, np.integer))
+    if many:
+        feature_idx = [int(j) for j in feature_idx]
     if sae_model is None and eng is None:
         return x[:, feature_idx].float().cpu()
     if sae_model is None:
@@ -138,10 +142,16 @@ def _series(sae_model, eng, x: torch.Tensor, feature_idx: int) -> torch.Tensor:
     if sae_model._variant == "l1":
         return sae_model.encode(x).latent[:, feature_idx].float().cpu()
     enc = sae_model.encode(x)                       # activation_tensor_from_indexed (activations.py:41-58)
-    dense = torch.zeros(x.shape[0], dtype=torch.float32, device=enc.top_acts.device)
-    hit = enc.top_indices == feature_idx
-    dense += (enc.top_acts.float() * hit).sum(dim=1)
-    return dense.cpu()
+
+    def column(j):
+        dense = torch.zeros(x.shape[0], dtype=torch.float32, device=enc.top_acts.device)
+        hit = enc.top_indices == j
+        dense += (enc.top_acts.float() * hit).sum(dim=1)
+        return dense.cpu()
+
+    if not many:
+        return column(feature_idx)
+    return torch.stack([column(j) for j in feature_idx], dim=1) if feature_idx else torch.zeros(x.shape[0], 0)
 
 
 @keep_rng

@@ -355,6 +355,27 @@ int sae_search_merge(const uint64_t* file_keys_dev, const uint64_t* aux_dev, int
 int sae_search_file_values(const uint64_t* file_keys_dev, const uint64_t* aux_dev, int64_t n_files, int64_t ncols, int flags,
                            const int32_t* latents_dev, int64_t n_latents, int64_t file0, int64_t out_stride, float* out_dev, void* stream);
 
+/* ---- File features: the reference's top_activations_for_audio (utils/activations.py:135-209, served as /top_features) for
+ * every file of a batch at once -- which latents describe a file.  Input: the file keys file_keys_dev[n_files][ncols] exactly as
+ * sae_search_files / sae_search_raw_files (absolute = 0) leave them.  Output per file, best first: top_latents_dev[n_files][n_top]
+ * (int32, -1 = empty slot) and top_keys_dev[n_files][n_top] (the latents' file keys, 0 = empty slot: value and first frame of the
+ * maximum, freud_amd/csrc/search_keys.h).
+ *
+ * Order: file key descending -- value descending, then the earlier first frame of the maximum, as the reference's stable sort over
+ * the frames in order gives -- and for equal keys the lower latent index (the reference leaves that case to torch.topk's
+ * unspecified order within a frame).  Zero rule: with SAE_FILE_TOP_POSITIVE only latents whose value is > 0 are reported (magnitude
+ * bits: a -0.0 is not positive); the reference pads a short answer of an SAE with zero-valued latents that torch.topk picks among
+ * ties.  Without the flag (raw mode) signed values are reported as they are, zero and negative included.  n_top may exceed ncols or
+ * the number of reportable latents: the remaining slots are empty.
+ *
+ * 1 <= n_top <= SAE_FILE_TOP_MAX, n_files >= 1, 1 <= ncols <= 2^24, non-null pointers: otherwise SAE_ERR_INVALID before anything
+ * is enqueued.  Caller-owned buffers, asynchronous on `stream`, runs on the current device, needs no context.  Exact and
+ * deterministic: two runs give bitwise identical tables. */
+enum { SAE_FILE_TOP_POSITIVE = 1 };      /* report only values > 0 (SAE latents) */
+#define SAE_FILE_TOP_MAX 1024
+int sae_file_top_features(const uint64_t* file_keys_dev, int64_t n_files, int64_t ncols, int n_top, int flags,
+                          int32_t* top_latents_dev, uint64_t* top_keys_dev, void* stream);
+
 /* ---- Feature statistics: how sparse the dictionary is on real data, in one pass over the data.  The SAE activations are never
  * collected or written.
  *
