@@ -37,6 +37,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "search.h"
 #include "file_top.h"
 #include "stats.h"
+#include "coact.h"
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
 
@@ -123,13 +124,15 @@ enum KernelId {
   KID_EXCHANGE,        // data parallel: the gradient exchange (peer-exchange kernel or ncclAllReduce), on the stream it runs on
   KID_STATS_XCHG,      // data parallel: the batch statistics (push inside finalize_losses, or the statistics kernel + its exchange)
   KID_STEP_TOTAL,
+  KID_COACT_PACK,      // feature co-activation (coact.h): the mask pack and the i8 update of sae_coact_files
+  KID_COACT_UPDATE,
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
                                               "dw_gemm", "bwd_fused_gemm", "reduce_grads", "clip_adam", "topk_enc_gemm", "topk_select",
                                               "topk_decode", "topk_ddense_gemm", "topk_dwdec_gemm", "topk_dwenc_gemm",
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
-                                              "fwd_bwd_total"};
+                                              "fwd_bwd_total", "coact_pack", "coact_update"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -139,7 +142,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT };
 
 struct sae_ctx {
   sae_config cfg;
@@ -293,6 +296,7 @@ struct sae_ctx {
   int eval_prec = 0;            // 0 = the training kernels' arithmetic (bf16 operands, fp32 accumulate), 1 = fp32 end to end
   LastCall last_call = LAST_FWD_BF16;   // what the last forward-like call left behind (no_forward_left, the getters)
   void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
+  int8_t* co_zt = nullptr;      // sae_coact_files scratch (coact.h): the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)]
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;
@@ -332,6 +336,8 @@ static int no_forward_left(const sae_ctx* c, bool after_search = true) {
     return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
   if (c->last_call == LAST_STATS)
     return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_COACT)
+    return fail(SAE_ERR_STATE, "the last call was a feature co-activation pass: it leaves no forward to read (run sae_eval first)");
   return SAE_OK;
 }
 
@@ -552,7 +558,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);
@@ -3093,6 +3099,7 @@ struct FilePassKind {           // the words of an entry point's messages and th
 };
 static const FilePassKind kSearchPass = {"sae_search_files", "search in a bf16 context", "search", SAE_SEARCH_UNFUSED};
 static const FilePassKind kStatsPass = {"sae_stats_files", "run the statistics in a bf16 context", "stats", SAE_STATS_UNFUSED};
+static const FilePassKind kCoactPass = {"sae_coact_files", "count co-activations in a bf16 context", "co-activation", 0};
 
 static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
   if (n_files <= 0 || rows_per_file <= 0) return fail(SAE_ERR_INVALID, "n_files=%lld and rows_per_file=%lld must be positive", (long long)n_files, (long long)rows_per_file);
@@ -3329,6 +3336,84 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
     if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return stats_l1_impl(c, xt, M, Trows, lengths, o, unfused, s); })) return rc;
   }
   c->last_call = LAST_STATS;
+  return SAE_OK;
+}
+
+// ---- feature co-activation (coact.h): C += Zt Zt^T of one batch of files on the i8 MFMA, and the neighbour keys of rows of C
+static_assert(SAE_COACT_JACCARD == CO_JACCARD && SAE_COACT_COND == CO_COND && SAE_COACT_COUNT == CO_COUNT, "freud_sae.h and coact.h disagree");
+
+static int coact_ensure(sae_ctx* c) {
+  if (c->co_zt) return SAE_OK;
+  HIP_TRY(hipMalloc((void**)&c->co_zt, (size_t)((int64_t)c->n_p * round_up(c->max_rows_p, CO_BK))));
+  return SAE_OK;
+}
+
+// the update of one batch's mask Zt [n_p][Kp] (n_p a multiple of CO_BM): the K split of coact.h's header
+static int coact_launch_update(sae_ctx* c, const int8_t* zt, int64_t Kp, int n_p, int n, int32_t* counts, hipStream_t s) {
+  const int nt = n_p / CO_BM;
+  const int64_t ntiles = (int64_t)nt * (nt + 1) / 2;
+  const int nsteps = (int)(Kp / CO_BK);
+  int ksplit = (int)std::min<int64_t>(std::max<int64_t>((CO_MIN_WGS + ntiles - 1) / ntiles, 1), nsteps);
+  const int per = (nsteps + ksplit - 1) / ksplit;
+  ksplit = (nsteps + per - 1) / per;
+  const dim3 grid((unsigned)nt, (unsigned)nt, (unsigned)ksplit);
+  ev_begin(c, KID_COACT_UPDATE, s);
+  if (ksplit > 1) hipLaunchKernelGGL(coact_update_kernel<true>, grid, dim3(256), 0, s, zt, Kp, n, per, counts);
+  else hipLaunchKernelGGL(coact_update_kernel<false>, grid, dim3(256), 0, s, zt, Kp, n, per, counts);
+  ev_end(c, KID_COACT_UPDATE, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+template <typename T>
+static int coact_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int64_t Kp, hipStream_t s) {
+  const GemmArgs g = file_pass_l1_front(c, x, M, s);
+  if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
+  ev_begin(c, KID_COACT_PACK, s);
+  hipLaunchKernelGGL(coact_pack_l1_kernel, dim3((unsigned)(Kp / 64), (unsigned)(c->n_p / 64)), dim3(256), 0, s, (const unsigned short*)c->c,
+                     (int64_t)c->n_p, c->n, M, Trows, lengths, c->co_zt, Kp);
+  ev_end(c, KID_COACT_PACK, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                               int flags, int32_t* counts, void* stream) {
+  int64_t M;
+  if (int rc = file_pass_begin(kCoactPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if ((reinterpret_cast<uintptr_t>(counts) & 3) != 0) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
+  if (int rc = coact_ensure(c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  const int64_t Kp = round_up(M, CO_BK);
+  if (c->topk) {
+    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the selection scattered into the zeroed mask
+    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+    ev_begin(c, KID_COACT_PACK, s);
+    const hipError_t memset_zt = hipMemsetAsync(c->co_zt, 0, (size_t)((int64_t)c->n_p * Kp), s);
+    if (memset_zt == hipSuccess)
+      hipLaunchKernelGGL(coact_pack_topk_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
+                         c->k, M, Trows, lengths, c->n, c->co_zt, Kp);
+    ev_end(c, KID_COACT_PACK, s);           // (the bracket closes whatever the memset answered)
+    HIP_TRY(memset_zt);
+    HIP_TRY(hipGetLastError());
+  } else {
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return coact_l1_impl(c, xt, M, Trows, lengths, Kp, s); })) return rc;
+  }
+  if (int rc = coact_launch_update(c, c->co_zt, Kp, c->n_p, c->n, counts, s)) return rc;
+  c->last_call = LAST_COACT;
+  return SAE_OK;
+}
+
+extern "C" int sae_coact_neighbor_keys(const int32_t* counts, int64_t n, int64_t row0, int64_t n_rows, int measure, uint64_t* keys, void* stream) {
+  if (!counts || !keys) return fail(SAE_ERR_INVALID, "null argument");
+  if (n < 1 || n > FT_MAX_COLS) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24]", (long long)n);
+  if (n_rows < 1 || row0 < 0 || row0 + n_rows > n)
+    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)n);
+  if (measure != SAE_COACT_JACCARD && measure != SAE_COACT_COND && measure != SAE_COACT_COUNT) return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
+  hipLaunchKernelGGL(coact_keys_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
+                     (hipStream_t)stream, counts, (int)n, row0, n_rows, measure, keys);
+  HIP_TRY(hipGetLastError());
   return SAE_OK;
 }
 

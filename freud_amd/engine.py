@@ -123,6 +123,8 @@ def load() -> C.CDLL:
         "sae_search_file_values": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i64, i64, i64, vp, vp]),
         "sae_file_top_features": (C.c_int, [vp, i64, i64, C.c_int, C.c_int, vp, vp, vp]),
         "sae_stats_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
+        "sae_coact_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
+        "sae_coact_neighbor_keys": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -162,12 +164,14 @@ EXPORTED_SYMBOLS = [
     "sae_search_files", "sae_search_raw_files", "sae_search_merge", "sae_search_file_values",
     "sae_stats_files",
     "sae_file_top_features",
+    "sae_coact_files", "sae_coact_neighbor_keys",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
 FILE_TOP_POSITIVE = 1                                               # include/freud_sae.h: SAE_FILE_TOP_POSITIVE
 FILE_TOP_MAX = 1024                                                 # include/freud_sae.h: SAE_FILE_TOP_MAX
 STATS_UNFUSED = 1                                                   # include/freud_sae.h: SAE_STATS_UNFUSED
+COACT_MEASURES = {"jaccard": 0, "cond": 1, "count": 2}              # include/freud_sae.h: SAE_COACT_*
 
 
 def stats_layout(n: int) -> dict:
@@ -563,6 +567,15 @@ class SaeEngine:
         _check(self._lib.sae_stats_files(self._ctx, xp, B, T, dt, lp, STATS_UNFUSED if unfused else 0,
                                          C.c_void_p(stats_block.data_ptr()), _stream_ptr(stream)))
 
+    # -- feature co-activation (include/freud_sae.h: sae_coact_files; freud_amd/coactivation.py) ---------------------------
+    def coact_files(self, x, counts, lengths=None, stream=None) -> None:
+        """Add the co-activation counts of x [n_files, T, d] (CUDA) to counts (a zero-initialised contiguous int32 CUDA tensor
+        [n_dict, n_dict]); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail
+        until the next eval() / step()."""
+        x, xp, B, T, _d, dt, lp = _files_args(x, "coact_files", lengths)
+        _check_coact_table(counts, self.n)
+        _check(self._lib.sae_coact_files(self._ctx, xp, B, T, dt, lp, 0, C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:
         out = np.empty(count, dtype=np.float32)
@@ -659,6 +672,21 @@ def file_top_features(file_keys, n_files: int, ncols: int, n_top: int, flags: in
         raise EngineError(f"top_latents must be a contiguous int32 CUDA tensor of >= {n_files * n_top} elements")
     _check(load().sae_file_top_features(C.c_void_p(file_keys.data_ptr()), int(n_files), int(ncols), int(n_top), int(flags),
                                         C.c_void_p(top_latents.data_ptr()), C.c_void_p(top_keys.data_ptr()), _stream_ptr(stream)))
+
+
+def _check_coact_table(counts, n: int) -> None:
+    import torch
+    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == n * n):
+        raise EngineError(f"counts must be a contiguous int32 CUDA tensor of {n} x {n} elements")
+
+
+def coact_neighbor_keys(counts, n: int, row0: int, n_rows: int, measure: int, keys, stream=None) -> None:
+    """keys [n_rows, n] (int64 holding uint64) = the neighbour keys of rows [row0, row0 + n_rows) of the count table counts [n, n]
+    for file_top_features(keys, n_rows, n, n_top, FILE_TOP_POSITIVE, ...); measure: a COACT_MEASURES value."""
+    _check_coact_table(counts, n)
+    _check_search_out(keys, max(int(n_rows), 0) * n)
+    _check(load().sae_coact_neighbor_keys(C.c_void_p(counts.data_ptr()), int(n), int(row0), int(n_rows), int(measure),
+                                          C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:

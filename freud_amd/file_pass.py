@@ -71,13 +71,15 @@ def keep_rng(fn):
 
 class FilePass:
     """The set-up of one pass, then its batches.  `sae`: see resolve_sae (None: raw mode, no engine); `what` is the noun of the
-    error messages ("feature search", "feature statistics").  Every check that needs no device comes before the one that does.
+    error messages ("feature search", "feature statistics").  `max_frames`: a pass over more than this many frames (files x T) is
+    refused.  Every check that needs no device comes before the one that does.
 
-    Attributes: model, eng (None in raw mode), device, T, d, n_total, batch_files, filenames.  Iterating yields
+    Attributes: model, eng (None in raw mode), device, T, d, n_total, n_frames (the frames that count: the trimmed lengths, or
+    files x T), batch_files, filenames.  Iterating yields
     (x [nb, T, d] on `device` in the shards' dtype, file0, nb, lengths[file0:file0 + nb] on `device` or None) in file order."""
 
     def __init__(self, sae, data_path: str, layer_name: str, *, what: str, lengths=None, subset_size: Optional[int] = None,
-                 batch_files: Optional[int] = None):
+                 batch_files: Optional[int] = None, max_frames: Optional[int] = None):
         from .loader import MemoryMappedActivationsDataset
 
         if batch_files is not None and int(batch_files) < 1:
@@ -87,7 +89,10 @@ class FilePass:
         if n_total == 0:
             raise ValueError(f"{data_path}: no files")
         T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
+        if max_frames is not None and n_total * T > max_frames:
+            raise ValueError(f"{n_total} files x {T} frames exceed the {max_frames} frames of one {what} pass")
         self._lens = check_lengths(lengths, n_total, T)
+        self.n_frames = int(self._lens.sum(dtype=np.int64)) if self._lens is not None else n_total * T
         model, eng = resolve_sae(sae)
         runs = f"the {what} run{'' if what.endswith('s') else 's'}"
 

@@ -419,6 +419,35 @@ enum { SAE_STATS_UNFUSED = 1 };
 int sae_stats_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
                     int flags, void* stats_dev, void* stream);
 
+/* ---- Feature co-activation: which latents fire together.  C[i][j] = the number of counted frames on which latents i and j are both
+ * active, for every pair, in one pass over the data; then per latent the neighbours that share the most frames with it.
+ *
+ * Semantics.  Frames count exactly as in sae_stats_files (lengths_dev, the first min(length, T) frames of a file), and "active" is
+ * its rule: the value encode() returns is > 0 (magnitude bits: a -0.0 is not active; a selected zero of a TopK row is not active).
+ * C is symmetric, C[i][i] is the fire_count of the statistics.  Counts are int32: THE CALLER GUARANTEES that at most 2^31 - 1 frames
+ * are counted into one table (freud_amd/coactivation.py refuses a pass whose files x T exceeds that).
+ *
+ * sae_coact_files adds one batch to counts_dev [n_dict][n_dict] (int32, row-major, caller-owned, zeroed before the first batch); after
+ * every call the table is the full symmetric matrix.  The batch's activity mask is packed as int8 into context scratch (allocated by
+ * the first call: n_dict rounded up to 128, times max_rows rounded up to 128, bytes) and the table is updated on the i8 MFMA, upper
+ * triangle of tiles only, mirrored on the way out.  Sums are integers: two runs give bitwise identical tables.  flags must be 0.
+ * n_files * rows_per_file <= max_rows; fp8 contexts: SAE_ERR_INVALID.  Shape and argument checks fail before anything is enqueued.
+ * Asynchronous on `stream`.  Training state is untouched; afterwards sae_latent_buffer, sae_topk_indices, sae_decode,
+ * sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the next sae_eval / step. */
+int sae_coact_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                    int flags, int32_t* counts_dev, void* stream);
+
+/* Neighbour keys of the rows [row0, row0 + n_rows) of a count table counts_dev [n][n]: keys_dev[n_rows][n] =
+ * ord(score) << 32 | C[i][j] (freud_amd/csrc/coact.h), 0 for j == i and for C[i][j] == 0.  score = one fp64 division converted once
+ * to fp32: SAE_COACT_JACCARD C[i][j] / (C[i][i] + C[j][j] - C[i][j]); SAE_COACT_COND C[i][j] / C[i][i]; SAE_COACT_COUNT C[i][j].
+ * sae_file_top_features(keys_dev, n_rows, n, n_top, SAE_FILE_TOP_POSITIVE, ...) then gives each latent's neighbours in the order
+ * score descending, then the larger count, then the lower partner index; the latent itself and partners it never fires with are not
+ * reported.  Null pointers, n outside [1, 2^24], an empty or out-of-range row block, an unknown measure: SAE_ERR_INVALID.  Needs no
+ * context, runs on the current device, asynchronous on `stream`, deterministic. */
+enum { SAE_COACT_JACCARD = 0, SAE_COACT_COND = 1, SAE_COACT_COUNT = 2 };
+int sae_coact_neighbor_keys(const int32_t* counts_dev, int64_t n, int64_t row0, int64_t n_rows, int measure, uint64_t* keys_dev,
+                            void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
