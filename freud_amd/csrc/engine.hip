@@ -341,6 +341,14 @@ static int no_forward_left(const sae_ctx* c, bool after_search = true) {
   return SAE_OK;
 }
 
+// the tensors of a bf16 forward (latent rows, top-k indices, 4k buffers, dx_hat, the fp8 operands) are not what the fp32
+// evaluation computed: it has its own buffers and leaves those of the last training step as they were
+static int no_bf16_forward_left(const sae_ctx* c) {
+  if (c->last_call == LAST_FWD_E32)
+    return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows, indices or debug tensors (run a bf16 sae_eval first)");
+  return SAE_OK;
+}
+
 static int dominant_kid(const sae_ctx* c) { return c->topk ? KID_TK_ENC : (c->use_fused_bwd ? KID_BWD_FUSED : KID_DW); }
 // Level 1 brackets the dominant kernel and the whole step on every PROF_PERIOD-th step only: an event record is a packet of
 // its own in the queue and costs ~6 us of idle GPU between two dependent kernels (kernel trace of the C2 step: 3 records
@@ -2586,7 +2594,7 @@ static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dt
 // ---- fp32 evaluation forward (eval_fp32.h): validate() of the reference on device='cpu' runs without autocast
 static int e32_ensure(sae_ctx* c, int64_t M) {
   if (c->e32_rows >= M && c->e32_x) return SAE_OK;
-  for (void** p : {(void**)&c->e32_x, (void**)&c->e32_pre, (void**)&c->e32_sel, (void**)&c->e32_xhat}) {
+  for (void** p : {(void**)&c->e32_x, (void**)&c->e32_pre, (void**)&c->e32_sel, (void**)&c->e32_xhat, (void**)&c->e32_part}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
   }
@@ -2596,7 +2604,7 @@ static int e32_ensure(sae_ctx* c, int64_t M) {
   HIP_TRY(hipMalloc((void**)&c->e32_pre, (size_t)rows * c->n_p * 4));
   if (c->topk) HIP_TRY(hipMalloc((void**)&c->e32_sel, (size_t)rows * c->n_p * 4));
   HIP_TRY(hipMalloc((void**)&c->e32_xhat, (size_t)rows * c->d_p * 4));
-  if (!c->e32_part) HIP_TRY(hipMalloc((void**)&c->e32_part, (size_t)E32_PART_DOUBLES * 8));
+  HIP_TRY(hipMalloc((void**)&c->e32_part, (size_t)(E32_FIXED_DOUBLES + e32_l1_parts(c->n_p, rows)) * 8));
   if (!c->e32_colmax) HIP_TRY(hipMalloc((void**)&c->e32_colmax, (size_t)c->n_p * 4));
   c->e32_rows = rows;
   return SAE_OK;
@@ -2613,8 +2621,9 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   const int d = c->d, n = c->n, d_p = c->d_p, n_p = c->n_p;
   int rc = e32_ensure(c, M);
   if (rc) return rc;
-  // partial-sum layout of e32_part (doubles): [0, E32_L1_PARTS) latent sums | 4 x E32_RES_BLOCKS residual sums | ... multi-TopK residual | total variance
-  double *l1_part = c->e32_part, *res_part = c->e32_part + E32_L1_PARTS, *res2_part = res_part + 4 * E32_RES_BLOCKS, *tv_part = res2_part + 4 * E32_RES_BLOCKS;
+  // partial-sum layout of e32_part (doubles): 4 x E32_RES_BLOCKS residual sums | ... multi-TopK residual | total variance | the latent
+  // sums, one per workgroup of e32_bias_relu_kernel (sized with the row buffers in e32_ensure)
+  double *res_part = c->e32_part, *res2_part = res_part + 4 * E32_RES_BLOCKS, *tv_part = res2_part + 4 * E32_RES_BLOCKS, *l1_part = c->e32_part + E32_FIXED_DOUBLES;
   const int grid_x = grid_for(M * d_p, 2048);
   HIP_TRY(hipMemsetAsync(c->e32_colmax, 0, (size_t)n_p * 4, s));
   E32Final f{};
@@ -2628,7 +2637,6 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
     hipLaunchKernelGGL(e32_load_x_kernel<T>, dim3(grid_x), dim3(256), 0, s, x, c->e32_x, (const float*)nullptr, M, d, d_p);
     e32_gemm<false>(c->e32_x, d_p, W, n_p, c->e32_pre, n_p, M, n_p, d_p, s);                       // x W: W is [d_p][n_p]
     const dim3 gb((n_p + 255) / 256, (unsigned)((M + 63) / 64));
-    if ((int64_t)gb.x * gb.y > E32_L1_PARTS) return fail(SAE_ERR_INVALID, "fp32 evaluation: %lld rows x %d latents exceed its partial-sum buffer", (long long)M, n_p);
     hipLaunchKernelGGL(e32_bias_relu_kernel, gb, dim3(256), 0, s, c->e32_pre, b, M, n, n_p, l1_part, c->e32_colmax);
     e32_gemm<true>(c->e32_pre, n_p, W, n_p, c->e32_xhat, d_p, M, d_p, n_p, s);                     // c W^T: W as [N = d_p][K = n_p]
     hipLaunchKernelGGL(e32_residual_kernel<T>, dim3(E32_RES_BLOCKS), dim3(256), 0, s, c->e32_xhat, d_p, (const float*)nullptr, x, M, d, res_part);
@@ -2639,17 +2647,16 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
     hipLaunchKernelGGL(e32_load_x_kernel<T>, dim3(grid_x), dim3(256), 0, s, x, c->e32_x, bd, M, d, d_p);          // sae_in = x - b_dec
     e32_gemm<true>(c->e32_x, d_p, We, d_p, c->e32_pre, n_p, M, n_p, d_p, s);                       // sae_in W_enc^T: W_enc is [n_p][d_p]
     const dim3 gb((n_p + 255) / 256, (unsigned)((M + 63) / 64));
-    if ((int64_t)gb.x * gb.y > E32_L1_PARTS) return fail(SAE_ERR_INVALID, "fp32 evaluation: %lld rows x %d latents exceed its partial-sum buffer", (long long)M, n_p);
     hipLaunchKernelGGL(e32_bias_relu_kernel, gb, dim3(256), 0, s, c->e32_pre, be, M, n, n_p, l1_part, (int*)nullptr);
     const int64_t T_rows = c->rows_per_file > 0 && M % c->rows_per_file == 0 ? c->rows_per_file : M;
     hipLaunchKernelGGL(e32_total_variance_kernel<T>, dim3(E32_RES_BLOCKS), dim3(256), 0, s, x, M / T_rows, T_rows * d, tv_part);
     f.tv_part = tv_part; f.n_tv = E32_RES_BLOCKS;
-    hipLaunchKernelGGL(e32_topk_select_kernel, dim3((unsigned)M), dim3(256), 0, s, c->e32_pre, c->e32_sel, n, n_p, c->k, (int*)nullptr);
+    hipLaunchKernelGGL(e32_topk_select_kernel, dim3((unsigned)M), dim3(256), 0, s, c->e32_pre, c->e32_sel, n, n_p, c->k);
     e32_gemm<false>(c->e32_sel, n_p, Wd, d_p, c->e32_xhat, d_p, M, d_p, n_p, s);                   // dense W_dec: W_dec is [n_p][d_p]
     hipLaunchKernelGGL(e32_residual_kernel<T>, dim3(E32_RES_BLOCKS), dim3(256), 0, s, c->e32_xhat, d_p, bd, x, M, d, res_part);
     f.res_part = res_part; f.n_res = E32_RES_BLOCKS;
     if (c->multi) {              // cfg.multi_topk: the returned encoding is the 4k one (topkautoencoder.py:134-136)
-      hipLaunchKernelGGL(e32_topk_select_kernel, dim3((unsigned)M), dim3(256), 0, s, c->e32_pre, c->e32_sel, n, n_p, c->k4, (int*)nullptr);
+      hipLaunchKernelGGL(e32_topk_select_kernel, dim3((unsigned)M), dim3(256), 0, s, c->e32_pre, c->e32_sel, n, n_p, c->k4);
       e32_gemm<false>(c->e32_sel, n_p, Wd, d_p, c->e32_xhat, d_p, M, d_p, n_p, s);
       hipLaunchKernelGGL(e32_residual_kernel<T>, dim3(E32_RES_BLOCKS), dim3(256), 0, s, c->e32_xhat, d_p, bd, x, M, d, res2_part);
       f.res2_part = res2_part; f.n_res2 = E32_RES_BLOCKS;
@@ -2658,8 +2665,7 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   }
   hipLaunchKernelGGL(e32_finalize_kernel, dim3(1), dim3(256), 0, s, f, c->G + c->nparams);
   HIP_TRY(hipGetLastError());
-  c->last_M = M;
-  c->last_M_p = round_up(M, c->row_pad);
+  // (last_M / last_M_p stay the last bf16 forward's: they index its buffers, which this path does not touch)
   c->last_call = LAST_FWD_E32;
   c->metrics_fresh = false;
   return SAE_OK;
@@ -2667,7 +2673,9 @@ static int eval_fp32_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
 
 static int eval_fp32_dispatch(sae_ctx* c, const void* x, int64_t M, int x_dtype, void* stream) {
   if (!c || !x) return fail(SAE_ERR_INVALID, "null argument");
-  if (M <= 0) return fail(SAE_ERR_INVALID, "M=%lld must be positive", (long long)M);
+  if (M <= 0 || M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "M=%lld outside (0, max_rows=%lld]", (long long)M, (long long)c->cfg.max_rows);
+  if ((M + 63) / 64 > 65535 || e32_l1_parts(c->n_p, M) > 0x7fffffff)      // grid.y of its kernels; the int count of the latent partials
+    return fail(SAE_ERR_INVALID, "fp32 evaluation: %lld rows x %d latents exceed its launch grid", (long long)M, c->n_p);
   USE_DEVICE(c);
   hipStream_t s = (hipStream_t)stream;
   c->last_dtype = x_dtype;
@@ -2800,6 +2808,7 @@ extern "C" int sae_read_metrics(sae_ctx* c, float out[SAE_NUM_METRICS], void* st
 
 // TopK: the masked dense rows of the last forward, written on demand when the step itself did not need them
 static int ensure_dense(sae_ctx* c) {
+  if (int rc = no_bf16_forward_left(c)) return rc;
   if (!c->topk || c->dense_valid || c->last_M <= 0) return SAE_OK;
   HIP_TRY(hipDeviceSynchronize());
   hipLaunchKernelGGL(topk_densify_kernel, dim3((unsigned)c->last_M_p), dim3(256), 0, (hipStream_t)0, c->top_vals, c->top_idx, c->k,
@@ -2814,6 +2823,8 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
   if (!c || !out) return fail(SAE_ERR_INVALID, "null argument");
   USE_DEVICE(c);
   HIP_TRY(hipDeviceSynchronize());
+  if (which == 0 || which == 1 || which == 3 || which == 8 || which == 9)      // tensors of the last bf16 forward
+    if (int rc = no_bf16_forward_left(c)) return rc;
   if (which == 0) {
     int rc_d = ensure_dense(c);
     if (rc_d) return rc_d;
@@ -2923,9 +2934,9 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
 extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride) {
   if (!c || !dev_ptr || !row_stride) return fail(SAE_ERR_INVALID, "null argument");
   if (int rc = no_forward_left(c)) return rc;
+  if (int rc = no_bf16_forward_left(c)) return rc;
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
-  if (c->last_call == LAST_FWD_E32) return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows");
   {
     int rc_d = ensure_dense(c);
     if (rc_d) return rc_d;
@@ -2939,6 +2950,7 @@ extern "C" int sae_topk_indices(sae_ctx* c, void** dev_ptr, int* k) {
   if (!c || !dev_ptr || !k) return fail(SAE_ERR_INVALID, "null argument");
   if (int rc = no_forward_left(c)) return rc;
   if (!c->topk) return fail(SAE_ERR_INVALID, "sae_topk_indices: not a TopK context");
+  if (int rc = no_bf16_forward_left(c)) return rc;
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   *dev_ptr = c->top_idx;
   *k = c->k;
@@ -2949,6 +2961,7 @@ extern "C" int sae_multi_topk_buffers(sae_ctx* c, void** dense_dev, int64_t* row
   if (!c || !dense_dev || !row_stride || !idx_dev || !k4) return fail(SAE_ERR_INVALID, "null argument");
   if (int rc = no_forward_left(c)) return rc;
   if (!c->topk || !c->multi) return fail(SAE_ERR_INVALID, "sae_multi_topk_buffers: not a TopK context with multi_topk");
+  if (int rc = no_bf16_forward_left(c)) return rc;
   if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   if (!c->multi_dense_valid) {      // a training step on the sparse backward keeps the 4k selection compact: densify on demand
     USE_DEVICE(c);
@@ -3015,13 +3028,13 @@ extern "C" int sae_latent_colmax(sae_ctx* c, float* out_host, int64_t capacity, 
   if (!c || !out_host) return fail(SAE_ERR_INVALID, "null argument");
   if (int rc = no_forward_left(c)) return rc;
   if (capacity < c->n) return fail(SAE_ERR_INVALID, "capacity too small");
-  if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   USE_DEVICE(c);
   if (c->last_call == LAST_FWD_E32) {
     HIP_TRY(hipMemcpyAsync(out_host, c->e32_colmax, (size_t)c->n * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return SAE_OK;
   }
+  if (c->last_M <= 0) return fail(SAE_ERR_STATE, "no forward has run yet");
   {
     int rc_d = ensure_dense(c);
     if (rc_d) return rc_d;

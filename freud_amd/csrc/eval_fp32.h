@@ -15,8 +15,9 @@
 
 constexpr int E32_BM = 64, E32_BN = 64, E32_BK = 16, E32_LD = 68;
 constexpr int E32_RES_BLOCKS = 512;                                  // workgroups (and partial sums) of the residual / variance passes
-constexpr int E32_L1_PARTS = 16384;                                   // (latent blocks of 256 columns x 64 rows: 1500 rows x 163 840 latents)
-constexpr int E32_PART_DOUBLES = E32_L1_PARTS + 2 * 4 * E32_RES_BLOCKS + E32_RES_BLOCKS;
+constexpr int E32_FIXED_DOUBLES = 2 * 4 * E32_RES_BLOCKS + E32_RES_BLOCKS;   // residual, multi-TopK residual and variance partials
+// partial sums of the latent: one per workgroup of e32_bias_relu_kernel (256 columns x 64 rows)
+inline int64_t e32_l1_parts(int n_p, int64_t M) { return (int64_t)((n_p + 255) / 256) * ((M + 63) / 64); }
 
 // C[M x N] = A[M x K] . B,  A row-major (K contiguous, lda);  B as [K][N] (BT = false, ldb = row pitch of a k-row) or as [N][K]
 // (BT = true: the operand is stored transposed, K contiguous).  K a multiple of 16, N a multiple of 64 (padded shapes); M arbitrary.
@@ -160,8 +161,7 @@ __global__ __launch_bounds__(256) void e32_total_variance_kernel(const T* __rest
 // the 31 value bits (non-negative floats order like their bit patterns): "at least k entries >= T".  Kept: every entry above it
 // and the first (k - those) entries equal to it in column order -- the engine's tie rule; if the k-th largest is 0 only the
 // positive entries (the zeros contribute nothing to the decode).  out = the masked dense row.
-__global__ __launch_bounds__(256) void e32_topk_select_kernel(const float* __restrict__ pre, float* __restrict__ out, int n, int n_p, int k,
-                                                              int* __restrict__ idx_out /* [M][k] or null */) {
+__global__ __launch_bounds__(256) void e32_topk_select_kernel(const float* __restrict__ pre, float* __restrict__ out, int n, int n_p, int k) {
   __shared__ int cnt[4];
   __shared__ int run;
   const int64_t row = blockIdx.x;
@@ -203,7 +203,6 @@ __global__ __launch_bounds__(256) void e32_topk_select_kernel(const float* __res
     if (t == 0) run += cnt[0] + cnt[1] + cnt[2] + cnt[3];
     __syncthreads();
   }
-  (void)idx_out;
 }
 
 // per-feature maxima of a non-negative fp32 [M][n_p] array (the selected TopK activations) into integer bit patterns

@@ -438,7 +438,10 @@ class SaeEngine:
 
     def set_eval_precision(self, precision: str) -> None:
         """"bf16" (default): eval() / eval_into() run the training kernels' arithmetic (CPU autocast's).  "fp32": fp32 end to end --
-        what the reference's validate() computes on device='cpu' (train_sae.py:162-166) and selects bestval.pth by."""
+        what the reference's validate() computes on device='cpu' (train_sae.py:162-166) and selects bestval.pth by.  The fp32
+        forward takes at most max_rows rows and leaves no bf16 latent: after it latent_buffer(), topk_indices_tensor(),
+        multi_topk_buffers() and debug_read(0 / 1 / 3 / 8 / 9) raise EngineError until the next bf16 eval() / step(); metrics(),
+        latent_colmax(), debug_read(2), get_params(), get_opt_state(), get_topk_state() and decode() stay valid."""
         if precision not in ("bf16", "fp32"):
             raise ValueError(f"Invalid evaluation precision: {precision}, must be 'bf16' or 'fp32'")
         _check(self._lib.sae_set_eval_precision(self._ctx, 3 if precision == "fp32" else PRECISION["bf16"]))
@@ -459,13 +462,13 @@ class SaeEngine:
 
     # -- inference ---------------------------------------------------------
     def latent_buffer(self):
-        """(device pointer, row stride in elements) of the bf16 latent of the last forward."""
+        """(device pointer, row stride in elements) of the bf16 latent of the last forward (EngineError after an fp32 evaluation)."""
         ptr, ld = C.c_void_p(), C.c_int64()
         _check(self._lib.sae_latent_buffer(self._ctx, C.byref(ptr), C.byref(ld)))
         return ptr.value, ld.value
 
     def topk_indices_tensor(self, rows: int, device):
-        """int32 [rows][k] torch view of the top-k indices of the last forward (TopK contexts)."""
+        """int32 [rows][k] torch view of the top-k indices of the last forward (TopK contexts; EngineError after an fp32 evaluation)."""
         import torch
         ptr, k = C.c_void_p(), C.c_int()
         _check(self._lib.sae_topk_indices(self._ctx, C.byref(ptr), C.byref(k)))
@@ -476,7 +479,8 @@ class SaeEngine:
         return torch.as_tensor(_Alias(), device=device)
 
     def multi_topk_buffers(self, rows: int, device):
-        """TopK with multi_topk: (bf16 [rows][n_dict] dense 4k activations, int32 [rows][4k] indices) of the last forward."""
+        """TopK with multi_topk: (bf16 [rows][n_dict] dense 4k activations, int32 [rows][4k] indices) of the last forward
+        (EngineError after an fp32 evaluation)."""
         import torch
         dptr, ld, iptr, k4 = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int()
         _check(self._lib.sae_multi_topk_buffers(self._ctx, C.byref(dptr), C.byref(ld), C.byref(iptr), C.byref(k4)))
@@ -505,7 +509,7 @@ class SaeEngine:
         return out
 
     def latent_colmax(self, stream=None) -> np.ndarray:
-        """max over rows of |latent| per dictionary feature for the last forward (validate())."""
+        """max over rows of |latent| per dictionary feature for the last forward (validate()), the fp32 evaluation included."""
         out = np.empty(self.n, dtype=np.float32)
         _check(self._lib.sae_latent_colmax(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), self.n, _stream_ptr(stream)))
         return out

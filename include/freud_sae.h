@@ -292,7 +292,12 @@ int sae_eval_into(sae_ctx* ctx, const void* x_dev, int64_t M, int x_dtype, float
  * topkautoencoder.py:93-151 without a dead mask) and what its bestval.pth selection (train_sae.py:585-595) rests on: fp32 matrix
  * instructions, fp32 bias / ReLU / top-k (ties: lowest column first), loss sums in double.  The in-place column normalisation of
  * the L1 weights happens first, exactly as in every other forward.  Training steps are not affected.  Any SAE_PREC_* other than
- * these two: SAE_ERR_INVALID. */
+ * these two: SAE_ERR_INVALID.
+ * The fp32 forward obeys M <= max_rows like every other forward and works in buffers of its own: it leaves no bf16 latent rows.
+ * While it is the last forward, sae_latent_buffer, sae_topk_indices, sae_multi_topk_buffers and sae_debug_read(0, 1, 3, 8, 9)
+ * return SAE_ERR_STATE (run a bf16 sae_eval to read those); sae_read_metrics and sae_latent_colmax answer for the fp32 forward,
+ * and sae_debug_read(2) (the gradients of the last training forward), sae_get_params, sae_get_opt_state, sae_get_topk_state and
+ * sae_decode stay valid. */
 int sae_set_eval_precision(sae_ctx* ctx, int precision);
 
 /* Copy the SAE_NUM_METRICS scalars to host.  Synchronises `stream`. */
