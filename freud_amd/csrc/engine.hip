@@ -38,6 +38,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "file_top.h"
 #include "stats.h"
 #include "coact.h"
+#include "manip.h"
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
 
@@ -126,13 +127,17 @@ enum KernelId {
   KID_STEP_TOTAL,
   KID_COACT_PACK,      // feature co-activation (coact.h): the mask pack and the i8 update of sae_coact_files
   KID_COACT_UPDATE,
+  KID_MANIP_SERIES,    // feature manipulation (manip.h): the series + operand rows, the standard decode, the apply rule
+  KID_MANIP_DECODE,
+  KID_MANIP_APPLY,
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
                                               "dw_gemm", "bwd_fused_gemm", "reduce_grads", "clip_adam", "topk_enc_gemm", "topk_select",
                                               "topk_decode", "topk_ddense_gemm", "topk_dwdec_gemm", "topk_dwenc_gemm",
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
-                                              "fwd_bwd_total", "coact_pack", "coact_update"};
+                                              "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
+                                              "manip_apply"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -297,6 +302,7 @@ struct sae_ctx {
   LastCall last_call = LAST_FWD_BF16;   // what the last forward-like call left behind (no_forward_left, the getters)
   void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
   int8_t* co_zt = nullptr;      // sae_coact_files scratch (coact.h): the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)]
+  float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;
@@ -566,7 +572,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->mn_w};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);
@@ -3426,6 +3432,105 @@ extern "C" int sae_coact_neighbor_keys(const int32_t* counts, int64_t n, int64_t
   if (measure != SAE_COACT_JACCARD && measure != SAE_COACT_COND && measure != SAE_COACT_COUNT) return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
   hipLaunchKernelGGL(coact_keys_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
                      (hipStream_t)stream, counts, (int)n, row0, n_rows, measure, keys);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- feature manipulation (manip.h): one encode, one decode, then a rank-one term per edit and variant
+static_assert(SAE_MANIP_SCALE == SM_SCALE && SAE_MANIP_SET == SM_SET && SAE_MANIP_MAX_EDITS == SM_MAX_EDITS &&
+              SAE_MANIP_MAX_VARIANTS == SM_MAX_VARIANTS, "freud_sae.h and manip.h disagree");
+static const FilePassKind kManipPass = {"sae_manipulate_files", "manipulate in a bf16 context", "manipulation", 0};
+
+// L1 standard decode: sae_decode's GEMM on the forward's own padded bf16 latent (no pad_latent copy), x_hat = c W^T with the
+// bf16 copy of the current W -- settled and cast exactly as sae_decode does, so the two agree to the bit
+static int manip_decode_l1(sae_ctx* c, int64_t M, float* x_hat, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  settle_weights(c, s);
+  const int64_t n8 = c->nW / 8;
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P, c->Wb, n8);
+  GemmArgs g{};
+  g.A0 = c->c; g.lda = n_p; g.B0 = c->Wb; g.ldb = n_p;
+  g.nbm = (int)(c->last_M_p / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
+  EpiStoreF32 e{};
+  e.out = x_hat; e.M = M; e.d = c->d; e.bias = nullptr;
+  return launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+}
+
+static void manip_decode_topk(sae_ctx* c, int64_t M, float* x_hat, hipStream_t s) {
+  const float* bd = c->P + 2 * c->nW + c->n_p;
+  const dim3 grid((unsigned)((M + 3) / 4));
+  auto launch = [&](auto np_tag) {
+    constexpr int NP = decltype(np_tag)::value;
+    hipLaunchKernelGGL(manip_topk_decode_kernel<NP>, grid, dim3(256), 0, s, c->top_vals, c->top_idx, c->k, c->Wd_b, bd, x_hat, M, c->d,
+                       c->d_p, c->n_p);
+  };
+  if (c->d_p == 384) launch(std::integral_constant<int, 3>{});
+  else if (c->d_p == 768) launch(std::integral_constant<int, 6>{});
+  else if (c->d_p == 1280) launch(std::integral_constant<int, 10>{});
+  else launch(std::integral_constant<int, 0>{});
+}
+
+extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* latents,
+                                    const int32_t* ops, int n_edits, const float* values, int n_variants, int flags, float* standard,
+                                    float* manipulated, float* series, void* stream) {
+  if (!latents || !ops || !values || !manipulated || !series) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_edits < 1 || n_edits > SAE_MANIP_MAX_EDITS) return fail(SAE_ERR_INVALID, "n_edits=%d outside [1, %d]", n_edits, SAE_MANIP_MAX_EDITS);
+  if (n_variants < 1 || n_variants > SAE_MANIP_MAX_VARIANTS)
+    return fail(SAE_ERR_INVALID, "n_variants=%d outside [1, %d]", n_variants, SAE_MANIP_MAX_VARIANTS);
+  ManipEdits ed{};
+  ed.n_edits = n_edits; ed.n_variants = n_variants;
+  for (int e = 0; e < n_edits; ++e) {
+    if (c && (latents[e] < 0 || latents[e] >= c->n)) return fail(SAE_ERR_INVALID, "edit %d: latent %d outside [0, %d)", e, latents[e], c->n);
+    for (int f = 0; f < e; ++f)
+      if (latents[f] == latents[e]) return fail(SAE_ERR_INVALID, "edits %d and %d name the same latent %d", f, e, latents[e]);
+    if (ops[e] != SAE_MANIP_SCALE && ops[e] != SAE_MANIP_SET) return fail(SAE_ERR_INVALID, "edit %d: unknown op %d", e, ops[e]);
+    ed.latents[e] = latents[e]; ed.ops[e] = ops[e];
+    for (int v = 0; v < n_variants; ++v) {
+      const float val = values[v * n_edits + e];
+      if (!std::isfinite(val)) return fail(SAE_ERR_INVALID, "variant %d, edit %d: the value is not finite", v, e);
+      ed.values[v][e] = val;
+    }
+  }
+  int64_t M;
+  if (int rc = file_pass_begin(kManipPass, c, x, standard, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_manipulate_files: the TopK decode serves d_model <= 1536");
+  if (!c->mn_w) HIP_TRY(hipMalloc((void**)&c->mn_w, (size_t)SM_MAX_EDITS * c->d_p * 4));
+  hipStream_t s = (hipStream_t)stream;
+  const int d = c->d;
+  // the bf16 eval forward: encode() -- and the state sae_eval leaves (latent rows, indices, metrics)
+  if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+
+  ev_begin(c, KID_MANIP_DECODE, s);
+  int rc = SAE_OK;
+  if (c->topk) manip_decode_topk(c, M, standard, s);
+  else rc = manip_decode_l1(c, M, standard, s);
+  ev_end(c, KID_MANIP_DECODE, s);
+  if (rc) return rc;
+
+  ev_begin(c, KID_MANIP_SERIES, s);
+  if (c->topk) {
+    hipLaunchKernelGGL(manip_series_topk_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, ed, series);
+    hipLaunchKernelGGL(manip_rows_kernel, dim3((d + 255) / 256, n_edits), dim3(256), 0, s, c->Wd_b, (int64_t)c->d_p, (int64_t)1, d, ed,
+                       c->mn_w, c->d_p);
+  } else {
+    hipLaunchKernelGGL(manip_series_kernel, dim3(grid_for(M * n_edits, 4096)), dim3(256), 0, s, c->c, (int64_t)c->n_p, M, ed, series);
+    hipLaunchKernelGGL(manip_rows_kernel, dim3((d + 255) / 256, n_edits), dim3(256), 0, s, c->Wb, (int64_t)1, (int64_t)c->n_p, d, ed,
+                       c->mn_w, c->d_p);
+  }
+  ev_end(c, KID_MANIP_SERIES, s);
+
+  ev_begin(c, KID_MANIP_APPLY, s);
+  {
+    const bool vec = d % 4 == 0 && ((reinterpret_cast<uintptr_t>(standard) | reinterpret_cast<uintptr_t>(manipulated)) & 15) == 0;
+    const int vw = vec ? 4 : 1;
+    const int nslab = (d + 32 * vw - 1) / (32 * vw);
+    // groups of 8 half waves, a multiple of the slabs: every frame x slab once, at most ~4096 groups striding over the frames
+    const int64_t per_slab = std::min<int64_t>((M + 7) / 8, std::max<int64_t>(4096 / nslab, 1));
+    const dim3 grid((unsigned)(per_slab * nslab));
+    if (vec) hipLaunchKernelGGL(manip_apply_kernel<4>, grid, dim3(256), 0, s, standard, series, c->mn_w, c->d_p, M, d, nslab, ed, manipulated);
+    else hipLaunchKernelGGL(manip_apply_kernel<1>, grid, dim3(256), 0, s, standard, series, c->mn_w, c->d_p, M, d, nslab, ed, manipulated);
+  }
+  ev_end(c, KID_MANIP_APPLY, s);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

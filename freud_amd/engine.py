@@ -125,6 +125,8 @@ def load() -> C.CDLL:
         "sae_stats_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
         "sae_coact_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
         "sae_coact_neighbor_keys": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, vp]),
+        "sae_manipulate_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.POINTER(i32), C.POINTER(i32), C.c_int, fptr, C.c_int, C.c_int,
+                                           vp, vp, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -165,6 +167,7 @@ EXPORTED_SYMBOLS = [
     "sae_stats_files",
     "sae_file_top_features",
     "sae_coact_files", "sae_coact_neighbor_keys",
+    "sae_manipulate_files",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
@@ -172,6 +175,9 @@ FILE_TOP_POSITIVE = 1                                               # include/fr
 FILE_TOP_MAX = 1024                                                 # include/freud_sae.h: SAE_FILE_TOP_MAX
 STATS_UNFUSED = 1                                                   # include/freud_sae.h: SAE_STATS_UNFUSED
 COACT_MEASURES = {"jaccard": 0, "cond": 1, "count": 2}              # include/freud_sae.h: SAE_COACT_*
+MANIP_OPS = {"scale": 0, "set": 1}                                  # include/freud_sae.h: SAE_MANIP_SCALE / SAE_MANIP_SET
+MANIP_MAX_EDITS = 16                                                # include/freud_sae.h: SAE_MANIP_MAX_EDITS
+MANIP_MAX_VARIANTS = 16                                             # include/freud_sae.h: SAE_MANIP_MAX_VARIANTS
 
 
 def stats_layout(n: int) -> dict:
@@ -579,6 +585,32 @@ class SaeEngine:
         x, xp, B, T, _d, dt, lp = _files_args(x, "coact_files", lengths)
         _check_coact_table(counts, self.n)
         _check(self._lib.sae_coact_files(self._ctx, xp, B, T, dt, lp, 0, C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+
+    # -- feature manipulation (include/freud_sae.h: sae_manipulate_files; freud_amd/manipulate.py) -------------------------
+    def manipulate_files(self, x, latents, ops, values, standard, manipulated, series, stream=None) -> None:
+        """Edit the latents `latents` [E] (ops [E]: MANIP_OPS values) of every frame of x [n_files, T, d] (CUDA) with each row of
+        values [V, E] and decode both ways, into contiguous fp32 CUDA tensors: standard (n_files * T * d elements), manipulated
+        (V times that) and series (E * n_files * T: the edited latents' own values per frame).  Asynchronous.  Afterwards the
+        context is as after eval(x)."""
+        import torch
+        x, xp, B, T, d, dt, _lp = _files_args(x, "manipulate_files", None)
+        lat = np.ascontiguousarray(np.asarray(latents, dtype=np.int32).reshape(-1))
+        op = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1))
+        val = np.ascontiguousarray(np.asarray(values, dtype=np.float32))
+        E = int(lat.size)
+        if E < 1 or E > MANIP_MAX_EDITS or op.size != E:
+            raise EngineError(f"manipulate_files: {E} latents and {op.size} ops; the engine takes 1 to {MANIP_MAX_EDITS} edits")
+        if val.ndim != 2 or val.shape[1] != E or not 1 <= val.shape[0] <= MANIP_MAX_VARIANTS:
+            raise EngineError(f"manipulate_files: values must be [1..{MANIP_MAX_VARIANTS}, {E}], got {val.shape}")
+        V, M = int(val.shape[0]), B * T
+        for name, t, numel in (("standard", standard, M * d), ("manipulated", manipulated, V * M * d), ("series", series, E * M)):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
+                raise EngineError(f"{name} must be a contiguous float32 CUDA tensor of {numel} elements")
+        self._note_shape(x)
+        _check(self._lib.sae_manipulate_files(self._ctx, xp, B, T, dt, lat.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              op.ctypes.data_as(C.POINTER(C.c_int32)), E, val.ctypes.data_as(C.POINTER(C.c_float)), V, 0,
+                                              C.c_void_p(standard.data_ptr()), C.c_void_p(manipulated.data_ptr()),
+                                              C.c_void_p(series.data_ptr()), _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:

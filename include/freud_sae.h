@@ -453,6 +453,48 @@ enum { SAE_COACT_JACCARD = 0, SAE_COACT_COND = 1, SAE_COACT_COUNT = 2 };
 int sae_coact_neighbor_keys(const int32_t* counts_dev, int64_t n, int64_t row0, int64_t n_rows, int measure, uint64_t* keys_dev,
                             void* stream);
 
+/* ---- Feature manipulation: the reference's manipulate_latent (utils/activations.py:243-272, served as /manipulate_feature) for
+ * a batch of files, several edited latents and a sweep of edit values at once -- everything between the cached activations and
+ * the tensors handed to whisper_subbed.forward: the standard reconstruction, the manipulated ones, and the per-frame series of
+ * the edited latents.  A decode is linear in the latent, so one encode and one decode serve any number of edits and variants.
+ *
+ * Semantics (freud_amd/csrc/manip.h).  x_dev is [n_files][rows_per_file][d]; M = n_files * rows_per_file.  ALL M frames are
+ * edited and decoded (the reference edits the padded frames too and trims only the series it returns, activations.py:283-289;
+ * trimming belongs to the caller).  Per frame t and edit e, a = the value freud_amd.models encode() returns for latent
+ * latents_host[e], widened exactly from bf16 to fp32: the stored L1 latent, or for TopK the selected activation and 0 where the
+ * latent is not among the row's k (activation_tensor_from_indexed, activations.py:41-58; a multi_topk context uses its k
+ * selection).  Variant v edits it with values_host[v * n_edits + e]:
+ *   SAE_MANIP_SCALE  new = a * value (the reference's manipulation_factor, activations.py:247-249, 261), one fp32 rounding;
+ *   SAE_MANIP_SET    new = value on every frame, selected or not (the latent clamped);
+ * delta = new - a, one fp32 rounding.  Outputs, all fp32, dense, caller-owned device memory:
+ *   series_dev      [n_edits][M]       a (the manipulated series is sm_new of it: the caller's arithmetic, one multiplication);
+ *   standard_dev    [M][d]             L1: latent . W^T, the decoder GEMM of sae_decode on the forward's own bf16 latent and the
+ *                                      bf16 copy of the current (normalised) W -- bit for bit sae_decode of sae_latent_buffer;
+ *                                      TopK: b_dec + sum_i top_acts[t][i] * bf16(W_dec)[top_indices[t][i]], fp32 fmaf in stored
+ *                                      list order (no dense row, no GEMM);
+ *   manipulated_dev [n_variants][M][d] fmaf(delta_{v,E-1}, w_{E-1}[c], ... fmaf(delta_{v,0}, w_0[c], standard[t][c])): the edits
+ *                                      in the order given, w_e = row latents_host[e] of the same bf16 decoder operand, widened.
+ *                                      An edit whose delta is zero is skipped, so a frame on which nothing changes (and every
+ *                                      frame of a SCALE by 1) is bit for bit standard.  This is the decode of the edited latent
+ *                                      WITHOUT rounding the edited value back to a bf16 GEMM operand.
+ *
+ * SAE_ERR_INVALID before anything is enqueued: a null pointer, n_edits outside [1, SAE_MANIP_MAX_EDITS], n_variants outside
+ * [1, SAE_MANIP_MAX_VARIANTS], a latent outside [0, n_dict), the same latent twice, an unknown op, a non-finite value, flags != 0,
+ * an fp8 context, n_files * rows_per_file > max_rows.  Asynchronous on `stream`; the host arrays are read before the call returns.
+ * Deterministic: two runs give bitwise identical outputs.  The first call allocates 64 x d bytes of context scratch (the operand
+ * rows).  Training state (parameters, moments, num_frames_since_fired) is untouched; the forward is the bf16 one whatever
+ * sae_set_eval_precision says, and afterwards the context is in the state sae_eval of the same batch leaves it in:
+ * sae_latent_buffer, sae_topk_indices, sae_read_metrics, sae_latent_colmax and sae_decode answer for this batch. */
+#define SAE_MANIP_MAX_EDITS 16
+#define SAE_MANIP_MAX_VARIANTS 16
+enum { SAE_MANIP_SCALE = 0, SAE_MANIP_SET = 1 };
+int sae_manipulate_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype,
+                         const int32_t* latents_host, const int32_t* ops_host, int n_edits,
+                         const float* values_host /* [n_variants][n_edits] */, int n_variants, int flags,
+                         float* standard_dev    /* [M][d]             */,
+                         float* manipulated_dev /* [n_variants][M][d] */,
+                         float* series_dev      /* [n_edits][M]       */, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
