@@ -97,25 +97,34 @@ def _check_args(sae, n_neighbors, measure) -> int:
     return n_neighbors
 
 
-def neighbor_tables(counts, n: int, n_neighbors: int, measure: str):
-    """The neighbour tables of a device count table counts [n, n] (int32 CUDA): selected in row blocks of at most KEY_BLOCK keys,
-    one read-back per block -> (partners, counts, scores) as decode_neighbor_table gives them."""
+def select_top_rows(n_rows: int, n_cols: int, n_top: int, write_keys, dev):
+    """Per row of a key table [n_rows, n_cols] its n_top best columns: built and selected in row blocks of at most KEY_BLOCK keys,
+    one read-back per block.  write_keys(row0, rows, keys) fills keys [rows, n_cols] (int64 CUDA holding the uint64 keys of
+    coact.h / labels.h) -> (partners, counts, scores) as decode_neighbor_table gives them."""
     from . import engine as E
 
-    dev = counts.device
-    rows = max(1, min(n, KEY_BLOCK // n))
-    keys = torch.empty(rows * n, dtype=torch.int64, device=dev)
-    lat = torch.empty(rows * n_neighbors, dtype=torch.int32, device=dev)
-    out = torch.empty(rows * n_neighbors, dtype=torch.int64, device=dev)
-    tl = np.empty((n, n_neighbors), np.int32)
-    tk = np.empty((n, n_neighbors), np.int64)
-    for r0 in range(0, n, rows):
-        nr = min(rows, n - r0)
-        E.coact_neighbor_keys(counts, n, r0, nr, COACT_MEASURES[measure], keys)
-        E.file_top_features(keys, nr, n, n_neighbors, FILE_TOP_POSITIVE, lat, out)
-        tl[r0:r0 + nr] = lat[:nr * n_neighbors].view(nr, n_neighbors).cpu().numpy()
-        tk[r0:r0 + nr] = out[:nr * n_neighbors].view(nr, n_neighbors).cpu().numpy()
+    rows = max(1, min(n_rows, KEY_BLOCK // n_cols))
+    keys = torch.empty(rows * n_cols, dtype=torch.int64, device=dev)
+    lat = torch.empty(rows * n_top, dtype=torch.int32, device=dev)
+    out = torch.empty(rows * n_top, dtype=torch.int64, device=dev)
+    tl = np.empty((n_rows, n_top), np.int32)
+    tk = np.empty((n_rows, n_top), np.int64)
+    for r0 in range(0, n_rows, rows):
+        nr = min(rows, n_rows - r0)
+        write_keys(r0, nr, keys)
+        E.file_top_features(keys, nr, n_cols, n_top, FILE_TOP_POSITIVE, lat, out)
+        tl[r0:r0 + nr] = lat[:nr * n_top].view(nr, n_top).cpu().numpy()
+        tk[r0:r0 + nr] = out[:nr * n_top].view(nr, n_top).cpu().numpy()
     return decode_neighbor_table(tl, tk)
+
+
+def neighbor_tables(counts, n: int, n_neighbors: int, measure: str):
+    """The neighbour tables of a device count table counts [n, n] (int32 CUDA) -> (partners, counts, scores) as
+    decode_neighbor_table gives them."""
+    from . import engine as E
+
+    return select_top_rows(n, n, n_neighbors, lambda r0, nr, keys: E.coact_neighbor_keys(counts, n, r0, nr, COACT_MEASURES[measure], keys),
+                           counts.device)
 
 
 @keep_rng

@@ -38,6 +38,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "file_top.h"
 #include "stats.h"
 #include "coact.h"
+#include "labels.h"
 #include "manip.h"
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
@@ -130,6 +131,8 @@ enum KernelId {
   KID_MANIP_SERIES,    // feature manipulation (manip.h): the series + operand rows, the standard decode, the apply rule
   KID_MANIP_DECODE,
   KID_MANIP_APPLY,
+  KID_LABEL_PACK,      // feature labels (labels.h): the label pack + label counts and the rectangular i8 update of sae_label_files
+  KID_LABEL_UPDATE,
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
@@ -137,7 +140,7 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "topk_decode", "topk_ddense_gemm", "topk_dwdec_gemm", "topk_dwenc_gemm",
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
-                                              "manip_apply"};
+                                              "manip_apply", "label_pack", "label_update"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -147,7 +150,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS };
 
 struct sae_ctx {
   sae_config cfg;
@@ -302,6 +305,8 @@ struct sae_ctx {
   LastCall last_call = LAST_FWD_BF16;   // what the last forward-like call left behind (no_forward_left, the getters)
   void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
   int8_t* co_zt = nullptr;      // sae_coact_files scratch (coact.h): the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)]
+  int8_t* lb_lt = nullptr;      // sae_label_files scratch (labels.h): the int8 label pack Lt [lb_rows][round_up(max_rows_p, CO_BK)]
+  int lb_rows = 0;              // its rows: the largest C_p = round_up(n_classes + 1, CO_BM) asked for so far
   float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
@@ -344,6 +349,8 @@ static int no_forward_left(const sae_ctx* c, bool after_search = true) {
     return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
   if (c->last_call == LAST_COACT)
     return fail(SAE_ERR_STATE, "the last call was a feature co-activation pass: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_LABELS)
+    return fail(SAE_ERR_STATE, "the last call was a feature label pass: it leaves no forward to read (run sae_eval first)");
   return SAE_OK;
 }
 
@@ -572,7 +579,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->mn_w};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->mn_w};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);
@@ -3396,15 +3403,9 @@ static int coact_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int
   return SAE_OK;
 }
 
-extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                               int flags, int32_t* counts, void* stream) {
-  int64_t M;
-  if (int rc = file_pass_begin(kCoactPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if ((reinterpret_cast<uintptr_t>(counts) & 3) != 0) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
-  if (int rc = coact_ensure(c)) return rc;
+// the batch's activity mask into c->co_zt: the encoder as encode() runs it, then the mask pack (sae_coact_files, sae_label_files)
+static int coact_encode_pack(sae_ctx* c, const void* x, int64_t M, int Trows, int x_dtype, const int32_t* lengths, int64_t Kp, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  const int64_t Kp = round_up(M, CO_BK);
   if (c->topk) {
     // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the selection scattered into the zeroed mask
     if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
@@ -3416,10 +3417,20 @@ extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64
     ev_end(c, KID_COACT_PACK, s);           // (the bracket closes whatever the memset answered)
     HIP_TRY(memset_zt);
     HIP_TRY(hipGetLastError());
-  } else {
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return coact_l1_impl(c, xt, M, Trows, lengths, Kp, s); })) return rc;
+    return SAE_OK;
   }
-  if (int rc = coact_launch_update(c, c->co_zt, Kp, c->n_p, c->n, counts, s)) return rc;
+  return with_x_type(x_dtype, x, [&](auto* xt) { return coact_l1_impl(c, xt, M, Trows, lengths, Kp, s); });
+}
+
+extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                               int flags, int32_t* counts, void* stream) {
+  int64_t M;
+  if (int rc = file_pass_begin(kCoactPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if ((reinterpret_cast<uintptr_t>(counts) & 3) != 0) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
+  if (int rc = coact_ensure(c)) return rc;
+  const int64_t Kp = round_up(M, CO_BK);
+  if (int rc = coact_encode_pack(c, x, M, (int)rows_per_file, x_dtype, lengths, Kp, stream)) return rc;
+  if (int rc = coact_launch_update(c, c->co_zt, Kp, c->n_p, c->n, counts, (hipStream_t)stream)) return rc;
   c->last_call = LAST_COACT;
   return SAE_OK;
 }
@@ -3432,6 +3443,84 @@ extern "C" int sae_coact_neighbor_keys(const int32_t* counts, int64_t n, int64_t
   if (measure != SAE_COACT_JACCARD && measure != SAE_COACT_COND && measure != SAE_COACT_COUNT) return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
   hipLaunchKernelGGL(coact_keys_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
                      (hipStream_t)stream, counts, (int)n, row0, n_rows, measure, keys);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- feature labels (labels.h): A += Lt Zt^T of one batch of files -- co-activation's mask against the frames' labels -- and the keys
+// of a block of rows of A in either orientation
+static_assert(SAE_LABEL_F1 == LB_F1 && SAE_LABEL_PRECISION == LB_PRECISION && SAE_LABEL_RECALL == LB_RECALL && SAE_LABEL_COUNT == LB_COUNT &&
+              SAE_LABEL_MAX_CLASSES == LB_MAX_CLASSES && SAE_LABEL_MAX_SLOTS == LB_MAX_SLOTS, "freud_sae.h and labels.h disagree");
+static const FilePassKind kLabelPass = {"sae_label_files", "count labels in a bf16 context", "label", 0};
+
+static int label_ensure(sae_ctx* c, int C_p) {
+  if (C_p <= c->lb_rows) return SAE_OK;
+  if (c->lb_lt) HIP_TRY(hipFree(c->lb_lt));          // (hipFree waits for the work that still reads it)
+  c->lb_lt = nullptr;
+  c->lb_rows = 0;
+  HIP_TRY(hipMalloc((void**)&c->lb_lt, (size_t)((int64_t)C_p * round_up(c->max_rows_p, CO_BK))));
+  c->lb_rows = C_p;
+  return SAE_OK;
+}
+
+extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                               const int32_t* labels, int n_slots, int n_classes, int flags, int32_t* counts, int64_t* label_count,
+                               void* stream) {
+  int64_t M;
+  if (!labels || !label_count) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_slots < 1 || n_slots > SAE_LABEL_MAX_SLOTS) return fail(SAE_ERR_INVALID, "n_slots=%d outside [1, %d]", n_slots, SAE_LABEL_MAX_SLOTS);
+  if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%d outside [1, %d]", n_classes, SAE_LABEL_MAX_CLASSES);
+  if ((reinterpret_cast<uintptr_t>(counts) & 3) != 0 || (reinterpret_cast<uintptr_t>(label_count) & 7) != 0)
+    return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned and label_count 8-byte aligned");
+  if (int rc = file_pass_begin(kLabelPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  const int C_p = (int)round_up(n_classes + 1, CO_BM);
+  if (int rc = coact_ensure(c)) return rc;
+  if (int rc = label_ensure(c, C_p)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  const int64_t Kp = round_up(M, CO_BK);
+  if (int rc = coact_encode_pack(c, x, M, Trows, x_dtype, lengths, Kp, stream)) return rc;
+
+  ev_begin(c, KID_LABEL_PACK, s);
+  const hipError_t memset_lt = hipMemsetAsync(c->lb_lt, 0, (size_t)((int64_t)C_p * Kp), s);
+  if (memset_lt == hipSuccess) {
+    hipLaunchKernelGGL(label_pack_kernel, dim3(grid_for(M * n_slots, 4096)), dim3(256), 0, s, labels, n_slots, n_classes, M, Trows, lengths,
+                       c->lb_lt, Kp);
+    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)(n_classes + 1)), dim3(256), 0, s, c->lb_lt, Kp, (unsigned long long*)label_count);
+  }
+  ev_end(c, KID_LABEL_PACK, s);             // (the bracket closes whatever the memset answered)
+  HIP_TRY(memset_lt);
+  HIP_TRY(hipGetLastError());
+
+  // the K split of coact.h's header over the rectangle's tiles
+  const int ntr = C_p / CO_BM, ntc = c->n_p / CO_BM;
+  const int nsteps = (int)(Kp / CO_BK);
+  int ksplit = (int)std::min<int64_t>(std::max<int64_t>((CO_MIN_WGS + ntr * ntc - 1) / (ntr * ntc), 1), nsteps);
+  const int per = (nsteps + ksplit - 1) / ksplit;
+  ksplit = (nsteps + per - 1) / per;
+  const dim3 grid((unsigned)ntc, (unsigned)ntr, (unsigned)ksplit);
+  ev_begin(c, KID_LABEL_UPDATE, s);
+  if (ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, per, counts);
+  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, per, counts);
+  ev_end(c, KID_LABEL_UPDATE, s);
+  HIP_TRY(hipGetLastError());
+  c->last_call = LAST_LABELS;
+  return SAE_OK;
+}
+
+extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count, int64_t n_classes, int64_t n, int measure, int by_latent,
+                              int64_t row0, int64_t n_rows, uint64_t* keys, void* stream) {
+  if (!counts || !label_count || !keys) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%lld outside [1, %d]", (long long)n_classes, SAE_LABEL_MAX_CLASSES);
+  if (n < 1 || n > FT_MAX_COLS) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24]", (long long)n);
+  if (by_latent != 0 && by_latent != 1) return fail(SAE_ERR_INVALID, "by_latent=%d is neither 0 nor 1", by_latent);
+  const int64_t rows_all = by_latent ? n : n_classes, ncols = by_latent ? n_classes : n;
+  if (n_rows < 1 || row0 < 0 || row0 + n_rows > rows_all)
+    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)rows_all);
+  if (measure != SAE_LABEL_F1 && measure != SAE_LABEL_PRECISION && measure != SAE_LABEL_RECALL && measure != SAE_LABEL_COUNT)
+    return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
+  hipLaunchKernelGGL(label_keys_kernel, dim3((unsigned)((ncols + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
+                     (hipStream_t)stream, counts, label_count, (int)n_classes, (int)n, measure, by_latent, row0, n_rows, keys);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

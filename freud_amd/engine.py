@@ -125,6 +125,8 @@ def load() -> C.CDLL:
         "sae_stats_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
         "sae_coact_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
         "sae_coact_neighbor_keys": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, vp]),
+        "sae_label_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+        "sae_label_keys": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, i64, i64, vp, vp]),
         "sae_manipulate_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.POINTER(i32), C.POINTER(i32), C.c_int, fptr, C.c_int, C.c_int,
                                            vp, vp, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
@@ -167,6 +169,7 @@ EXPORTED_SYMBOLS = [
     "sae_stats_files",
     "sae_file_top_features",
     "sae_coact_files", "sae_coact_neighbor_keys",
+    "sae_label_files", "sae_label_keys",
     "sae_manipulate_files",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
@@ -175,6 +178,9 @@ FILE_TOP_POSITIVE = 1                                               # include/fr
 FILE_TOP_MAX = 1024                                                 # include/freud_sae.h: SAE_FILE_TOP_MAX
 STATS_UNFUSED = 1                                                   # include/freud_sae.h: SAE_STATS_UNFUSED
 COACT_MEASURES = {"jaccard": 0, "cond": 1, "count": 2}              # include/freud_sae.h: SAE_COACT_*
+LABEL_MEASURES = {"f1": 0, "precision": 1, "recall": 2, "count": 3}  # include/freud_sae.h: SAE_LABEL_*
+LABEL_MAX_CLASSES = 4096                                            # include/freud_sae.h: SAE_LABEL_MAX_CLASSES
+LABEL_MAX_SLOTS = 16                                                # include/freud_sae.h: SAE_LABEL_MAX_SLOTS
 MANIP_OPS = {"scale": 0, "set": 1}                                  # include/freud_sae.h: SAE_MANIP_SCALE / SAE_MANIP_SET
 MANIP_MAX_EDITS = 16                                                # include/freud_sae.h: SAE_MANIP_MAX_EDITS
 MANIP_MAX_VARIANTS = 16                                             # include/freud_sae.h: SAE_MANIP_MAX_VARIANTS
@@ -586,6 +592,21 @@ class SaeEngine:
         _check_coact_table(counts, self.n)
         _check(self._lib.sae_coact_files(self._ctx, xp, B, T, dt, lp, 0, C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
 
+    # -- feature labels (include/freud_sae.h: sae_label_files; freud_amd/feature_labels.py) ---------------------------------
+    def label_files(self, x, labels, n_classes: int, counts, label_count, lengths=None, stream=None) -> None:
+        """Add the label counts of x [n_files, T, d] (CUDA) with labels (a contiguous int32 CUDA tensor [n_files, T, n_slots]: class
+        ids in [0, n_classes), -1 = empty) to counts (zero-initialised contiguous int32 CUDA [n_classes + 1, n_dict]) and label_count
+        (zero-initialised int64 CUDA [n_classes + 1]); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards
+        the last-forward getters fail until the next eval() / step()."""
+        import torch
+        x, xp, B, T, _d, dt, lp = _files_args(x, "label_files", lengths)
+        if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3
+                and tuple(labels.shape[:2]) == (B, T)):
+            raise EngineError(f"labels must be a contiguous int32 CUDA tensor [{B}, {T}, n_slots]")
+        _check_label_table(counts, label_count, n_classes, self.n)
+        _check(self._lib.sae_label_files(self._ctx, xp, B, T, dt, lp, C.c_void_p(labels.data_ptr()), int(labels.shape[2]), int(n_classes),
+                                         0, C.c_void_p(counts.data_ptr()), C.c_void_p(label_count.data_ptr()), _stream_ptr(stream)))
+
     # -- feature manipulation (include/freud_sae.h: sae_manipulate_files; freud_amd/manipulate.py) -------------------------
     def manipulate_files(self, x, latents, ops, values, standard, manipulated, series, stream=None) -> None:
         """Edit the latents `latents` [E] (ops [E]: MANIP_OPS values) of every frame of x [n_files, T, d] (CUDA) with each row of
@@ -723,6 +744,25 @@ def coact_neighbor_keys(counts, n: int, row0: int, n_rows: int, measure: int, ke
     _check_search_out(keys, max(int(n_rows), 0) * n)
     _check(load().sae_coact_neighbor_keys(C.c_void_p(counts.data_ptr()), int(n), int(row0), int(n_rows), int(measure),
                                           C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
+
+
+def _check_label_table(counts, label_count, n_classes: int, n: int) -> None:
+    import torch
+    rows = int(n_classes) + 1
+    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == rows * n):
+        raise EngineError(f"counts must be a contiguous int32 CUDA tensor of {rows} x {n} elements")
+    if not (label_count.is_cuda and label_count.dtype == torch.int64 and label_count.is_contiguous() and label_count.numel() == rows):
+        raise EngineError(f"label_count must be a contiguous int64 CUDA tensor of {rows} elements")
+
+
+def label_keys(counts, label_count, n_classes: int, n: int, measure: int, by_latent: int, row0: int, n_rows: int, keys, stream=None) -> None:
+    """keys (int64 holding uint64) = the keys of rows [row0, row0 + n_rows) of the label table counts [n_classes + 1, n] /
+    label_count [n_classes + 1]: [n_rows, n] (by_latent 0: a row is a label) or [n_rows, n_classes] (1: a row is a latent), for
+    file_top_features(keys, n_rows, columns, n_top, FILE_TOP_POSITIVE, ...); measure: a LABEL_MEASURES value."""
+    _check_label_table(counts, label_count, n_classes, n)
+    _check_search_out(keys, max(int(n_rows), 0) * (int(n_classes) if by_latent else n))
+    _check(load().sae_label_keys(C.c_void_p(counts.data_ptr()), C.c_void_p(label_count.data_ptr()), int(n_classes), int(n), int(measure),
+                                 int(by_latent), int(row0), int(n_rows), C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:

@@ -453,6 +453,48 @@ enum { SAE_COACT_JACCARD = 0, SAE_COACT_COND = 1, SAE_COACT_COUNT = 2 };
 int sae_coact_neighbor_keys(const int32_t* counts_dev, int64_t n, int64_t row0, int64_t n_rows, int measure, uint64_t* keys_dev,
                             void* stream);
 
+/* ---- Feature labels: which latents detect which labels of the data (an ESC-50 class, a speaker, the phoneme of a 20 ms frame), in
+ * one pass over the files.  The reference has no counterpart: its README reaches such statements by listening.
+ *
+ * Semantics.  Frames count exactly as in sae_stats_files / sae_coact_files (lengths_dev: the first min(length, T) frames of a file;
+ * without, all T), and "active" is their rule: the value encode() returns is > 0 (magnitude bits: a -0.0 and a selected zero of a
+ * TopK row are not active; a multi_topk context uses its k selection).  Every frame carries up to n_slots class ids in
+ * [0, n_classes) in labels_dev [n_files * rows_per_file][n_slots] (int32); -1 is an empty slot, the ids of one frame are distinct,
+ * any other id outside the range is ignored.  1 <= n_slots <= SAE_LABEL_MAX_SLOTS, 1 <= n_classes <= SAE_LABEL_MAX_CLASSES.
+ *
+ * A[l][j] = counts_dev [n_classes + 1][n_dict] (int32, row-major) is the number of counted frames that carry label l and on which
+ * latent j is active; row n_classes is the "any" row, the number of counted frames on which j is active (the fire_count of the
+ * statistics, the diagonal of the co-activation table).  label_count_dev [n_classes + 1] (int64) is the number of counted frames
+ * that carry l; entry n_classes is the number of counted frames.  Both are running totals, caller-owned, zeroed before the first
+ * batch.  Counts are int32: THE CALLER GUARANTEES that at most 2^31 - 1 frames are counted into one table
+ * (freud_amd/feature_labels.py refuses a pass whose files x T exceeds that).
+ *
+ * sae_label_files adds one batch.  The activity mask is packed exactly as by sae_coact_files, into the same context scratch; the
+ * labels are packed as int8 into scratch of their own (allocated by the first call, grown when a later call brings more classes:
+ * n_classes + 1 rounded up to 128, times max_rows rounded up to 128, bytes) and A += labels x mask runs on the i8 MFMA.  Sums are
+ * integers: two runs give bitwise identical tables.  flags must be 0.  n_files * rows_per_file <= max_rows; fp8 contexts:
+ * SAE_ERR_INVALID.  Null pointers, n_slots or n_classes out of range, unknown flags and bad shapes fail before anything is
+ * enqueued.  Asynchronous on `stream`.  Training state is untouched; afterwards sae_latent_buffer, sae_topk_indices, sae_decode,
+ * sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the next sae_eval / step. */
+#define SAE_LABEL_MAX_CLASSES 4096
+#define SAE_LABEL_MAX_SLOTS 16
+int sae_label_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                    const int32_t* labels_dev, int n_slots, int n_classes, int flags, int32_t* counts_dev, int64_t* label_count_dev,
+                    void* stream);
+
+/* Keys of a block of rows [row0, row0 + n_rows) of a label table (counts_dev, label_count_dev as sae_label_files leaves them; n =
+ * n_dict).  by_latent = 0: the rows are labels, keys_dev [n_rows][n] -- a label's latents; by_latent = 1: the rows are latents,
+ * keys_dev [n_rows][n_classes] -- a latent's labels (the "any" row is never a partner).  A key is ord(score) << 32 | A[l][j]
+ * (freud_amd/csrc/labels.h), 0 where A[l][j] == 0.  score = ONE fp64 division converted once to fp32, with fire[j] =
+ * A[n_classes][j]: SAE_LABEL_F1 2 A / (fire[j] + label_count[l]); SAE_LABEL_PRECISION A / fire[j]; SAE_LABEL_RECALL
+ * A / label_count[l]; SAE_LABEL_COUNT A.  sae_file_top_features(keys_dev, n_rows, columns, n_top, SAE_FILE_TOP_POSITIVE, ...) then
+ * gives each row's partners in the order score descending, then the larger count, then the lower index.  Null pointers, n_classes
+ * or n out of range, an empty or out-of-range row block, an unknown measure or orientation: SAE_ERR_INVALID.  Needs no context,
+ * runs on the current device, asynchronous on `stream`, deterministic. */
+enum { SAE_LABEL_F1 = 0, SAE_LABEL_PRECISION = 1, SAE_LABEL_RECALL = 2, SAE_LABEL_COUNT = 3 };
+int sae_label_keys(const int32_t* counts_dev, const int64_t* label_count_dev, int64_t n_classes, int64_t n, int measure, int by_latent,
+                   int64_t row0, int64_t n_rows, uint64_t* keys_dev, void* stream);
+
 /* ---- Feature manipulation: the reference's manipulate_latent (utils/activations.py:243-272, served as /manipulate_feature) for
  * a batch of files, several edited latents and a sweep of edit values at once -- everything between the cached activations and
  * the tensors handed to whisper_subbed.forward: the standard reconstruction, the manipulated ones, and the per-frame series of
