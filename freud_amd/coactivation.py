@@ -97,13 +97,17 @@ def _check_args(sae, n_neighbors, measure) -> int:
     return n_neighbors
 
 
-def select_top_rows(n_rows: int, n_cols: int, n_top: int, write_keys, dev):
+def select_top_rows(n_rows: int, n_cols: int, n_top: int, write_keys, dev, *, flags: int = FILE_TOP_POSITIVE, row_align: int = 1):
     """Per row of a key table [n_rows, n_cols] its n_top best columns: built and selected in row blocks of at most KEY_BLOCK keys,
     one read-back per block.  write_keys(row0, rows, keys) fills keys [rows, n_cols] (int64 CUDA holding the uint64 keys of
-    coact.h / labels.h) -> (partners, counts, scores) as decode_neighbor_table gives them."""
+    coact.h / labels.h / dict_match.h) -> (partners, counts, scores) as decode_neighbor_table gives them.  flags: those of
+    file_top_features (the scores of co-activation and labels are positive; a cosine is signed and passes 0).  row_align: blocks
+    begin at multiples of it where KEY_BLOCK leaves room for one (a key writer that works on aligned tiles computes no row twice)."""
     from . import engine as E
 
     rows = max(1, min(n_rows, KEY_BLOCK // n_cols))
+    if row_align > 1 and row_align <= rows < n_rows:
+        rows -= rows % row_align
     keys = torch.empty(rows * n_cols, dtype=torch.int64, device=dev)
     lat = torch.empty(rows * n_top, dtype=torch.int32, device=dev)
     out = torch.empty(rows * n_top, dtype=torch.int64, device=dev)
@@ -112,7 +116,7 @@ def select_top_rows(n_rows: int, n_cols: int, n_top: int, write_keys, dev):
     for r0 in range(0, n_rows, rows):
         nr = min(rows, n_rows - r0)
         write_keys(r0, nr, keys)
-        E.file_top_features(keys, nr, n_cols, n_top, FILE_TOP_POSITIVE, lat, out)
+        E.file_top_features(keys, nr, n_cols, n_top, flags, lat, out)
         tl[r0:r0 + nr] = lat[:nr * n_top].view(nr, n_top).cpu().numpy()
         tk[r0:r0 + nr] = out[:nr * n_top].view(nr, n_top).cpu().numpy()
     return decode_neighbor_table(tl, tk)

@@ -40,6 +40,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "coact.h"
 #include "labels.h"
 #include "manip.h"
+#include "dict_match.h"
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
 
@@ -3521,6 +3522,65 @@ extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count,
     return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
   hipLaunchKernelGGL(label_keys_kernel, dim3((unsigned)((ncols + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
                      (hipStream_t)stream, counts, label_count, (int)n_classes, (int)n, measure, by_latent, row0, n_rows, keys);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- dictionary comparison (dict_match.h): unit decoder directions as a K-concatenated hi / lo bf16 operand, and the cosine keys of
+// a block of A's rows against all of B through the row x row tile GEMM
+static_assert(SAE_DICT_MAX_D == DM_MAX_D && SAE_DICT_LEFT == DM_LEFT && SAE_DICT_RIGHT == DM_RIGHT && DM_MAX_N == FT_MAX_COLS &&
+              DM_ROW_ALIGN == G2_BM && DM_ROW_ALIGN == G2_BN && DM_K_ALIGN == GEMM_BK, "freud_sae.h, dict_match.h and gemm256.h disagree");
+
+static bool dict_dims_ok(int64_t n, int64_t d) { return n >= 1 && n <= DM_MAX_N && d >= 1 && d <= DM_MAX_D; }
+
+extern "C" int64_t sae_dict_pack_bytes(int64_t n, int64_t d) { return dict_dims_ok(n, d) ? dm_pack_bytes(n, d) : 0; }
+
+extern "C" int sae_dict_pack(const float* w, int64_t n, int64_t d, int64_t dir_stride, int64_t elem_stride, int side, void* packed,
+                             float* norms, void* stream) {
+  if (!w || !packed || !norms) return fail(SAE_ERR_INVALID, "null argument");
+  if (!dict_dims_ok(n, d)) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24] or d=%lld outside [1, %d]", (long long)n, (long long)d, DM_MAX_D);
+  if (dir_stride < 1 || elem_stride < 1) return fail(SAE_ERR_INVALID, "dir_stride=%lld, elem_stride=%lld: strides are positive element counts", (long long)dir_stride, (long long)elem_stride);
+  if (side != DM_LEFT && side != DM_RIGHT) return fail(SAE_ERR_INVALID, "side=%d is neither 0 nor 1", side);
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0 || (reinterpret_cast<uintptr_t>(w) & 3) != 0 || (reinterpret_cast<uintptr_t>(norms) & 3) != 0)
+    return fail(SAE_ERR_INVALID, "the packed operand must be 16-byte aligned, the weights and norms 4-byte aligned");
+  const int64_t rows_p = dm_rows_p(n);
+  hipStream_t s = (hipStream_t)stream;
+  if (elem_stride == 1)
+    hipLaunchKernelGGL(dict_pack_rows_kernel, dim3((unsigned)(rows_p / 4)), dim3(256), 0, s, w, n, (int)d, dir_stride, side, (unsigned short*)packed, norms);
+  else
+    hipLaunchKernelGGL(dict_pack_cols_kernel, dim3((unsigned)(rows_p / 64)), dim3(256), 0, s, w, n, (int)d, dir_stride, elem_stride, side,
+                       (unsigned short*)packed, norms);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_dict_sim_keys(const void* packed_a, int64_t n_a, const void* packed_b, int64_t n_b, int64_t d, int64_t row0, int64_t n_rows,
+                                 int self_mode, uint64_t* keys, void* stream) {
+  if (!packed_a || !packed_b || !keys) return fail(SAE_ERR_INVALID, "null argument");
+  if (!dict_dims_ok(n_a, d) || !dict_dims_ok(n_b, d))
+    return fail(SAE_ERR_INVALID, "n_a=%lld, n_b=%lld outside [1, 2^24] or d=%lld outside [1, %d]", (long long)n_a, (long long)n_b, (long long)d, DM_MAX_D);
+  if (self_mode != 0 && self_mode != 1) return fail(SAE_ERR_INVALID, "self_mode=%d is neither 0 nor 1", self_mode);
+  if (self_mode && n_a != n_b) return fail(SAE_ERR_INVALID, "self mode with n_a=%lld != n_b=%lld", (long long)n_a, (long long)n_b);
+  if (n_rows < 1 || row0 < 0 || row0 + n_rows > n_a)
+    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)n_a);
+  if (((reinterpret_cast<uintptr_t>(packed_a) | reinterpret_cast<uintptr_t>(packed_b)) & 15) != 0 || (reinterpret_cast<uintptr_t>(keys) & 7) != 0)
+    return fail(SAE_ERR_INVALID, "the packed operands must be 16-byte aligned and the keys 8-byte aligned");
+  const int64_t ld = dm_ld(d);
+  const int64_t row_base = row0 / DM_ROW_ALIGN * DM_ROW_ALIGN;                   // (the cover stays inside dm_rows_p(n_a))
+  const int64_t nbm = (dm_rows_p(row0 + n_rows) - row_base) / DM_ROW_ALIGN, nbn = dm_rows_p(n_b) / DM_ROW_ALIGN;
+  if (nbm * nbn > (1 << 30)) return fail(SAE_ERR_INVALID, "a row block of %lld x %lld tiles: split it", (long long)nbm, (long long)nbn);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  GemmArgs g{};
+  g.A0 = (const bf16_t*)packed_a + row_base * ld; g.lda = ld; g.B0 = (const bf16_t*)packed_b; g.ldb = ld;
+  g.nbm = (int)nbm; g.nbn = (int)nbn;                                            // (256 x 256 tiles: the kernel is launched directly)
+  g.ktiles0 = g.ktiles = (int)(ld / GEMM_BK); g.splits = 1;
+  EpiDictKeys e{};
+  e.keys = keys; e.n_b = n_b; e.n_rows = n_rows; e.row_lo = (int)(row0 - row_base);
+  e.self_base = self_mode ? row_base : -((int64_t)1 << 40);
+  auto kern = gemm256_bf16_kernel<OP_ROW, OP_ROW, EpiDictKeys>;
+  LDS_ATTR(kern, G2_LDS_BYTES, dev);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nbm * nbn)), dim3(512), G2_LDS_BYTES, (hipStream_t)stream, g, e);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

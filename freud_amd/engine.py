@@ -127,6 +127,9 @@ def load() -> C.CDLL:
         "sae_coact_neighbor_keys": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, vp]),
         "sae_label_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "sae_label_keys": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, i64, i64, vp, vp]),
+        "sae_dict_pack_bytes": (i64, [i64, i64]),
+        "sae_dict_pack": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
+        "sae_dict_sim_keys": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_int, vp, vp]),
         "sae_manipulate_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.POINTER(i32), C.POINTER(i32), C.c_int, fptr, C.c_int, C.c_int,
                                            vp, vp, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
@@ -170,6 +173,7 @@ EXPORTED_SYMBOLS = [
     "sae_file_top_features",
     "sae_coact_files", "sae_coact_neighbor_keys",
     "sae_label_files", "sae_label_keys",
+    "sae_dict_pack_bytes", "sae_dict_pack", "sae_dict_sim_keys",
     "sae_manipulate_files",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
@@ -181,6 +185,9 @@ COACT_MEASURES = {"jaccard": 0, "cond": 1, "count": 2}              # include/fr
 LABEL_MEASURES = {"f1": 0, "precision": 1, "recall": 2, "count": 3}  # include/freud_sae.h: SAE_LABEL_*
 LABEL_MAX_CLASSES = 4096                                            # include/freud_sae.h: SAE_LABEL_MAX_CLASSES
 LABEL_MAX_SLOTS = 16                                                # include/freud_sae.h: SAE_LABEL_MAX_SLOTS
+DICT_LEFT, DICT_RIGHT = 0, 1                                        # include/freud_sae.h: SAE_DICT_LEFT / SAE_DICT_RIGHT
+DICT_MAX_D = 8192                                                   # include/freud_sae.h: SAE_DICT_MAX_D
+DICT_MAX_N = 1 << 24
 MANIP_OPS = {"scale": 0, "set": 1}                                  # include/freud_sae.h: SAE_MANIP_SCALE / SAE_MANIP_SET
 MANIP_MAX_EDITS = 16                                                # include/freud_sae.h: SAE_MANIP_MAX_EDITS
 MANIP_MAX_VARIANTS = 16                                             # include/freud_sae.h: SAE_MANIP_MAX_VARIANTS
@@ -763,6 +770,44 @@ def label_keys(counts, label_count, n_classes: int, n: int, measure: int, by_lat
     _check_search_out(keys, max(int(n_rows), 0) * (int(n_classes) if by_latent else n))
     _check(load().sae_label_keys(C.c_void_p(counts.data_ptr()), C.c_void_p(label_count.data_ptr()), int(n_classes), int(n), int(measure),
                                  int(by_latent), int(row0), int(n_rows), C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
+
+
+def dict_pack_bytes(n: int, d: int) -> int:
+    """Bytes of the packed operand of a dictionary of n directions of length d (include/freud_sae.h, sae_dict_pack)."""
+    b = int(load().sae_dict_pack_bytes(int(n), int(d)))
+    if b <= 0:
+        raise EngineError(f"n={n} outside [1, 2^24] or d={d} outside [1, {DICT_MAX_D}]")
+    return b
+
+
+def dict_pack(w, n: int, d: int, dir_stride: int, elem_stride: int, side: int, packed, norms, stream=None) -> None:
+    """The unit directions of w (fp32 CUDA; direction i, element e at w.data_ptr() + 4 (i dir_stride + e elem_stride), all inside its
+    storage) as the split bf16 GEMM operand `packed` (a CUDA tensor of >= dict_pack_bytes(n, d) bytes) and norms [n] (fp32)."""
+    import torch
+    n, d, dir_stride, elem_stride = int(n), int(d), int(dir_stride), int(elem_stride)
+    if not (w.is_cuda and w.dtype == torch.float32):
+        raise EngineError("the directions must be a float32 CUDA tensor")
+    if n >= 1 and d >= 1 and dir_stride >= 1 and elem_stride >= 1:
+        last = w.storage_offset() + (n - 1) * dir_stride + (d - 1) * elem_stride
+        if last >= w.untyped_storage().nbytes() // 4:
+            raise EngineError(f"{n} directions of length {d} with strides ({dir_stride}, {elem_stride}) reach past the tensor's storage")
+    if not (packed.is_cuda and packed.is_contiguous() and packed.numel() * packed.element_size() >= dict_pack_bytes(n, d)):
+        raise EngineError(f"packed must be a contiguous CUDA tensor of >= {dict_pack_bytes(n, d)} bytes")
+    if not (norms.is_cuda and norms.dtype == torch.float32 and norms.is_contiguous() and norms.numel() >= n):
+        raise EngineError(f"norms must be a contiguous float32 CUDA tensor of >= {n} elements")
+    _check(load().sae_dict_pack(C.c_void_p(w.data_ptr()), n, d, dir_stride, elem_stride, int(side), C.c_void_p(packed.data_ptr()),
+                                C.c_void_p(norms.data_ptr()), _stream_ptr(stream)))
+
+
+def dict_sim_keys(packed_a, n_a: int, packed_b, n_b: int, d: int, row0: int, n_rows: int, self_mode: bool, keys, stream=None) -> None:
+    """keys [n_rows, n_b] (int64 holding uint64) = the cosine keys of the directions [row0, row0 + n_rows) of A against all of B, from
+    their packed operands (dict_pack with DICT_LEFT / DICT_RIGHT), for file_top_features(keys, n_rows, n_b, n_top, 0, ...)."""
+    for t, n in ((packed_a, n_a), (packed_b, n_b)):
+        if not (t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= dict_pack_bytes(n, d)):
+            raise EngineError(f"a packed operand must be a contiguous CUDA tensor of >= {dict_pack_bytes(n, d)} bytes")
+    _check_search_out(keys, max(int(n_rows), 0) * int(n_b))
+    _check(load().sae_dict_sim_keys(C.c_void_p(packed_a.data_ptr()), int(n_a), C.c_void_p(packed_b.data_ptr()), int(n_b), int(d), int(row0),
+                                    int(n_rows), int(bool(self_mode)), C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:

@@ -495,6 +495,47 @@ enum { SAE_LABEL_F1 = 0, SAE_LABEL_PRECISION = 1, SAE_LABEL_RECALL = 2, SAE_LABE
 int sae_label_keys(const int32_t* counts_dev, const int64_t* label_count_dev, int64_t n_classes, int64_t n, int measure, int by_latent,
                    int64_t row0, int64_t n_rows, uint64_t* keys_dev, void* stream);
 
+/* ---- Dictionary comparison: what a dictionary IS against another one, or against itself -- which 32x latents an 8x latent split
+ * into, whether two runs found the same features (mean max cosine similarity), which latents duplicate each other.  All of it is
+ * the cosines between unit decoder directions and, per direction of A, its nearest directions of B.
+ *
+ * Semantics (freud_amd/csrc/dict_match.h).  A dictionary is n directions of length d in fp32: direction i, element e is
+ * w_dev[i * dir_stride + e * elem_stride] (strides in elements, >= 1).  TopK: the rows of W_dec [n][d] (dir_stride d, elem_stride
+ * 1); L1: the columns of the tied decoder.weight [d][n] (dir_stride 1, elem_stride n).  Both are read in place.
+ *   Unit direction  u = w / ||w||.  ||w|| = the IEEE square root of an fp32 sum of squares taken in one fixed order (64 partial
+ *                   sums, partial l adding the elements l, l + 64, ... in order with one fused multiply-add each, then the xor
+ *                   butterfly 32, 16, 8, 4, 2, 1 over the partials); the division is the IEEE one.  The order does not depend on
+ *                   the strides: the same dictionary in either layout gives the same bits.  A direction of norm 0 stays the zero
+ *                   vector, its cosine with everything is 0.  Weights must be finite (freud_amd/dictionary_match.py refuses others).
+ *   Cosine          S[i][j] = <ua_i, ub_j>, fp32 accumulation on the bf16 MFMA.  Each unit vector is split as hi = bf16(u),
+ *                   lo = bf16(u - hi) and the product is hi.hi + hi.lo + lo.hi (the dropped lo.lo is at most 2^-18 relative):
+ *                   concatenated along K, one bf16 GEMM with K = 3 d.
+ *   Answer          per direction i of A its directions of B by cosine descending, then the lower index.  Signed values as they
+ *                   are: no positivity filter, no clamp (1 + 1 ulp on a duplicate is reported as computed).
+ *   Self mode       B is A: direction i is not its own neighbour (its duplicates are).
+ *   Determinism     every output is written by one lane, there are no atomics: two runs give bitwise identical outputs, and the
+ *                   keys of a row do not depend on the row block they were computed in.
+ *
+ * sae_dict_pack_bytes: the size of a packed operand for n directions of length d (0 when n or d is out of range).
+ * sae_dict_pack: w_dev -> packed_dev (sae_dict_pack_bytes(n, d) bytes, 16-byte aligned, every byte written; the format is opaque:
+ * n rounded up to 256 rows of three K segments of d rounded up to 64 bf16, SAE_DICT_LEFT packs [hi | hi | lo], SAE_DICT_RIGHT
+ * [hi | lo | hi]) and norms_dev [n] (fp32).  A comparison packs A with SAE_DICT_LEFT and B with SAE_DICT_RIGHT; self mode packs
+ * the same dictionary both ways.
+ * sae_dict_sim_keys: keys_dev [n_rows][n_b] = ord(S[row0 + r][j]) << 32 (freud_amd/csrc/search_keys.h: order-preserving, -0.0 as
+ * 0.0, never 0 for a finite value) for the rows [row0, row0 + n_rows) of A, and 0 at j == row0 + r in self mode.
+ * sae_file_top_features(keys_dev, n_rows, n_b, n_neighbors, 0, ...) then gives the answer (a key of 0 is never reported).
+ *
+ * 1 <= n <= 2^24, 1 <= d <= SAE_DICT_MAX_D, side SAE_DICT_LEFT or SAE_DICT_RIGHT, self mode only with n_a == n_b, a non-empty row
+ * block inside [0, n_a) of at most 2^30 256 x 256 tiles, non-null pointers: otherwise SAE_ERR_INVALID before anything is enqueued.
+ * The calls need no context, run on the current device and are asynchronous on `stream`. */
+#define SAE_DICT_MAX_D 8192
+enum { SAE_DICT_LEFT = 0, SAE_DICT_RIGHT = 1 };
+int64_t sae_dict_pack_bytes(int64_t n, int64_t d);
+int sae_dict_pack(const float* w_dev, int64_t n, int64_t d, int64_t dir_stride, int64_t elem_stride, int side, void* packed_dev,
+                  float* norms_dev, void* stream);
+int sae_dict_sim_keys(const void* packed_a_dev, int64_t n_a, const void* packed_b_dev, int64_t n_b, int64_t d, int64_t row0,
+                      int64_t n_rows, int self_mode, uint64_t* keys_dev, void* stream);
+
 /* ---- Feature manipulation: the reference's manipulate_latent (utils/activations.py:243-272, served as /manipulate_feature) for
  * a batch of files, several edited latents and a sweep of edit values at once -- everything between the cached activations and
  * the tensors handed to whisper_subbed.forward: the standard reconstruction, the manipulated ones, and the per-frame series of
