@@ -3057,9 +3057,9 @@ extern "C" int sae_latent_colmax(sae_ctx* c, float* out_host, int64_t capacity, 
   int* bits = reinterpret_cast<int*>(c->db_part);   // scratch, free outside of a backward pass
   HIP_TRY(hipMemsetAsync(bits, 0, (size_t)c->n_p * 4, s));
   const int rows_per_block = 256;
-  dim3 grid(c->n_p / 128 / 2 > 0 ? c->n_p / 256 : 1, (unsigned)((c->last_M + rows_per_block - 1) / rows_per_block));
-  if (c->n_p % 256 != 0) grid.x = (c->n_p + 255) / 256;
-  hipLaunchKernelGGL(latent_colmax_kernel, grid, dim3(256), 0, s, c->topk ? c->dense : c->c, bits, c->last_M, c->n_p,
+  // (n_p is a multiple of 128, not of 256: the tail block's columns >= n_p would read the next row and write past the memset)
+  dim3 grid((c->n_p + 255) / 256, (unsigned)((c->last_M + rows_per_block - 1) / rows_per_block));
+  hipLaunchKernelGGL(latent_colmax_bounded_kernel, grid, dim3(256), 0, s, c->topk ? c->dense : c->c, bits, c->last_M, c->n_p, c->n_p,
                      rows_per_block);
   HIP_TRY(hipGetLastError());
   std::vector<float> tmp(c->n_p);

@@ -821,18 +821,8 @@ __global__ __launch_bounds__(256) void gnorm_partial_kernel(const float* __restr
 }
 
 // per-feature max over rows of the (non-negative) latent c[M_p][n_p]  (validate(): train_sae.py:176-178)
-__global__ __launch_bounds__(256) void latent_colmax_kernel(const bf16_t* __restrict__ c, int* __restrict__ out_bits,
-                                                             int64_t M, int n_p, int rows_per_block) {
-  // grid (n_p/256, ceil(M/rows_per_block)); thread -> one column; non-negative floats order like ints
-  const int col = blockIdx.x * 256 + threadIdx.x;
-  const int64_t r0 = (int64_t)blockIdx.y * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < M ? r0 + rows_per_block : M;
-  float m = 0.f;
-  for (int64_t r = r0; r < r1; ++r) m = fmaxf(m, (float)c[r * n_p + col]);
-  atomicMax(out_bits + col, __float_as_int(m));
-}
-
-// the same into a caller-owned row of exactly n (un-padded) columns
+// into a row of n <= n_p columns: grid (ceil(n/256), ceil(M/rows_per_block)); thread -> one column; non-negative floats order
+// like ints.  n_p is a multiple of 128 only, so the last block is cut at n.
 __global__ __launch_bounds__(256) void latent_colmax_bounded_kernel(const bf16_t* __restrict__ c, int* __restrict__ out_bits,
                                                                      int64_t M, int n_p, int n, int rows_per_block) {
   const int col = blockIdx.x * 256 + threadIdx.x;

@@ -518,7 +518,11 @@ class SaeEngine:
         import torch
         assert latent.is_cuda and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
         assert latent.dim() == 2 and latent.stride(1) == 1
-        dt = {torch.float32: DTYPE["float32"], torch.bfloat16: DTYPE["bfloat16"]}[latent.dtype]
+        dt = {torch.float32: DTYPE["float32"], torch.bfloat16: DTYPE["bfloat16"]}.get(latent.dtype)
+        if dt is None:
+            raise EngineError(f"unsupported latent dtype {latent.dtype}: decode takes float32 or bfloat16")
+        if latent.shape[1] < self.n:     # (the C side sees the row stride only: a narrow view of a wide tensor would pass it)
+            raise EngineError(f"latent has {latent.shape[1]} columns, the dictionary {self.n}")
         _check(self._lib.sae_decode(self._ctx, C.c_void_p(latent.data_ptr()), dt, int(latent.stride(0)), int(latent.shape[0]),
                                     C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
 

@@ -11,7 +11,9 @@ init_sae_from_checkpoint (dataset/activations.py:16-31) -- run unchanged against
 
 These are NOT torch modules and have no autograd: training goes through freud_amd.train_sae / the C ABI.  Arithmetic is
 the engine's (bf16 MFMA operands, fp32 accumulation): the reference's inference runs fp32 on CPU and fp16 autocast on
-cuda; latents agree with the fp32 reference to bf16 rounding (tests/test_models_gpu.py states the tolerances).  Like
+cuda; latents agree with the fp32 reference to bf16 rounding (tests/test_models_gpu.py states the tolerances).  decode() is,
+element by element, within 2^-8 |s| + n_p 2^-23 S + 2^-22 (|s| + |b_dec|) of the float64 product s of the engine's own bf16 operands
+(S: the same product of absolute values; tests/decode_reference.py derives it) and exact on one-hot rows.  Like
 the reference's encode(), L1 encode renormalises the decoder columns in place.  Inputs are torch tensors on the engine's
 GPU (or CPU tensors, which are moved), shaped [..., d_model]; outputs keep the leading shape.
 """
@@ -222,8 +224,10 @@ class TopKAutoEncoder(_EngineModel):
         if dead_mask is not None and bool(torch.as_tensor(dead_mask).any()):
             raise NotImplementedError("the AuxK branch belongs to training: use freud_amd.train_sae / the C ABI")
         x2, lead = self._flat(x)
-        self._eng_rows_per_file = x.shape[-2] if x.dim() >= 3 else 0
-        self._ensure(x2.shape[0]).set_topk_options(float("inf"), self._eng_rows_per_file)   # T of x.mean(0) (:104)
+        # x.mean(0) (:104) runs over the leading dimension: the engine's T is the rows of ONE of its entries -- 1 for a [M][d] input, whose
+        # mean is over its rows (T = 0 would make the batch one file: zero variance, which the engine like the reference replaces by 1)
+        self._eng_rows_per_file = int(np.prod(x.shape[1:-1])) if x.dim() >= 2 else 0
+        self._ensure(x2.shape[0]).set_topk_options(float("inf"), self._eng_rows_per_file)
         acts, idx, dense = self._encode_flat(x2)
         m = self._eng.metrics()
         if self.cfg.multi_topk:        # forward() re-binds sae_out / encoded to the 4k selection (topkautoencoder.py:134-147)
