@@ -39,6 +39,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "stats.h"
 #include "coact.h"
 #include "labels.h"
+#include "hist.h"
 #include "manip.h"
 #include "dict_match.h"
 
@@ -134,6 +135,7 @@ enum KernelId {
   KID_MANIP_APPLY,
   KID_LABEL_PACK,      // feature labels (labels.h): the label pack + label counts and the rectangular i8 update of sae_label_files
   KID_LABEL_UPDATE,
+  KID_HIST,            // activation histograms (hist.h): every kernel of sae_hist_files after the encoder
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
@@ -141,7 +143,7 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "topk_decode", "topk_ddense_gemm", "topk_dwdec_gemm", "topk_dwenc_gemm",
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
-                                              "manip_apply", "label_pack", "label_update"};
+                                              "manip_apply", "label_pack", "label_update", "hist"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -151,7 +153,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST };
 
 struct sae_ctx {
   sae_config cfg;
@@ -308,6 +310,8 @@ struct sae_ctx {
   int8_t* co_zt = nullptr;      // sae_coact_files scratch (coact.h): the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)]
   int8_t* lb_lt = nullptr;      // sae_label_files scratch (labels.h): the int8 label pack Lt [lb_rows][round_up(max_rows_p, CO_BK)]
   int lb_rows = 0;              // its rows: the largest C_p = round_up(n_classes + 1, CO_BM) asked for so far
+  uint32_t* hs_fmax = nullptr;  // sae_hist_files scratch of a TopK context (hist.h): the file maxima [hs_files][n] of one batch
+  int64_t hs_files = 0;         // its files: the largest n_files asked for so far
   float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
@@ -352,6 +356,8 @@ static int no_forward_left(const sae_ctx* c, bool after_search = true) {
     return fail(SAE_ERR_STATE, "the last call was a feature co-activation pass: it leaves no forward to read (run sae_eval first)");
   if (c->last_call == LAST_LABELS)
     return fail(SAE_ERR_STATE, "the last call was a feature label pass: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_HIST)
+    return fail(SAE_ERR_STATE, "the last call was an activation histogram pass: it leaves no forward to read (run sae_eval first)");
   return SAE_OK;
 }
 
@@ -580,7 +586,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->mn_w};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->hs_fmax, c->mn_w};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);
@@ -3523,6 +3529,105 @@ extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count,
   hipLaunchKernelGGL(label_keys_kernel, dim3((unsigned)((ncols + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
                      (hipStream_t)stream, counts, label_count, (int)n_classes, (int)n, measure, by_latent, row0, n_rows, keys);
   HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- activation histograms (hist.h): per latent the histogram of its value on every counted frame and of every file's maximum,
+// and the frame histogram of a few chosen latents split by label
+static_assert(SAE_HIST_MAX_BINS == HB_MAX_BINS && SAE_HIST_MAX_SEL == HIST_MAX_SEL, "freud_sae.h, hist_bins.h and hist.h disagree");
+static const FilePassKind kHistPass = {"sae_hist_files", "build the histograms in a bf16 context", "histogram", 0};
+
+static int hist_ensure(sae_ctx* c, int64_t n_files) {
+  if (!c->topk || n_files <= c->hs_files) return SAE_OK;
+  if (c->hs_fmax) HIP_TRY(hipFree(c->hs_fmax));        // (hipFree waits for the work that still reads it)
+  c->hs_fmax = nullptr;
+  c->hs_files = 0;
+  HIP_TRY(hipMalloc((void**)&c->hs_fmax, (size_t)(n_files * c->n) * 4));
+  c->hs_files = n_files;
+  return SAE_OK;
+}
+
+// the stored latent of launch_encoder binned by hist_l1_kernel.  Chunks of whole files: the fewest files per chunk that still give
+// HIST_MIN_WGS workgroups (every chunk flushes its non-empty bins with global adds, so fewer chunks are cheaper).  Columns per
+// workgroup: 256 while the counters fit 48 KiB of LDS (O P <= 96), else 128.
+constexpr int HIST_MIN_WGS = 1024;
+static void hist_launch_l1(sae_ctx* c, int64_t n_files, int Trows, const int* lengths, HistSpec sp, int64_t* frame_hist, int64_t* file_max_hist,
+                           hipStream_t s) {
+  const int reg = hist_regular(sp);
+  const int nt = reg <= 96 ? 256 : 128;
+  const int colblocks = (c->n + nt - 1) / nt;
+  const int64_t want = std::min<int64_t>(n_files, (HIST_MIN_WGS + colblocks - 1) / colblocks);
+  const int fpc = (int)(n_files / want);
+  const int64_t chunks = (n_files + fpc - 1) / fpc;
+  hipLaunchKernelGGL(hist_l1_kernel, dim3((unsigned)colblocks, (unsigned)chunks), dim3(nt), (size_t)((reg + 1) / 2) * nt * 4, s,
+                     (const unsigned short*)c->c, (int64_t)c->n_p, c->n, n_files, Trows, lengths, fpc, sp, frame_hist, file_max_hist);
+}
+
+template <typename T>
+static int hist_l1_encode(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
+  const GemmArgs g = file_pass_l1_front(c, x, M, s);
+  return launch_encoder<T>(c, g, M, s);
+}
+
+extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                              int lo_exp, int octaves, int sub_bits, int flags, int64_t* frame_hist, int64_t* file_max_hist,
+                              int64_t* n_frames, const int32_t* labels, int n_slots, int n_classes, const int32_t* sel_latents, int n_sel,
+                              int64_t* label_hist, int64_t* label_count, void* stream) {
+  int64_t M;
+  const HistSpec sp{lo_exp, octaves, sub_bits};
+  if (!hist_spec_ok(sp))
+    return fail(SAE_ERR_INVALID, "histogram spec lo_exp=%d octaves=%d sub_bits=%d: -126 <= lo_exp, octaves >= 1, lo_exp + octaves <= 128, "
+                "sub_bits in 0..3, octaves << sub_bits <= %d", lo_exp, octaves, sub_bits, HB_MAX_REGULAR);
+  if (!file_max_hist || !n_frames) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_sel < 0 || n_sel > SAE_HIST_MAX_SEL) return fail(SAE_ERR_INVALID, "n_sel=%d outside [0, %d]", n_sel, SAE_HIST_MAX_SEL);
+  if (n_sel > 0) {
+    if (!labels || !sel_latents || !label_hist || !label_count) return fail(SAE_ERR_INVALID, "n_sel=%d needs labels, sel_latents, label_hist and label_count", n_sel);
+    if (n_slots < 1 || n_slots > SAE_LABEL_MAX_SLOTS) return fail(SAE_ERR_INVALID, "n_slots=%d outside [1, %d]", n_slots, SAE_LABEL_MAX_SLOTS);
+    if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%d outside [1, %d]", n_classes, SAE_LABEL_MAX_CLASSES);
+  }
+  for (const void* p : {(const void*)frame_hist, (const void*)file_max_hist, (const void*)n_frames, (const void*)label_hist, (const void*)label_count})
+    if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return fail(SAE_ERR_INVALID, "the histogram arrays must be 8-byte aligned");
+  if (int rc = file_pass_begin(kHistPass, c, x, frame_hist, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (int rc = hist_ensure(c, n_files)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+
+  // the encoder as encode() runs it: the stored L1 latent, or the eval forward's top-k selection (the k of encode())
+  if (c->topk) {
+    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+  } else {
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return hist_l1_encode(c, xt, M, s); })) return rc;
+  }
+
+  ev_begin(c, KID_HIST, s);
+  hipError_t memset_fmax = hipSuccess;
+  hipLaunchKernelGGL(hist_frames_kernel, dim3(1), dim3(256), 0, s, n_files, Trows, lengths, n_frames, n_sel > 0 ? label_count + n_classes : nullptr);
+  if (c->topk) {
+    memset_fmax = hipMemsetAsync(c->hs_fmax, 0, (size_t)(n_files * c->n) * 4, s);
+    if (memset_fmax == hipSuccess) {
+      hipLaunchKernelGGL(hist_topk_scatter_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
+                         c->k, M, Trows, lengths, c->n, sp, frame_hist, c->hs_fmax);
+      hipLaunchKernelGGL(hist_topk_finish_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->hs_fmax, n_files, c->n, sp, n_frames,
+                         frame_hist, file_max_hist);
+    }
+  } else {
+    hist_launch_l1(c, n_files, Trows, lengths, sp, frame_hist, file_max_hist, s);
+  }
+  if (n_sel > 0 && memset_fmax == hipSuccess) {
+    const dim3 grid(grid_for(M * n_sel, 4096));
+    if (c->topk)
+      hipLaunchKernelGGL(hist_label_kernel<true>, grid, dim3(256), 0, s, (const unsigned short*)c->top_vals, (int64_t)0, c->top_idx, c->k, c->n, M,
+                         Trows, lengths, labels, n_slots, n_classes, sel_latents, n_sel, sp, label_hist, label_count);
+    else
+      hipLaunchKernelGGL(hist_label_kernel<false>, grid, dim3(256), 0, s, (const unsigned short*)c->c, (int64_t)c->n_p, (const int*)nullptr, 0, c->n,
+                         M, Trows, lengths, labels, n_slots, n_classes, sel_latents, n_sel, sp, label_hist, label_count);
+    hipLaunchKernelGGL(hist_label_any_kernel, dim3((unsigned)n_sel), dim3(256), 0, s, frame_hist, sel_latents, c->n, n_classes, hist_nbins(sp),
+                       label_hist);
+  }
+  ev_end(c, KID_HIST, s);                   // (the bracket closes whatever the memset answered)
+  HIP_TRY(memset_fmax);
+  HIP_TRY(hipGetLastError());
+  c->last_call = LAST_HIST;
   return SAE_OK;
 }
 

@@ -127,6 +127,8 @@ def load() -> C.CDLL:
         "sae_coact_neighbor_keys": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, vp]),
         "sae_label_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
         "sae_label_keys": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, i64, i64, vp, vp]),
+        "sae_hist_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
+                                     vp, C.c_int, vp, vp, vp]),
         "sae_dict_pack_bytes": (i64, [i64, i64]),
         "sae_dict_pack": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
         "sae_dict_sim_keys": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_int, vp, vp]),
@@ -173,6 +175,7 @@ EXPORTED_SYMBOLS = [
     "sae_file_top_features",
     "sae_coact_files", "sae_coact_neighbor_keys",
     "sae_label_files", "sae_label_keys",
+    "sae_hist_files",
     "sae_dict_pack_bytes", "sae_dict_pack", "sae_dict_sim_keys",
     "sae_manipulate_files",
 ]
@@ -185,6 +188,8 @@ COACT_MEASURES = {"jaccard": 0, "cond": 1, "count": 2}              # include/fr
 LABEL_MEASURES = {"f1": 0, "precision": 1, "recall": 2, "count": 3}  # include/freud_sae.h: SAE_LABEL_*
 LABEL_MAX_CLASSES = 4096                                            # include/freud_sae.h: SAE_LABEL_MAX_CLASSES
 LABEL_MAX_SLOTS = 16                                                # include/freud_sae.h: SAE_LABEL_MAX_SLOTS
+HIST_MAX_REGULAR = 128                                              # freud_amd/csrc/hist_bins.h: octaves << sub_bits at most
+HIST_MAX_SEL = 64                                                   # include/freud_sae.h: SAE_HIST_MAX_SEL
 DICT_LEFT, DICT_RIGHT = 0, 1                                        # include/freud_sae.h: SAE_DICT_LEFT / SAE_DICT_RIGHT
 DICT_MAX_D = 8192                                                   # include/freud_sae.h: SAE_DICT_MAX_D
 DICT_MAX_N = 1 << 24
@@ -199,6 +204,18 @@ def stats_layout(n: int) -> dict:
     return {"n_frames": (0, "int64", 1), "fire_count": (8, "int64", n), "act_sum": (8 + 8 * n, "float64", n),
             "act_sq_sum": (8 + 16 * n, "float64", n), "l0_hist": (8 + 24 * n, "int64", n + 1),
             "act_max": (16 + 32 * n, "float32", n), "bytes": 16 + 36 * n}
+
+
+def hist_nbins(spec) -> int:
+    """Bins of a histogram spec (lo_exp, octaves, sub_bits) -- freud_amd/csrc/hist_bins.h; ValueError for a spec outside its limits."""
+    lo_exp, octaves, sub_bits = (int(v) for v in spec)
+    if sub_bits < 0 or sub_bits > 3:
+        raise ValueError(f"sub_bits={sub_bits} outside [0, 3]")
+    if lo_exp < -126 or octaves < 1 or lo_exp + octaves > 128:
+        raise ValueError(f"lo_exp={lo_exp}, octaves={octaves}: -126 <= lo_exp, octaves >= 1 and lo_exp + octaves <= 128")
+    if (octaves << sub_bits) > HIST_MAX_REGULAR:
+        raise ValueError(f"octaves={octaves} x {1 << sub_bits} bins per octave > {HIST_MAX_REGULAR}")
+    return (octaves << sub_bits) + 3
 
 
 def _check(rc: int) -> None:
@@ -617,6 +634,44 @@ class SaeEngine:
         _check_label_table(counts, label_count, n_classes, self.n)
         _check(self._lib.sae_label_files(self._ctx, xp, B, T, dt, lp, C.c_void_p(labels.data_ptr()), int(labels.shape[2]), int(n_classes),
                                          0, C.c_void_p(counts.data_ptr()), C.c_void_p(label_count.data_ptr()), _stream_ptr(stream)))
+
+    # -- activation histograms (include/freud_sae.h: sae_hist_files; freud_amd/activation_hist.py) ------------------------------
+    def hist_files(self, x, spec, frame_hist, file_max_hist, n_frames, lengths=None, labels=None, n_classes: int = 0, sel_latents=None,
+                   label_hist=None, label_count=None, stream=None) -> None:
+        """Add the activation histograms of x [n_files, T, d] (CUDA) for spec = (lo_exp, octaves, sub_bits), NB = hist_nbins(spec),
+        to frame_hist and file_max_hist (zero-initialised contiguous int64 CUDA [n_dict, NB]) and n_frames (int64 CUDA [1]); lengths:
+        int32 CUDA tensor [n_files] or None.  With sel_latents (int32 CUDA [n_sel], n_sel <= HIST_MAX_SEL) and labels (contiguous
+        int32 CUDA [n_files, T, n_slots], as label_files) also to label_hist (int64 CUDA [n_sel, n_classes + 1, NB]) and label_count
+        (int64 CUDA [n_classes + 1]).  The same arrays go to every call of one pass.  Asynchronous.  Afterwards the last-forward
+        getters fail until the next eval() / step()."""
+        import torch
+        x, xp, B, T, _d, dt, lp = _files_args(x, "hist_files", lengths)
+        lo_exp, octaves, sub_bits = (int(v) for v in spec)
+        nb = hist_nbins(spec)
+
+        def i64(t, numel, name):
+            if not (t is not None and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == numel):
+                raise EngineError(f"{name} must be a contiguous int64 CUDA tensor of {numel} elements")
+            return C.c_void_p(t.data_ptr())
+
+        fh, mh, nf = i64(frame_hist, self.n * nb, "frame_hist"), i64(file_max_hist, self.n * nb, "file_max_hist"), i64(n_frames, 1, "n_frames")
+        n_sel = 0 if sel_latents is None else int(sel_latents.numel())
+        lab = sel = lh = lc = None
+        n_slots = 0
+        if n_sel:
+            if n_sel > HIST_MAX_SEL:
+                raise EngineError(f"{n_sel} chosen latents > {HIST_MAX_SEL}")
+            if not (sel_latents.is_cuda and sel_latents.dtype == torch.int32 and sel_latents.is_contiguous()):
+                raise EngineError("sel_latents must be a contiguous int32 CUDA tensor")
+            if not (labels is not None and labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3
+                    and tuple(labels.shape[:2]) == (B, T)):
+                raise EngineError(f"labels must be a contiguous int32 CUDA tensor [{B}, {T}, n_slots]")
+            n_slots = int(labels.shape[2])
+            lab, sel = C.c_void_p(labels.data_ptr()), C.c_void_p(sel_latents.data_ptr())
+            lh = i64(label_hist, n_sel * (int(n_classes) + 1) * nb, "label_hist")
+            lc = i64(label_count, int(n_classes) + 1, "label_count")
+        _check(self._lib.sae_hist_files(self._ctx, xp, B, T, dt, lp, lo_exp, octaves, sub_bits, 0, fh, mh, nf, lab, n_slots, int(n_classes),
+                                        sel, n_sel, lh, lc, _stream_ptr(stream)))
 
     # -- feature manipulation (include/freud_sae.h: sae_manipulate_files; freud_amd/manipulate.py) -------------------------
     def manipulate_files(self, x, latents, ops, values, standard, manipulated, series, stream=None) -> None:

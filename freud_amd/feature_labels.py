@@ -20,7 +20,8 @@ Two answers: per label its best latents, per latent its best labels, both ordere
 the lower index.  A pair that never meets is not reported; empty slots hold -1, count 0 and score NaN.  Everything is exact integer
 arithmetic on the i8 matrix cores: two runs give bitwise identical arrays.
 
-Out of scope: per-label activation sums or means (floats; counts only here), labels for raw (no-SAE) activations, and deriving
+Out of scope: per-label activation sums or means (floats; counts only here -- the DISTRIBUTION of a latent's value per label, in
+exact integer bins, is freud_amd.activation_hist's label_latents), labels for raw (no-SAE) activations, and deriving
 the labels from file names or alignments (the caller's job).
 
     python -m freud_amd.feature_labels --sae CKPT --data_path DIR --layer_name L (--file_labels f.npy | --frame_labels f.npy)
@@ -172,6 +173,16 @@ def _check_args(sae, data_path, layer_name, subset_size, file_labels, frame_labe
     return a, per_file, n_classes, n_top
 
 
+def batch_labels(labels: np.ndarray, per_file: bool, file0: int, nb: int, T: int, device) -> torch.Tensor:
+    """The labels of files [file0, file0 + nb) as the engine takes them: contiguous int32 [nb, T, S] on `device`, per-file labels
+    expanded to every frame of their file (`labels`, `per_file`: what _check_args returns)."""
+    S = int(labels.shape[-1])
+    lab = torch.from_numpy(np.ascontiguousarray(labels[file0:file0 + nb], dtype=np.int32)).to(device)
+    if per_file:
+        lab = lab.reshape(nb, 1, S).expand(nb, T, S)
+    return lab.reshape(nb, T, S).contiguous()
+
+
 @keep_rng
 def feature_labels(sae, data_path: str, layer_name: str, *, file_labels=None, frame_labels=None, n_classes: Optional[int] = None,
                    class_names=None, n_top: int = 16, measure: str = "f1", lengths=None, subset_size: Optional[int] = None,
@@ -187,16 +198,13 @@ def feature_labels(sae, data_path: str, layer_name: str, *, file_labels=None, fr
     # (the counts are int32: FilePass refuses more than MAX_FRAMES frames before it loads the SAE or touches the device)
     fp = FilePass(sae, data_path, layer_name, what="feature labels", lengths=lengths, subset_size=subset_size, batch_files=batch_files,
                   max_frames=MAX_FRAMES)
-    n, T, S = fp.eng.n, fp.T, int(labels.shape[-1])
+    n, T = fp.eng.n, fp.T
     m = LABEL_MEASURES[measure]
     with torch.cuda.device(fp.device):
         table = torch.zeros(C + 1, n, dtype=torch.int32, device=fp.device)
         lcount = torch.zeros(C + 1, dtype=torch.int64, device=fp.device)
         for x, file0, nb, lb in fp:
-            lab = torch.from_numpy(np.ascontiguousarray(labels[file0:file0 + nb], dtype=np.int32)).to(fp.device)
-            if per_file:
-                lab = lab.reshape(nb, 1, S).expand(nb, T, S)
-            fp.eng.label_files(x, lab.reshape(nb, T, S).contiguous(), C, table, lcount, lb)
+            fp.eng.label_files(x, batch_labels(labels, per_file, file0, nb, T, fp.device), C, table, lcount, lb)
         by_label = CO.select_top_rows(C, n, n_top, lambda r0, nr, keys: E.label_keys(table, lcount, C, n, m, False, r0, nr, keys), fp.device)
         by_latent = CO.select_top_rows(n, C, min(n_top, C), lambda r0, nr, keys: E.label_keys(table, lcount, C, n, m, True, r0, nr, keys),
                                        fp.device)

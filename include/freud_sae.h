@@ -495,6 +495,39 @@ enum { SAE_LABEL_F1 = 0, SAE_LABEL_PRECISION = 1, SAE_LABEL_RECALL = 2, SAE_LABE
 int sae_label_keys(const int32_t* counts_dev, const int64_t* label_count_dev, int64_t n_classes, int64_t n, int measure, int by_latent,
                    int64_t row0, int64_t n_rows, uint64_t* keys_dev, void* stream);
 
+/* ---- Activation histograms: how strongly every latent fires -- per latent the histogram of its value over the counted frames, the
+ * histogram of every file's maximum (the reference GUI's "Histogram of Max Activation Values per File", for all latents at once)
+ * and, for a few chosen latents, the frame histogram split by the frames' labels (the reference's plot_polysemantic.py).
+ *
+ * Semantics.  Frames count exactly as in sae_stats_files (lengths_dev: the first min(length, T) frames of a file; without, all T).
+ * The value binned is the one encode() returns, on its bf16 bit pattern (freud_amd/csrc/hist_bins.h), mag = bits & 0x7FFF.  With
+ * L = lo_exp (>= -126), O = octaves (>= 1, L + O <= 128), s = sub_bits (0..3), P = 2^s and O P <= 128, there are NB = O P + 3 bins:
+ * bin 0: mag == 0 (inactive: a -0.0 and a selected zero of a TopK row as well; a multi_topk context uses its k selection); bin 1:
+ * 0 < a < 2^L; bin 2 + i, 0 <= i < O P: i = (mag >> (7 - s)) - ((L + 127) << s), lower edge 2^(L + i / P) (1 + (i % P) / P); bin
+ * NB - 1: a >= 2^(L + O), Inf and NaN patterns included.  Every edge is a bf16 value: the counts are exact.
+ *
+ * sae_hist_files adds one batch to frame_hist_dev [n_dict][NB] (per latent and bin, the counted frames), file_max_hist_dev
+ * [n_dict][NB] (per latent, one count per file in the bin of the file's maximum over its counted frames; all inactive: bin 0) and
+ * n_frames_dev [1].  With n_sel > 0 (at most SAE_HIST_MAX_SEL) it also adds to label_hist_dev [n_sel][n_classes + 1][NB] -- for
+ * l < n_classes the counted frames that carry label l and on which latent sel_latents_dev[s] falls in the bin, row n_classes the
+ * "any" row: frame_hist of that latent -- and to label_count_dev [n_classes + 1], both with the labels_dev layout and rules of
+ * sae_label_files; a chosen latent outside [0, n_dict) counts nowhere.  n_sel = 0: the five label arguments are ignored.  All
+ * arrays are int64 running totals, caller-owned, zeroed before the first batch and passed TOGETHER to every call of one pass (bin
+ * 0 of a TopK context and the "any" rows are derived from the totals).  Sums are integers: two runs give bitwise identical arrays.
+ *
+ * An L1 context bins the stored latent of its ordinary encoder; a TopK context its selection, with scratch for the file maxima
+ * (n_files x n_dict words, allocated by the first call and grown when a later one brings more files).  flags must be 0.  n_files *
+ * rows_per_file <= max_rows; fp8 contexts: SAE_ERR_INVALID.  A bad spec, n_sel outside [0, SAE_HIST_MAX_SEL], label pointers
+ * missing while n_sel > 0, n_slots or n_classes out of range, null or misaligned arrays, unknown flags and bad shapes fail before
+ * anything is enqueued.  Asynchronous on `stream`.  Training state is untouched; afterwards sae_latent_buffer, sae_topk_indices,
+ * sae_decode, sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the next sae_eval / step. */
+#define SAE_HIST_MAX_BINS 131
+#define SAE_HIST_MAX_SEL 64
+int sae_hist_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                   int lo_exp, int octaves, int sub_bits, int flags, int64_t* frame_hist_dev, int64_t* file_max_hist_dev,
+                   int64_t* n_frames_dev, const int32_t* labels_dev, int n_slots, int n_classes, const int32_t* sel_latents_dev, int n_sel,
+                   int64_t* label_hist_dev, int64_t* label_count_dev, void* stream);
+
 /* ---- Dictionary comparison: what a dictionary IS against another one, or against itself -- which 32x latents an 8x latent split
  * into, whether two runs found the same features (mean max cosine similarity), which latents duplicate each other.  All of it is
  * the cosines between unit decoder directions and, per direction of A, its nearest directions of B.
