@@ -42,6 +42,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "hist.h"
 #include "manip.h"
 #include "dict_match.h"
+#include "recon.h"
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
 
@@ -136,6 +137,10 @@ enum KernelId {
   KID_LABEL_PACK,      // feature labels (labels.h): the label pack + label counts and the rectangular i8 update of sae_label_files
   KID_LABEL_UPDATE,
   KID_HIST,            // activation histograms (hist.h): every kernel of sae_hist_files after the encoder
+  KID_RECON_DECODE,    // reconstruction report (recon.h): the decode of the forward's latent, the residual sweep, the attribution
+  KID_RECON_RESID,     //   (L1: the GEMM with EpiAttr; TopK: the dots and the column walk) with the fold
+  KID_RECON_ATTR,
+  KID_RECON_ATTR_STREAM,   // ... the same bracket when the attribution GEMM ran in the streaming form (gemm256s.h)
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
@@ -143,7 +148,8 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "topk_decode", "topk_ddense_gemm", "topk_dwdec_gemm", "topk_dwenc_gemm",
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
-                                              "manip_apply", "label_pack", "label_update", "hist"};
+                                              "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
+                                              "recon_resid", "recon_attr", "recon_attr_stream"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -153,7 +159,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON };
 
 struct sae_ctx {
   sae_config cfg;
@@ -313,6 +319,7 @@ struct sae_ctx {
   uint32_t* hs_fmax = nullptr;  // sae_hist_files scratch of a TopK context (hist.h): the file maxima [hs_files][n] of one batch
   int64_t hs_files = 0;         // its files: the largest n_files asked for so far
   float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
+  float* rc_buf = nullptr;      // sae_recon_files scratch (recon.h): x_hat / r, the slabs, the row and dimension partials, TopK's p
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;
@@ -358,6 +365,8 @@ static int no_forward_left(const sae_ctx* c, bool after_search = true) {
     return fail(SAE_ERR_STATE, "the last call was a feature label pass: it leaves no forward to read (run sae_eval first)");
   if (c->last_call == LAST_HIST)
     return fail(SAE_ERR_STATE, "the last call was an activation histogram pass: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_RECON)
+    return fail(SAE_ERR_STATE, "the last call was a reconstruction report: it leaves no forward to read (run sae_eval first)");
   return SAE_OK;
 }
 
@@ -586,7 +595,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->hs_fmax, c->mn_w};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->hs_fmax, c->mn_w, c->rc_buf};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);
@@ -1612,6 +1621,12 @@ static int launch_gemm_stream(const GemmArgs& g, const Epi& epi, hipStream_t s) 
   return SAE_OK;
 }
 
+// functors that opt out of gemm256.h's tile-walking (PERSIST) instantiation: static constexpr bool NO_PERSIST = true
+template <class E, class = void>
+struct epi_no_persist { static constexpr bool value = false; };
+template <class E>
+struct epi_no_persist<E, std::void_t<decltype(E::NO_PERSIST)>> { static constexpr bool value = E::NO_PERSIST; };
+
 template <int AM, int BM_, class Epi>
 static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   if constexpr (epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW) {
@@ -1632,6 +1647,9 @@ static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
     const int grid_est = (((g.grid_hint + 3) / 4 + 7) / 8) * 8;          // 256x256 tiles, a multiple of 8
     // (the caller sets grid_hint only for a SMALL estimated extent: the persistent instantiation's tile loop costs the K loop
     // ~10 %, while the workgroups that start only to exit are cheap until they are the great majority)
+    if constexpr (epi_no_persist<Epi>::value) {              // (a functor whose state does not fit the tile-walking instantiation)
+      hipLaunchKernelGGL(kern256, dim3(grid_max), dim3(512), lds256, s, g2, epi);
+    } else
     if (G2_PERSIST_STATIC > 0 && !g.dyn && g2.splits == 1 && g2.tail_tiles == 0 && grid_max >= 4 * G2_PERSIST_STATIC) {
       // big static launches (the K = d GEMMs: tens of thousands of tiles) as G2_PERSIST_STATIC resident workgroups that walk
       // the tiles: encoder / dpre -2 %, TopK encoder -2.5 % against one workgroup per tile (same box; 256 / 512 / 1024 measure alike)
@@ -3786,6 +3804,177 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
   }
   ev_end(c, KID_MANIP_APPLY, s);
   HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- reconstruction report (recon.h): the residual of encode() -> decode() per frame, its sums per file and per model dimension,
+// and per latent the attribution sums P_j = sum a_j (r . w_j), sum a_j^2 and |w_j|^2
+static_assert(SAE_RECON_UNFUSED == 1, "freud_sae.h and engine.hip disagree");
+static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruction report in a bf16 context", "reconstruction", SAE_RECON_UNFUSED};
+
+struct ReconScratch {           // c->rc_buf carved up (floats)
+  float *xr, *slab_p, *slab_q, *rowpart, *dimpart, *p;
+};
+
+static ReconScratch recon_scratch(const sae_ctx* c) {
+  const int64_t rows = c->cfg.max_rows, nrb = c->max_rows_p / STATS_RB, nch = c->d_p / RC_CW;
+  ReconScratch r;
+  r.xr = c->rc_buf;
+  r.slab_p = r.xr + round_up(rows * c->d, 4);
+  r.slab_q = r.slab_p + nrb * c->n_p;
+  r.rowpart = r.slab_q + nrb * c->n_p;
+  r.dimpart = r.rowpart + rows * nch * 2;
+  r.p = r.dimpart + nrb * 3 * c->d_p;
+  return r;
+}
+
+static int recon_ensure(sae_ctx* c) {
+  if (c->rc_buf) return SAE_OK;
+  const ReconScratch r = recon_scratch(c);        // (offsets from a null base: only their differences are used)
+  const int64_t floats = (r.p - r.xr) + (c->topk ? c->cfg.max_rows * (int64_t)c->k : 0);
+  HIP_TRY(hipMalloc((void**)&c->rc_buf, (size_t)floats * 4));
+  return SAE_OK;
+}
+
+static ReconOut recon_out(void* block, int n, int d) {
+  char* b = (char*)block;
+  ReconOut o;
+  o.n_frames = (unsigned long long*)(b + SAE_RECON_N_FRAMES(n, d));
+  o.attr = (double*)(b + SAE_RECON_ATTR_SUM(n, d));
+  o.asq = (double*)(b + SAE_RECON_ACT_SQ_SUM(n, d));
+  o.sx = (double*)(b + SAE_RECON_SUM_X(n, d));
+  o.sxx = (double*)(b + SAE_RECON_SUM_X_SQ(n, d));
+  o.srr = (double*)(b + SAE_RECON_SUM_R_SQ(n, d));
+  o.wnorm = (float*)(b + SAE_RECON_DEC_NORM_SQ(n, d));
+  return o;
+}
+
+template <typename T>
+static void recon_launch_resid(sae_ctx* c, const T* x, const ReconScratch& sc, float* resid, bf16_t* rb, bf16_t* lat, int64_t rows_cover,
+                               int64_t M, int Trows, const int* lengths, hipStream_t s) {
+  const dim3 grid((unsigned)(rows_cover / STATS_RB), (unsigned)(c->d_p / RC_CW));
+  hipLaunchKernelGGL(recon_resid_kernel<T>, grid, dim3(256), 0, s, x, sc.xr, resid, rb, lat, c->n_p, M, Trows, 1.0f / (float)Trows, lengths,
+                     c->d, c->d_p, sc.rowpart, sc.dimpart);
+}
+
+static void recon_launch_fold(sae_ctx* c, const ReconScratch& sc, int nrb_lat, int nrb_dim, int64_t n_files, int Trows, const int* lengths,
+                              const ReconOut& o, double* file_out, hipStream_t s) {
+  const int nb_lat = (c->n + 255) / 256, nb_dim = (c->d + 255) / 256, nb_files = (int)((n_files + 3) / 4);
+  hipLaunchKernelGGL(recon_fold_kernel, dim3((unsigned)(nb_lat + nb_dim + nb_files)), dim3(256), 0, s, sc.slab_p, sc.slab_q, nrb_lat, c->n,
+                     c->n_p, sc.dimpart, nrb_dim, c->d, c->d_p, sc.rowpart, c->d_p / RC_CW, (int)n_files, Trows, lengths, o, file_out, nb_lat,
+                     nb_dim);
+}
+
+// L1: the stored latent of launch_encoder; x_hat by sae_decode's GEMM on that latent (settled weights, their bf16 cast: bit for bit
+// manip_decode_l1); the residual sweep writes r_b into c->dxh (free in a file pass) and zeroes the latent rows that do not count;
+// the attribution is the backward's dpre-shaped GEMM r_b [M_p][d_p] x Wt [n_p][d_p] with EpiAttr: in the streaming form where
+// launch_gemm would take it (gemm_streams), in the tile forms elsewhere and with `unfused` (SAE_RECON_UNFUSED).
+template <typename T>
+static int recon_l1_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
+                         double* file_out, float* resid, bool unfused, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  const GemmArgs g = file_pass_l1_front(c, x, M, s);
+  const int64_t Mp = (int64_t)g.nbm * 128;
+  if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
+  const ReconScratch sc = recon_scratch(c);
+
+  ev_begin(c, KID_RECON_DECODE, s);
+  settle_weights(c, s);
+  const int64_t n8 = c->nW / 8;
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P, c->Wb, n8);
+  GemmArgs gd{};
+  gd.A0 = c->c; gd.lda = n_p; gd.B0 = c->Wb; gd.ldb = n_p;
+  gd.nbm = (int)(round_up(M, c->row_pad) / 128); gd.nbn = d_p / 128; gd.ktiles0 = gd.ktiles = n_p / 64; gd.splits = 1;   // (sae_decode's M_p)
+  EpiStoreF32 ed{};
+  ed.out = sc.xr; ed.M = M; ed.d = c->d; ed.bias = nullptr;
+  int rc = launch_gemm<OP_ROW, OP_ROW>(gd, ed, s);
+  ev_end(c, KID_RECON_DECODE, s);
+  if (rc) return rc;
+
+  ev_begin(c, KID_RECON_RESID, s);
+  recon_launch_resid(c, x, sc, resid, c->dxh, c->c, Mp, M, Trows, lengths, s);
+  hipLaunchKernelGGL(recon_wnorm_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->Wb, (int64_t)1, (int64_t)n_p, c->d, c->n,
+                     o.wnorm);
+  ev_end(c, KID_RECON_RESID, s);
+
+  const GemmArgs ga = enc_gemm_args(c, c->dxh, Mp);
+  EpiAttr ea{};
+  ea.c = c->c; ea.slab_p = sc.slab_p; ea.slab_q = sc.slab_q; ea.n_p = n_p;
+  const bool no_stream_was = g_no_stream;
+  if (unfused) g_no_stream = true;                 // (the tile forms for this launch only)
+  const int kid = gemm_streams<OP_ROW, OP_ROW, EpiAttr>(ga) ? KID_RECON_ATTR_STREAM : KID_RECON_ATTR;
+  ev_begin(c, kid, s);
+  rc = launch_gemm<OP_ROW, OP_ROW>(ga, ea, s);
+  g_no_stream = no_stream_was;
+  if (!rc) recon_launch_fold(c, sc, (int)(Mp / STATS_RB), (int)(Mp / STATS_RB), n_files, Trows, lengths, o, file_out, s);
+  ev_end(c, kid, s);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+template <typename T>
+static int recon_topk_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
+                           double* file_out, float* resid, hipStream_t s) {
+  const ReconScratch sc = recon_scratch(c);
+  const int64_t rows_cover = round_up(M, STATS_RB);
+  ev_begin(c, KID_RECON_DECODE, s);
+  manip_decode_topk(c, M, sc.xr, s);
+  ev_end(c, KID_RECON_DECODE, s);
+
+  ev_begin(c, KID_RECON_RESID, s);
+  recon_launch_resid(c, x, sc, resid, (bf16_t*)nullptr, (bf16_t*)nullptr, rows_cover, M, Trows, lengths, s);
+  hipLaunchKernelGGL(recon_wnorm_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->Wd_b, (int64_t)c->d_p, (int64_t)1, c->d,
+                     c->n, o.wnorm);
+  ev_end(c, KID_RECON_RESID, s);
+
+  ev_begin(c, KID_RECON_ATTR, s);
+  {
+    const dim3 grid((unsigned)((M + 3) / 4));
+    auto launch = [&](auto np_tag) {
+      constexpr int NP = decltype(np_tag)::value;
+      hipLaunchKernelGGL(recon_topk_attr_kernel<NP>, grid, dim3(256), 0, s, sc.xr, c->top_vals, c->top_idx, c->k, c->Wd_b, sc.p, M, c->d,
+                         c->d_p, c->n_p);
+    };
+    if (c->d_p == 384) launch(std::integral_constant<int, 3>{});
+    else if (c->d_p == 768) launch(std::integral_constant<int, 6>{});
+    else if (c->d_p == 1280) launch(std::integral_constant<int, 10>{});
+    else launch(std::integral_constant<int, 0>{});
+  }
+  const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
+  hipLaunchKernelGGL(recon_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
+                     c->top_idx, (const unsigned short*)c->top_vals, sc.p, c->k, M, Trows, lengths, c->n, c->n_p, sc.slab_p, sc.slab_q);
+  recon_launch_fold(c, sc, nrb, (int)(rows_cover / STATS_RB), n_files, Trows, lengths, o, file_out, s);
+  ev_end(c, KID_RECON_ATTR, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                               int flags, void* block, double* file_out, float* resid, void* stream) {
+  int64_t M;
+  if (!file_out) return fail(SAE_ERR_INVALID, "null argument");
+  if (int rc = file_pass_begin(kReconPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (((reinterpret_cast<uintptr_t>(block) | reinterpret_cast<uintptr_t>(file_out)) & 7) != 0 || (reinterpret_cast<uintptr_t>(resid) & 3) != 0)
+    return fail(SAE_ERR_INVALID, "the report block and file_out must be 8-byte aligned, resid 4-byte aligned");
+  if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_recon_files: the TopK decode serves d_model <= 1536");
+  if ((c->max_rows_p / STATS_RB) * (int64_t)c->n_p >= ((int64_t)1 << 31))
+    return fail(SAE_ERR_INVALID, "sae_recon_files: max_rows / 128 x n_dict = %lld slab entries >= 2^31", (long long)((c->max_rows_p / STATS_RB) * (int64_t)c->n_p));
+  if (int rc = recon_ensure(c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  const ReconOut o = recon_out(block, c->n, c->d);
+  if (c->topk) {
+    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the sparse decode and the attribution of the selection
+    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_topk_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, s); }))
+      return rc;
+  } else {
+    const bool unfused = (flags & SAE_RECON_UNFUSED) != 0;
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_l1_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, unfused, s); }))
+      return rc;
+  }
+  c->last_call = LAST_RECON;
   return SAE_OK;
 }
 

@@ -134,6 +134,7 @@ def load() -> C.CDLL:
         "sae_dict_sim_keys": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_int, vp, vp]),
         "sae_manipulate_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.POINTER(i32), C.POINTER(i32), C.c_int, fptr, C.c_int, C.c_int,
                                            vp, vp, vp, vp]),
+        "sae_recon_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -178,6 +179,7 @@ EXPORTED_SYMBOLS = [
     "sae_hist_files",
     "sae_dict_pack_bytes", "sae_dict_pack", "sae_dict_sim_keys",
     "sae_manipulate_files",
+    "sae_recon_files",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
@@ -196,6 +198,7 @@ DICT_MAX_N = 1 << 24
 MANIP_OPS = {"scale": 0, "set": 1}                                  # include/freud_sae.h: SAE_MANIP_SCALE / SAE_MANIP_SET
 MANIP_MAX_EDITS = 16                                                # include/freud_sae.h: SAE_MANIP_MAX_EDITS
 MANIP_MAX_VARIANTS = 16                                             # include/freud_sae.h: SAE_MANIP_MAX_VARIANTS
+RECON_UNFUSED = 1                                                   # include/freud_sae.h: SAE_RECON_UNFUSED
 
 
 def stats_layout(n: int) -> dict:
@@ -204,6 +207,15 @@ def stats_layout(n: int) -> dict:
     return {"n_frames": (0, "int64", 1), "fire_count": (8, "int64", n), "act_sum": (8 + 8 * n, "float64", n),
             "act_sq_sum": (8 + 16 * n, "float64", n), "l0_hist": (8 + 24 * n, "int64", n + 1),
             "act_max": (16 + 32 * n, "float32", n), "bytes": 16 + 36 * n}
+
+
+def recon_layout(n: int, d: int) -> dict:
+    """Byte offsets of the sae_recon_files block for n latents and d model dimensions (include/freud_sae.h: SAE_RECON_*):
+    name -> (offset, dtype, count), plus "bytes": the block's size."""
+    return {"n_frames": (0, "int64", 1), "attr_sum": (8, "float64", n), "act_sq_sum": (8 + 8 * n, "float64", n),
+            "sum_x": (8 + 16 * n, "float64", d), "sum_x_sq": (8 + 16 * n + 8 * d, "float64", d),
+            "sum_r_sq": (8 + 16 * n + 16 * d, "float64", d), "dec_norm_sq": (8 + 16 * n + 24 * d, "float32", n),
+            "bytes": (8 + 20 * n + 24 * d + 7) // 8 * 8}
 
 
 def hist_nbins(spec) -> int:
@@ -699,6 +711,26 @@ class SaeEngine:
                                               C.c_void_p(standard.data_ptr()), C.c_void_p(manipulated.data_ptr()),
                                               C.c_void_p(series.data_ptr()), _stream_ptr(stream)))
 
+    # -- reconstruction report (include/freud_sae.h: sae_recon_files; freud_amd/reconstruction.py) -------------------------
+    def recon_files(self, x, block, file_out, lengths=None, resid=None, unfused: bool = False, stream=None) -> None:
+        """Add the reconstruction report of x [n_files, T, d] (CUDA) to block (a zero-initialised uint8 CUDA tensor of
+        recon_layout(n, d)["bytes"] bytes) and write file_out (float64 CUDA [n_files, 2]: sum r^2, sum x^2 per file) and, if given,
+        resid (float32 CUDA, n_files * T * d elements: r = x - x_hat, 0 on frames that do not count); lengths: int32 CUDA tensor
+        [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
+        import torch
+        x, xp, B, T, d, dt, lp = _files_args(x, "recon_files", lengths)
+        nbytes = recon_layout(self.n, self.d)["bytes"]
+        if not (block.is_cuda and block.dtype == torch.uint8 and block.is_contiguous() and block.numel() >= nbytes):
+            raise EngineError(f"block must be a contiguous uint8 CUDA tensor of >= {nbytes} bytes")
+        if not (file_out.is_cuda and file_out.dtype == torch.float64 and file_out.is_contiguous() and file_out.numel() == 2 * B):
+            raise EngineError(f"file_out must be a contiguous float64 CUDA tensor of {2 * B} elements")
+        if resid is not None and not (resid.is_cuda and resid.dtype == torch.float32 and resid.is_contiguous()
+                                      and resid.numel() == B * T * d):
+            raise EngineError(f"resid must be a contiguous float32 CUDA tensor of {B * T * d} elements")
+        _check(self._lib.sae_recon_files(self._ctx, xp, B, T, dt, lp, RECON_UNFUSED if unfused else 0, C.c_void_p(block.data_ptr()),
+                                         C.c_void_p(file_out.data_ptr()), C.c_void_p(resid.data_ptr()) if resid is not None else None,
+                                         _stream_ptr(stream)))
+
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:
         out = np.empty(count, dtype=np.float32)
@@ -712,7 +744,7 @@ class SaeEngine:
         _check(self._lib.sae_profile(self._ctx, level))
 
     def kernel_times(self) -> Dict[str, tuple]:
-        n = 32
+        n = 48
         ms = (C.c_float * n)()
         cnt = (C.c_int32 * n)()
         _check(self._lib.sae_kernel_times(self._ctx, ms, cnt, n))

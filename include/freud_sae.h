@@ -611,6 +611,76 @@ int sae_manipulate_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64
                          float* manipulated_dev /* [n_variants][M][d] */,
                          float* series_dev      /* [n_edits][M]       */, void* stream);
 
+/* ---- Reconstruction report: how well the dictionary reconstructs the data, where it fails, and which latents carry the
+ * reconstruction -- in one pass over the data.  Nothing of size frames x latents is stored.
+ *
+ * Both decoders are linear in the latent.  With r = x - x_hat the residual of a frame, a_j the value of latent j on it and w_j
+ * its decoder direction, zeroing latent j changes the frame's squared error by 2 a_j (r . w_j) + a_j^2 |w_j|^2.  Summed over the
+ * data, P_j = sum a_j (r . w_j) and Q_j = |w_j|^2 sum a_j^2 give
+ *   ablation_j = 2 P_j + Q_j     the squared error latent j is worth,
+ *   rescale_j  = 1 + P_j / Q_j   the least-squares gain of latent j with everything else held fixed (the shrinkage diagnostic of
+ *                                an L1 dictionary: the L1 penalty pushes it above 1).
+ *
+ * Semantics (freud_amd/csrc/recon.h).
+ *   Frames   count exactly as in sae_stats_files (lengths_dev: the first min(length, T) frames of a file; without, all T).
+ *   a        is the value freud_amd.models encode() returns: the bf16 L1 latent, or the TopK k selection (a multi_topk context uses
+ *            its k selection); a selected zero contributes nothing.
+ *   x_hat    L1: sae_decode's GEMM on the forward's own latent, as sae_manipulate_files' standard_dev: the bf16 copy of the
+ *            normalised W, the output rounded to bf16, no bias -- bit for bit models.decode(encode(x).latent).  TopK: the sparse
+ *            fp32 decode of the compact selection with the bf16 W_dec, plus b_dec (standard_dev of sae_manipulate_files).
+ *   r        = float(x) - x_hat, ONE fp32 subtraction on the delivered x (f32, or f16 / bf16 widened exactly), not on the engine's
+ *            bf16 copy.  r = 0 on frames that do not count.
+ * Per latent j < n, over the counted frames:
+ *   attr_sum[j]    = P_j = sum a s, with s = r_b . w_j for L1 (r_b = bf16(r), round to nearest even; w_j the column of the bf16
+ *                    normalised W; accumulated in fp32 by the MFMA and NOT rounded to bf16) and s = r . w_j in fp32 for TopK
+ *                    (w_j = row j of the bf16 W_dec); a s is one fp32 product;
+ *   act_sq_sum[j]  = sum a^2;
+ *   dec_norm_sq[j] = |w_j|^2 of that decoder operand (written, not accumulated).
+ * Per model dimension i < d: sum_x[i], sum_x_sq[i], sum_r_sq[i] over the counted frames.
+ * Per file f of the batch: file_out[f] = {sum r^2, sum x^2} over the file's counted frames (written, not accumulated).
+ * resid_dev (fp32 [M][d], may be null) receives r itself: the per-frame error.
+ *
+ * Output block: caller-owned, 8-byte aligned, SAE_RECON_BYTES(n, d) bytes of running totals; zero it before the first batch,
+ * every call adds one batch.  Byte offsets:
+ *   SAE_RECON_N_FRAMES    int64                frames counted
+ *   SAE_RECON_ATTR_SUM    float64 [n]
+ *   SAE_RECON_ACT_SQ_SUM  float64 [n]
+ *   SAE_RECON_SUM_X       float64 [d]
+ *   SAE_RECON_SUM_X_SQ    float64 [d]
+ *   SAE_RECON_SUM_R_SQ    float64 [d]
+ *   SAE_RECON_DEC_NORM_SQ float32 [n]
+ *
+ * Determinism: every float sum is a fixed-order fp32 partial written with plain stores -- per (row, 64 columns) for the file
+ * sums, per (128-row block, column) for the model dimensions and the L1 latents, per (256-row block, latent) for TopK -- folded
+ * in a fixed order into the fp64 totals.  No float atomics: two runs over the same batches give bitwise identical blocks.
+ *
+ * Out of scope: raw (no-SAE) activations; fp8 contexts; the ignored_index mask of the reference's mse_loss (an element of x equal
+ * to -1 is data here); re-encoding after an ablation (the effect is first order in the decoder only); joint ablations. */
+#define SAE_RECON_N_FRAMES(n, d) ((int64_t)0)
+#define SAE_RECON_ATTR_SUM(n, d) ((int64_t)8)
+#define SAE_RECON_ACT_SQ_SUM(n, d) ((int64_t)8 + 8 * (int64_t)(n))
+#define SAE_RECON_SUM_X(n, d) ((int64_t)8 + 16 * (int64_t)(n))
+#define SAE_RECON_SUM_X_SQ(n, d) ((int64_t)8 + 16 * (int64_t)(n) + 8 * (int64_t)(d))
+#define SAE_RECON_SUM_R_SQ(n, d) ((int64_t)8 + 16 * (int64_t)(n) + 16 * (int64_t)(d))
+#define SAE_RECON_DEC_NORM_SQ(n, d) ((int64_t)8 + 16 * (int64_t)(n) + 24 * (int64_t)(d))
+#define SAE_RECON_BYTES(n, d) (((int64_t)8 + 20 * (int64_t)(n) + 24 * (int64_t)(d) + 7) / 8 * 8)
+enum { SAE_RECON_UNFUSED = 1 };
+
+/* Add the report of one batch (x_dev [n_files][rows_per_file][d], x_dtype) to block_dev and write file_out_dev / resid_dev.
+ * L1: the encoder with the stored latent, the decoder GEMM, the residual sweep, then the attribution as the epilogue of the
+ * backward's dpre-shaped GEMM (r_b x W) -- in the streaming GEMM where its conditions hold (as for sae_stats_files: an even number
+ * of 128-row blocks, 2048 tiles of 256 x 256), in the tile GEMMs elsewhere; flags = SAE_RECON_UNFUSED keeps it off the streaming
+ * kernel, so the two forms can be compared (they associate the fp32 sums of a 128-row block differently).  TopK: the eval forward, the sparse decode, the sweep, one dot
+ * per selected slot and a column walk of the selection; d_model <= 1536.  n_files * rows_per_file <= max_rows; fp8 contexts:
+ * SAE_ERR_INVALID.  Shape and argument checks fail before anything is enqueued.  Asynchronous on `stream`; the first call
+ * allocates the context's scratch (4 d bytes per row, 8 bytes per 128 rows and latent, 4 k bytes per row for TopK).  Training
+ * state (parameters, moments, num_frames_since_fired) is untouched; the stored latent is not valid afterwards, and
+ * sae_latent_buffer, sae_topk_indices, sae_decode, sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return
+ * SAE_ERR_STATE until the next sae_eval / step. */
+int sae_recon_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                    int flags, void* block_dev, double* file_out_dev /* [n_files][2] */, float* resid_dev /* or null */,
+                    void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
