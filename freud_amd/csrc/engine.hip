@@ -40,6 +40,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "coact.h"
 #include "labels.h"
 #include "hist.h"
+#include "collect.h"
 #include "manip.h"
 #include "dict_match.h"
 #include "recon.h"
@@ -141,6 +142,7 @@ enum KernelId {
   KID_RECON_RESID,     //   (L1: the GEMM with EpiAttr; TopK: the dots and the column walk) with the fold
   KID_RECON_ATTR,
   KID_RECON_ATTR_STREAM,   // ... the same bracket when the attribution GEMM ran in the streaming form (gemm256s.h)
+  KID_COLLECT,         // feature collection (collect.h): the row collect kernel of sae_collect_files after the encoder
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
@@ -149,7 +151,7 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
-                                              "recon_resid", "recon_attr", "recon_attr_stream"};
+                                              "recon_resid", "recon_attr", "recon_attr_stream", "collect"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -159,7 +161,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT };
 
 struct sae_ctx {
   sae_config cfg;
@@ -367,6 +369,8 @@ static int no_forward_left(const sae_ctx* c, bool after_search = true) {
     return fail(SAE_ERR_STATE, "the last call was an activation histogram pass: it leaves no forward to read (run sae_eval first)");
   if (c->last_call == LAST_RECON)
     return fail(SAE_ERR_STATE, "the last call was a reconstruction report: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_COLLECT)
+    return fail(SAE_ERR_STATE, "the last call was a feature collection: it leaves no forward to read (run sae_eval first)");
   return SAE_OK;
 }
 
@@ -3975,6 +3979,59 @@ extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64
       return rc;
   }
   c->last_call = LAST_RECON;
+  return SAE_OK;
+}
+
+// ---- feature collection (collect.h): every row's K slots of the latent encode() returns, in the reference's indexed form
+static_assert(SAE_COLLECT_IDX32 == CL_IDX32 && SAE_COLLECT_MAX_K == CL_MAX_K, "freud_sae.h and collect.h disagree");
+static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32};
+// Grids of what is resident at once, the kernels stride over the rest of the rows: collect_l1_kernel holds 98 VGPRs (4 waves per SIMD:
+// 4 workgroups of 256 threads per CU), collect_topk_kernel 32 KiB of LDS (5 per CU); 256 CUs
+constexpr int COLLECT_L1_WGS = 256 * 4, COLLECT_TOPK_WGS = 256 * 5;
+
+template <typename T>
+static int collect_l1_encode(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
+  const GemmArgs g = file_pass_l1_front(c, x, M, s);
+  return launch_encoder<T>(c, g, M, s);
+}
+
+template <typename IdxT>
+static void collect_launch(sae_ctx* c, int64_t M, int K, float* values, IdxT* indices, int64_t* stats, hipStream_t s) {
+  unsigned long long* st = reinterpret_cast<unsigned long long*>(stats);
+  if (c->topk)
+    hipLaunchKernelGGL(collect_topk_kernel<IdxT>, dim3(grid_for(M, COLLECT_TOPK_WGS, 4)), dim3(CL_THREADS), 0, s, c->top_idx,
+                       (const unsigned short*)c->top_vals, c->k, M, K, values, indices, st);
+  else
+    hipLaunchKernelGGL(collect_l1_kernel<IdxT>, dim3(grid_for(M, COLLECT_L1_WGS, 1)), dim3(CL_THREADS), 0, s, (const unsigned short*)c->c,
+                       (int64_t)c->n_p, c->n, M, K, values, indices, st);
+}
+
+extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, int K, int flags,
+                                 float* values, void* indices, int64_t* stats, void* stream) {
+  int64_t M;
+  if (!indices || !stats) return fail(SAE_ERR_INVALID, "null argument");
+  if (int rc = file_pass_begin(kCollectPass, c, x, values, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  const bool idx32 = (flags & SAE_COLLECT_IDX32) != 0;
+  if ((reinterpret_cast<uintptr_t>(stats) & 7) != 0 || (reinterpret_cast<uintptr_t>(values) & 3) != 0 ||
+      (reinterpret_cast<uintptr_t>(indices) & (idx32 ? 3 : 7)) != 0)
+    return fail(SAE_ERR_INVALID, "stats must be 8-byte aligned, values 4-byte aligned, indices aligned to their type");
+  const int k_max = c->topk ? c->k : std::min(c->n, (int)SAE_COLLECT_MAX_K);
+  if (K < 1 || K > k_max)
+    return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max, c->topk ? "the context's k" : "min(n_dict, SAE_COLLECT_MAX_K)");
+  hipStream_t s = (hipStream_t)stream;
+
+  // the encoder as encode() runs it: the stored L1 latent, or the eval forward's top-k selection (the k of encode())
+  if (c->topk) {
+    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+  } else {
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return collect_l1_encode(c, xt, M, s); })) return rc;
+  }
+  ev_begin(c, KID_COLLECT, s);
+  if (idx32) collect_launch(c, M, K, values, (int32_t*)indices, stats, s);
+  else collect_launch(c, M, K, values, (int64_t*)indices, stats, s);
+  ev_end(c, KID_COLLECT, s);
+  HIP_TRY(hipGetLastError());
+  c->last_call = LAST_COLLECT;
   return SAE_OK;
 }
 

@@ -135,6 +135,7 @@ def load() -> C.CDLL:
         "sae_manipulate_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.POINTER(i32), C.POINTER(i32), C.c_int, fptr, C.c_int, C.c_int,
                                            vp, vp, vp, vp]),
         "sae_recon_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
+        "sae_collect_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -180,6 +181,7 @@ EXPORTED_SYMBOLS = [
     "sae_dict_pack_bytes", "sae_dict_pack", "sae_dict_sim_keys",
     "sae_manipulate_files",
     "sae_recon_files",
+    "sae_collect_files",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
@@ -192,6 +194,8 @@ LABEL_MAX_CLASSES = 4096                                            # include/fr
 LABEL_MAX_SLOTS = 16                                                # include/freud_sae.h: SAE_LABEL_MAX_SLOTS
 HIST_MAX_REGULAR = 128                                              # freud_amd/csrc/hist_bins.h: octaves << sub_bits at most
 HIST_MAX_SEL = 64                                                   # include/freud_sae.h: SAE_HIST_MAX_SEL
+COLLECT_IDX32 = 1                                                   # include/freud_sae.h: SAE_COLLECT_IDX32
+COLLECT_MAX_K = 1024                                                # include/freud_sae.h: SAE_COLLECT_MAX_K
 DICT_LEFT, DICT_RIGHT = 0, 1                                        # include/freud_sae.h: SAE_DICT_LEFT / SAE_DICT_RIGHT
 DICT_MAX_D = 8192                                                   # include/freud_sae.h: SAE_DICT_MAX_D
 DICT_MAX_N = 1 << 24
@@ -730,6 +734,25 @@ class SaeEngine:
         _check(self._lib.sae_recon_files(self._ctx, xp, B, T, dt, lp, RECON_UNFUSED if unfused else 0, C.c_void_p(block.data_ptr()),
                                          C.c_void_p(file_out.data_ptr()), C.c_void_p(resid.data_ptr()) if resid is not None else None,
                                          _stream_ptr(stream)))
+
+    # -- feature collection (include/freud_sae.h: sae_collect_files; freud_amd/collect_features.py) ------------------------------
+    def collect_files(self, x, K: int, values, indices, stats, stream=None) -> None:
+        """Write the K slots of every row of x [n_files, T, d] (CUDA) -- the first K entries of the stable descending sort of the
+        latent row encode() returns -- to values (contiguous float32 CUDA, n_files * T * K elements) and indices (int64 or int32
+        CUDA of the same size; its dtype chooses the form), and add the batch to stats (zero-initialised contiguous int64 CUDA [8]).
+        Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
+        import torch
+        x, xp, B, T, _d, dt, _lp = _files_args(x, "collect_files", None)
+        numel = B * T * int(K)
+        if not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.numel() == numel):
+            raise EngineError(f"values must be a contiguous float32 CUDA tensor of {numel} elements")
+        if not (indices.is_cuda and indices.dtype in (torch.int64, torch.int32) and indices.is_contiguous() and indices.numel() == numel):
+            raise EngineError(f"indices must be a contiguous int64 or int32 CUDA tensor of {numel} elements")
+        if not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() == 8):
+            raise EngineError("stats must be a contiguous int64 CUDA tensor of 8 elements")
+        _check(self._lib.sae_collect_files(self._ctx, xp, B, T, dt, int(K), COLLECT_IDX32 if indices.dtype == torch.int32 else 0,
+                                           C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                           _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:

@@ -681,6 +681,46 @@ int sae_recon_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t ro
                     int flags, void* block_dev, double* file_out_dev /* [n_files][2] */, float* resid_dev /* or null */,
                     void* stream);
 
+/* ---- Feature collection: the SAE features of a dataset in the reference's indexed form (collect_activations.py with sae_model
+ * set: <layer>_activation_values.npy + <layer>_feature_indices.npy, read back as activation_type == "indexed"), written from the
+ * cached layer activations -- one encode per row and a per-row select.
+ *
+ * Semantics.  Every frame (row) of every file is stored, all T of them: the reference collects untrimmed and trims at search time,
+ * so there is no lengths argument.  Let a be the latent row exactly as freud_amd.models encode() returns it -- L1: the bf16
+ * c = relu(x W + b) that sae_eval leaves in sae_latent_buffer; TopK: the scatter of the k selection, 0 elsewhere (a multi_topk
+ * context uses its k selection).  The row's K slots are the first K entries of a stable descending sort of a: value descending,
+ * equal values by the lower column -- numpy.argsort(-a, kind="stable")[:K].  So
+ *   - slots are sorted: the first K' slots of a row are its top K', and a store can be truncated by prefix;
+ *   - a row with fewer than K positive latents is padded with zero-valued latents in increasing column order, stored as +0.0 even
+ *     where the latent holds a bf16 -0.0 (a latent is ACTIVE iff its magnitude bits are non-zero and its sign is clear, as in
+ *     sae_stats_files);
+ *   - the indices of a row are always distinct (the reference's activation_tensor_from_indexed raises on a repeated index);
+ *   - for TopK this is the engine's own tie rule (lowest column first, selected zeros included): the store is the selection itself,
+ *     canonically ordered.
+ * Limits: L1 1 <= K <= min(n_dict, SAE_COLLECT_MAX_K); TopK 1 <= K <= k.
+ *
+ * values_dev [n_files * rows_per_file][K] fp32 (the bf16 value widened: exact) and indices_dev of the same shape, int64 or, with
+ * SAE_COLLECT_IDX32, int32: caller-owned device memory, dense, in file order -- one file's block is one row of the .npy files.
+ *
+ * stats_dev: caller-owned int64[8], 8-byte aligned, running totals: zero it before the first batch, every call adds one batch.
+ * Integer adds and integer maxima only, so it is order-free and deterministic.
+ *   [0] rows collected                          [1] active latents stored
+ *   [2] active latents dropped (active in the row but beyond slot K)
+ *   [3] rows that dropped at least one          [4] largest number of active latents in a row
+ *   [5] bf16 bit pattern of the largest dropped value (0 if none)        [6], [7] reserved, left 0
+ * The store equals the latent iff [2] is 0.
+ *
+ * The call is the bf16 eval encoder followed by the collect kernels (freud_amd/csrc/collect.h), asynchronous on `stream`.  n_files
+ * * rows_per_file <= max_rows; fp8 contexts: SAE_ERR_INVALID.  K out of range (TopK: K > k), unknown flag bits, null pointers, a
+ * misaligned values_dev, indices_dev or stats_dev and bad shapes fail before anything is enqueued.  Training state (parameters,
+ * moments, num_frames_since_fired) is untouched; afterwards sae_latent_buffer, sae_topk_indices, sae_decode,
+ * sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the next sae_eval / step, as after
+ * sae_stats_files.  Exact and deterministic: two runs give the same bytes. */
+enum { SAE_COLLECT_IDX32 = 1 };
+#define SAE_COLLECT_MAX_K 1024
+int sae_collect_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, int K, int flags,
+                      float* values_dev, void* indices_dev, int64_t* stats_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
