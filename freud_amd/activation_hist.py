@@ -39,7 +39,7 @@ import torch
 
 from . import feature_labels as FL
 from .engine import HIST_MAX_SEL, hist_nbins
-from .file_pass import FilePass, keep_rng
+from .file_pass import FilePass, is_raw, keep_rng
 
 _ARRAYS = ("frame_hist", "file_max_hist", "label_hist", "label_latents", "label_count")
 
@@ -196,7 +196,7 @@ def activation_histograms(sae, data_path: str, layer_name: str, *, lo_exp: int =
         raise ValueError("label_latents need file_labels or frame_labels")
     if sel is None and has_labels:
         raise ValueError("file_labels / frame_labels need label_latents (the latents whose histogram is split by label)")
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         raise ValueError("activation histograms need an SAE (histograms of raw activations are not provided)")
     labels, per_file, C = None, False, 0
     if sel is not None:

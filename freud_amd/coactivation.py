@@ -32,7 +32,7 @@ import torch
 
 from .engine import COACT_MEASURES, FILE_TOP_MAX, FILE_TOP_POSITIVE
 from .feature_search import unord
-from .file_pass import FilePass, keep_rng
+from .file_pass import FilePass, is_raw, keep_rng
 
 MAX_FRAMES = 2 ** 31 - 1          # int32 counts
 KEY_BLOCK = 1 << 25               # keys per neighbour-selection block (256 MiB of 64-bit keys)
@@ -87,7 +87,7 @@ def decode_neighbor_table(top_latents: np.ndarray, top_keys: np.ndarray):
 
 
 def _check_args(sae, n_neighbors, measure) -> int:
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         raise ValueError("feature co-activation needs an SAE (raw-activation co-activation is not provided)")
     n_neighbors = int(n_neighbors)
     if n_neighbors < 1 or n_neighbors > FILE_TOP_MAX:

@@ -249,9 +249,9 @@ def collect_features(sae, data_path: str, layer_name: str, out_folder: str, *, k
     most min(n_dict, 1024).  batch_files: files per engine call (default: file_pass.default_batch_files); the files written do not
     depend on it."""
     import torch
-    from .file_pass import FilePass, keep_rng
+    from .file_pass import FilePass, is_raw, keep_rng
 
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         raise ValueError("feature collection needs an SAE: the raw activations are the shards themselves")
     if layout not in ("indexed", "tensor"):
         raise ValueError(f"layout={layout!r} is neither 'indexed' nor 'tensor'")

@@ -105,6 +105,18 @@ static int with_x_type(int x_dtype, const void* x, F&& f) {
   }
 }
 
+// the one dispatch of the sparse TopK kernels on d_p: f(integral_constant<NP>), NP = d_p / 128 where a kernel is specialised, else 0
+template <class F>
+static void with_np(int d_p, F&& f) {
+  if (d_p == 384) f(std::integral_constant<int, 3>{});
+  else if (d_p == 768) f(std::integral_constant<int, 6>{});
+  else if (d_p == 1280) f(std::integral_constant<int, 10>{});
+  else f(std::integral_constant<int, 0>{});
+}
+
+// the entry points' test of a pointer argument against the alignment its kernels need (a null optional pointer passes)
+static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
 // ------------------------------------------------------------------------------------------
 // kernel ids for profiling
 // ------------------------------------------------------------------------------------------
@@ -162,6 +174,24 @@ struct EvRing {
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
 enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT };
+
+// A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
+// of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
+struct FilePassKind {
+  const char *fn, *fp8_advice, *flags_noun;
+  int flags_mask;
+  LastCall leaves;
+  const char* left_by;
+};
+static const FilePassKind kSearchPass = {"sae_search_files", "search in a bf16 context", "search", SAE_SEARCH_UNFUSED, LAST_SEARCH, "a feature search"};
+static const FilePassKind kStatsPass = {"sae_stats_files", "run the statistics in a bf16 context", "stats", SAE_STATS_UNFUSED, LAST_STATS, "a feature statistics pass"};
+static const FilePassKind kCoactPass = {"sae_coact_files", "count co-activations in a bf16 context", "co-activation", 0, LAST_COACT, "a feature co-activation pass"};
+static const FilePassKind kLabelPass = {"sae_label_files", "count labels in a bf16 context", "label", 0, LAST_LABELS, "a feature label pass"};
+static const FilePassKind kHistPass = {"sae_hist_files", "build the histograms in a bf16 context", "histogram", 0, LAST_HIST, "an activation histogram pass"};
+static const FilePassKind kManipPass = {"sae_manipulate_files", "manipulate in a bf16 context", "manipulation", 0, LAST_FWD_BF16, nullptr};
+static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruction report in a bf16 context", "reconstruction", SAE_RECON_UNFUSED, LAST_RECON, "a reconstruction report"};
+static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32, LAST_COLLECT, "a feature collection"};
+static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass};
 
 struct sae_ctx {
   sae_config cfg;
@@ -357,22 +387,14 @@ static int use_device(const sae_ctx* c) {
 
 // the getters of the last forward refuse after a file pass (after_search = false: after a statistics pass only)
 static int no_forward_left(const sae_ctx* c, bool after_search = true) {
-  if (c->last_call == LAST_SEARCH && after_search)
-    return fail(SAE_ERR_STATE, "the last call was a feature search: it leaves no forward to read (run sae_eval first)");
-  if (c->last_call == LAST_STATS)
-    return fail(SAE_ERR_STATE, "the last call was a feature statistics pass: it leaves no forward to read (run sae_eval first)");
-  if (c->last_call == LAST_COACT)
-    return fail(SAE_ERR_STATE, "the last call was a feature co-activation pass: it leaves no forward to read (run sae_eval first)");
-  if (c->last_call == LAST_LABELS)
-    return fail(SAE_ERR_STATE, "the last call was a feature label pass: it leaves no forward to read (run sae_eval first)");
-  if (c->last_call == LAST_HIST)
-    return fail(SAE_ERR_STATE, "the last call was an activation histogram pass: it leaves no forward to read (run sae_eval first)");
-  if (c->last_call == LAST_RECON)
-    return fail(SAE_ERR_STATE, "the last call was a reconstruction report: it leaves no forward to read (run sae_eval first)");
-  if (c->last_call == LAST_COLLECT)
-    return fail(SAE_ERR_STATE, "the last call was a feature collection: it leaves no forward to read (run sae_eval first)");
+  if (c->last_call == LAST_SEARCH && !after_search) return SAE_OK;
+  for (const FilePassKind* k : kFilePasses)
+    if (c->last_call == k->leaves)
+      return fail(SAE_ERR_STATE, "the last call was %s: it leaves no forward to read (run sae_eval first)", k->left_by);
   return SAE_OK;
 }
+
+static void file_pass_end(const FilePassKind& kind, sae_ctx* c) { c->last_call = kind.leaves; }
 
 // the tensors of a bf16 forward (latent rows, top-k indices, 4k buffers, dx_hat, the fp8 operands) are not what the fp32
 // evaluation computed: it has its own buffers and leaves those of the last training step as they were
@@ -2336,10 +2358,7 @@ static int topk_fwd_bwd(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool b
         hipLaunchKernelGGL((topk_decode_kernel<T, NP>), dim3((unsigned)(Mp / 4)), dim3(256), 0, s, x, c->multi_vals, c->multi_idx,
                            c->k4, c->Wd_b, bd, c->em, c->dh, c->m2_part, M, d, d_p, n_p, 0, (const int*)nullptr);
     };
-    if (d_p == 384) launch_decode(std::integral_constant<int, 3>{});
-    else if (d_p == 768) launch_decode(std::integral_constant<int, 6>{});
-    else if (d_p == 1280) launch_decode(std::integral_constant<int, 10>{});
-    else launch_decode(std::integral_constant<int, 0>{});
+    with_np(d_p, launch_decode);
     if (auxc) {   // e_hat = A_aux W_dec[dead] over the compact dead set: K = ND_p (device side), e_hat - e and its squares in the epilogue
       HIP_TRY(hipMemsetAsync(c->a2_part, 0, (size_t)Mp * 4, s));
       GemmArgs g{};
@@ -3021,6 +3040,9 @@ extern "C" int sae_multi_topk_buffers(sae_ctx* c, void** dense_dev, int64_t* row
   return SAE_OK;
 }
 
+// (defined below sae_decode, whose TopK GEMM is instantiated first: the kernels keep their place in the code object, as at launch_encoder)
+static int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s);
+
 extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int64_t ld, int64_t M, float* x_hat, void* stream) {
   if (!c || !latent || !x_hat) return fail(SAE_ERR_INVALID, "null argument");
   if (M <= 0 || M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "M=%lld outside (0, max_rows=%lld]", (long long)M, (long long)c->cfg.max_rows);
@@ -3038,32 +3060,39 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
     hipLaunchKernelGGL(pad_latent_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)latent, ld, M, c->n, lat, Mp, n_p);
   else
     hipLaunchKernelGGL(pad_latent_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)latent, ld, M, c->n, lat, Mp, n_p);
-  GemmArgs g{};
-  g.A0 = lat; g.lda = n_p;
-  g.nbm = (int)(Mp / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
-  EpiStoreF32 e{};
-  e.out = x_hat; e.M = M; e.d = c->d;
   int rc;
-  const int64_t n8 = c->nW / 8;
-  const int cg = grid_for(n8, 2048);
   if (c->topk) {
     // W_dec [n_p][d_p] fp32 -> bf16 (K = n is the slow dimension of this operand: transposed-read mode)
     float* Wd = c->P + c->nW + c->n_p;
-    hipLaunchKernelGGL(cast_bf16_kernel, dim3(cg), dim3(256), 0, s, Wd, c->Wd_b, n8);
-    g.B0 = c->Wd_b; g.ldb = d_p;
-    e.bias = c->P + 2 * c->nW + c->n_p;
+    const int64_t n8 = c->nW / 8;
+    hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, Wd, c->Wd_b, n8);
+    GemmArgs g{};
+    g.A0 = lat; g.lda = n_p; g.B0 = c->Wd_b; g.ldb = d_p;
+    g.nbm = (int)(Mp / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
+    EpiStoreF32 e{};
+    e.out = x_hat; e.M = M; e.d = c->d; e.bias = c->P + 2 * c->nW + c->n_p;
     rc = launch_gemm<OP_ROW, OP_KMAJOR>(g, e, s);
   } else {
-    // current W [d_p][n_p] as is (decode() does not renormalise); the copy is refreshed by the next forward anyway
-    settle_weights(c, s);
-    hipLaunchKernelGGL(cast_bf16_kernel, dim3(cg), dim3(256), 0, s, c->P, c->Wb, n8);
-    g.B0 = c->Wb; g.ldb = n_p;
-    e.bias = nullptr;
-    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+    rc = decode_l1_latent(c, lat, Mp / 128, M, x_hat, s);
   }
   if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return SAE_OK;
+}
+
+// x_hat [M][d] = lat W^T of an L1 context, no bias: `lat` the padded bf16 latent [nbm * 128][n_p], W the current weights as they are
+// (settled, not renormalised: decode()) in their bf16 copy, which the next forward refreshes anyway.  The one L1 decode of a stored
+// latent: sae_decode, sae_manipulate_files and sae_recon_files agree to the bit because they all run this.
+static int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s) {
+  settle_weights(c, s);
+  const int64_t n8 = c->nW / 8;
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P, c->Wb, n8);
+  GemmArgs g{};
+  g.A0 = lat; g.lda = c->n_p; g.B0 = c->Wb; g.ldb = c->n_p;
+  g.nbm = (int)nbm; g.nbn = c->d_p / 128; g.ktiles0 = g.ktiles = c->n_p / 64; g.splits = 1;
+  EpiStoreF32 e{};
+  e.out = x_hat; e.M = M; e.d = c->d; e.bias = nullptr;
+  return launch_gemm<OP_ROW, OP_ROW>(g, e, s);
 }
 
 extern "C" int sae_latent_colmax(sae_ctx* c, float* out_host, int64_t capacity, void* stream) {
@@ -3147,15 +3176,7 @@ static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int n
   return SAE_OK;
 }
 
-// ---- what sae_search_files and sae_stats_files share: one batch of files encoded with the training kernels
-struct FilePassKind {           // the words of an entry point's messages and the flags it knows
-  const char *fn, *fp8_advice, *flags_noun;
-  int flags_mask;
-};
-static const FilePassKind kSearchPass = {"sae_search_files", "search in a bf16 context", "search", SAE_SEARCH_UNFUSED};
-static const FilePassKind kStatsPass = {"sae_stats_files", "run the statistics in a bf16 context", "stats", SAE_STATS_UNFUSED};
-static const FilePassKind kCoactPass = {"sae_coact_files", "count co-activations in a bf16 context", "co-activation", 0};
-
+// ---- what the file passes share (FilePassKind, above): one batch of files encoded with the training kernels
 static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
   if (n_files <= 0 || rows_per_file <= 0) return fail(SAE_ERR_INVALID, "n_files=%lld and rows_per_file=%lld must be positive", (long long)n_files, (long long)rows_per_file);
   if (n_files > 65535) return fail(SAE_ERR_INVALID, "n_files=%lld > 65535 in one call", (long long)n_files);
@@ -3164,7 +3185,7 @@ static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
   return SAE_OK;
 }
 
-// the front door of both entry points: argument checks (nothing is enqueued when one fails), then the context's device
+// the front door of every file pass: argument checks (nothing is enqueued when one fails), then the context's device
 static int file_pass_begin(const FilePassKind& kind, sae_ctx* c, const void* x, const void* out, int64_t n_files, int64_t rows_per_file,
                            int x_dtype, int flags, int64_t* M) {
   if (!c || !x || !out) return fail(SAE_ERR_INVALID, "null argument");
@@ -3179,7 +3200,7 @@ static int file_pass_begin(const FilePassKind& kind, sae_ctx* c, const void* x, 
 }
 
 // L1: forward_impl's weights preparation and bf16 copy of x, then the GEMM arguments of its encoder -- for the epilogue the pass
-// brings (EpiSearch, EpiStats) where the GEMM streams, for launch_encoder and a reduction of the stored latent where it does not
+// brings (EpiSearch, EpiStats) where the GEMM streams, for file_pass_l1_encode and a reduction of the stored latent where it does not
 template <typename T>
 static GemmArgs file_pass_l1_front(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
   int64_t Mp = round_up(M, 128);
@@ -3198,6 +3219,22 @@ static int file_pass_l1_fused(sae_ctx* c, const GemmArgs& g, const Epi& e, hipSt
   return rc;
 }
 
+// L1: the batch's latent as encode() returns it, stored as bf16 rows in c->c -- the front (the caller's own `front` where it has run
+// one to decide on its fused form), then the ordinary encoder.  Mp: the rows the front padded to.
+template <typename T>
+static int file_pass_l1_encode(sae_ctx* c, const T* x, int64_t M, hipStream_t s, const GemmArgs* front = nullptr, int64_t* Mp = nullptr) {
+  const GemmArgs g = front ? *front : file_pass_l1_front(c, x, M, s);
+  if (Mp) *Mp = (int64_t)g.nbm * 128;
+  return launch_encoder<T>(c, g, M, s);
+}
+
+// The encoder as encode() runs it: the stored L1 latent, or c->top_idx / c->top_vals of the eval forward (encoder GEMM + top-k
+// selection, the k of encode())
+static int file_pass_encode(sae_ctx* c, const void* x, int64_t M, int x_dtype, hipStream_t s) {
+  if (c->topk) return dispatch_fwd_bwd(c, x, M, x_dtype, s, false);
+  return with_x_type(x_dtype, x, [&](auto* xt) { return file_pass_l1_encode(c, xt, M, s); });
+}
+
 // L1 search: where the streaming GEMM does not apply (small or odd shapes, FREUD_GEMM_STREAM=0, force_gemm128) or `unfused` is asked
 // for (the baseline of tools/bench_search.py), the latent is stored by the ordinary encoder and reduced by the column kernel.
 template <typename T>
@@ -3210,7 +3247,7 @@ static int search_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, int64_t 
     e.bias = c->P + c->nW; e.keys = keys; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n;
     return file_pass_l1_fused(c, g, e, s);
   }
-  if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
+  if (int rc = file_pass_l1_encode(c, x, M, s, &g)) return rc;
   return search_launch_colreduce(c->c, SAE_DTYPE_BF16, c->n_p, c->n, Trows, n_files, lengths, false, keys, nullptr, s);
 }
 
@@ -3221,10 +3258,10 @@ extern "C" int sae_search_files(sae_ctx* c, const void* x, int64_t n_files, int6
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   if (c->topk) {
-    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the selection scattered into the keys
+    // the keys filled, then the selection of encode() scattered into them
     const int64_t nk = n_files * c->n;
     hipLaunchKernelGGL(search_fill_kernel, dim3(grid_for(nk, 4096)), dim3(256), 0, s, file_keys, nk, (uint64_t)SK_KEY_ZERO_FRAME0);
-    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+    if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
     hipLaunchKernelGGL(search_topk_scatter_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, Trows,
                        lengths, c->n, file_keys);
     HIP_TRY(hipGetLastError());
@@ -3233,7 +3270,7 @@ extern "C" int sae_search_files(sae_ctx* c, const void* x, int64_t n_files, int6
     if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return search_l1_impl(c, xt, M, Trows, n_files, lengths, file_keys, unfused, s); }))
       return rc;
   }
-  c->last_call = LAST_SEARCH;
+  file_pass_end(kSearchPass, c);
   return SAE_OK;
 }
 
@@ -3356,7 +3393,7 @@ static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int
     if (int rc = file_pass_l1_fused(c, g, e, s)) return rc;
     stats_launch_l0(L0Bytes{l0b, n_p / 64}, M, Trows, lengths, c->n, o, s);
   } else {
-    if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
+    if (int rc = file_pass_l1_encode(c, x, M, s, &g)) return rc;
     const unsigned short* lat = (const unsigned short*)c->c;
     hipLaunchKernelGGL(stats_colreduce_kernel, dim3((unsigned)((c->n + 255) / 256), (unsigned)nrb), dim3(256), 0, s, lat, (int64_t)n_p, c->n,
                        M, Trows, lengths, sl);
@@ -3371,14 +3408,14 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
                                int flags, void* stats, void* stream) {
   int64_t M;
   if (int rc = file_pass_begin(kStatsPass, c, x, stats, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if ((reinterpret_cast<uintptr_t>(stats) & 7) != 0) return fail(SAE_ERR_INVALID, "the stats block must be 8-byte aligned");
+  if (misaligned(stats, 8)) return fail(SAE_ERR_INVALID, "the stats block must be 8-byte aligned");
   if (int rc = stats_ensure(c)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   const StatsOut o = stats_out(stats, c->n);
   if (c->topk) {
-    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the statistics of the selection
-    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+    // the statistics of encode()'s selection
+    if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
     const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
     const unsigned short* vals = (const unsigned short*)c->top_vals;
     hipLaunchKernelGGL(stats_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
@@ -3390,7 +3427,7 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
     const bool unfused = (flags & SAE_STATS_UNFUSED) != 0;
     if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return stats_l1_impl(c, xt, M, Trows, lengths, o, unfused, s); })) return rc;
   }
-  c->last_call = LAST_STATS;
+  file_pass_end(kStatsPass, c);
   return SAE_OK;
 }
 
@@ -3403,31 +3440,25 @@ static int coact_ensure(sae_ctx* c) {
   return SAE_OK;
 }
 
-// the update of one batch's mask Zt [n_p][Kp] (n_p a multiple of CO_BM): the K split of coact.h's header
+// the K split of coact.h's header: enough slices of the Kp / CO_BK steps that `tiles` output tiles fill CO_MIN_WGS workgroups, `per` steps each
+struct KSplit { int ksplit, per; };
+static KSplit coact_ksplit(int64_t tiles, int64_t Kp) {
+  const int nsteps = (int)(Kp / CO_BK);
+  const int want = (int)std::min<int64_t>(std::max<int64_t>((CO_MIN_WGS + tiles - 1) / tiles, 1), nsteps);
+  const int per = (nsteps + want - 1) / want;
+  return {(nsteps + per - 1) / per, per};
+}
+
+// the update of one batch's mask Zt [n_p][Kp] (n_p a multiple of CO_BM)
 static int coact_launch_update(sae_ctx* c, const int8_t* zt, int64_t Kp, int n_p, int n, int32_t* counts, hipStream_t s) {
   const int nt = n_p / CO_BM;
   const int64_t ntiles = (int64_t)nt * (nt + 1) / 2;
-  const int nsteps = (int)(Kp / CO_BK);
-  int ksplit = (int)std::min<int64_t>(std::max<int64_t>((CO_MIN_WGS + ntiles - 1) / ntiles, 1), nsteps);
-  const int per = (nsteps + ksplit - 1) / ksplit;
-  ksplit = (nsteps + per - 1) / per;
-  const dim3 grid((unsigned)nt, (unsigned)nt, (unsigned)ksplit);
+  const KSplit ks = coact_ksplit(ntiles, Kp);
+  const dim3 grid((unsigned)nt, (unsigned)nt, (unsigned)ks.ksplit);
   ev_begin(c, KID_COACT_UPDATE, s);
-  if (ksplit > 1) hipLaunchKernelGGL(coact_update_kernel<true>, grid, dim3(256), 0, s, zt, Kp, n, per, counts);
-  else hipLaunchKernelGGL(coact_update_kernel<false>, grid, dim3(256), 0, s, zt, Kp, n, per, counts);
+  if (ks.ksplit > 1) hipLaunchKernelGGL(coact_update_kernel<true>, grid, dim3(256), 0, s, zt, Kp, n, ks.per, counts);
+  else hipLaunchKernelGGL(coact_update_kernel<false>, grid, dim3(256), 0, s, zt, Kp, n, ks.per, counts);
   ev_end(c, KID_COACT_UPDATE, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-template <typename T>
-static int coact_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int64_t Kp, hipStream_t s) {
-  const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
-  ev_begin(c, KID_COACT_PACK, s);
-  hipLaunchKernelGGL(coact_pack_l1_kernel, dim3((unsigned)(Kp / 64), (unsigned)(c->n_p / 64)), dim3(256), 0, s, (const unsigned short*)c->c,
-                     (int64_t)c->n_p, c->n, M, Trows, lengths, c->co_zt, Kp);
-  ev_end(c, KID_COACT_PACK, s);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }
@@ -3435,32 +3466,34 @@ static int coact_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int
 // the batch's activity mask into c->co_zt: the encoder as encode() runs it, then the mask pack (sae_coact_files, sae_label_files)
 static int coact_encode_pack(sae_ctx* c, const void* x, int64_t M, int Trows, int x_dtype, const int32_t* lengths, int64_t Kp, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (c->topk) {
-    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the selection scattered into the zeroed mask
-    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
-    ev_begin(c, KID_COACT_PACK, s);
-    const hipError_t memset_zt = hipMemsetAsync(c->co_zt, 0, (size_t)((int64_t)c->n_p * Kp), s);
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
+  ev_begin(c, KID_COACT_PACK, s);
+  hipError_t memset_zt = hipSuccess;
+  if (c->topk) {                            // the selection scattered into the zeroed mask
+    memset_zt = hipMemsetAsync(c->co_zt, 0, (size_t)((int64_t)c->n_p * Kp), s);
     if (memset_zt == hipSuccess)
       hipLaunchKernelGGL(coact_pack_topk_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
                          c->k, M, Trows, lengths, c->n, c->co_zt, Kp);
-    ev_end(c, KID_COACT_PACK, s);           // (the bracket closes whatever the memset answered)
-    HIP_TRY(memset_zt);
-    HIP_TRY(hipGetLastError());
-    return SAE_OK;
+  } else {
+    hipLaunchKernelGGL(coact_pack_l1_kernel, dim3((unsigned)(Kp / 64), (unsigned)(c->n_p / 64)), dim3(256), 0, s, (const unsigned short*)c->c,
+                       (int64_t)c->n_p, c->n, M, Trows, lengths, c->co_zt, Kp);
   }
-  return with_x_type(x_dtype, x, [&](auto* xt) { return coact_l1_impl(c, xt, M, Trows, lengths, Kp, s); });
+  ev_end(c, KID_COACT_PACK, s);             // (the bracket closes whatever the memset answered)
+  HIP_TRY(memset_zt);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
 }
 
 extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
                                int flags, int32_t* counts, void* stream) {
   int64_t M;
   if (int rc = file_pass_begin(kCoactPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if ((reinterpret_cast<uintptr_t>(counts) & 3) != 0) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
+  if (misaligned(counts, 4)) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
   if (int rc = coact_ensure(c)) return rc;
   const int64_t Kp = round_up(M, CO_BK);
   if (int rc = coact_encode_pack(c, x, M, (int)rows_per_file, x_dtype, lengths, Kp, stream)) return rc;
   if (int rc = coact_launch_update(c, c->co_zt, Kp, c->n_p, c->n, counts, (hipStream_t)stream)) return rc;
-  c->last_call = LAST_COACT;
+  file_pass_end(kCoactPass, c);
   return SAE_OK;
 }
 
@@ -3480,7 +3513,6 @@ extern "C" int sae_coact_neighbor_keys(const int32_t* counts, int64_t n, int64_t
 // of a block of rows of A in either orientation
 static_assert(SAE_LABEL_F1 == LB_F1 && SAE_LABEL_PRECISION == LB_PRECISION && SAE_LABEL_RECALL == LB_RECALL && SAE_LABEL_COUNT == LB_COUNT &&
               SAE_LABEL_MAX_CLASSES == LB_MAX_CLASSES && SAE_LABEL_MAX_SLOTS == LB_MAX_SLOTS, "freud_sae.h and labels.h disagree");
-static const FilePassKind kLabelPass = {"sae_label_files", "count labels in a bf16 context", "label", 0};
 
 static int label_ensure(sae_ctx* c, int C_p) {
   if (C_p <= c->lb_rows) return SAE_OK;
@@ -3499,7 +3531,7 @@ extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64
   if (!labels || !label_count) return fail(SAE_ERR_INVALID, "null argument");
   if (n_slots < 1 || n_slots > SAE_LABEL_MAX_SLOTS) return fail(SAE_ERR_INVALID, "n_slots=%d outside [1, %d]", n_slots, SAE_LABEL_MAX_SLOTS);
   if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%d outside [1, %d]", n_classes, SAE_LABEL_MAX_CLASSES);
-  if ((reinterpret_cast<uintptr_t>(counts) & 3) != 0 || (reinterpret_cast<uintptr_t>(label_count) & 7) != 0)
+  if (misaligned(counts, 4) || misaligned(label_count, 8))
     return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned and label_count 8-byte aligned");
   if (int rc = file_pass_begin(kLabelPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   const int C_p = (int)round_up(n_classes + 1, CO_BM);
@@ -3523,17 +3555,14 @@ extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64
 
   // the K split of coact.h's header over the rectangle's tiles
   const int ntr = C_p / CO_BM, ntc = c->n_p / CO_BM;
-  const int nsteps = (int)(Kp / CO_BK);
-  int ksplit = (int)std::min<int64_t>(std::max<int64_t>((CO_MIN_WGS + ntr * ntc - 1) / (ntr * ntc), 1), nsteps);
-  const int per = (nsteps + ksplit - 1) / ksplit;
-  ksplit = (nsteps + per - 1) / per;
-  const dim3 grid((unsigned)ntc, (unsigned)ntr, (unsigned)ksplit);
+  const KSplit ks = coact_ksplit(ntr * ntc, Kp);
+  const dim3 grid((unsigned)ntc, (unsigned)ntr, (unsigned)ks.ksplit);
   ev_begin(c, KID_LABEL_UPDATE, s);
-  if (ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, per, counts);
-  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, per, counts);
+  if (ks.ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, ks.per, counts);
+  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, ks.per, counts);
   ev_end(c, KID_LABEL_UPDATE, s);
   HIP_TRY(hipGetLastError());
-  c->last_call = LAST_LABELS;
+  file_pass_end(kLabelPass, c);
   return SAE_OK;
 }
 
@@ -3557,7 +3586,6 @@ extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count,
 // ---- activation histograms (hist.h): per latent the histogram of its value on every counted frame and of every file's maximum,
 // and the frame histogram of a few chosen latents split by label
 static_assert(SAE_HIST_MAX_BINS == HB_MAX_BINS && SAE_HIST_MAX_SEL == HIST_MAX_SEL, "freud_sae.h, hist_bins.h and hist.h disagree");
-static const FilePassKind kHistPass = {"sae_hist_files", "build the histograms in a bf16 context", "histogram", 0};
 
 static int hist_ensure(sae_ctx* c, int64_t n_files) {
   if (!c->topk || n_files <= c->hs_files) return SAE_OK;
@@ -3569,7 +3597,7 @@ static int hist_ensure(sae_ctx* c, int64_t n_files) {
   return SAE_OK;
 }
 
-// the stored latent of launch_encoder binned by hist_l1_kernel.  Chunks of whole files: the fewest files per chunk that still give
+// the stored latent of file_pass_encode binned by hist_l1_kernel.  Chunks of whole files: the fewest files per chunk that still give
 // HIST_MIN_WGS workgroups (every chunk flushes its non-empty bins with global adds, so fewer chunks are cheaper).  Columns per
 // workgroup: 256 while the counters fit 48 KiB of LDS (O P <= 96), else 128.
 constexpr int HIST_MIN_WGS = 1024;
@@ -3583,12 +3611,6 @@ static void hist_launch_l1(sae_ctx* c, int64_t n_files, int Trows, const int* le
   const int64_t chunks = (n_files + fpc - 1) / fpc;
   hipLaunchKernelGGL(hist_l1_kernel, dim3((unsigned)colblocks, (unsigned)chunks), dim3(nt), (size_t)((reg + 1) / 2) * nt * 4, s,
                      (const unsigned short*)c->c, (int64_t)c->n_p, c->n, n_files, Trows, lengths, fpc, sp, frame_hist, file_max_hist);
-}
-
-template <typename T>
-static int hist_l1_encode(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
-  const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  return launch_encoder<T>(c, g, M, s);
 }
 
 extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
@@ -3608,18 +3630,12 @@ extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_
     if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%d outside [1, %d]", n_classes, SAE_LABEL_MAX_CLASSES);
   }
   for (const void* p : {(const void*)frame_hist, (const void*)file_max_hist, (const void*)n_frames, (const void*)label_hist, (const void*)label_count})
-    if ((reinterpret_cast<uintptr_t>(p) & 7) != 0) return fail(SAE_ERR_INVALID, "the histogram arrays must be 8-byte aligned");
+    if (misaligned(p, 8)) return fail(SAE_ERR_INVALID, "the histogram arrays must be 8-byte aligned");
   if (int rc = file_pass_begin(kHistPass, c, x, frame_hist, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   if (int rc = hist_ensure(c, n_files)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
-
-  // the encoder as encode() runs it: the stored L1 latent, or the eval forward's top-k selection (the k of encode())
-  if (c->topk) {
-    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
-  } else {
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return hist_l1_encode(c, xt, M, s); })) return rc;
-  }
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
 
   ev_begin(c, KID_HIST, s);
   hipError_t memset_fmax = hipSuccess;
@@ -3649,7 +3665,7 @@ extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_
   ev_end(c, KID_HIST, s);                   // (the bracket closes whatever the memset answered)
   HIP_TRY(memset_fmax);
   HIP_TRY(hipGetLastError());
-  c->last_call = LAST_HIST;
+  file_pass_end(kHistPass, c);
   return SAE_OK;
 }
 
@@ -3668,7 +3684,7 @@ extern "C" int sae_dict_pack(const float* w, int64_t n, int64_t d, int64_t dir_s
   if (!dict_dims_ok(n, d)) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24] or d=%lld outside [1, %d]", (long long)n, (long long)d, DM_MAX_D);
   if (dir_stride < 1 || elem_stride < 1) return fail(SAE_ERR_INVALID, "dir_stride=%lld, elem_stride=%lld: strides are positive element counts", (long long)dir_stride, (long long)elem_stride);
   if (side != DM_LEFT && side != DM_RIGHT) return fail(SAE_ERR_INVALID, "side=%d is neither 0 nor 1", side);
-  if ((reinterpret_cast<uintptr_t>(packed) & 15) != 0 || (reinterpret_cast<uintptr_t>(w) & 3) != 0 || (reinterpret_cast<uintptr_t>(norms) & 3) != 0)
+  if (misaligned(packed, 16) || misaligned(w, 4) || misaligned(norms, 4))
     return fail(SAE_ERR_INVALID, "the packed operand must be 16-byte aligned, the weights and norms 4-byte aligned");
   const int64_t rows_p = dm_rows_p(n);
   hipStream_t s = (hipStream_t)stream;
@@ -3690,7 +3706,7 @@ extern "C" int sae_dict_sim_keys(const void* packed_a, int64_t n_a, const void* 
   if (self_mode && n_a != n_b) return fail(SAE_ERR_INVALID, "self mode with n_a=%lld != n_b=%lld", (long long)n_a, (long long)n_b);
   if (n_rows < 1 || row0 < 0 || row0 + n_rows > n_a)
     return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)n_a);
-  if (((reinterpret_cast<uintptr_t>(packed_a) | reinterpret_cast<uintptr_t>(packed_b)) & 15) != 0 || (reinterpret_cast<uintptr_t>(keys) & 7) != 0)
+  if (misaligned(packed_a, 16) || misaligned(packed_b, 16) || misaligned(keys, 8))
     return fail(SAE_ERR_INVALID, "the packed operands must be 16-byte aligned and the keys 8-byte aligned");
   const int64_t ld = dm_ld(d);
   const int64_t row_base = row0 / DM_ROW_ALIGN * DM_ROW_ALIGN;                   // (the cover stays inside dm_rows_p(n_a))
@@ -3715,35 +3731,15 @@ extern "C" int sae_dict_sim_keys(const void* packed_a, int64_t n_a, const void* 
 // ---- feature manipulation (manip.h): one encode, one decode, then a rank-one term per edit and variant
 static_assert(SAE_MANIP_SCALE == SM_SCALE && SAE_MANIP_SET == SM_SET && SAE_MANIP_MAX_EDITS == SM_MAX_EDITS &&
               SAE_MANIP_MAX_VARIANTS == SM_MAX_VARIANTS, "freud_sae.h and manip.h disagree");
-static const FilePassKind kManipPass = {"sae_manipulate_files", "manipulate in a bf16 context", "manipulation", 0};
-
-// L1 standard decode: sae_decode's GEMM on the forward's own padded bf16 latent (no pad_latent copy), x_hat = c W^T with the
-// bf16 copy of the current W -- settled and cast exactly as sae_decode does, so the two agree to the bit
-static int manip_decode_l1(sae_ctx* c, int64_t M, float* x_hat, hipStream_t s) {
-  const int d_p = c->d_p, n_p = c->n_p;
-  settle_weights(c, s);
-  const int64_t n8 = c->nW / 8;
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P, c->Wb, n8);
-  GemmArgs g{};
-  g.A0 = c->c; g.lda = n_p; g.B0 = c->Wb; g.ldb = n_p;
-  g.nbm = (int)(c->last_M_p / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
-  EpiStoreF32 e{};
-  e.out = x_hat; e.M = M; e.d = c->d; e.bias = nullptr;
-  return launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-}
 
 static void manip_decode_topk(sae_ctx* c, int64_t M, float* x_hat, hipStream_t s) {
   const float* bd = c->P + 2 * c->nW + c->n_p;
   const dim3 grid((unsigned)((M + 3) / 4));
-  auto launch = [&](auto np_tag) {
+  with_np(c->d_p, [&](auto np_tag) {
     constexpr int NP = decltype(np_tag)::value;
     hipLaunchKernelGGL(manip_topk_decode_kernel<NP>, grid, dim3(256), 0, s, c->top_vals, c->top_idx, c->k, c->Wd_b, bd, x_hat, M, c->d,
                        c->d_p, c->n_p);
-  };
-  if (c->d_p == 384) launch(std::integral_constant<int, 3>{});
-  else if (c->d_p == 768) launch(std::integral_constant<int, 6>{});
-  else if (c->d_p == 1280) launch(std::integral_constant<int, 10>{});
-  else launch(std::integral_constant<int, 0>{});
+  });
 }
 
 extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* latents,
@@ -3779,7 +3775,7 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
   ev_begin(c, KID_MANIP_DECODE, s);
   int rc = SAE_OK;
   if (c->topk) manip_decode_topk(c, M, standard, s);
-  else rc = manip_decode_l1(c, M, standard, s);
+  else rc = decode_l1_latent(c, c->c, c->last_M_p / 128, M, standard, s);    // (the forward's own padded latent: no pad_latent copy)
   ev_end(c, KID_MANIP_DECODE, s);
   if (rc) return rc;
 
@@ -3797,7 +3793,7 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
 
   ev_begin(c, KID_MANIP_APPLY, s);
   {
-    const bool vec = d % 4 == 0 && ((reinterpret_cast<uintptr_t>(standard) | reinterpret_cast<uintptr_t>(manipulated)) & 15) == 0;
+    const bool vec = d % 4 == 0 && !misaligned(standard, 16) && !misaligned(manipulated, 16);
     const int vw = vec ? 4 : 1;
     const int nslab = (d + 32 * vw - 1) / (32 * vw);
     // groups of 8 half waves, a multiple of the slabs: every frame x slab once, at most ~4096 groups striding over the frames
@@ -3814,7 +3810,6 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
 // ---- reconstruction report (recon.h): the residual of encode() -> decode() per frame, its sums per file and per model dimension,
 // and per latent the attribution sums P_j = sum a_j (r . w_j), sum a_j^2 and |w_j|^2
 static_assert(SAE_RECON_UNFUSED == 1, "freud_sae.h and engine.hip disagree");
-static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruction report in a bf16 context", "reconstruction", SAE_RECON_UNFUSED};
 
 struct ReconScratch {           // c->rc_buf carved up (floats)
   float *xr, *slab_p, *slab_q, *rowpart, *dimpart, *p;
@@ -3869,29 +3864,20 @@ static void recon_launch_fold(sae_ctx* c, const ReconScratch& sc, int nrb_lat, i
                      nb_dim);
 }
 
-// L1: the stored latent of launch_encoder; x_hat by sae_decode's GEMM on that latent (settled weights, their bf16 cast: bit for bit
-// manip_decode_l1); the residual sweep writes r_b into c->dxh (free in a file pass) and zeroes the latent rows that do not count;
+// L1: the stored latent of file_pass_l1_encode; x_hat by decode_l1_latent on that latent; the residual sweep writes r_b into c->dxh
+// (free in a file pass) and zeroes the latent rows that do not count;
 // the attribution is the backward's dpre-shaped GEMM r_b [M_p][d_p] x Wt [n_p][d_p] with EpiAttr: in the streaming form where
 // launch_gemm would take it (gemm_streams), in the tile forms elsewhere and with `unfused` (SAE_RECON_UNFUSED).
 template <typename T>
 static int recon_l1_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
                          double* file_out, float* resid, bool unfused, hipStream_t s) {
-  const int d_p = c->d_p, n_p = c->n_p;
-  const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  const int64_t Mp = (int64_t)g.nbm * 128;
-  if (int rc = launch_encoder<T>(c, g, M, s)) return rc;
+  const int n_p = c->n_p;
+  int64_t Mp;
+  if (int rc = file_pass_l1_encode(c, x, M, s, nullptr, &Mp)) return rc;
   const ReconScratch sc = recon_scratch(c);
 
   ev_begin(c, KID_RECON_DECODE, s);
-  settle_weights(c, s);
-  const int64_t n8 = c->nW / 8;
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P, c->Wb, n8);
-  GemmArgs gd{};
-  gd.A0 = c->c; gd.lda = n_p; gd.B0 = c->Wb; gd.ldb = n_p;
-  gd.nbm = (int)(round_up(M, c->row_pad) / 128); gd.nbn = d_p / 128; gd.ktiles0 = gd.ktiles = n_p / 64; gd.splits = 1;   // (sae_decode's M_p)
-  EpiStoreF32 ed{};
-  ed.out = sc.xr; ed.M = M; ed.d = c->d; ed.bias = nullptr;
-  int rc = launch_gemm<OP_ROW, OP_ROW>(gd, ed, s);
+  int rc = decode_l1_latent(c, c->c, round_up(M, c->row_pad) / 128, M, sc.xr, s);      // (sae_decode's M_p)
   ev_end(c, KID_RECON_DECODE, s);
   if (rc) return rc;
 
@@ -3935,15 +3921,11 @@ static int recon_topk_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, i
   ev_begin(c, KID_RECON_ATTR, s);
   {
     const dim3 grid((unsigned)((M + 3) / 4));
-    auto launch = [&](auto np_tag) {
+    with_np(c->d_p, [&](auto np_tag) {
       constexpr int NP = decltype(np_tag)::value;
       hipLaunchKernelGGL(recon_topk_attr_kernel<NP>, grid, dim3(256), 0, s, sc.xr, c->top_vals, c->top_idx, c->k, c->Wd_b, sc.p, M, c->d,
                          c->d_p, c->n_p);
-    };
-    if (c->d_p == 384) launch(std::integral_constant<int, 3>{});
-    else if (c->d_p == 768) launch(std::integral_constant<int, 6>{});
-    else if (c->d_p == 1280) launch(std::integral_constant<int, 10>{});
-    else launch(std::integral_constant<int, 0>{});
+    });
   }
   const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
   hipLaunchKernelGGL(recon_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
@@ -3959,7 +3941,7 @@ extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64
   int64_t M;
   if (!file_out) return fail(SAE_ERR_INVALID, "null argument");
   if (int rc = file_pass_begin(kReconPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (((reinterpret_cast<uintptr_t>(block) | reinterpret_cast<uintptr_t>(file_out)) & 7) != 0 || (reinterpret_cast<uintptr_t>(resid) & 3) != 0)
+  if (misaligned(block, 8) || misaligned(file_out, 8) || misaligned(resid, 4))
     return fail(SAE_ERR_INVALID, "the report block and file_out must be 8-byte aligned, resid 4-byte aligned");
   if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_recon_files: the TopK decode serves d_model <= 1536");
   if ((c->max_rows_p / STATS_RB) * (int64_t)c->n_p >= ((int64_t)1 << 31))
@@ -3969,8 +3951,8 @@ extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64
   const int Trows = (int)rows_per_file;
   const ReconOut o = recon_out(block, c->n, c->d);
   if (c->topk) {
-    // the eval forward (encoder GEMM + top-k selection, the k of encode()), then the sparse decode and the attribution of the selection
-    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
+    // the sparse decode and the attribution of encode()'s selection
+    if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
     if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_topk_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, s); }))
       return rc;
   } else {
@@ -3978,22 +3960,15 @@ extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64
     if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_l1_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, unfused, s); }))
       return rc;
   }
-  c->last_call = LAST_RECON;
+  file_pass_end(kReconPass, c);
   return SAE_OK;
 }
 
 // ---- feature collection (collect.h): every row's K slots of the latent encode() returns, in the reference's indexed form
 static_assert(SAE_COLLECT_IDX32 == CL_IDX32 && SAE_COLLECT_MAX_K == CL_MAX_K, "freud_sae.h and collect.h disagree");
-static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32};
 // Grids of what is resident at once, the kernels stride over the rest of the rows: collect_l1_kernel holds 98 VGPRs (4 waves per SIMD:
 // 4 workgroups of 256 threads per CU), collect_topk_kernel 32 KiB of LDS (5 per CU); 256 CUs
 constexpr int COLLECT_L1_WGS = 256 * 4, COLLECT_TOPK_WGS = 256 * 5;
-
-template <typename T>
-static int collect_l1_encode(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
-  const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  return launch_encoder<T>(c, g, M, s);
-}
 
 template <typename IdxT>
 static void collect_launch(sae_ctx* c, int64_t M, int K, float* values, IdxT* indices, int64_t* stats, hipStream_t s) {
@@ -4012,26 +3987,19 @@ extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int
   if (!indices || !stats) return fail(SAE_ERR_INVALID, "null argument");
   if (int rc = file_pass_begin(kCollectPass, c, x, values, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   const bool idx32 = (flags & SAE_COLLECT_IDX32) != 0;
-  if ((reinterpret_cast<uintptr_t>(stats) & 7) != 0 || (reinterpret_cast<uintptr_t>(values) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(indices) & (idx32 ? 3 : 7)) != 0)
+  if (misaligned(stats, 8) || misaligned(values, 4) || misaligned(indices, idx32 ? 4 : 8))
     return fail(SAE_ERR_INVALID, "stats must be 8-byte aligned, values 4-byte aligned, indices aligned to their type");
   const int k_max = c->topk ? c->k : std::min(c->n, (int)SAE_COLLECT_MAX_K);
   if (K < 1 || K > k_max)
     return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max, c->topk ? "the context's k" : "min(n_dict, SAE_COLLECT_MAX_K)");
   hipStream_t s = (hipStream_t)stream;
-
-  // the encoder as encode() runs it: the stored L1 latent, or the eval forward's top-k selection (the k of encode())
-  if (c->topk) {
-    if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
-  } else {
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return collect_l1_encode(c, xt, M, s); })) return rc;
-  }
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
   ev_begin(c, KID_COLLECT, s);
   if (idx32) collect_launch(c, M, K, values, (int32_t*)indices, stats, s);
   else collect_launch(c, M, K, values, (int64_t*)indices, stats, s);
   ev_end(c, KID_COLLECT, s);
   HIP_TRY(hipGetLastError());
-  c->last_call = LAST_COLLECT;
+  file_pass_end(kCollectPass, c);
   return SAE_OK;
 }
 

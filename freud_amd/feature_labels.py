@@ -41,7 +41,7 @@ import torch
 from . import coactivation as CO
 from . import engine as E
 from .engine import FILE_TOP_MAX, LABEL_MAX_CLASSES, LABEL_MAX_SLOTS, LABEL_MEASURES
-from .file_pass import FilePass, keep_rng
+from .file_pass import FilePass, is_raw, keep_rng
 
 MAX_FRAMES = 2 ** 31 - 1          # int32 counts
 _SCAN_ELEMS = 1 << 24             # label ids checked per slice of a (possibly memory-mapped) label array
@@ -133,7 +133,7 @@ def _check_args(sae, data_path, layer_name, subset_size, file_labels, frame_labe
     """Every argument rule that needs no SAE and no device -> (labels as [n_files, S] or [n_files, T, S], per_file, n_classes, n_top)."""
     from .loader import MemoryMappedActivationsDataset
 
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         raise ValueError("feature labels need an SAE (labels for raw activations are not provided)")
     n_top = int(n_top)
     if n_top < 1 or n_top > FILE_TOP_MAX:

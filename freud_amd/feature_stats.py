@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .file_pass import FilePass, keep_rng
+from .file_pass import FilePass, is_raw, keep_rng
 
 _FIELDS = ("fire_count", "act_sum", "act_sq_sum", "act_max", "l0_hist")
 
@@ -101,7 +101,7 @@ def feature_stats(sae, data_path: str, layer_name: str, *, lengths=None, subset_
     picks the fused L1 path where it can); unfused: force the stored-latent L1 path (tests, benchmarks)."""
     from . import engine as E
 
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         raise ValueError("feature statistics need an SAE (raw-activation statistics are not provided)")
     fp = FilePass(sae, data_path, layer_name, what="feature statistics", lengths=lengths, subset_size=subset_size,
                   batch_files=batch_files)

@@ -25,9 +25,14 @@ def check_lengths(lengths, n_total: int, T: int) -> Optional[np.ndarray]:
     return np.minimum(a.astype(np.int64), T).astype(np.int32)
 
 
+def is_raw(sae) -> bool:
+    """Whether `sae` asks for raw mode: None, or the command lines' "none"."""
+    return sae is None or (isinstance(sae, str) and sae.lower() == "none")
+
+
 def resolve_sae(sae):
     """None (raw mode) | checkpoint path | freud_amd.models instance | SaeEngine -> (model or None, engine or None)."""
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         return None, None
     if isinstance(sae, str):
         from .models import init_sae_from_checkpoint

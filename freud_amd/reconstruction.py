@@ -31,7 +31,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .file_pass import FilePass, keep_rng
+from .file_pass import FilePass, is_raw, keep_rng
 
 _FIELDS = ("attr_sum", "act_sq_sum", "dec_norm_sq", "sum_x", "sum_x_sq", "sum_r_sq", "file_sse", "file_energy")
 
@@ -146,7 +146,7 @@ def reconstruction_report(sae, data_path: str, layer_name: str, *, lengths=None,
     SAE_RECON_UNFUSED (keeps the L1 attribution GEMM off the streaming kernel)."""
     from . import engine as E
 
-    if sae is None or (isinstance(sae, str) and sae.lower() == "none"):
+    if is_raw(sae):
         raise ValueError("a reconstruction report needs an SAE (there is nothing to reconstruct raw activations with)")
     fp = FilePass(sae, data_path, layer_name, what="reconstruction report", lengths=lengths, subset_size=subset_size,
                   batch_files=batch_files)
