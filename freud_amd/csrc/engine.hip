@@ -41,6 +41,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "labels.h"
 #include "hist.h"
 #include "collect.h"
+#include "findex.h"
 #include "manip.h"
 #include "dict_match.h"
 #include "recon.h"
@@ -4000,6 +4001,107 @@ extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int
   ev_end(c, KID_COLLECT, s);
   HIP_TRY(hipGetLastError());
   file_pass_end(kCollectPass, c);
+  return SAE_OK;
+}
+
+// ---- feature index (findex.h): the latent-major postings of an indexed store; context-free, like sae_search_merge
+static_assert(SAE_FINDEX_IDX32 == FI_IDX32 && SAE_FINDEX_NSTATS == FI_NSTATS && SAE_COLLECT_MAX_K == FI_MAX_K, "freud_sae.h and findex.h disagree");
+
+static int64_t findex_blocks(int64_t rows) { return (rows + FI_ROWS - 1) / FI_ROWS; }
+
+static int findex_batch_check(const void* values, const void* indices, int64_t rows, int K, int flags, int64_t n_dict) {
+  if (!values || !indices) return fail(SAE_ERR_INVALID, "null argument");
+  if (flags & ~SAE_FINDEX_IDX32) return fail(SAE_ERR_INVALID, "unknown feature-index flags 0x%x", flags);
+  if (rows < 1 || findex_blocks(rows) > 0x7FFFFFFFll) return fail(SAE_ERR_INVALID, "rows=%lld outside [1, 2^31 * %d)", (long long)rows, FI_ROWS);
+  if (K < 1 || K > FI_MAX_K) return fail(SAE_ERR_INVALID, "K=%d outside [1, %d]", K, FI_MAX_K);
+  if (n_dict < 1 || n_dict > FI_MAX_N) return fail(SAE_ERR_INVALID, "n_dict=%lld outside [1, 2^30]", (long long)n_dict);
+  if (misaligned(values, 4) || misaligned(indices, (flags & SAE_FINDEX_IDX32) ? 4 : 8))
+    return fail(SAE_ERR_INVALID, "values must be 4-byte aligned, indices aligned to their type");
+  return SAE_OK;
+}
+
+extern "C" int64_t sae_findex_workspace_bytes(int64_t max_rows, int64_t n_range) {
+  if (max_rows < 1 || n_range < 1 || n_range > FI_MAX_N) return -1;
+  return findex_blocks(max_rows) * n_range * 4;
+}
+
+template <typename IdxT>
+static void findex_count_launch(const uint32_t* vb, const IdxT* idx, int64_t rows, int K, int64_t n_dict, int j0, int j1,
+                                unsigned long long* totals, unsigned int* counts, unsigned long long* stats, hipStream_t s) {
+  const dim3 grid((unsigned)findex_blocks(rows), (unsigned)((j1 - j0 + FI_SEG - 1) / FI_SEG));
+  const size_t lds = (size_t)std::min(j1 - j0, FI_SEG) * 4;
+  if (K <= 64) hipLaunchKernelGGL((fi_count_kernel<IdxT, true>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, totals, counts, stats);
+  else hipLaunchKernelGGL((fi_count_kernel<IdxT, false>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, totals, counts, stats);
+}
+
+template <typename IdxT>
+static void findex_fill_launch(const uint32_t* vb, const IdxT* idx, int64_t rows, int K, int64_t n_dict, int j0, int j1, uint64_t pos0,
+                               const unsigned int* block_off, uint32_t* positions, uint32_t* values, uint64_t capacity,
+                               unsigned long long* err, hipStream_t s) {
+  const dim3 grid((unsigned)findex_blocks(rows), (unsigned)((j1 - j0 + FI_SEG - 1) / FI_SEG));
+  const size_t lds = (size_t)std::min(j1 - j0, FI_SEG) * 4;
+  if (K <= 64)
+    hipLaunchKernelGGL((fi_fill_kernel<IdxT, true>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, (unsigned long long)pos0, block_off,
+                       positions, values, (unsigned long long)capacity, err);
+  else
+    hipLaunchKernelGGL((fi_fill_kernel<IdxT, false>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, (unsigned long long)pos0, block_off,
+                       positions, values, (unsigned long long)capacity, err);
+}
+
+extern "C" int sae_findex_count(const float* values, const void* indices, int64_t rows, int K, int flags, int64_t n_dict, int64_t* totals,
+                                int64_t* stats, void* stream) {
+  if (!totals || !stats) return fail(SAE_ERR_INVALID, "null argument");
+  if (int rc = findex_batch_check(values, indices, rows, K, flags, n_dict)) return rc;
+  if (misaligned(totals, 8) || misaligned(stats, 8)) return fail(SAE_ERR_INVALID, "totals and stats must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t* vb = reinterpret_cast<const uint32_t*>(values);
+  unsigned long long *tt = reinterpret_cast<unsigned long long*>(totals), *st = reinterpret_cast<unsigned long long*>(stats);
+  if (flags & SAE_FINDEX_IDX32) findex_count_launch(vb, (const int32_t*)indices, rows, K, n_dict, 0, (int)n_dict, tt, nullptr, st, s);
+  else findex_count_launch(vb, (const int64_t*)indices, rows, K, n_dict, 0, (int)n_dict, tt, nullptr, st, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_findex_fill(const float* values, const void* indices, int64_t rows, int K, int flags, int64_t n_dict, int64_t j0, int64_t j1,
+                               int64_t pos0, int64_t* cursor, int64_t out_base, uint32_t* positions_out, float* values_out,
+                               int64_t capacity, void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
+  if (!cursor || !positions_out || !values_out || !workspace || !err) return fail(SAE_ERR_INVALID, "null argument");
+  if (int rc = findex_batch_check(values, indices, rows, K, flags, n_dict)) return rc;
+  if (j0 < 0 || j1 <= j0 || j1 > n_dict) return fail(SAE_ERR_INVALID, "latent range [%lld, %lld) outside [0, %lld)", (long long)j0, (long long)j1, (long long)n_dict);
+  if (pos0 < 0 || pos0 + rows > 0x100000000ll) return fail(SAE_ERR_INVALID, "positions [%lld, %lld) do not fit 32 bits", (long long)pos0, (long long)(pos0 + rows));
+  if (out_base < 0 || capacity < 0 || capacity >= 0xFFFFFFFFll)
+    return fail(SAE_ERR_INVALID, "out_base=%lld, capacity=%lld: a range holds fewer than 2^32 - 1 slots", (long long)out_base, (long long)capacity);
+  if (workspace_bytes < sae_findex_workspace_bytes(rows, j1 - j0))
+    return fail(SAE_ERR_INVALID, "workspace of %lld bytes < sae_findex_workspace_bytes(%lld, %lld)", (long long)workspace_bytes, (long long)rows, (long long)(j1 - j0));
+  if (misaligned(cursor, 8) || misaligned(err, 8) || misaligned(workspace, 4) || misaligned(positions_out, 4) || misaligned(values_out, 4))
+    return fail(SAE_ERR_INVALID, "cursor and err must be 8-byte aligned, workspace and the outputs 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t* vb = reinterpret_cast<const uint32_t*>(values);
+  unsigned int* counts = reinterpret_cast<unsigned int*>(workspace);
+  unsigned long long* er = reinterpret_cast<unsigned long long*>(err);
+  uint32_t* vout = reinterpret_cast<uint32_t*>(values_out);
+  const bool i32 = (flags & SAE_FINDEX_IDX32) != 0;
+  if (i32) findex_count_launch(vb, (const int32_t*)indices, rows, K, n_dict, (int)j0, (int)j1, nullptr, counts, nullptr, s);
+  else findex_count_launch(vb, (const int64_t*)indices, rows, K, n_dict, (int)j0, (int)j1, nullptr, counts, nullptr, s);
+  hipLaunchKernelGGL(fi_scan_kernel, dim3((unsigned)((j1 - j0 + 63) / 64)), dim3(1024), 0, s, counts, (int)findex_blocks(rows), (int)j0, (int)j1,
+                     reinterpret_cast<long long*>(cursor), (long long)out_base);
+  if (i32) findex_fill_launch(vb, (const int32_t*)indices, rows, K, n_dict, (int)j0, (int)j1, (uint64_t)pos0, counts, positions_out, vout, (uint64_t)capacity, er, s);
+  else findex_fill_launch(vb, (const int64_t*)indices, rows, K, n_dict, (int)j0, (int)j1, (uint64_t)pos0, counts, positions_out, vout, (uint64_t)capacity, er, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_findex_verify(const int64_t* starts, int64_t n_dict, int64_t j0, int64_t j1, int64_t out_base, const uint32_t* positions,
+                                 int64_t capacity, int64_t limit, int64_t* err, void* stream) {
+  if (!starts || !positions || !err) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_dict < 1 || n_dict > FI_MAX_N || j0 < 0 || j1 <= j0 || j1 > n_dict)
+    return fail(SAE_ERR_INVALID, "latent range [%lld, %lld) outside [0, n_dict=%lld)", (long long)j0, (long long)j1, (long long)n_dict);
+  if (limit < 1 || limit > 0x100000000ll || out_base < 0 || capacity < 0) return fail(SAE_ERR_INVALID, "limit=%lld outside [1, 2^32], or out_base or capacity < 0", (long long)limit);
+  if (misaligned(starts, 8) || misaligned(err, 8) || misaligned(positions, 4)) return fail(SAE_ERR_INVALID, "starts and err must be 8-byte aligned");
+  hipLaunchKernelGGL(fi_verify_kernel, dim3((unsigned)((j1 - j0 + FI_VERIFY_WAVES - 1) / FI_VERIFY_WAVES)), dim3(64 * FI_VERIFY_WAVES), 0,
+                     (hipStream_t)stream, reinterpret_cast<const long long*>(starts), (int)j0, (int)j1, (long long)out_base, positions,
+                     (long long)capacity, (unsigned long long)limit, reinterpret_cast<unsigned long long*>(err));
+  HIP_TRY(hipGetLastError());
   return SAE_OK;
 }
 

@@ -136,6 +136,10 @@ def load() -> C.CDLL:
                                            vp, vp, vp, vp]),
         "sae_recon_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
         "sae_collect_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "sae_findex_workspace_bytes": (i64, [i64, i64]),
+        "sae_findex_count": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, i64, vp, vp, vp]),
+        "sae_findex_fill": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, i64, i64, i64, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp]),
+        "sae_findex_verify": (C.c_int, [vp, i64, i64, i64, i64, vp, i64, i64, vp, vp]),
         "sae_profile": (C.c_int, [vp, C.c_int]),
         "sae_profile_period": (C.c_int, [vp, C.c_int]),
         "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
@@ -182,6 +186,7 @@ EXPORTED_SYMBOLS = [
     "sae_manipulate_files",
     "sae_recon_files",
     "sae_collect_files",
+    "sae_findex_workspace_bytes", "sae_findex_count", "sae_findex_fill", "sae_findex_verify",
 ]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
@@ -196,6 +201,10 @@ HIST_MAX_REGULAR = 128                                              # freud_amd/
 HIST_MAX_SEL = 64                                                   # include/freud_sae.h: SAE_HIST_MAX_SEL
 COLLECT_IDX32 = 1                                                   # include/freud_sae.h: SAE_COLLECT_IDX32
 COLLECT_MAX_K = 1024                                                # include/freud_sae.h: SAE_COLLECT_MAX_K
+FINDEX_IDX32 = 1                                                    # include/freud_sae.h: SAE_FINDEX_IDX32
+FINDEX_NSTATS = 8                                                   # include/freud_sae.h: SAE_FINDEX_NSTATS
+FINDEX_STAT_NAMES = ("slots", "zero_slots", "out_of_range", "posted")
+FINDEX_ROWS, FINDEX_SEGMENT = 128, 16384                            # freud_amd/csrc/findex.h: FI_ROWS, FI_SEG (rows per block, latents per LDS segment)
 DICT_LEFT, DICT_RIGHT = 0, 1                                        # include/freud_sae.h: SAE_DICT_LEFT / SAE_DICT_RIGHT
 DICT_MAX_D = 8192                                                   # include/freud_sae.h: SAE_DICT_MAX_D
 DICT_MAX_N = 1 << 24
@@ -837,6 +846,77 @@ def search_merge(file_keys, aux, n_files: int, ncols: int, file0: int, n_top: in
     _check(load().sae_search_merge(C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if aux is not None else None,
                                    int(n_files), int(ncols), int(file0), int(n_top), int(flags), float(min_val), float(max_val),
                                    C.c_void_p(top_keys.data_ptr()), C.c_void_p(top_frames.data_ptr()), _stream_ptr(stream)))
+
+
+# -- feature index (include/freud_sae.h: sae_findex_*; freud_amd/feature_index.py) ---------------------------------------------------
+def _findex_dev(name: str, t, dtype, numel: int, exact: bool = False) -> None:
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and (t.numel() == numel if exact else t.numel() >= numel)):
+        raise EngineError(f"{name} must be a contiguous {dtype} CUDA tensor of {'' if exact else '>= '}{numel} elements")
+
+
+def _findex_batch(values, indices):
+    import torch
+    if not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.dim() == 2):
+        raise EngineError("values must be a contiguous float32 CUDA tensor [rows, K]")
+    if indices.dtype not in (torch.int32, torch.int64):
+        raise EngineError(f"indices must be int32 or int64, got {indices.dtype}")
+    if not (indices.is_cuda and indices.is_contiguous() and tuple(indices.shape) == tuple(values.shape) and indices.device == values.device):
+        raise EngineError(f"indices must be a contiguous CUDA tensor of the values' shape {tuple(values.shape)}")
+    rows, K = (int(v) for v in values.shape)
+    return rows, K, FINDEX_IDX32 if indices.dtype == torch.int32 else 0
+
+
+def findex_workspace_bytes(max_rows: int, n_range: int) -> int:
+    """Bytes of workspace that findex_fill needs for batches of at most max_rows rows and a range of n_range latents."""
+    nbytes = int(load().sae_findex_workspace_bytes(int(max_rows), int(n_range)))
+    if nbytes < 0:
+        raise EngineError(f"findex_workspace_bytes: max_rows={max_rows}, n_range={n_range} out of range")
+    return nbytes
+
+
+def findex_count(values, indices, n_dict: int, totals, stats, stream=None) -> None:
+    """Sweep 1 of the feature index: totals int64 [n_dict] += the batch's posted slots per latent, stats int64 [FINDEX_NSTATS] += the
+    tallies (FINDEX_STAT_NAMES)."""
+    import torch
+    rows, K, flags = _findex_batch(values, indices)
+    _findex_dev("totals", totals, torch.int64, int(n_dict), exact=True)
+    _findex_dev("stats", stats, torch.int64, FINDEX_NSTATS, exact=True)
+    _check(load().sae_findex_count(C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), rows, K, flags, int(n_dict),
+                                   C.c_void_p(totals.data_ptr()), C.c_void_p(stats.data_ptr()), _stream_ptr(stream)))
+
+
+def findex_fill(values, indices, n_dict: int, j0: int, j1: int, pos0: int, cursor, out_base: int, positions_out, values_out, workspace,
+                err, stream=None) -> None:
+    """Sweep 2: the batch's posted slots of the latents [j0, j1) written behind each list's cursor (int64 [n_dict], absolute, advanced
+    by the call) into positions_out (int32 holding uint32) / values_out (float32), whose element 0 is absolute slot out_base;
+    workspace: a uint8 tensor of >= findex_workspace_bytes(rows, j1 - j0); err int64 [2]."""
+    import torch
+    rows, K, flags = _findex_batch(values, indices)
+    _findex_dev("cursor", cursor, torch.int64, int(n_dict), exact=True)
+    _findex_dev("err", err, torch.int64, 2, exact=True)
+    if not (positions_out.is_cuda and positions_out.dtype == torch.int32 and positions_out.is_contiguous() and positions_out.dim() == 1):
+        raise EngineError("positions_out must be a contiguous 1-D int32 CUDA tensor (it holds the uint32 position words)")
+    _findex_dev("values_out", values_out, torch.float32, positions_out.numel(), exact=True)
+    need = findex_workspace_bytes(rows, int(j1) - int(j0)) if 0 <= int(j0) < int(j1) else 0
+    _findex_dev("workspace", workspace, torch.uint8, need)
+    _check(load().sae_findex_fill(C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), rows, K, flags, int(n_dict), int(j0), int(j1),
+                                  int(pos0), C.c_void_p(cursor.data_ptr()), int(out_base), C.c_void_p(positions_out.data_ptr()),
+                                  C.c_void_p(values_out.data_ptr()), int(positions_out.numel()), C.c_void_p(workspace.data_ptr()),
+                                  int(workspace.numel()), C.c_void_p(err.data_ptr()), _stream_ptr(stream)))
+
+
+def findex_verify(starts, j0: int, j1: int, out_base: int, positions, limit: int, err, stream=None) -> None:
+    """err[0] += the slots of the finished lists [j0, j1) (starts int64 [n_dict + 1], absolute; positions as findex_fill wrote them)
+    whose position is not strictly greater than its predecessor's in the list, or is >= limit."""
+    import torch
+    if not (starts.is_cuda and starts.dtype == torch.int64 and starts.is_contiguous() and starts.dim() == 1 and starts.numel() >= 2):
+        raise EngineError("starts must be a contiguous 1-D int64 CUDA tensor [n_dict + 1]")
+    _findex_dev("err", err, torch.int64, 2, exact=True)
+    if not (positions.is_cuda and positions.dtype == torch.int32 and positions.is_contiguous() and positions.dim() == 1):
+        raise EngineError("positions must be a contiguous 1-D int32 CUDA tensor")
+    _check(load().sae_findex_verify(C.c_void_p(starts.data_ptr()), int(starts.numel()) - 1, int(j0), int(j1), int(out_base),
+                                    C.c_void_p(positions.data_ptr()), int(positions.numel()), int(limit), C.c_void_p(err.data_ptr()),
+                                    _stream_ptr(stream)))
 
 
 def file_top_features(file_keys, n_files: int, ncols: int, n_top: int, flags: int, top_latents, top_keys, stream=None) -> None:

@@ -721,6 +721,44 @@ enum { SAE_COLLECT_IDX32 = 1 };
 int sae_collect_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, int K, int flags,
                       float* values_dev, void* indices_dev, int64_t* stats_dev, void* stream);
 
+/* ---- Feature index: the latent-major postings of an indexed feature store -- for every latent the (position, value) of the slots
+ * that fire it, positions ascending (freud_amd/feature_index.py; kernels: freud_amd/csrc/findex.h).  The reference has no index:
+ * it rebuilds one latent's series from the row-major store by scanning every slot of every file, per query
+ * (src/utils/activations.py:41-58, activation_tensor_from_indexed, called per batch by top_activations, :95-101).  The index is
+ * that scan made once for all latents: a stable counting sort of the store's slots by latent.
+ *
+ * Context-free (no sae_ctx, like sae_search_merge), asynchronous on `stream`, all pointers caller-owned DEVICE memory.  A batch is
+ * values_dev [rows][K] fp32 and indices_dev [rows][K] int64 (int32 with SAE_FINDEX_IDX32): rows of whole files in file order,
+ * 1 <= K <= SAE_COLLECT_MAX_K, 1 <= n_dict <= 2^30.  A slot is POSTED iff its value is not +-0.0 and its index lies in
+ * [0, n_dict); an index outside is counted and never used as an address.  The position of row r of a batch is pos0 + r
+ * (pos0 = file0 * T), below 2^32.
+ *
+ * sae_findex_count (sweep 1): totals_dev int64 [n_dict] += the batch's posted slots per latent; stats_dev int64
+ *   [SAE_FINDEX_NSTATS] += [0] slots seen, [1] zero slots skipped, [2] non-zero slots with an index outside [0, n_dict),
+ *   [3] slots posted; [4..7] reserved.  Integer adds only: order-free.  The caller zeroes both before the first batch.
+ * sae_findex_fill (sweep 2), for a latent range [j0, j1): cursor_dev int64 [n_dict] holds every list's next free slot (absolute:
+ *   it starts at the exclusive prefix sum of the totals).  Each posted slot of a latent j of the range is written to
+ *   positions_out_dev / values_out_dev [cursor[j] - out_base + r], r = its rank among the batch's slots of latent j in row order,
+ *   as (pos0 + row, the stored value bits); then cursor[j] advances by the batch's count.  out_base = the first slot of list j0,
+ *   capacity = the slots the two buffers hold (< 2^32 - 1); a place at or beyond capacity is not written and counted in
+ *   err_dev[1].  The place follows from the data alone (findex.h: Determinism); no float atomics, no returning global atomics.
+ *   workspace_dev: sae_findex_workspace_bytes(rows, j1 - j0) bytes, 4-byte aligned, scratch (no state is kept in it between calls).
+ * sae_findex_verify: over the finished lists of [j0, j1) (starts_dev int64 [n_dict + 1], absolute), err_dev[0] += the slots whose
+ *   position is not strictly greater than the one before it in its list or is >= limit (= n_files * T).  Non-zero means that a
+ *   row of the store repeats an index.  err_dev: int64 [2], zeroed by the caller.
+ * sae_findex_workspace_bytes: bytes of workspace for batches of at most max_rows rows and a range of n_range latents; -1 for
+ *   arguments out of range. */
+enum { SAE_FINDEX_IDX32 = 1 };
+#define SAE_FINDEX_NSTATS 8
+int64_t sae_findex_workspace_bytes(int64_t max_rows, int64_t n_range);
+int sae_findex_count(const float* values_dev, const void* indices_dev, int64_t rows, int K, int flags, int64_t n_dict, int64_t* totals_dev,
+                     int64_t* stats_dev, void* stream);
+int sae_findex_fill(const float* values_dev, const void* indices_dev, int64_t rows, int K, int flags, int64_t n_dict, int64_t j0, int64_t j1,
+                    int64_t pos0, int64_t* cursor_dev, int64_t out_base, uint32_t* positions_out_dev, float* values_out_dev,
+                    int64_t capacity, void* workspace_dev, int64_t workspace_bytes, int64_t* err_dev, void* stream);
+int sae_findex_verify(const int64_t* starts_dev, int64_t n_dict, int64_t j0, int64_t j1, int64_t out_base, const uint32_t* positions_dev,
+                      int64_t capacity, int64_t limit, int64_t* err_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
