@@ -40,6 +40,7 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "coact.h"
 #include "labels.h"
 #include "hist.h"
+#include "timing.h"
 #include "collect.h"
 #include "findex.h"
 #include "manip.h"
@@ -156,6 +157,7 @@ enum KernelId {
   KID_RECON_ATTR,
   KID_RECON_ATTR_STREAM,   // ... the same bracket when the attribution GEMM ran in the streaming form (gemm256s.h)
   KID_COLLECT,         // feature collection (collect.h): the row collect kernel of sae_collect_files after the encoder
+  KID_TIMING,          // feature timing (timing.h): every kernel of sae_timing_files after the encoder
   KID_COUNT
 };
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
@@ -164,7 +166,7 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
-                                              "recon_resid", "recon_attr", "recon_attr_stream", "collect"};
+                                              "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing"};
 constexpr int EV_RING = 64;
 
 struct EvRing {
@@ -174,7 +176,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING };
 
 // A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
 // of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
@@ -192,7 +194,9 @@ static const FilePassKind kHistPass = {"sae_hist_files", "build the histograms i
 static const FilePassKind kManipPass = {"sae_manipulate_files", "manipulate in a bf16 context", "manipulation", 0, LAST_FWD_BF16, nullptr};
 static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruction report in a bf16 context", "reconstruction", SAE_RECON_UNFUSED, LAST_RECON, "a reconstruction report"};
 static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32, LAST_COLLECT, "a feature collection"};
-static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass};
+static const FilePassKind kTimingPass = {"sae_timing_files", "time the features in a bf16 context", "timing", SAE_TIMING_ONE_CHUNK, LAST_TIMING, "a feature timing pass"};
+static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
+                                                  &kTimingPass};
 
 struct sae_ctx {
   sae_config cfg;
@@ -3667,6 +3671,65 @@ extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_
   HIP_TRY(memset_fmax);
   HIP_TRY(hipGetLastError());
   file_pass_end(kHistPass, c);
+  return SAE_OK;
+}
+
+// ---- feature timing (timing.h): per latent the histograms of its run durations and of the gaps between its runs, and six totals
+static_assert(SAE_TIMING_ACTIVE == TB_ACTIVE && SAE_TIMING_SPAN == TB_SPAN && SAE_TIMING_RUNS == TB_RUNS && SAE_TIMING_FILES == TB_FILES &&
+              SAE_TIMING_LONGEST == TB_LONGEST && SAE_TIMING_CENSORED == TB_CENSORED && SAE_TIMING_NTOTALS == TB_NTOTALS &&
+              SAE_TIMING_MAX_BINS == TB_MAX_BINS && SAE_TIMING_MAX_BRIDGE == TB_MAX_BRIDGE && TM_MAX_K == SAE_COLLECT_MAX_K,
+              "freud_sae.h, timing_bins.h and timing.h disagree");
+
+// the stored latent of file_pass_encode walked by timing_l1_kernel.  Chunks of whole files as in hist_launch_l1.  Columns per
+// workgroup from the LDS the spec needs: 2 ((NB + 1) / 2) dwords per column -- 256 while that fits 48 KiB (NB <= 48), else 128 (NB = 111:
+// 56 KiB).  one_chunk (SAE_TIMING_ONE_CHUNK): every file of the call in one chunk -- the same arrays from another geometry.
+static void timing_launch_l1(sae_ctx* c, int64_t n_files, int Trows, const int* lengths, int sub_bits, int bridge, uint32_t threshold,
+                             bool one_chunk, int64_t* run_hist, int64_t* gap_hist, int64_t* totals, hipStream_t s) {
+  const int nq = (timing_nbins(sub_bits, Trows) + 1) / 2;
+  const int nt = nq <= 24 ? 256 : 128;
+  const int colblocks = (c->n + nt - 1) / nt;
+  const int64_t want = std::min<int64_t>(n_files, (HIST_MIN_WGS + colblocks - 1) / colblocks);
+  const int fpc = one_chunk ? (int)n_files : (int)(n_files / want);
+  const int64_t chunks = (n_files + fpc - 1) / fpc;
+  hipLaunchKernelGGL(timing_l1_kernel, dim3((unsigned)colblocks, (unsigned)chunks), dim3(nt), (size_t)2 * nq * nt * 4, s,
+                     (const unsigned short*)c->c, (int64_t)c->n_p, c->n, n_files, Trows, lengths, fpc, sub_bits, bridge, threshold, run_hist,
+                     gap_hist, totals);
+}
+
+extern "C" int sae_timing_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                                int sub_bits, int bridge, uint32_t threshold_bits, int flags, int64_t* run_hist, int64_t* gap_hist,
+                                int64_t* totals, int64_t* n_frames, void* stream) {
+  int64_t M;
+  if (!timing_spec_ok(sub_bits, bridge, threshold_bits, rows_per_file))
+    return fail(SAE_ERR_INVALID, "timing sub_bits=%d bridge=%d threshold_bits=0x%x rows_per_file=%lld: sub_bits in 0..3, bridge in 0..%d, "
+                "threshold_bits <= 0x%x, 1 <= rows_per_file <= %d", sub_bits, bridge, threshold_bits, (long long)rows_per_file, TB_MAX_BRIDGE,
+                TB_MAX_THRESHOLD, TB_MAX_ROWS);
+  if (!gap_hist || !totals || !n_frames) return fail(SAE_ERR_INVALID, "null argument");
+  for (const void* p : {(const void*)run_hist, (const void*)gap_hist, (const void*)totals, (const void*)n_frames})
+    if (misaligned(p, 8)) return fail(SAE_ERR_INVALID, "the timing arrays must be 8-byte aligned");
+  if (int rc = file_pass_begin(kTimingPass, c, x, run_hist, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (c->topk && (c->k < 1 || c->k > TM_MAX_K)) return fail(SAE_ERR_INVALID, "sae_timing_files: k=%d outside [1, %d]", c->k, TM_MAX_K);
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
+
+  ev_begin(c, KID_TIMING, s);
+  hipLaunchKernelGGL(hist_frames_kernel, dim3(1), dim3(256), 0, s, n_files, Trows, lengths, n_frames, (int64_t*)nullptr);
+  if (c->topk) {
+    const dim3 grid((unsigned)n_files, (unsigned)((c->n + TM_SEG - 1) / TM_SEG));
+    if (c->k <= 64)
+      hipLaunchKernelGGL(timing_topk_kernel<true>, grid, dim3(64), 0, s, c->top_idx, (const unsigned short*)c->top_vals, c->k, Trows, lengths,
+                         c->n, sub_bits, bridge, threshold_bits, run_hist, gap_hist, totals);
+    else
+      hipLaunchKernelGGL(timing_topk_kernel<false>, grid, dim3(64), 0, s, c->top_idx, (const unsigned short*)c->top_vals, c->k, Trows, lengths,
+                         c->n, sub_bits, bridge, threshold_bits, run_hist, gap_hist, totals);
+  } else {
+    timing_launch_l1(c, n_files, Trows, lengths, sub_bits, bridge, threshold_bits, (flags & SAE_TIMING_ONE_CHUNK) != 0, run_hist, gap_hist,
+                     totals, s);
+  }
+  ev_end(c, KID_TIMING, s);
+  HIP_TRY(hipGetLastError());
+  file_pass_end(kTimingPass, c);
   return SAE_OK;
 }
 

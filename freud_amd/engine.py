@@ -129,6 +129,7 @@ def load() -> C.CDLL:
         "sae_label_keys": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, i64, i64, vp, vp]),
         "sae_hist_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
                                      vp, C.c_int, vp, vp, vp]),
+        "sae_timing_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp]),
         "sae_dict_pack_bytes": (i64, [i64, i64]),
         "sae_dict_pack": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
         "sae_dict_sim_keys": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_int, vp, vp]),
@@ -182,6 +183,7 @@ EXPORTED_SYMBOLS = [
     "sae_coact_files", "sae_coact_neighbor_keys",
     "sae_label_files", "sae_label_keys",
     "sae_hist_files",
+    "sae_timing_files",
     "sae_dict_pack_bytes", "sae_dict_pack", "sae_dict_sim_keys",
     "sae_manipulate_files",
     "sae_recon_files",
@@ -199,6 +201,9 @@ LABEL_MAX_CLASSES = 4096                                            # include/fr
 LABEL_MAX_SLOTS = 16                                                # include/freud_sae.h: SAE_LABEL_MAX_SLOTS
 HIST_MAX_REGULAR = 128                                              # freud_amd/csrc/hist_bins.h: octaves << sub_bits at most
 HIST_MAX_SEL = 64                                                   # include/freud_sae.h: SAE_HIST_MAX_SEL
+TIMING_ACTIVE, TIMING_SPAN, TIMING_RUNS, TIMING_FILES, TIMING_LONGEST, TIMING_CENSORED, TIMING_NTOTALS = range(7)   # include/freud_sae.h: SAE_TIMING_*
+TIMING_ONE_CHUNK = 1                                                # include/freud_sae.h: SAE_TIMING_ONE_CHUNK
+TIMING_MAX_BINS, TIMING_MAX_BRIDGE, TIMING_MAX_ROWS = 111, 15, 65535  # include/freud_sae.h: SAE_TIMING_MAX_*; freud_amd/csrc/timing_bins.h: TB_MAX_ROWS
 COLLECT_IDX32 = 1                                                   # include/freud_sae.h: SAE_COLLECT_IDX32
 COLLECT_MAX_K = 1024                                                # include/freud_sae.h: SAE_COLLECT_MAX_K
 FINDEX_IDX32 = 1                                                    # include/freud_sae.h: SAE_FINDEX_IDX32
@@ -241,6 +246,25 @@ def hist_nbins(spec) -> int:
     if (octaves << sub_bits) > HIST_MAX_REGULAR:
         raise ValueError(f"octaves={octaves} x {1 << sub_bits} bins per octave > {HIST_MAX_REGULAR}")
     return (octaves << sub_bits) + 3
+
+
+def timing_index(L: int, sub_bits: int) -> int:
+    """idx of a duration or gap of L >= 1 frames (bin = idx - 1) -- freud_amd/csrc/timing_bins.h, integers only."""
+    L, s = int(L), int(sub_bits)
+    if L < (2 << s):
+        return L
+    sh = (L.bit_length() - 1) - s
+    return (sh << s) + (L >> sh)
+
+
+def timing_nbins(sub_bits: int, T: int) -> int:
+    """Bins of the feature timing for files of T frames -- freud_amd/csrc/timing_bins.h; ValueError for a spec outside its limits."""
+    sub_bits, T = int(sub_bits), int(T)
+    if sub_bits < 0 or sub_bits > 3:
+        raise ValueError(f"sub_bits={sub_bits} outside [0, 3]")
+    if T < 1 or T > TIMING_MAX_ROWS:
+        raise ValueError(f"T={T} frames per file outside [1, {TIMING_MAX_ROWS}]")
+    return timing_index(T, sub_bits)
 
 
 def _check(rc: int) -> None:
@@ -697,6 +721,34 @@ class SaeEngine:
             lc = i64(label_count, int(n_classes) + 1, "label_count")
         _check(self._lib.sae_hist_files(self._ctx, xp, B, T, dt, lp, lo_exp, octaves, sub_bits, 0, fh, mh, nf, lab, n_slots, int(n_classes),
                                         sel, n_sel, lh, lc, _stream_ptr(stream)))
+
+    # -- feature timing (include/freud_sae.h: sae_timing_files; freud_amd/feature_timing.py) -----------------------------------
+    def timing_files(self, x, sub_bits: int, bridge: int, threshold_bits: int, run_hist, gap_hist, totals, n_frames, lengths=None,
+                     one_chunk: bool = False, stream=None) -> None:
+        """Add the run-duration and gap histograms of x [n_files, T, d] (CUDA), NB = timing_nbins(sub_bits, T), to run_hist and gap_hist
+        (zero-initialised contiguous int64 CUDA [n_dict, NB]), the totals to totals (int64 CUDA [n_dict, TIMING_NTOTALS]) and the
+        counted frames to n_frames (int64 CUDA [1]); bridge in [0, TIMING_MAX_BRIDGE]; a frame is active iff the bf16 magnitude bits
+        of its value exceed threshold_bits; lengths: int32 CUDA tensor [n_files] or None.  The same arrays go to every call of one
+        pass.  one_chunk: an L1 context walks all files of the call in one chunk per column block (another launch geometry, the same
+        arrays; slower).  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
+        import torch
+        x, xp, B, T, _d, dt, lp = _files_args(x, "timing_files", lengths)
+        nb = timing_nbins(sub_bits, T)
+
+        def i64(t, numel, name):
+            if not (t is not None and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == numel):
+                raise EngineError(f"{name} must be a contiguous int64 CUDA tensor of {numel} elements")
+            return C.c_void_p(t.data_ptr())
+
+        rh, gh = i64(run_hist, self.n * nb, "run_hist"), i64(gap_hist, self.n * nb, "gap_hist")
+        tt, nf = i64(totals, self.n * TIMING_NTOTALS, "totals"), i64(n_frames, 1, "n_frames")
+        if not 0 <= int(bridge) <= TIMING_MAX_BRIDGE:
+            raise EngineError(f"bridge={bridge} outside [0, {TIMING_MAX_BRIDGE}]")
+        if not 0 <= int(threshold_bits) <= 0x7F80:
+            raise EngineError(f"threshold_bits={threshold_bits} outside [0, 0x7F80]")
+        _check(self._lib.sae_timing_files(self._ctx, xp, B, T, dt, lp, int(sub_bits), int(bridge), int(threshold_bits),
+                                          TIMING_ONE_CHUNK if one_chunk else 0, rh, gh, tt, nf,
+                                          _stream_ptr(stream)))
 
     # -- feature manipulation (include/freud_sae.h: sae_manipulate_files; freud_amd/manipulate.py) -------------------------
     def manipulate_files(self, x, latents, ops, values, standard, manipulated, series, stream=None) -> None:

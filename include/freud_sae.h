@@ -528,6 +528,47 @@ int sae_hist_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t row
                    int64_t* n_frames_dev, const int32_t* labels_dev, int n_slots, int n_classes, const int32_t* sel_latents_dev, int n_sel,
                    int64_t* label_hist_dev, int64_t* label_count_dev, void* stream);
 
+/* ---- Feature timing: for HOW LONG every latent fires -- per latent the histogram of its run durations, the histogram of the gaps
+ * between consecutive runs of a file, and six totals.  A frame is one 20 ms step of Whisper's 30 s window; every other pass treats
+ * the frames of a file as an unordered bag, this one carries state from frame t to frame t + 1.
+ *
+ * Semantics (freud_amd/csrc/timing_bins.h).  Frames count exactly as in sae_stats_files (lengths_dev: the first min(length, T)
+ * frames of a file; without, all T); runs never cross a file boundary and never see an uncounted frame.  A frame is ACTIVE iff
+ * mag > threshold_bits, mag = bits & 0x7FFF of the bf16 value encode() returns: threshold_bits = 0 is the rule of the statistics
+ * (a -0.0 and a selected zero of a TopK row are inactive); a multi_topk context uses its k selection.  RUNS with a bridge g =
+ * `bridge` (0 <= g <= SAE_TIMING_MAX_BRIDGE): with the active frames t1 < t2 < ... of a latent within one file's counted frames,
+ * neighbours a < b belong to the same run iff b - a - 1 <= g.  A run's DURATION is last - first + 1, bridged frames included.  The
+ * GAP between two consecutive runs of one file is b - a - 1 (> g); the silence before the first and after the last run of a file
+ * is no gap.  A run is CENSORED iff it starts on frame 0 or ends on the last counted frame of its file: its duration is a lower
+ * bound.  BINS, integers only: with s = sub_bits (0..3), P = 2^s and a duration or gap L >= 1, idx = L if L < 2P, else idx = sh P +
+ * (L >> sh) with sh = floor(log2 L) - s; bin = idx - 1.  The lower edge of idx is idx if idx < 2P, else (P + idx % P) << (idx / P -
+ * 1).  NB = idx(rows_per_file) bins; rows_per_file <= 65535 for this entry point, so NB <= SAE_TIMING_MAX_BINS.  s = 2: the
+ * durations 1..7 have a bin each (20-140 ms), then four bins per octave; T = 1500: 37 bins.
+ *
+ * sae_timing_files adds one batch to run_hist_dev [n_dict][NB], gap_hist_dev [n_dict][NB], totals_dev [n_dict][SAE_TIMING_NTOTALS]
+ * (SAE_TIMING_ACTIVE: active frames; _SPAN: the sum of the durations; _RUNS; _FILES: files with at least one run; _LONGEST: the
+ * longest run, a running MAXIMUM; _CENSORED) and n_frames_dev [1].  All are int64 running totals, caller-owned, zeroed before the
+ * first batch and passed together to every call of one pass.  Per latent: sum(run_hist) == RUNS, sum(gap_hist) == RUNS - FILES,
+ * SPAN == ACTIVE at g = 0 and SPAN >= ACTIVE otherwise, LONGEST <= rows_per_file.  Every sum is an integer add and LONGEST an integer
+ * max: two runs give bitwise identical arrays, whatever the batch and the launch geometry.
+ *
+ * An L1 context walks the stored latent of its ordinary encoder, a TopK context its selection (the indices of a row are distinct;
+ * an index outside [0, n_dict) is ignored).  flags: 0, or SAE_TIMING_ONE_CHUNK -- an L1 context then walks all files of the call
+ * in ONE chunk per column block instead of the chunks its launcher forms (a TopK context ignores it); the arrays do not depend on
+ * it, which is what the tests use it for: it is slower.  n_files * rows_per_file <= max_rows; fp8 contexts: SAE_ERR_INVALID.
+ * Null or misaligned arrays, sub_bits outside 0..3, bridge outside [0, SAE_TIMING_MAX_BRIDGE], threshold_bits > 0x7F80,
+ * rows_per_file > 65535, unknown flags and bad shapes fail before anything is enqueued.  Asynchronous on `stream`.  Training state
+ * is untouched; afterwards sae_latent_buffer, sae_topk_indices, sae_decode, sae_multi_topk_buffers, sae_latent_colmax and
+ * sae_read_metrics return SAE_ERR_STATE until the next sae_eval / step. */
+enum { SAE_TIMING_ACTIVE = 0, SAE_TIMING_SPAN = 1, SAE_TIMING_RUNS = 2, SAE_TIMING_FILES = 3, SAE_TIMING_LONGEST = 4, SAE_TIMING_CENSORED = 5,
+       SAE_TIMING_NTOTALS = 6 };
+#define SAE_TIMING_ONE_CHUNK 1
+#define SAE_TIMING_MAX_BINS 111
+#define SAE_TIMING_MAX_BRIDGE 15
+int sae_timing_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                     int sub_bits, int bridge, uint32_t threshold_bits, int flags, int64_t* run_hist_dev, int64_t* gap_hist_dev,
+                     int64_t* totals_dev, int64_t* n_frames_dev, void* stream);
+
 /* ---- Dictionary comparison: what a dictionary IS against another one, or against itself -- which 32x latents an 8x latent split
  * into, whether two runs found the same features (mean max cosine similarity), which latents duplicate each other.  All of it is
  * the cosines between unit decoder directions and, per direction of A, its nearest directions of B.
