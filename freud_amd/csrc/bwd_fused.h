@@ -102,6 +102,9 @@ __device__ __forceinline__ bf16x8 tr_frag_perm(const char* img, int col0, int s,
 constexpr int BF_RING = 12;      // fragment ring (divides 72); the prefetch distance is BF_RING - 1 MFMAs
 
 // two LDS-DMA pieces whose LDS destinations are base + l0 / base + l1: the addition IS the write of M0
+// (-Winline-asm off for these statements, as at common.h's glds16_x2: M0 is clobbered on purpose)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 __device__ __forceinline__ void glds16_x2_add(const void* sbase0, const void* sbase1, unsigned voff0, unsigned voff1, unsigned base,
                                               unsigned l0, unsigned l1) {
   asm volatile(
@@ -127,6 +130,7 @@ __device__ __forceinline__ void glds16_x2_add_nt(const void* sbase0, const void*
       : "s"(sbase0), "s"(sbase1), "v"(voff0), "v"(voff1), "s"(base), "s"(l0), "s"(l1)
       : "memory", "m0", "scc");
 }
+#pragma clang diagnostic pop
 
 __global__ __launch_bounds__(256, 1) void bwd_fused_d384_kernel(BwdFusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];

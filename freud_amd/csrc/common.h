@@ -16,6 +16,10 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 __device__ __forceinline__ float bf16_round(float v) { return (float)(bf16_t)v; }
 
+// an activation element (fp32 / fp16 / bf16) as fp32
+template <typename T>
+__device__ __forceinline__ float load_as_float(const T* p) { return (float)*p; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -80,6 +84,9 @@ __device__ __forceinline__ float block_sum_256_lds(float v, float* red) {
 // (Round 6: M0 is declared CLOBBERED instead of being saved and restored around every statement -- nothing else in these kernels lives in
 // M0 (gfx9 LDS instructions do not read it), so the save / restore pair was two scalar instructions per statement on the one issue
 // port a single-wave-per-SIMD kernel has: 6 of the fused forward's ~28 scalar instructions per iteration.)
+// (-Winline-asm off for these statements: the compiler warns that it does not preserve a clobbered M0, which is what is asked of it)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 __device__ __forceinline__ void glds16_x2(const void* sbase0, const void* sbase1, unsigned voff0, unsigned voff1,
                                           unsigned dst0, unsigned dst1) {
   asm volatile(
@@ -99,6 +106,7 @@ __device__ __forceinline__ void glds4(const void* sbase, unsigned voff, unsigned
 __device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned dst) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0" : : "s"(sbase), "v"(voff), "s"(dst) : "memory", "m0");
 }
+#pragma clang diagnostic pop
 
 // A loop whose index is a TEMPLATE constant.  `#pragma unroll` gives up silently above LLVM's size threshold; the loop then stays
 // rolled and every register array it indexes goes to the stack (fwd_fused2.h's slot loop in round 5: 1.8 KB of scratch per lane after

@@ -23,10 +23,6 @@
 #include <mutex>
 #include <unistd.h>
 
-static thread_local bool g_force_gemm128 = false;   // (the CURRENT call's context: set by use_device, like g_device -- ADVICE r5)
-                                                    // sae_config.force_gemm128: keep every GEMM on the 128x128 kernel (A/B timing, tests)
-static thread_local bool g_no_stream = false;       // FREUD_GEMM_STREAM=0 / debug_flags 86: the K = d GEMMs in gemm256.h's tile form (A/B timing, tests)
-static thread_local int g_device = 0;  // device of the context the current call works on (set by use_device)
 #include "bwd_fused.h"
 #include "fwd_fused.h"
 #include "fwd_fused2.h"
@@ -34,26 +30,19 @@ static thread_local int g_device = 0;  // device of the context the current call
 #include "topk_sparse.h"
 #include "topk_aux.h"
 #include "eval_fp32.h"
-#include "search.h"
-#include "file_top.h"
-#include "stats.h"
-#include "coact.h"
-#include "labels.h"
-#include "hist.h"
-#include "timing.h"
-#include "collect.h"
-#include "findex.h"
-#include "manip.h"
-#include "dict_match.h"
-#include "recon.h"
+#include "engine_internal.h"
+#include "gemm_launch.h"
 
-constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
+// (declared in engine_internal.h)
+__thread bool g_force_gemm128 = false;
+__thread bool g_no_stream = false;
+__thread int g_device = 0;
 
 // ------------------------------------------------------------------------------------------
 // error handling
 // ------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
@@ -66,15 +55,9 @@ static int fail(int code, const char* fmt, ...) {
     if (r_ != ncclSuccess) return fail(SAE_ERR_HIP, "%s failed: %s (%s:%d)", #expr, ncclGetErrorString(r_), \
                                        __FILE__, __LINE__);                                                 \
   } while (0)
-#define HIP_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) return fail(SAE_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                      __FILE__, __LINE__);                                              \
-  } while (0)
 
 // dynamic-LDS opt-in (> 64 KiB) is a per-device function attribute: remember (function, device) pairs
-static int ensure_lds_attr(const void* fn, int bytes, int device) {
+int ensure_lds_attr(const void* fn, int bytes, int device) {
   static std::vector<std::pair<const void*, int>> done;
   static std::mutex mu;                     // contexts of several host threads share the cache
   std::lock_guard<std::mutex> lock(mu);
@@ -84,82 +67,7 @@ static int ensure_lds_attr(const void* fn, int bytes, int device) {
   done.emplace_back(fn, device);
   return SAE_OK;
 }
-#define LDS_ATTR(fn, bytes, device)                                           \
-  do {                                                                        \
-    int rc_ = ensure_lds_attr(reinterpret_cast<const void*>(fn), (bytes), (device)); \
-    if (rc_) return rc_;                                                      \
-  } while (0)
 
-// workgroups of `per` items that cover n items, at most `cap` of them (the kernels behind it stride over the rest)
-static int grid_for(int64_t n, int cap, int per = 256) {
-  const int64_t g = (n + per - 1) / per;
-  return (int)(g < cap ? g : cap);
-}
-
-// the one dispatch on an activation dtype of include/freud_sae.h: f(typed pointer) -> status
-template <class F>
-static int with_x_type(int x_dtype, const void* x, F&& f) {
-  switch (x_dtype) {
-    case SAE_DTYPE_F32: return f((const float*)x);
-    case SAE_DTYPE_F16: return f((const _Float16*)x);
-    case SAE_DTYPE_BF16: return f((const bf16_t*)x);
-    default: return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  }
-}
-
-// the one dispatch of the sparse TopK kernels on d_p: f(integral_constant<NP>), NP = d_p / 128 where a kernel is specialised, else 0
-template <class F>
-static void with_np(int d_p, F&& f) {
-  if (d_p == 384) f(std::integral_constant<int, 3>{});
-  else if (d_p == 768) f(std::integral_constant<int, 6>{});
-  else if (d_p == 1280) f(std::integral_constant<int, 10>{});
-  else f(std::integral_constant<int, 0>{});
-}
-
-// the entry points' test of a pointer argument against the alignment its kernels need (a null optional pointer passes)
-static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
-
-// ------------------------------------------------------------------------------------------
-// kernel ids for profiling
-// ------------------------------------------------------------------------------------------
-enum KernelId {
-  KID_PREP_W = 0,
-  KID_PREP_X,
-  KID_ENC_FWD,
-  KID_DEC_FWD,
-  KID_FWD_FUSED,
-  KID_DPRE,
-  KID_DW,
-  KID_BWD_FUSED,
-  KID_REDUCE,
-  KID_OPT,
-  KID_TK_ENC,
-  KID_TK_SELECT,
-  KID_TK_DECODE,
-  KID_TK_DDENSE,
-  KID_TK_DWD,
-  KID_TK_DWE,
-  KID_TK_DSAE,
-  KID_TK_AUX,
-  KID_EXCHANGE,        // data parallel: the gradient exchange (peer-exchange kernel or ncclAllReduce), on the stream it runs on
-  KID_STATS_XCHG,      // data parallel: the batch statistics (push inside finalize_losses, or the statistics kernel + its exchange)
-  KID_STEP_TOTAL,
-  KID_COACT_PACK,      // feature co-activation (coact.h): the mask pack and the i8 update of sae_coact_files
-  KID_COACT_UPDATE,
-  KID_MANIP_SERIES,    // feature manipulation (manip.h): the series + operand rows, the standard decode, the apply rule
-  KID_MANIP_DECODE,
-  KID_MANIP_APPLY,
-  KID_LABEL_PACK,      // feature labels (labels.h): the label pack + label counts and the rectangular i8 update of sae_label_files
-  KID_LABEL_UPDATE,
-  KID_HIST,            // activation histograms (hist.h): every kernel of sae_hist_files after the encoder
-  KID_RECON_DECODE,    // reconstruction report (recon.h): the decode of the forward's latent, the residual sweep, the attribution
-  KID_RECON_RESID,     //   (L1: the GEMM with EpiAttr; TopK: the dots and the column walk) with the fold
-  KID_RECON_ATTR,
-  KID_RECON_ATTR_STREAM,   // ... the same bracket when the attribution GEMM ran in the streaming form (gemm256s.h)
-  KID_COLLECT,         // feature collection (collect.h): the row collect kernel of sae_collect_files after the encoder
-  KID_TIMING,          // feature timing (timing.h): every kernel of sae_timing_files after the encoder
-  KID_COUNT
-};
 static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm", "dec_fwd_gemm", "fwd_fused_gemm", "dpre_gemm",
                                               "dw_gemm", "bwd_fused_gemm", "reduce_grads", "clip_adam", "topk_enc_gemm", "topk_select",
                                               "topk_decode", "topk_ddense_gemm", "topk_dwdec_gemm", "topk_dwenc_gemm",
@@ -167,209 +75,6 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
                                               "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing"};
-constexpr int EV_RING = 64;
-
-struct EvRing {
-  hipEvent_t beg[EV_RING], end[EV_RING];
-  int n = 0;  // recorded since last read
-};
-
-// What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
-// per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING };
-
-// A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
-// of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
-struct FilePassKind {
-  const char *fn, *fp8_advice, *flags_noun;
-  int flags_mask;
-  LastCall leaves;
-  const char* left_by;
-};
-static const FilePassKind kSearchPass = {"sae_search_files", "search in a bf16 context", "search", SAE_SEARCH_UNFUSED, LAST_SEARCH, "a feature search"};
-static const FilePassKind kStatsPass = {"sae_stats_files", "run the statistics in a bf16 context", "stats", SAE_STATS_UNFUSED, LAST_STATS, "a feature statistics pass"};
-static const FilePassKind kCoactPass = {"sae_coact_files", "count co-activations in a bf16 context", "co-activation", 0, LAST_COACT, "a feature co-activation pass"};
-static const FilePassKind kLabelPass = {"sae_label_files", "count labels in a bf16 context", "label", 0, LAST_LABELS, "a feature label pass"};
-static const FilePassKind kHistPass = {"sae_hist_files", "build the histograms in a bf16 context", "histogram", 0, LAST_HIST, "an activation histogram pass"};
-static const FilePassKind kManipPass = {"sae_manipulate_files", "manipulate in a bf16 context", "manipulation", 0, LAST_FWD_BF16, nullptr};
-static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruction report in a bf16 context", "reconstruction", SAE_RECON_UNFUSED, LAST_RECON, "a reconstruction report"};
-static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32, LAST_COLLECT, "a feature collection"};
-static const FilePassKind kTimingPass = {"sae_timing_files", "time the features in a bf16 context", "timing", SAE_TIMING_ONE_CHUNK, LAST_TIMING, "a feature timing pass"};
-static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
-                                                  &kTimingPass};
-
-struct sae_ctx {
-  sae_config cfg;
-  int d, n, d_p, n_p;
-  int64_t max_rows_p;
-  int64_t nW;       // d_p * n_p
-  int64_t nparams;  // nW + n_p
-  // flat parameter / state buffers: [W (d_p*n_p) | b (n_p)]
-  float *P = nullptr, *Mom = nullptr, *Var = nullptr;
-  float* G = nullptr;  // [grads (nparams) | metrics (8)]
-  bf16_t *Wb = nullptr, *Wt = nullptr;
-  // SAE_PREC_FP8: encoder / decoder GEMMs on e4m3 operands (l1_fp8.h); every padded dimension is a multiple of 256 then
-  bool fp8 = false;
-  bool fp8_bwd = false;         // SAE_PREC_FP8_BWD: the dpre GEMM of the backward on e4m3 operands too (dxh8 = e4m3(dx_hat s_g))
-  unsigned char* dxh8 = nullptr;
-  int row_pad = 128;            // M_p = round_up(M, row_pad)
-  unsigned char *x8 = nullptr, *c8 = nullptr, *W8 = nullptr, *W8t = nullptr;
-  float *scal8 = nullptr, *x8_part = nullptr;
-  bool use_fused_fwd = false;
-  int fwd_variant = 2;          // fused forward: 2 = fwd_fused2.h (decoder split along d), 1 = fwd_fused.h (FREUD_FWD=1: A/B, stamps)
-  bf16_t *xb = nullptr, *c = nullptr, *dxh = nullptr, *dpre = nullptr;
-  // generic L1 backward (round 5): dx_hat^T and x^T, [d_p][M_p] -- the weight-gradient GEMM's d-side operand K-contiguous, so that its
-  // fragments come by ds_read_b128 instead of twice as many transposing reads (null: the k-major x k-major form)
-  bf16_t *dxhT = nullptr, *xT = nullptr;
-  float *slab = nullptr, *db_part = nullptr, *l1_part = nullptr, *sq_part = nullptr, *scal = nullptr;
-  double* gn_part = nullptr;
-  float* cn_part = nullptr;
-  bool cn_valid = false;       // cn_part holds the column-norm partials of the CURRENT weights (left by optimizer_l1_kernel)
-  bool wb_valid = false;       // TopK: We_b / Wd_b are the bf16 copies of the CURRENT weights (left by optimizer_kernel)
-  // L1, d_p <= 384 (optimizer_l1_cols_kernel): the update left the fp32 master UN-normalised (the reference's state after
-  // optimizer.step()), the column denominators in cnorm and the bf16 copies Wb / Wt of the NORMALISED weights.
-  //   wn_pending              that state holds;
-  //   wn_fwd_seen             ... and one forward has used the copies since: the reference's W is normalised by now
-  //                           (l1autoencoder.py:71-73), ours is so in effect -- the next update divides while loading, any other
-  //                           reader of the master (settle_weights) has the division carried out first.
-  float* cnorm = nullptr;
-  bool wn_pending = false, wn_fwd_seen = false;
-  sae_grad_ready_fn grad_ready = nullptr;   // data-parallel overlap hook (sae_set_grad_ready_callback)
-  void* grad_ready_user = nullptr;
-  int dw_chunk_rows = 0;       // generic L1 path: rows (of d_p) per weight-gradient GEMM launch when a hook is set
-  int dw_chunk_splits = 1;     // its split-K factor
-  int dw_col_chunks = 1;       // ... with the peer exchange: COLUMN chunks of dW instead (each reads only its own columns of the
-  int dw_col_splits = 1;       //     latent / dpre streams, where a row chunk re-reads all of them), and their split-K factor
-  float* cnt_part = nullptr;   // fused forward: per-workgroup masked-entry counts
-  int gn_blocks = 0;
-  bool step_fused_call = false; // set by sae_step: forward_backward and optimizer_step back to back
-  bool gn_valid = false;       // gn_part holds the sum of squares of the UNSCALED local gradient
-  bool metrics_fresh = false;  // the loss scalars were written by a forward and not yet averaged by an optimizer step
-  const bf16_t* xb_cur = nullptr;   // bf16 GEMM copy of the current batch (== the caller's x when no copy is needed)
-  unsigned int* masked = nullptr;
-  int dw_splits = 1;
-  // plain (single-launch) weight-gradient GEMM of the generic L1 path: whole tiles written straight into the gradient, the tiles
-  // left over after whole rounds in K pieces through dw_tail (gemm_tail_plan); 0 = uniform split-K through the slabs
-  int dw_tail_tiles = 0, dw_tail_pieces = 0;
-  float* dw_tail = nullptr;
-  int bwd_splits = 1;       // row ranges of the fused backward
-  int bwd_range_splits = 1; // ... when it is launched in column-tile ranges (bwd_ranges > 1)
-  bool use_fused_bwd = false;
-  // ---- TopK variant (topkautoencoder.py): flat params [We (n_p*d_p) | be (n_p) | Wd (n_p*d_p) | bd (d_p)]
-  bool topk = false;
-  int k = 0, k_aux_cap = 0;
-  int64_t rows_per_file = 0;          // T: x is [B][T][d] for x.mean(0); 0 = the whole batch is one file
-  double dead_threshold = 1e300;
-  bf16_t *We_b = nullptr, *Wd_b = nullptr, *xs = nullptr, *pre = nullptr, *dense = nullptr, *aux_dense = nullptr;
-  bf16_t *de_b = nullptr, *dh_b = nullptr;
-  float *e = nullptr, *dh = nullptr, *e2_part = nullptr, *a2_part = nullptr, *dbd_part = nullptr, *ds_part = nullptr, *tkf = nullptr;
-  int *top_idx = nullptr, *aux_idx = nullptr, *tk = nullptr;
-  bf16_t *top_vals = nullptr, *aux_vals = nullptr, *multi_vals = nullptr;   // selected activations, compact [M_p][kcap]
-  unsigned short* tile_max = nullptr;   // [M_p][n_p / 64] maxima of the pre-activation tiles (tile-driven select)
-  unsigned char* sel_flag = nullptr;    // [M_p] rows the tile-driven select left to the general kernel
-  bool dense_valid = false;     // the masked dense rows of the last forward were written (else: topk_densify on demand)
-  bool multi_dense_valid = false;   // the same for the multi-TopK (4k) rows
-  // AuxK on the compacted dead set (topk_aux.h)
-  float* be_r = nullptr;            // encoder bias rounded to bf16 (as float), refreshed every step
-  int slab_splits = 1;              // slabs allocated in c->slab (TopK)
-  bool aux_compact = false;
-  int *tkd = nullptr, *dead_cols = nullptr, *vec_rank = nullptr;
-  unsigned char* vec_bits = nullptr;
-  bf16_t* Wdd_b = nullptr;          // [n_p][d_p] rows of W_dec of the dead latents, compact
-  float* aux_dbe_part = nullptr;    // [M_p / 128][n_p] column sums of the AuxK d pre-activations, compact columns
-  int* dead_hint = nullptr;     // pinned host copy of tk[0] (number of dead latents), refreshed asynchronously every step
-  double* tv_part = nullptr;
-  long long* nfsf = nullptr;
-  long long* dbe_fx = nullptr;  // [n_p] fixed-point d b_enc accumulator of the sparse d-activation kernel
-  bool topk_sparse_da = false;  // sparse d pre-activations (topk_dacts_kernel) instead of the dense ddense GEMM + mask
-  // CSC backward (topk_sparse.h): the selection sorted by latent, all three gradients as gathered weighted row sums
-  bool topk_csc = false;
-  unsigned short* csc_counts = nullptr;
-  unsigned int *csc_block_off = nullptr, *csc_total = nullptr, *csc_start = nullptr, *csc_item_start = nullptr, *csc_item_latent = nullptr;
-  unsigned int* csc_multi = nullptr;      // [0] = number of latents with no or several work items, [4 ...] = those latents (csc_items_kernel)
-  CscEntry* csc_entries = nullptr;
-  float *csc_part = nullptr, *csc_pbe = nullptr;
-  int64_t csc_max_items = 0;
-  // cfg.multi_topk (topkautoencoder.py:134-140): a second selection of 4k latents, its decode and its FVU / 8 in the loss
-  bool multi = false;
-  int k4 = 0;
-  bf16_t *multi_dense = nullptr, *dm_b = nullptr;
-  int* multi_idx = nullptr;
-  float *em = nullptr, *m2_part = nullptr;
-  unsigned char* dead = nullptr;
-  // ---- data parallel (dp_kernels.h): batch statistics the losses normalise by, summed over the ranks
-  double* stats = nullptr;      // [stats_cap] doubles
-  int64_t stats_cap = 0, stats_n = 0;   // capacity / doubles the last sae_batch_stats wrote
-  unsigned int* stats_part = nullptr;
-  int dp_world = 0;             // > 0: forward_backward normalises by `stats` (which the host, or the engine's own RCCL
-                                // communicator, has summed over dp_world ranks) instead of this rank's own batch
-  // in-engine RCCL (sae_dist_init): statistics and gradient ranges are all-reduced on a communication stream
-  bool dist = false;
-  ncclComm_t comm = nullptr;
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t ev_x = nullptr, ev_stats = nullptr, ev_done = nullptr;
-  hipEvent_t ev_range[16] = {};
-  int ev_range_i = 0;
-  int payload = SAE_DTYPE_F32;  // SAE_DTYPE_BF16: the fused d = 384 path all-reduces a bf16 copy of the gradient (sae_dist_set_payload)
-  bf16_t* Gb = nullptr;         // that copy
-  bool grads_in_bf16 = false;   // the current step's summed gradient lives in Gb (the optimizer step converts it back)
-  int dist_error = 0;           // a collective of the current call failed to enqueue (message in dist_errmsg)
-  char dist_errmsg[256] = "";
-  // peer exchange over hipIpc mappings (p2p_exchange.h): the exchange of the in-engine protocol when sae_p2p_init was called
-  bool p2p = false;
-  int p2p_rank = 0;
-  float* p2p_G[P2P_MAX_WORLD] = {};
-  bf16_t* p2p_Gb[P2P_MAX_WORLD] = {};
-  double* p2p_stats[P2P_MAX_WORLD] = {};
-  unsigned long long* p2p_sig[P2P_MAX_WORLD] = {};
-  void* p2p_opened[4 * P2P_MAX_WORLD] = {};      // peer mappings to close
-  int p2p_nopened = 0;
-  unsigned long long* sig = nullptr;             // this rank's flag block (uncached device memory)
-  unsigned int* p2p_status = nullptr;            // device words: [0] sticky failure bits the exchange kernels set (P2P_ST_*), [1] self-test mismatches
-  unsigned int* p2p_status_host = nullptr;       // host-mapped mirror of word 0 (hipHostMalloc): sae_dist_poll reads it without a sync
-  unsigned int* p2p_status_hostdev = nullptr;    // its device address
-  int p2p_fault_kind = 0, p2p_fault_rank = -1;   // FREUD_P2P_FAULT=skip_phase2:<rank>[:<after exchanges>] (tests: the guards must catch it)
-  unsigned long long p2p_fault_after = 0;
-  float* col_stage = nullptr;                    // in-engine RCCL, d >= 1024: contiguous staging of the dW column chunks ([d_p x n_p] floats)
-  float* audit_dst = nullptr;                    // sae_dist_audit: every gradient exchange first copies its segments here
-  bool finegrained = false;                      // FREUD_P2P_FINEGRAINED=1: G / Gb / stats in fine-grained device memory
-  unsigned long long p2p_epoch[P2P_CHANNELS] = {};
-  unsigned long long p2p_epoch_push = 0;         // epoch of the statistics push inside finalize_losses_kernel
-  // 120 s of the 100 MHz clock (FREUD_P2P_TIMEOUT_MS): a LIVENESS bound, not a skew budget -- a rank may be late by a loader
-  // stall, a validation pass or a checkpoint write; a failed context fails fast afterwards (sticky status, poisoned flags)
-  unsigned long long p2p_timeout_ticks = 12000000000ull;
-  bool gn_from_exchange = false;                 // gn_part holds the sum of squares of the EXCHANGED gradient
-  int bal_m = 0;                // balanced fused backward (bwd_fused.h): quanta per workgroup (0 = uniform row ranges), workgroups,
-  int bal_grid = 0;             //   and the blockIdx -> workgroup table (XCD-aware)
-  short* bal_map = nullptr;
-  int bwd_ranges = 1;           // fused d = 384 backward: column-tile ranges launched one after the other, each range reduced and
-                                // exchanged on the communication stream under the next range's backward (sae_dist_set_overlap)
-  // fp32 evaluation forward (eval_fp32.h; sae_set_eval_precision): buffers sized lazily for the largest evaluation batch seen
-  bool stats_inline = true;     // fused d = 384 L1 path with the peer exchange: statistics pushed inside finalize_losses_kernel (see inline_stats)
-  bool no_stream = false;       // this context's K = d GEMMs stay on the tile form (FREUD_GEMM_STREAM=0 / debug_flags 86 at ITS creation)
-  int eval_prec = 0;            // 0 = the training kernels' arithmetic (bf16 operands, fp32 accumulate), 1 = fp32 end to end
-  LastCall last_call = LAST_FWD_BF16;   // what the last forward-like call left behind (no_forward_left, the getters)
-  void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
-  int8_t* co_zt = nullptr;      // sae_coact_files scratch (coact.h): the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)]
-  int8_t* lb_lt = nullptr;      // sae_label_files scratch (labels.h): the int8 label pack Lt [lb_rows][round_up(max_rows_p, CO_BK)]
-  int lb_rows = 0;              // its rows: the largest C_p = round_up(n_classes + 1, CO_BM) asked for so far
-  uint32_t* hs_fmax = nullptr;  // sae_hist_files scratch of a TopK context (hist.h): the file maxima [hs_files][n] of one batch
-  int64_t hs_files = 0;         // its files: the largest n_files asked for so far
-  float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
-  float* rc_buf = nullptr;      // sae_recon_files scratch (recon.h): x_hat / r, the slabs, the row and dimension partials, TopK's p
-  int64_t e32_rows = 0;
-  float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
-  double* e32_part = nullptr;
-  int* e32_colmax = nullptr;
-  int64_t step = 0;
-  int64_t last_M = 0, last_M_p = 0;
-  int last_dtype = 0;
-  int profile = 0;
-  int64_t prof_tick = 0;        // forward/backward calls since sae_profile (level 1 samples every prof_period-th)
-  int prof_period = 8;
-  EvRing ev[KID_COUNT];
-  bool ev_init = false;
-};
 
 // fused d = 384 L1 path with the peer exchange: the batch statistics are exchanged inside finalize_losses_kernel (StatsPush)
 // (FREUD_DP_STATS=stream: the statistics leave the critical path instead -- a pass over x and their exchange on the communication stream
@@ -377,58 +82,12 @@ struct sae_ctx {
 // exchange)
 static bool inline_stats(const sae_ctx* c) { return c->p2p && c->use_fused_fwd && !c->topk && c->stats_inline; }
 
-static int use_device(const sae_ctx* c) {
+int use_device(const sae_ctx* c) {
   HIP_TRY(hipSetDevice(c->cfg.device_id));
   g_device = c->cfg.device_id;
   g_force_gemm128 = c->cfg.force_gemm128 == 1;      // per-context launch choices travel with the call, not with the last sae_create
   g_no_stream = c->no_stream;
   return SAE_OK;
-}
-#define USE_DEVICE(c)          \
-  do {                         \
-    int rc_ = use_device(c);   \
-    if (rc_) return rc_;       \
-  } while (0)
-
-// the getters of the last forward refuse after a file pass (after_search = false: after a statistics pass only)
-static int no_forward_left(const sae_ctx* c, bool after_search = true) {
-  if (c->last_call == LAST_SEARCH && !after_search) return SAE_OK;
-  for (const FilePassKind* k : kFilePasses)
-    if (c->last_call == k->leaves)
-      return fail(SAE_ERR_STATE, "the last call was %s: it leaves no forward to read (run sae_eval first)", k->left_by);
-  return SAE_OK;
-}
-
-static void file_pass_end(const FilePassKind& kind, sae_ctx* c) { c->last_call = kind.leaves; }
-
-// the tensors of a bf16 forward (latent rows, top-k indices, 4k buffers, dx_hat, the fp8 operands) are not what the fp32
-// evaluation computed: it has its own buffers and leaves those of the last training step as they were
-static int no_bf16_forward_left(const sae_ctx* c) {
-  if (c->last_call == LAST_FWD_E32)
-    return fail(SAE_ERR_STATE, "the last forward was an fp32 evaluation: it leaves no bf16 latent rows, indices or debug tensors (run a bf16 sae_eval first)");
-  return SAE_OK;
-}
-
-static int dominant_kid(const sae_ctx* c) { return c->topk ? KID_TK_ENC : (c->use_fused_bwd ? KID_BWD_FUSED : KID_DW); }
-// Level 1 brackets the dominant kernel and the whole step on every PROF_PERIOD-th step only: an event record is a packet of
-// its own in the queue and costs ~6 us of idle GPU between two dependent kernels (kernel trace of the C2 step: 3 records
-// per step were 3 % of it), so the timed region of bench.py samples instead of instrumenting every step (sae_profile_period).
-static bool ev_on(const sae_ctx* c, int kid) {
-  if (c->profile >= 2) return true;
-  return c->profile == 1 && (kid == dominant_kid(c) || kid == KID_STEP_TOTAL) && (c->prof_tick % c->prof_period) == 0;
-}
-static void ev_begin(sae_ctx* c, int kid, hipStream_t s) {
-  if (ev_on(c, kid)) {
-    EvRing& r = c->ev[kid];
-    (void)hipEventRecord(r.beg[r.n % EV_RING], s);   // a failure stays sticky and is reported by the hipGetLastError that ends the call
-  }
-}
-static void ev_end(sae_ctx* c, int kid, hipStream_t s) {
-  if (ev_on(c, kid)) {
-    EvRing& r = c->ev[kid];
-    (void)hipEventRecord(r.end[r.n % EV_RING], s);
-    r.n++;
-  }
 }
 
 extern "C" const char* sae_last_error(void) { return g_err; }
@@ -1625,86 +1284,8 @@ extern "C" int sae_dist_poll(sae_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// launches
+// launches (the bf16 GEMM launchers: gemm_launch.h)
 // ------------------------------------------------------------------------------------------
-// true: launch_gemm runs this GEMM in the streaming form of gemm256s.h (the K = d GEMMs: row-major x row-major, one K segment,
-// thousands of static output tiles) -- callers that size a per-workgroup output of the functor ask first
-template <int AM, int BM_, class Epi>
-static bool gemm_streams(const GemmArgs& g) {
-  if constexpr (!(epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW)) return false;
-  if (g_no_stream || g_force_gemm128 || g.nbm % 2 != 0 || g.nbn % 2 != 0) return false;
-  if (g.ktiles % 2 != 0) return false;                     // (the static-stage K loop walks the K tiles in pairs: gemm256s.h)
-  return !g.dyn && g.splits == 1 && g.tail_tiles == 0 && g.ktiles == g.ktiles0 && g.ktiles >= 2 && g.seg1_gate == nullptr && g.lda == g.ldb &&
-         (g.nbm / 2) * (g.nbn / 2) >= 4 * G2_PERSIST_STATIC;
-}
-
-// the streaming form itself, for a GEMM that gemm_streams() accepted (the file passes launch it with epilogues that have only the
-// streaming interface, so they cannot go through launch_gemm, whose tile-form branches would be instantiated with them)
-template <class Epi>
-static int launch_gemm_stream(const GemmArgs& g, const Epi& epi, hipStream_t s) {
-  auto kerns = gemm256s_bf16_kernel<Epi>;
-  LDS_ATTR(kerns, G2S_LDS_BYTES, g_device);
-  GemmArgs g2 = g;
-  g2.nbm = g.nbm / 2;
-  g2.nbn = g.nbn / 2;
-  hipLaunchKernelGGL(kerns, dim3(G2_PERSIST_STATIC), dim3(512), G2S_LDS_BYTES, s, g2, epi);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// functors that opt out of gemm256.h's tile-walking (PERSIST) instantiation: static constexpr bool NO_PERSIST = true
-template <class E, class = void>
-struct epi_no_persist { static constexpr bool value = false; };
-template <class E>
-struct epi_no_persist<E, std::void_t<decltype(E::NO_PERSIST)>> { static constexpr bool value = E::NO_PERSIST; };
-
-template <int AM, int BM_, class Epi>
-static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
-  if constexpr (epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW) {
-    if (gemm_streams<AM, BM_, Epi>(g)) return launch_gemm_stream(g, epi, s);
-  }
-  if (!g_force_gemm128 && g.nbm % 2 == 0 && g.nbn % 2 == 0) {   // both output dimensions are multiples of 256
-    auto kern256 = gemm256_bf16_kernel<AM, BM_, Epi>;
-    constexpr bool a3 = epi_deep_a_ring<Epi>::value;     // (gemm256.h: three A slots + two B slots)
-    constexpr int lds256 = a3 ? G2_A3_LDS_BYTES : (epi_rounds_first<Epi>::value && G2_BF16_LDS_BYTES > G2_LDS_BYTES) ? G2_BF16_LDS_BYTES : G2_LDS_BYTES;
-    static_assert(G2_A3_LDS_BYTES >= G2_BF16_LDS_BYTES && G2_A3_LDS_BYTES >= G2_LDS_BYTES, "the epilogues reuse the ring's LDS");
-    LDS_ATTR(kern256, lds256, g_device);
-    GemmArgs g2 = g;
-    g2.nbm = g.nbm / 2;
-    g2.nbn = g.nbn / 2;
-    const int grid_max = (g.dyn && g.grid_cover > 0) ? g.grid_cover
-                         : g2.tail_tiles > 0    ? g2.nbm * g2.nbn + g2.tail_tiles * (g2.tail_pieces - 1)
-                                                : g2.nbm * g2.nbn * g2.splits;
-    const int grid_est = (((g.grid_hint + 3) / 4 + 7) / 8) * 8;          // 256x256 tiles, a multiple of 8
-    // (the caller sets grid_hint only for a SMALL estimated extent: the persistent instantiation's tile loop costs the K loop
-    // ~10 %, while the workgroups that start only to exit are cheap until they are the great majority)
-    if constexpr (epi_no_persist<Epi>::value) {              // (a functor whose state does not fit the tile-walking instantiation)
-      hipLaunchKernelGGL(kern256, dim3(grid_max), dim3(512), lds256, s, g2, epi);
-    } else
-    if (G2_PERSIST_STATIC > 0 && !g.dyn && g2.splits == 1 && g2.tail_tiles == 0 && grid_max >= 4 * G2_PERSIST_STATIC) {
-      // big static launches (the K = d GEMMs: tens of thousands of tiles) as G2_PERSIST_STATIC resident workgroups that walk
-      // the tiles: encoder / dpre -2 %, TopK encoder -2.5 % against one workgroup per tile (same box; 256 / 512 / 1024 measure alike)
-      auto kernp = gemm256_bf16_kernel<AM, BM_, Epi, true>;
-      LDS_ATTR(kernp, lds256, g_device);
-      hipLaunchKernelGGL(kernp, dim3(G2_PERSIST_STATIC), dim3(512), lds256, s, g2, epi);
-    } else if (g.dyn && g.grid_hint > 0 && grid_est < grid_max) {
-      auto kernp = gemm256_bf16_kernel<AM, BM_, Epi, true>;
-      LDS_ATTR(kernp, lds256, g_device);
-      hipLaunchKernelGGL(kernp, dim3(grid_est < 256 ? 256 : grid_est), dim3(512), lds256, s, g2, epi);
-    } else {
-      hipLaunchKernelGGL(kern256, dim3(grid_max), dim3(512), lds256, s, g2, epi);
-    }
-    HIP_TRY(hipGetLastError());
-    return SAE_OK;
-  }
-  auto kern = gemm_bf16_kernel<AM, BM_, Epi>;
-  LDS_ATTR(kern, GEMM_LDS_BYTES, g_device);
-  const int grid = (g.dyn && g.grid_cover > 0) ? g.grid_cover : g.nbm * g.nbn * g.splits;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), GEMM_LDS_BYTES, s, g, epi);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
 template <class Epi>
 static bool gemm8_streams(const Gemm8Args& g) {
   if constexpr (!epi_stream<Epi>::value) return false;
@@ -1731,7 +1312,7 @@ static int launch_gemm8(const Gemm8Args& g, const Epi& epi, hipStream_t s) {
 }
 
 // The in-place column normalisation every L1 forward starts with (l1autoencoder.py:71-73), and the bf16 copies of the result.
-static void prep_weights_l1(sae_ctx* c, hipStream_t s) {
+void prep_weights_l1(sae_ctx* c, hipStream_t s) {
   const int d_p = c->d_p, n_p = c->n_p;
   float* W = c->P;
   if (c->wn_pending && !c->wn_fwd_seen) {
@@ -1762,7 +1343,7 @@ static int launch_prep_x(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStrea
 }
 
 // x W: xb [Mp][d_p] times Wt [n_p][d_p]
-static GemmArgs enc_gemm_args(const sae_ctx* c, const bf16_t* xb, int64_t Mp) {
+GemmArgs enc_gemm_args(const sae_ctx* c, const bf16_t* xb, int64_t Mp) {
   GemmArgs g{};
   g.A0 = xb; g.B0 = c->Wt; g.lda = c->d_p; g.ldb = c->d_p;
   g.nbm = (int)(Mp / 128); g.nbn = c->n_p / 128; g.ktiles0 = g.ktiles = c->d_p / 64; g.splits = 1;
@@ -2614,7 +2195,7 @@ static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dt
 // all-reduce on the communication stream, concurrent with the weight preparation and the forward kernels (they depend on
 // x only); (2) [the step's kernels; every gradient range is all-reduced on the communication stream as soon as it is
 // final, notify_grads]; (3) the compute stream waits for the last of those all-reduces.
-static int dispatch_fwd_bwd(sae_ctx* c, const void* x, int64_t M, int x_dtype, void* stream, bool backward) {
+int dispatch_fwd_bwd(sae_ctx* c, const void* x, int64_t M, int x_dtype, void* stream, bool backward) {
   if (!c || !x) return fail(SAE_ERR_INVALID, "null argument");
   if (M <= 0 || M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "M=%lld outside (0, max_rows=%lld]", (long long)M, (long long)c->cfg.max_rows);
   USE_DEVICE(c);
@@ -3046,7 +2627,7 @@ extern "C" int sae_multi_topk_buffers(sae_ctx* c, void** dense_dev, int64_t* row
 }
 
 // (defined below sae_decode, whose TopK GEMM is instantiated first: the kernels keep their place in the code object, as at launch_encoder)
-static int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s);
+int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s);
 
 extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int64_t ld, int64_t M, float* x_hat, void* stream) {
   if (!c || !latent || !x_hat) return fail(SAE_ERR_INVALID, "null argument");
@@ -3088,7 +2669,7 @@ extern "C" int sae_decode(sae_ctx* c, const void* latent, int latent_dtype, int6
 // x_hat [M][d] = lat W^T of an L1 context, no bias: `lat` the padded bf16 latent [nbm * 128][n_p], W the current weights as they are
 // (settled, not renormalised: decode()) in their bf16 copy, which the next forward refreshes anyway.  The one L1 decode of a stored
 // latent: sae_decode, sae_manipulate_files and sae_recon_files agree to the bit because they all run this.
-static int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s) {
+int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s) {
   settle_weights(c, s);
   const int64_t n8 = c->nW / 8;
   hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P, c->Wb, n8);
@@ -3159,1014 +2740,17 @@ extern "C" int sae_eval_into(sae_ctx* c, const void* x, int64_t M, int x_dtype, 
   return SAE_OK;
 }
 
-// ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
-static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
-                                   bool absolute, uint64_t* keys, uint64_t* aux, hipStream_t s) {
-  const int chunk = 128;
-  const dim3 grid((unsigned)((ncols + 255) / 256), (unsigned)n_files, (unsigned)((Trows + chunk - 1) / chunk));
-  const int64_t pairs = n_files * ncols;
-  const unsigned fgrid = (unsigned)((pairs + 255) / 256);
-  int rc = with_x_type(x_dtype, x, [&](auto* xt) {
-    using T = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
-    if (absolute) {
-      hipLaunchKernelGGL((search_colreduce_kernel<T, true>), grid, dim3(256), 0, s, xt, ld, ncols, Trows, lengths, chunk, keys, aux);
-      hipLaunchKernelGGL(search_abs_fixup_kernel<T>, dim3(fgrid), dim3(256), 0, s, xt, ld, ncols, Trows, n_files, keys, aux);
-    } else {
-      hipLaunchKernelGGL((search_colreduce_kernel<T, false>), grid, dim3(256), 0, s, xt, ld, ncols, Trows, lengths, chunk, keys, nullptr);
-    }
+// ---- the L1 encoder's front for passes.hip: launch_prep_x and launch_encoder behind plain functions (engine_internal.h).  Down
+// here, behind every caller of the training paths, so that the kernels are instantiated where they always were.
+// (x_dtype was checked at the pass's front door, file_pass_begin; the count of partials launch_prep_x returns is the training forward's)
+void launch_prep_x_dtype(sae_ctx* c, const void* x, int x_dtype, int64_t M, int64_t Mp, hipStream_t s) {
+  (void)with_x_type(x_dtype, x, [&](auto* xt) {
+    launch_prep_x(c, xt, M, Mp, s);
     return (int)SAE_OK;
   });
-  if (rc) return rc;
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
 }
 
-// ---- what the file passes share (FilePassKind, above): one batch of files encoded with the training kernels
-static int search_shape_check(int64_t n_files, int64_t rows_per_file) {
-  if (n_files <= 0 || rows_per_file <= 0) return fail(SAE_ERR_INVALID, "n_files=%lld and rows_per_file=%lld must be positive", (long long)n_files, (long long)rows_per_file);
-  if (n_files > 65535) return fail(SAE_ERR_INVALID, "n_files=%lld > 65535 in one call", (long long)n_files);
-  // (the column reduction launches one grid z-slice per 128 rows of a file: at most 65535 of them)
-  if (rows_per_file > 65535ll * 128) return fail(SAE_ERR_INVALID, "rows_per_file=%lld > %lld", (long long)rows_per_file, 65535ll * 128);
-  return SAE_OK;
-}
-
-// the front door of every file pass: argument checks (nothing is enqueued when one fails), then the context's device
-static int file_pass_begin(const FilePassKind& kind, sae_ctx* c, const void* x, const void* out, int64_t n_files, int64_t rows_per_file,
-                           int x_dtype, int flags, int64_t* M) {
-  if (!c || !x || !out) return fail(SAE_ERR_INVALID, "null argument");
-  if (c->fp8) return fail(SAE_ERR_INVALID, "%s: fp8 contexts are not supported (%s)", kind.fn, kind.fp8_advice);
-  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
-  *M = n_files * rows_per_file;
-  if (*M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "n_files * rows_per_file = %lld > max_rows=%lld", (long long)*M, (long long)c->cfg.max_rows);
-  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  if (flags & ~kind.flags_mask) return fail(SAE_ERR_INVALID, "unknown %s flags 0x%x", kind.flags_noun, flags);
-  USE_DEVICE(c);
-  return SAE_OK;
-}
-
-// L1: forward_impl's weights preparation and bf16 copy of x, then the GEMM arguments of its encoder -- for the epilogue the pass
-// brings (EpiSearch, EpiStats) where the GEMM streams, for file_pass_l1_encode and a reduction of the stored latent where it does not
-template <typename T>
-static GemmArgs file_pass_l1_front(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
-  int64_t Mp = round_up(M, 128);
-  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);    // (an even number of row blocks: the streaming GEMM's condition)
-  prep_weights_l1(c, s);
-  launch_prep_x(c, x, M, Mp, s);
-  return enc_gemm_args(c, c->xb, Mp);
-}
-
-// the pass's own epilogue in the streaming GEMM, inside the encoder's event bracket
-template <class Epi>
-static int file_pass_l1_fused(sae_ctx* c, const GemmArgs& g, const Epi& e, hipStream_t s) {
-  ev_begin(c, KID_ENC_FWD, s);
-  const int rc = launch_gemm_stream(g, e, s);
-  ev_end(c, KID_ENC_FWD, s);
-  return rc;
-}
-
-// L1: the batch's latent as encode() returns it, stored as bf16 rows in c->c -- the front (the caller's own `front` where it has run
-// one to decide on its fused form), then the ordinary encoder.  Mp: the rows the front padded to.
-template <typename T>
-static int file_pass_l1_encode(sae_ctx* c, const T* x, int64_t M, hipStream_t s, const GemmArgs* front = nullptr, int64_t* Mp = nullptr) {
-  const GemmArgs g = front ? *front : file_pass_l1_front(c, x, M, s);
-  if (Mp) *Mp = (int64_t)g.nbm * 128;
-  return launch_encoder<T>(c, g, M, s);
-}
-
-// The encoder as encode() runs it: the stored L1 latent, or c->top_idx / c->top_vals of the eval forward (encoder GEMM + top-k
-// selection, the k of encode())
-static int file_pass_encode(sae_ctx* c, const void* x, int64_t M, int x_dtype, hipStream_t s) {
-  if (c->topk) return dispatch_fwd_bwd(c, x, M, x_dtype, s, false);
-  return with_x_type(x_dtype, x, [&](auto* xt) { return file_pass_l1_encode(c, xt, M, s); });
-}
-
-// L1 search: where the streaming GEMM does not apply (small or odd shapes, FREUD_GEMM_STREAM=0, force_gemm128) or `unfused` is asked
-// for (the baseline of tools/bench_search.py), the latent is stored by the ordinary encoder and reduced by the column kernel.
-template <typename T>
-static int search_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, int64_t n_files, const int* lengths, uint64_t* keys, bool unfused,
-                          hipStream_t s) {
-  const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  HIP_TRY(hipMemsetAsync(keys, 0, (size_t)n_files * c->n * 8, s));
-  if (!unfused && Trows <= 65535 && gemm_streams<OP_ROW, OP_ROW, EpiSearch>(g)) {
-    EpiSearch e{};
-    e.bias = c->P + c->nW; e.keys = keys; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n;
-    return file_pass_l1_fused(c, g, e, s);
-  }
-  if (int rc = file_pass_l1_encode(c, x, M, s, &g)) return rc;
-  return search_launch_colreduce(c->c, SAE_DTYPE_BF16, c->n_p, c->n, Trows, n_files, lengths, false, keys, nullptr, s);
-}
-
-extern "C" int sae_search_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                                int flags, uint64_t* file_keys, void* stream) {
-  int64_t M;
-  if (int rc = file_pass_begin(kSearchPass, c, x, file_keys, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  if (c->topk) {
-    // the keys filled, then the selection of encode() scattered into them
-    const int64_t nk = n_files * c->n;
-    hipLaunchKernelGGL(search_fill_kernel, dim3(grid_for(nk, 4096)), dim3(256), 0, s, file_keys, nk, (uint64_t)SK_KEY_ZERO_FRAME0);
-    if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-    hipLaunchKernelGGL(search_topk_scatter_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, Trows,
-                       lengths, c->n, file_keys);
-    HIP_TRY(hipGetLastError());
-  } else {
-    const bool unfused = (flags & SAE_SEARCH_UNFUSED) != 0;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return search_l1_impl(c, xt, M, Trows, n_files, lengths, file_keys, unfused, s); }))
-      return rc;
-  }
-  file_pass_end(kSearchPass, c);
-  return SAE_OK;
-}
-
-extern "C" int sae_search_raw_files(const void* x, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths,
-                                    int absolute, uint64_t* file_keys, uint64_t* aux, void* stream) {
-  if (!x || !file_keys || (absolute && !aux)) return fail(SAE_ERR_INVALID, "null argument");
-  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
-  if (d <= 0 || d > (1 << 24)) return fail(SAE_ERR_INVALID, "d=%lld outside (0, 2^24]", (long long)d);
-  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
-  hipStream_t s = (hipStream_t)stream;
-  HIP_TRY(hipMemsetAsync(file_keys, 0, (size_t)(n_files * d) * 8, s));
-  if (absolute) HIP_TRY(hipMemsetAsync(aux, 0, (size_t)(n_files * d) * 8, s));
-  return search_launch_colreduce(x, x_dtype, d, (int)d, (int)rows_per_file, n_files, lengths, absolute != 0, file_keys, aux, s);
-}
-
-extern "C" int sae_search_merge(const uint64_t* file_keys, const uint64_t* aux, int64_t n_files, int64_t ncols, int64_t file0, int n_top,
-                                int flags, double min_val, double max_val, uint64_t* top_keys, int32_t* top_frames, void* stream) {
-  if (!file_keys || !top_keys || !top_frames) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_files <= 0 || ncols <= 0 || file0 < 0) return fail(SAE_ERR_INVALID, "n_files=%lld, ncols=%lld, file0=%lld", (long long)n_files, (long long)ncols, (long long)file0);
-  if (file0 + n_files >= 0xFFFFFFFFll) return fail(SAE_ERR_INVALID, "file indices beyond 2^32 - 2");
-  if (n_top < 1 || n_top > SAE_SEARCH_MAX_TOP) return fail(SAE_ERR_INVALID, "n_top=%d outside [1, %d]", n_top, SAE_SEARCH_MAX_TOP);
-  if (flags & ~(SAE_SEARCH_ABS | SAE_SEARCH_MIN | SAE_SEARCH_MAX)) return fail(SAE_ERR_INVALID, "unknown merge flags 0x%x", flags);
-  hipLaunchKernelGGL(search_merge_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, (hipStream_t)stream, file_keys, aux, n_files,
-                     ncols, file0, n_top, flags, min_val, max_val, top_keys, top_frames);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_search_file_values(const uint64_t* file_keys, const uint64_t* aux, int64_t n_files, int64_t ncols, int flags,
-                                      const int32_t* latents, int64_t n_latents, int64_t file0, int64_t out_stride, float* out, void* stream) {
-  if (!file_keys || !latents || !out) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_files <= 0 || ncols <= 0 || n_latents <= 0 || file0 < 0) return fail(SAE_ERR_INVALID, "empty or negative extent");
-  if (out_stride < file0 + n_files) return fail(SAE_ERR_INVALID, "out_stride=%lld < file0 + n_files=%lld", (long long)out_stride, (long long)(file0 + n_files));
-  const int64_t total = n_latents * n_files;
-  hipLaunchKernelGGL(search_values_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, file_keys, aux, n_files,
-                     ncols, flags, latents, n_latents, file0, out_stride, out);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// ---- file features (file_top.h): the top-N latents of every file of a batch, selected from its file keys
-static_assert(SAE_FILE_TOP_POSITIVE == FT_POSITIVE && SAE_FILE_TOP_MAX == FT_MAX_TOP, "freud_sae.h and file_top.h disagree");
-
-extern "C" int sae_file_top_features(const uint64_t* file_keys, int64_t n_files, int64_t ncols, int n_top, int flags, int32_t* top_latents,
-                                     uint64_t* top_keys, void* stream) {
-  if (!file_keys || !top_latents || !top_keys) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_files < 1 || ncols < 1) return fail(SAE_ERR_INVALID, "n_files=%lld, ncols=%lld", (long long)n_files, (long long)ncols);
-  if (n_files > 0x7FFFFFFFll || ncols > FT_MAX_COLS) return fail(SAE_ERR_INVALID, "n_files=%lld > 2^31 - 1 or ncols=%lld > 2^24", (long long)n_files, (long long)ncols);
-  if (n_top < 1 || n_top > SAE_FILE_TOP_MAX) return fail(SAE_ERR_INVALID, "n_top=%d outside [1, %d]", n_top, SAE_FILE_TOP_MAX);
-  if (flags & ~SAE_FILE_TOP_POSITIVE) return fail(SAE_ERR_INVALID, "unknown file-top flags 0x%x", flags);
-  hipLaunchKernelGGL(file_top_kernel, dim3((unsigned)n_files), dim3(FT_THREADS), 0, (hipStream_t)stream, file_keys, ncols, n_top, flags,
-                     top_latents, top_keys);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// ---- feature statistics (stats.h): per-latent firing counts, sums, maxima and the L0 histogram of one batch of files
-// fs_slab: the slab [max_rows_p / STATS_RB][n] x 4 words of 4 bytes, then (L1) one L0 byte per row and 64 latents
-static int64_t stats_slab_words(const sae_ctx* c) { return (c->max_rows_p / STATS_RB) * (int64_t)c->n; }
-static uint8_t* stats_l0_bytes(const sae_ctx* c) { return (uint8_t*)c->fs_slab + stats_slab_words(c) * 16; }
-
-static int stats_ensure(sae_ctx* c) {
-  if (c->fs_slab) return SAE_OK;
-  const int64_t l0_bytes = c->topk ? 0 : c->max_rows_p * (int64_t)(c->n_p / 64);
-  HIP_TRY(hipMalloc(&c->fs_slab, (size_t)(stats_slab_words(c) * 16 + l0_bytes)));
-  return SAE_OK;
-}
-
-static StatsSlab stats_slab(sae_ctx* c) {
-  const int64_t words = stats_slab_words(c);
-  StatsSlab sl;
-  sl.cnt = (uint32_t*)c->fs_slab;
-  sl.mx = sl.cnt + words;
-  sl.sum = (float*)(sl.mx + words);
-  sl.sq = sl.sum + words;
-  return sl;
-}
-
-struct StatsOut {               // the caller's block (include/freud_sae.h, SAE_STATS_*)
-  unsigned long long *n_frames, *fire, *hist;
-  double *asum, *asq;
-  float* amax;
-};
-
-static StatsOut stats_out(void* block, int n) {
-  char* b = (char*)block;
-  StatsOut o;
-  o.n_frames = (unsigned long long*)(b + SAE_STATS_N_FRAMES(n));
-  o.fire = (unsigned long long*)(b + SAE_STATS_FIRE_COUNT(n));
-  o.asum = (double*)(b + SAE_STATS_ACT_SUM(n));
-  o.asq = (double*)(b + SAE_STATS_ACT_SQ_SUM(n));
-  o.hist = (unsigned long long*)(b + SAE_STATS_L0_HIST(n));
-  o.amax = (float*)(b + SAE_STATS_ACT_MAX(n));
-  return o;
-}
-
-template <class Src>
-static void stats_launch_l0(Src src, int64_t M, int T, const int* lengths, int n, const StatsOut& o, hipStream_t s) {
-  hipLaunchKernelGGL(stats_l0_kernel<Src>, dim3(grid_for(M, 1024, 4)), dim3(256), 0, s, src, M, T, lengths, n + 1, o.hist, o.n_frames);
-}
-
-static void stats_launch_fold(sae_ctx* c, int nrb, const StatsOut& o, hipStream_t s) {
-  hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, stats_slab(c), nrb, c->n, o.fire, o.asum, o.asq,
-                     o.amax);
-}
-
-// L1 statistics: where the streaming GEMM does not apply, or `unfused` is asked for, the ordinary encoder stores the latent and two
-// kernels reduce it (column statistics into the slab, row counts into the histogram).
-template <typename T>
-static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, const StatsOut& o, bool unfused, hipStream_t s) {
-  const int n_p = c->n_p;
-  const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  const StatsSlab sl = stats_slab(c);
-  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
-  if (!unfused && gemm_streams<OP_ROW, OP_ROW, EpiStats>(g)) {
-    uint8_t* l0b = stats_l0_bytes(c);
-    EpiStats e{};
-    e.bias = c->P + c->nW; e.slab = sl; e.l0b = l0b; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n; e.ncb = n_p / 64;
-    e.inv_T = 1.0f / (float)Trows;
-    if (int rc = file_pass_l1_fused(c, g, e, s)) return rc;
-    stats_launch_l0(L0Bytes{l0b, n_p / 64}, M, Trows, lengths, c->n, o, s);
-  } else {
-    if (int rc = file_pass_l1_encode(c, x, M, s, &g)) return rc;
-    const unsigned short* lat = (const unsigned short*)c->c;
-    hipLaunchKernelGGL(stats_colreduce_kernel, dim3((unsigned)((c->n + 255) / 256), (unsigned)nrb), dim3(256), 0, s, lat, (int64_t)n_p, c->n,
-                       M, Trows, lengths, sl);
-    stats_launch_l0(L0Latent{lat, n_p, c->n}, M, Trows, lengths, c->n, o, s);
-  }
-  stats_launch_fold(c, nrb, o, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                               int flags, void* stats, void* stream) {
-  int64_t M;
-  if (int rc = file_pass_begin(kStatsPass, c, x, stats, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (misaligned(stats, 8)) return fail(SAE_ERR_INVALID, "the stats block must be 8-byte aligned");
-  if (int rc = stats_ensure(c)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  const StatsOut o = stats_out(stats, c->n);
-  if (c->topk) {
-    // the statistics of encode()'s selection
-    if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-    const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
-    const unsigned short* vals = (const unsigned short*)c->top_vals;
-    hipLaunchKernelGGL(stats_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
-                       c->top_idx, vals, c->k, M, Trows, lengths, c->n, stats_slab(c));
-    stats_launch_l0(L0Topk{vals, c->k}, M, Trows, lengths, c->n, o, s);
-    stats_launch_fold(c, nrb, o, s);
-    HIP_TRY(hipGetLastError());
-  } else {
-    const bool unfused = (flags & SAE_STATS_UNFUSED) != 0;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return stats_l1_impl(c, xt, M, Trows, lengths, o, unfused, s); })) return rc;
-  }
-  file_pass_end(kStatsPass, c);
-  return SAE_OK;
-}
-
-// ---- feature co-activation (coact.h): C += Zt Zt^T of one batch of files on the i8 MFMA, and the neighbour keys of rows of C
-static_assert(SAE_COACT_JACCARD == CO_JACCARD && SAE_COACT_COND == CO_COND && SAE_COACT_COUNT == CO_COUNT, "freud_sae.h and coact.h disagree");
-
-static int coact_ensure(sae_ctx* c) {
-  if (c->co_zt) return SAE_OK;
-  HIP_TRY(hipMalloc((void**)&c->co_zt, (size_t)((int64_t)c->n_p * round_up(c->max_rows_p, CO_BK))));
-  return SAE_OK;
-}
-
-// the K split of coact.h's header: enough slices of the Kp / CO_BK steps that `tiles` output tiles fill CO_MIN_WGS workgroups, `per` steps each
-struct KSplit { int ksplit, per; };
-static KSplit coact_ksplit(int64_t tiles, int64_t Kp) {
-  const int nsteps = (int)(Kp / CO_BK);
-  const int want = (int)std::min<int64_t>(std::max<int64_t>((CO_MIN_WGS + tiles - 1) / tiles, 1), nsteps);
-  const int per = (nsteps + want - 1) / want;
-  return {(nsteps + per - 1) / per, per};
-}
-
-// the update of one batch's mask Zt [n_p][Kp] (n_p a multiple of CO_BM)
-static int coact_launch_update(sae_ctx* c, const int8_t* zt, int64_t Kp, int n_p, int n, int32_t* counts, hipStream_t s) {
-  const int nt = n_p / CO_BM;
-  const int64_t ntiles = (int64_t)nt * (nt + 1) / 2;
-  const KSplit ks = coact_ksplit(ntiles, Kp);
-  const dim3 grid((unsigned)nt, (unsigned)nt, (unsigned)ks.ksplit);
-  ev_begin(c, KID_COACT_UPDATE, s);
-  if (ks.ksplit > 1) hipLaunchKernelGGL(coact_update_kernel<true>, grid, dim3(256), 0, s, zt, Kp, n, ks.per, counts);
-  else hipLaunchKernelGGL(coact_update_kernel<false>, grid, dim3(256), 0, s, zt, Kp, n, ks.per, counts);
-  ev_end(c, KID_COACT_UPDATE, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// the batch's activity mask into c->co_zt: the encoder as encode() runs it, then the mask pack (sae_coact_files, sae_label_files)
-static int coact_encode_pack(sae_ctx* c, const void* x, int64_t M, int Trows, int x_dtype, const int32_t* lengths, int64_t Kp, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-  ev_begin(c, KID_COACT_PACK, s);
-  hipError_t memset_zt = hipSuccess;
-  if (c->topk) {                            // the selection scattered into the zeroed mask
-    memset_zt = hipMemsetAsync(c->co_zt, 0, (size_t)((int64_t)c->n_p * Kp), s);
-    if (memset_zt == hipSuccess)
-      hipLaunchKernelGGL(coact_pack_topk_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
-                         c->k, M, Trows, lengths, c->n, c->co_zt, Kp);
-  } else {
-    hipLaunchKernelGGL(coact_pack_l1_kernel, dim3((unsigned)(Kp / 64), (unsigned)(c->n_p / 64)), dim3(256), 0, s, (const unsigned short*)c->c,
-                       (int64_t)c->n_p, c->n, M, Trows, lengths, c->co_zt, Kp);
-  }
-  ev_end(c, KID_COACT_PACK, s);             // (the bracket closes whatever the memset answered)
-  HIP_TRY(memset_zt);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                               int flags, int32_t* counts, void* stream) {
-  int64_t M;
-  if (int rc = file_pass_begin(kCoactPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (misaligned(counts, 4)) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
-  if (int rc = coact_ensure(c)) return rc;
-  const int64_t Kp = round_up(M, CO_BK);
-  if (int rc = coact_encode_pack(c, x, M, (int)rows_per_file, x_dtype, lengths, Kp, stream)) return rc;
-  if (int rc = coact_launch_update(c, c->co_zt, Kp, c->n_p, c->n, counts, (hipStream_t)stream)) return rc;
-  file_pass_end(kCoactPass, c);
-  return SAE_OK;
-}
-
-extern "C" int sae_coact_neighbor_keys(const int32_t* counts, int64_t n, int64_t row0, int64_t n_rows, int measure, uint64_t* keys, void* stream) {
-  if (!counts || !keys) return fail(SAE_ERR_INVALID, "null argument");
-  if (n < 1 || n > FT_MAX_COLS) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24]", (long long)n);
-  if (n_rows < 1 || row0 < 0 || row0 + n_rows > n)
-    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)n);
-  if (measure != SAE_COACT_JACCARD && measure != SAE_COACT_COND && measure != SAE_COACT_COUNT) return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
-  hipLaunchKernelGGL(coact_keys_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
-                     (hipStream_t)stream, counts, (int)n, row0, n_rows, measure, keys);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// ---- feature labels (labels.h): A += Lt Zt^T of one batch of files -- co-activation's mask against the frames' labels -- and the keys
-// of a block of rows of A in either orientation
-static_assert(SAE_LABEL_F1 == LB_F1 && SAE_LABEL_PRECISION == LB_PRECISION && SAE_LABEL_RECALL == LB_RECALL && SAE_LABEL_COUNT == LB_COUNT &&
-              SAE_LABEL_MAX_CLASSES == LB_MAX_CLASSES && SAE_LABEL_MAX_SLOTS == LB_MAX_SLOTS, "freud_sae.h and labels.h disagree");
-
-static int label_ensure(sae_ctx* c, int C_p) {
-  if (C_p <= c->lb_rows) return SAE_OK;
-  if (c->lb_lt) HIP_TRY(hipFree(c->lb_lt));          // (hipFree waits for the work that still reads it)
-  c->lb_lt = nullptr;
-  c->lb_rows = 0;
-  HIP_TRY(hipMalloc((void**)&c->lb_lt, (size_t)((int64_t)C_p * round_up(c->max_rows_p, CO_BK))));
-  c->lb_rows = C_p;
-  return SAE_OK;
-}
-
-extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                               const int32_t* labels, int n_slots, int n_classes, int flags, int32_t* counts, int64_t* label_count,
-                               void* stream) {
-  int64_t M;
-  if (!labels || !label_count) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_slots < 1 || n_slots > SAE_LABEL_MAX_SLOTS) return fail(SAE_ERR_INVALID, "n_slots=%d outside [1, %d]", n_slots, SAE_LABEL_MAX_SLOTS);
-  if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%d outside [1, %d]", n_classes, SAE_LABEL_MAX_CLASSES);
-  if (misaligned(counts, 4) || misaligned(label_count, 8))
-    return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned and label_count 8-byte aligned");
-  if (int rc = file_pass_begin(kLabelPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  const int C_p = (int)round_up(n_classes + 1, CO_BM);
-  if (int rc = coact_ensure(c)) return rc;
-  if (int rc = label_ensure(c, C_p)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  const int64_t Kp = round_up(M, CO_BK);
-  if (int rc = coact_encode_pack(c, x, M, Trows, x_dtype, lengths, Kp, stream)) return rc;
-
-  ev_begin(c, KID_LABEL_PACK, s);
-  const hipError_t memset_lt = hipMemsetAsync(c->lb_lt, 0, (size_t)((int64_t)C_p * Kp), s);
-  if (memset_lt == hipSuccess) {
-    hipLaunchKernelGGL(label_pack_kernel, dim3(grid_for(M * n_slots, 4096)), dim3(256), 0, s, labels, n_slots, n_classes, M, Trows, lengths,
-                       c->lb_lt, Kp);
-    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)(n_classes + 1)), dim3(256), 0, s, c->lb_lt, Kp, (unsigned long long*)label_count);
-  }
-  ev_end(c, KID_LABEL_PACK, s);             // (the bracket closes whatever the memset answered)
-  HIP_TRY(memset_lt);
-  HIP_TRY(hipGetLastError());
-
-  // the K split of coact.h's header over the rectangle's tiles
-  const int ntr = C_p / CO_BM, ntc = c->n_p / CO_BM;
-  const KSplit ks = coact_ksplit(ntr * ntc, Kp);
-  const dim3 grid((unsigned)ntc, (unsigned)ntr, (unsigned)ks.ksplit);
-  ev_begin(c, KID_LABEL_UPDATE, s);
-  if (ks.ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, ks.per, counts);
-  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, ks.per, counts);
-  ev_end(c, KID_LABEL_UPDATE, s);
-  HIP_TRY(hipGetLastError());
-  file_pass_end(kLabelPass, c);
-  return SAE_OK;
-}
-
-extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count, int64_t n_classes, int64_t n, int measure, int by_latent,
-                              int64_t row0, int64_t n_rows, uint64_t* keys, void* stream) {
-  if (!counts || !label_count || !keys) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%lld outside [1, %d]", (long long)n_classes, SAE_LABEL_MAX_CLASSES);
-  if (n < 1 || n > FT_MAX_COLS) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24]", (long long)n);
-  if (by_latent != 0 && by_latent != 1) return fail(SAE_ERR_INVALID, "by_latent=%d is neither 0 nor 1", by_latent);
-  const int64_t rows_all = by_latent ? n : n_classes, ncols = by_latent ? n_classes : n;
-  if (n_rows < 1 || row0 < 0 || row0 + n_rows > rows_all)
-    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)rows_all);
-  if (measure != SAE_LABEL_F1 && measure != SAE_LABEL_PRECISION && measure != SAE_LABEL_RECALL && measure != SAE_LABEL_COUNT)
-    return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
-  hipLaunchKernelGGL(label_keys_kernel, dim3((unsigned)((ncols + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
-                     (hipStream_t)stream, counts, label_count, (int)n_classes, (int)n, measure, by_latent, row0, n_rows, keys);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// ---- activation histograms (hist.h): per latent the histogram of its value on every counted frame and of every file's maximum,
-// and the frame histogram of a few chosen latents split by label
-static_assert(SAE_HIST_MAX_BINS == HB_MAX_BINS && SAE_HIST_MAX_SEL == HIST_MAX_SEL, "freud_sae.h, hist_bins.h and hist.h disagree");
-
-static int hist_ensure(sae_ctx* c, int64_t n_files) {
-  if (!c->topk || n_files <= c->hs_files) return SAE_OK;
-  if (c->hs_fmax) HIP_TRY(hipFree(c->hs_fmax));        // (hipFree waits for the work that still reads it)
-  c->hs_fmax = nullptr;
-  c->hs_files = 0;
-  HIP_TRY(hipMalloc((void**)&c->hs_fmax, (size_t)(n_files * c->n) * 4));
-  c->hs_files = n_files;
-  return SAE_OK;
-}
-
-// the stored latent of file_pass_encode binned by hist_l1_kernel.  Chunks of whole files: the fewest files per chunk that still give
-// HIST_MIN_WGS workgroups (every chunk flushes its non-empty bins with global adds, so fewer chunks are cheaper).  Columns per
-// workgroup: 256 while the counters fit 48 KiB of LDS (O P <= 96), else 128.
-constexpr int HIST_MIN_WGS = 1024;
-static void hist_launch_l1(sae_ctx* c, int64_t n_files, int Trows, const int* lengths, HistSpec sp, int64_t* frame_hist, int64_t* file_max_hist,
-                           hipStream_t s) {
-  const int reg = hist_regular(sp);
-  const int nt = reg <= 96 ? 256 : 128;
-  const int colblocks = (c->n + nt - 1) / nt;
-  const int64_t want = std::min<int64_t>(n_files, (HIST_MIN_WGS + colblocks - 1) / colblocks);
-  const int fpc = (int)(n_files / want);
-  const int64_t chunks = (n_files + fpc - 1) / fpc;
-  hipLaunchKernelGGL(hist_l1_kernel, dim3((unsigned)colblocks, (unsigned)chunks), dim3(nt), (size_t)((reg + 1) / 2) * nt * 4, s,
-                     (const unsigned short*)c->c, (int64_t)c->n_p, c->n, n_files, Trows, lengths, fpc, sp, frame_hist, file_max_hist);
-}
-
-extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                              int lo_exp, int octaves, int sub_bits, int flags, int64_t* frame_hist, int64_t* file_max_hist,
-                              int64_t* n_frames, const int32_t* labels, int n_slots, int n_classes, const int32_t* sel_latents, int n_sel,
-                              int64_t* label_hist, int64_t* label_count, void* stream) {
-  int64_t M;
-  const HistSpec sp{lo_exp, octaves, sub_bits};
-  if (!hist_spec_ok(sp))
-    return fail(SAE_ERR_INVALID, "histogram spec lo_exp=%d octaves=%d sub_bits=%d: -126 <= lo_exp, octaves >= 1, lo_exp + octaves <= 128, "
-                "sub_bits in 0..3, octaves << sub_bits <= %d", lo_exp, octaves, sub_bits, HB_MAX_REGULAR);
-  if (!file_max_hist || !n_frames) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_sel < 0 || n_sel > SAE_HIST_MAX_SEL) return fail(SAE_ERR_INVALID, "n_sel=%d outside [0, %d]", n_sel, SAE_HIST_MAX_SEL);
-  if (n_sel > 0) {
-    if (!labels || !sel_latents || !label_hist || !label_count) return fail(SAE_ERR_INVALID, "n_sel=%d needs labels, sel_latents, label_hist and label_count", n_sel);
-    if (n_slots < 1 || n_slots > SAE_LABEL_MAX_SLOTS) return fail(SAE_ERR_INVALID, "n_slots=%d outside [1, %d]", n_slots, SAE_LABEL_MAX_SLOTS);
-    if (n_classes < 1 || n_classes > SAE_LABEL_MAX_CLASSES) return fail(SAE_ERR_INVALID, "n_classes=%d outside [1, %d]", n_classes, SAE_LABEL_MAX_CLASSES);
-  }
-  for (const void* p : {(const void*)frame_hist, (const void*)file_max_hist, (const void*)n_frames, (const void*)label_hist, (const void*)label_count})
-    if (misaligned(p, 8)) return fail(SAE_ERR_INVALID, "the histogram arrays must be 8-byte aligned");
-  if (int rc = file_pass_begin(kHistPass, c, x, frame_hist, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (int rc = hist_ensure(c, n_files)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-
-  ev_begin(c, KID_HIST, s);
-  hipError_t memset_fmax = hipSuccess;
-  hipLaunchKernelGGL(hist_frames_kernel, dim3(1), dim3(256), 0, s, n_files, Trows, lengths, n_frames, n_sel > 0 ? label_count + n_classes : nullptr);
-  if (c->topk) {
-    memset_fmax = hipMemsetAsync(c->hs_fmax, 0, (size_t)(n_files * c->n) * 4, s);
-    if (memset_fmax == hipSuccess) {
-      hipLaunchKernelGGL(hist_topk_scatter_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
-                         c->k, M, Trows, lengths, c->n, sp, frame_hist, c->hs_fmax);
-      hipLaunchKernelGGL(hist_topk_finish_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->hs_fmax, n_files, c->n, sp, n_frames,
-                         frame_hist, file_max_hist);
-    }
-  } else {
-    hist_launch_l1(c, n_files, Trows, lengths, sp, frame_hist, file_max_hist, s);
-  }
-  if (n_sel > 0 && memset_fmax == hipSuccess) {
-    const dim3 grid(grid_for(M * n_sel, 4096));
-    if (c->topk)
-      hipLaunchKernelGGL(hist_label_kernel<true>, grid, dim3(256), 0, s, (const unsigned short*)c->top_vals, (int64_t)0, c->top_idx, c->k, c->n, M,
-                         Trows, lengths, labels, n_slots, n_classes, sel_latents, n_sel, sp, label_hist, label_count);
-    else
-      hipLaunchKernelGGL(hist_label_kernel<false>, grid, dim3(256), 0, s, (const unsigned short*)c->c, (int64_t)c->n_p, (const int*)nullptr, 0, c->n,
-                         M, Trows, lengths, labels, n_slots, n_classes, sel_latents, n_sel, sp, label_hist, label_count);
-    hipLaunchKernelGGL(hist_label_any_kernel, dim3((unsigned)n_sel), dim3(256), 0, s, frame_hist, sel_latents, c->n, n_classes, hist_nbins(sp),
-                       label_hist);
-  }
-  ev_end(c, KID_HIST, s);                   // (the bracket closes whatever the memset answered)
-  HIP_TRY(memset_fmax);
-  HIP_TRY(hipGetLastError());
-  file_pass_end(kHistPass, c);
-  return SAE_OK;
-}
-
-// ---- feature timing (timing.h): per latent the histograms of its run durations and of the gaps between its runs, and six totals
-static_assert(SAE_TIMING_ACTIVE == TB_ACTIVE && SAE_TIMING_SPAN == TB_SPAN && SAE_TIMING_RUNS == TB_RUNS && SAE_TIMING_FILES == TB_FILES &&
-              SAE_TIMING_LONGEST == TB_LONGEST && SAE_TIMING_CENSORED == TB_CENSORED && SAE_TIMING_NTOTALS == TB_NTOTALS &&
-              SAE_TIMING_MAX_BINS == TB_MAX_BINS && SAE_TIMING_MAX_BRIDGE == TB_MAX_BRIDGE && TM_MAX_K == SAE_COLLECT_MAX_K,
-              "freud_sae.h, timing_bins.h and timing.h disagree");
-
-// the stored latent of file_pass_encode walked by timing_l1_kernel.  Chunks of whole files as in hist_launch_l1.  Columns per
-// workgroup from the LDS the spec needs: 2 ((NB + 1) / 2) dwords per column -- 256 while that fits 48 KiB (NB <= 48), else 128 (NB = 111:
-// 56 KiB).  one_chunk (SAE_TIMING_ONE_CHUNK): every file of the call in one chunk -- the same arrays from another geometry.
-static void timing_launch_l1(sae_ctx* c, int64_t n_files, int Trows, const int* lengths, int sub_bits, int bridge, uint32_t threshold,
-                             bool one_chunk, int64_t* run_hist, int64_t* gap_hist, int64_t* totals, hipStream_t s) {
-  const int nq = (timing_nbins(sub_bits, Trows) + 1) / 2;
-  const int nt = nq <= 24 ? 256 : 128;
-  const int colblocks = (c->n + nt - 1) / nt;
-  const int64_t want = std::min<int64_t>(n_files, (HIST_MIN_WGS + colblocks - 1) / colblocks);
-  const int fpc = one_chunk ? (int)n_files : (int)(n_files / want);
-  const int64_t chunks = (n_files + fpc - 1) / fpc;
-  hipLaunchKernelGGL(timing_l1_kernel, dim3((unsigned)colblocks, (unsigned)chunks), dim3(nt), (size_t)2 * nq * nt * 4, s,
-                     (const unsigned short*)c->c, (int64_t)c->n_p, c->n, n_files, Trows, lengths, fpc, sub_bits, bridge, threshold, run_hist,
-                     gap_hist, totals);
-}
-
-extern "C" int sae_timing_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                                int sub_bits, int bridge, uint32_t threshold_bits, int flags, int64_t* run_hist, int64_t* gap_hist,
-                                int64_t* totals, int64_t* n_frames, void* stream) {
-  int64_t M;
-  if (!timing_spec_ok(sub_bits, bridge, threshold_bits, rows_per_file))
-    return fail(SAE_ERR_INVALID, "timing sub_bits=%d bridge=%d threshold_bits=0x%x rows_per_file=%lld: sub_bits in 0..3, bridge in 0..%d, "
-                "threshold_bits <= 0x%x, 1 <= rows_per_file <= %d", sub_bits, bridge, threshold_bits, (long long)rows_per_file, TB_MAX_BRIDGE,
-                TB_MAX_THRESHOLD, TB_MAX_ROWS);
-  if (!gap_hist || !totals || !n_frames) return fail(SAE_ERR_INVALID, "null argument");
-  for (const void* p : {(const void*)run_hist, (const void*)gap_hist, (const void*)totals, (const void*)n_frames})
-    if (misaligned(p, 8)) return fail(SAE_ERR_INVALID, "the timing arrays must be 8-byte aligned");
-  if (int rc = file_pass_begin(kTimingPass, c, x, run_hist, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (c->topk && (c->k < 1 || c->k > TM_MAX_K)) return fail(SAE_ERR_INVALID, "sae_timing_files: k=%d outside [1, %d]", c->k, TM_MAX_K);
-  hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-
-  ev_begin(c, KID_TIMING, s);
-  hipLaunchKernelGGL(hist_frames_kernel, dim3(1), dim3(256), 0, s, n_files, Trows, lengths, n_frames, (int64_t*)nullptr);
-  if (c->topk) {
-    const dim3 grid((unsigned)n_files, (unsigned)((c->n + TM_SEG - 1) / TM_SEG));
-    if (c->k <= 64)
-      hipLaunchKernelGGL(timing_topk_kernel<true>, grid, dim3(64), 0, s, c->top_idx, (const unsigned short*)c->top_vals, c->k, Trows, lengths,
-                         c->n, sub_bits, bridge, threshold_bits, run_hist, gap_hist, totals);
-    else
-      hipLaunchKernelGGL(timing_topk_kernel<false>, grid, dim3(64), 0, s, c->top_idx, (const unsigned short*)c->top_vals, c->k, Trows, lengths,
-                         c->n, sub_bits, bridge, threshold_bits, run_hist, gap_hist, totals);
-  } else {
-    timing_launch_l1(c, n_files, Trows, lengths, sub_bits, bridge, threshold_bits, (flags & SAE_TIMING_ONE_CHUNK) != 0, run_hist, gap_hist,
-                     totals, s);
-  }
-  ev_end(c, KID_TIMING, s);
-  HIP_TRY(hipGetLastError());
-  file_pass_end(kTimingPass, c);
-  return SAE_OK;
-}
-
-// ---- dictionary comparison (dict_match.h): unit decoder directions as a K-concatenated hi / lo bf16 operand, and the cosine keys of
-// a block of A's rows against all of B through the row x row tile GEMM
-static_assert(SAE_DICT_MAX_D == DM_MAX_D && SAE_DICT_LEFT == DM_LEFT && SAE_DICT_RIGHT == DM_RIGHT && DM_MAX_N == FT_MAX_COLS &&
-              DM_ROW_ALIGN == G2_BM && DM_ROW_ALIGN == G2_BN && DM_K_ALIGN == GEMM_BK, "freud_sae.h, dict_match.h and gemm256.h disagree");
-
-static bool dict_dims_ok(int64_t n, int64_t d) { return n >= 1 && n <= DM_MAX_N && d >= 1 && d <= DM_MAX_D; }
-
-extern "C" int64_t sae_dict_pack_bytes(int64_t n, int64_t d) { return dict_dims_ok(n, d) ? dm_pack_bytes(n, d) : 0; }
-
-extern "C" int sae_dict_pack(const float* w, int64_t n, int64_t d, int64_t dir_stride, int64_t elem_stride, int side, void* packed,
-                             float* norms, void* stream) {
-  if (!w || !packed || !norms) return fail(SAE_ERR_INVALID, "null argument");
-  if (!dict_dims_ok(n, d)) return fail(SAE_ERR_INVALID, "n=%lld outside [1, 2^24] or d=%lld outside [1, %d]", (long long)n, (long long)d, DM_MAX_D);
-  if (dir_stride < 1 || elem_stride < 1) return fail(SAE_ERR_INVALID, "dir_stride=%lld, elem_stride=%lld: strides are positive element counts", (long long)dir_stride, (long long)elem_stride);
-  if (side != DM_LEFT && side != DM_RIGHT) return fail(SAE_ERR_INVALID, "side=%d is neither 0 nor 1", side);
-  if (misaligned(packed, 16) || misaligned(w, 4) || misaligned(norms, 4))
-    return fail(SAE_ERR_INVALID, "the packed operand must be 16-byte aligned, the weights and norms 4-byte aligned");
-  const int64_t rows_p = dm_rows_p(n);
-  hipStream_t s = (hipStream_t)stream;
-  if (elem_stride == 1)
-    hipLaunchKernelGGL(dict_pack_rows_kernel, dim3((unsigned)(rows_p / 4)), dim3(256), 0, s, w, n, (int)d, dir_stride, side, (unsigned short*)packed, norms);
-  else
-    hipLaunchKernelGGL(dict_pack_cols_kernel, dim3((unsigned)(rows_p / 64)), dim3(256), 0, s, w, n, (int)d, dir_stride, elem_stride, side,
-                       (unsigned short*)packed, norms);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_dict_sim_keys(const void* packed_a, int64_t n_a, const void* packed_b, int64_t n_b, int64_t d, int64_t row0, int64_t n_rows,
-                                 int self_mode, uint64_t* keys, void* stream) {
-  if (!packed_a || !packed_b || !keys) return fail(SAE_ERR_INVALID, "null argument");
-  if (!dict_dims_ok(n_a, d) || !dict_dims_ok(n_b, d))
-    return fail(SAE_ERR_INVALID, "n_a=%lld, n_b=%lld outside [1, 2^24] or d=%lld outside [1, %d]", (long long)n_a, (long long)n_b, (long long)d, DM_MAX_D);
-  if (self_mode != 0 && self_mode != 1) return fail(SAE_ERR_INVALID, "self_mode=%d is neither 0 nor 1", self_mode);
-  if (self_mode && n_a != n_b) return fail(SAE_ERR_INVALID, "self mode with n_a=%lld != n_b=%lld", (long long)n_a, (long long)n_b);
-  if (n_rows < 1 || row0 < 0 || row0 + n_rows > n_a)
-    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)n_a);
-  if (misaligned(packed_a, 16) || misaligned(packed_b, 16) || misaligned(keys, 8))
-    return fail(SAE_ERR_INVALID, "the packed operands must be 16-byte aligned and the keys 8-byte aligned");
-  const int64_t ld = dm_ld(d);
-  const int64_t row_base = row0 / DM_ROW_ALIGN * DM_ROW_ALIGN;                   // (the cover stays inside dm_rows_p(n_a))
-  const int64_t nbm = (dm_rows_p(row0 + n_rows) - row_base) / DM_ROW_ALIGN, nbn = dm_rows_p(n_b) / DM_ROW_ALIGN;
-  if (nbm * nbn > (1 << 30)) return fail(SAE_ERR_INVALID, "a row block of %lld x %lld tiles: split it", (long long)nbm, (long long)nbn);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  GemmArgs g{};
-  g.A0 = (const bf16_t*)packed_a + row_base * ld; g.lda = ld; g.B0 = (const bf16_t*)packed_b; g.ldb = ld;
-  g.nbm = (int)nbm; g.nbn = (int)nbn;                                            // (256 x 256 tiles: the kernel is launched directly)
-  g.ktiles0 = g.ktiles = (int)(ld / GEMM_BK); g.splits = 1;
-  EpiDictKeys e{};
-  e.keys = keys; e.n_b = n_b; e.n_rows = n_rows; e.row_lo = (int)(row0 - row_base);
-  e.self_base = self_mode ? row_base : -((int64_t)1 << 40);
-  auto kern = gemm256_bf16_kernel<OP_ROW, OP_ROW, EpiDictKeys>;
-  LDS_ATTR(kern, G2_LDS_BYTES, dev);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(nbm * nbn)), dim3(512), G2_LDS_BYTES, (hipStream_t)stream, g, e);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// ---- feature manipulation (manip.h): one encode, one decode, then a rank-one term per edit and variant
-static_assert(SAE_MANIP_SCALE == SM_SCALE && SAE_MANIP_SET == SM_SET && SAE_MANIP_MAX_EDITS == SM_MAX_EDITS &&
-              SAE_MANIP_MAX_VARIANTS == SM_MAX_VARIANTS, "freud_sae.h and manip.h disagree");
-
-static void manip_decode_topk(sae_ctx* c, int64_t M, float* x_hat, hipStream_t s) {
-  const float* bd = c->P + 2 * c->nW + c->n_p;
-  const dim3 grid((unsigned)((M + 3) / 4));
-  with_np(c->d_p, [&](auto np_tag) {
-    constexpr int NP = decltype(np_tag)::value;
-    hipLaunchKernelGGL(manip_topk_decode_kernel<NP>, grid, dim3(256), 0, s, c->top_vals, c->top_idx, c->k, c->Wd_b, bd, x_hat, M, c->d,
-                       c->d_p, c->n_p);
-  });
-}
-
-extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* latents,
-                                    const int32_t* ops, int n_edits, const float* values, int n_variants, int flags, float* standard,
-                                    float* manipulated, float* series, void* stream) {
-  if (!latents || !ops || !values || !manipulated || !series) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_edits < 1 || n_edits > SAE_MANIP_MAX_EDITS) return fail(SAE_ERR_INVALID, "n_edits=%d outside [1, %d]", n_edits, SAE_MANIP_MAX_EDITS);
-  if (n_variants < 1 || n_variants > SAE_MANIP_MAX_VARIANTS)
-    return fail(SAE_ERR_INVALID, "n_variants=%d outside [1, %d]", n_variants, SAE_MANIP_MAX_VARIANTS);
-  ManipEdits ed{};
-  ed.n_edits = n_edits; ed.n_variants = n_variants;
-  for (int e = 0; e < n_edits; ++e) {
-    if (c && (latents[e] < 0 || latents[e] >= c->n)) return fail(SAE_ERR_INVALID, "edit %d: latent %d outside [0, %d)", e, latents[e], c->n);
-    for (int f = 0; f < e; ++f)
-      if (latents[f] == latents[e]) return fail(SAE_ERR_INVALID, "edits %d and %d name the same latent %d", f, e, latents[e]);
-    if (ops[e] != SAE_MANIP_SCALE && ops[e] != SAE_MANIP_SET) return fail(SAE_ERR_INVALID, "edit %d: unknown op %d", e, ops[e]);
-    ed.latents[e] = latents[e]; ed.ops[e] = ops[e];
-    for (int v = 0; v < n_variants; ++v) {
-      const float val = values[v * n_edits + e];
-      if (!std::isfinite(val)) return fail(SAE_ERR_INVALID, "variant %d, edit %d: the value is not finite", v, e);
-      ed.values[v][e] = val;
-    }
-  }
-  int64_t M;
-  if (int rc = file_pass_begin(kManipPass, c, x, standard, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_manipulate_files: the TopK decode serves d_model <= 1536");
-  if (!c->mn_w) HIP_TRY(hipMalloc((void**)&c->mn_w, (size_t)SM_MAX_EDITS * c->d_p * 4));
-  hipStream_t s = (hipStream_t)stream;
-  const int d = c->d;
-  // the bf16 eval forward: encode() -- and the state sae_eval leaves (latent rows, indices, metrics)
-  if (int rc = dispatch_fwd_bwd(c, x, M, x_dtype, stream, false)) return rc;
-
-  ev_begin(c, KID_MANIP_DECODE, s);
-  int rc = SAE_OK;
-  if (c->topk) manip_decode_topk(c, M, standard, s);
-  else rc = decode_l1_latent(c, c->c, c->last_M_p / 128, M, standard, s);    // (the forward's own padded latent: no pad_latent copy)
-  ev_end(c, KID_MANIP_DECODE, s);
-  if (rc) return rc;
-
-  ev_begin(c, KID_MANIP_SERIES, s);
-  if (c->topk) {
-    hipLaunchKernelGGL(manip_series_topk_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, ed, series);
-    hipLaunchKernelGGL(manip_rows_kernel, dim3((d + 255) / 256, n_edits), dim3(256), 0, s, c->Wd_b, (int64_t)c->d_p, (int64_t)1, d, ed,
-                       c->mn_w, c->d_p);
-  } else {
-    hipLaunchKernelGGL(manip_series_kernel, dim3(grid_for(M * n_edits, 4096)), dim3(256), 0, s, c->c, (int64_t)c->n_p, M, ed, series);
-    hipLaunchKernelGGL(manip_rows_kernel, dim3((d + 255) / 256, n_edits), dim3(256), 0, s, c->Wb, (int64_t)1, (int64_t)c->n_p, d, ed,
-                       c->mn_w, c->d_p);
-  }
-  ev_end(c, KID_MANIP_SERIES, s);
-
-  ev_begin(c, KID_MANIP_APPLY, s);
-  {
-    const bool vec = d % 4 == 0 && !misaligned(standard, 16) && !misaligned(manipulated, 16);
-    const int vw = vec ? 4 : 1;
-    const int nslab = (d + 32 * vw - 1) / (32 * vw);
-    // groups of 8 half waves, a multiple of the slabs: every frame x slab once, at most ~4096 groups striding over the frames
-    const int64_t per_slab = std::min<int64_t>((M + 7) / 8, std::max<int64_t>(4096 / nslab, 1));
-    const dim3 grid((unsigned)(per_slab * nslab));
-    if (vec) hipLaunchKernelGGL(manip_apply_kernel<4>, grid, dim3(256), 0, s, standard, series, c->mn_w, c->d_p, M, d, nslab, ed, manipulated);
-    else hipLaunchKernelGGL(manip_apply_kernel<1>, grid, dim3(256), 0, s, standard, series, c->mn_w, c->d_p, M, d, nslab, ed, manipulated);
-  }
-  ev_end(c, KID_MANIP_APPLY, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-// ---- reconstruction report (recon.h): the residual of encode() -> decode() per frame, its sums per file and per model dimension,
-// and per latent the attribution sums P_j = sum a_j (r . w_j), sum a_j^2 and |w_j|^2
-static_assert(SAE_RECON_UNFUSED == 1, "freud_sae.h and engine.hip disagree");
-
-struct ReconScratch {           // c->rc_buf carved up (floats)
-  float *xr, *slab_p, *slab_q, *rowpart, *dimpart, *p;
-};
-
-static ReconScratch recon_scratch(const sae_ctx* c) {
-  const int64_t rows = c->cfg.max_rows, nrb = c->max_rows_p / STATS_RB, nch = c->d_p / RC_CW;
-  ReconScratch r;
-  r.xr = c->rc_buf;
-  r.slab_p = r.xr + round_up(rows * c->d, 4);
-  r.slab_q = r.slab_p + nrb * c->n_p;
-  r.rowpart = r.slab_q + nrb * c->n_p;
-  r.dimpart = r.rowpart + rows * nch * 2;
-  r.p = r.dimpart + nrb * 3 * c->d_p;
-  return r;
-}
-
-static int recon_ensure(sae_ctx* c) {
-  if (c->rc_buf) return SAE_OK;
-  const ReconScratch r = recon_scratch(c);        // (offsets from a null base: only their differences are used)
-  const int64_t floats = (r.p - r.xr) + (c->topk ? c->cfg.max_rows * (int64_t)c->k : 0);
-  HIP_TRY(hipMalloc((void**)&c->rc_buf, (size_t)floats * 4));
-  return SAE_OK;
-}
-
-static ReconOut recon_out(void* block, int n, int d) {
-  char* b = (char*)block;
-  ReconOut o;
-  o.n_frames = (unsigned long long*)(b + SAE_RECON_N_FRAMES(n, d));
-  o.attr = (double*)(b + SAE_RECON_ATTR_SUM(n, d));
-  o.asq = (double*)(b + SAE_RECON_ACT_SQ_SUM(n, d));
-  o.sx = (double*)(b + SAE_RECON_SUM_X(n, d));
-  o.sxx = (double*)(b + SAE_RECON_SUM_X_SQ(n, d));
-  o.srr = (double*)(b + SAE_RECON_SUM_R_SQ(n, d));
-  o.wnorm = (float*)(b + SAE_RECON_DEC_NORM_SQ(n, d));
-  return o;
-}
-
-template <typename T>
-static void recon_launch_resid(sae_ctx* c, const T* x, const ReconScratch& sc, float* resid, bf16_t* rb, bf16_t* lat, int64_t rows_cover,
-                               int64_t M, int Trows, const int* lengths, hipStream_t s) {
-  const dim3 grid((unsigned)(rows_cover / STATS_RB), (unsigned)(c->d_p / RC_CW));
-  hipLaunchKernelGGL(recon_resid_kernel<T>, grid, dim3(256), 0, s, x, sc.xr, resid, rb, lat, c->n_p, M, Trows, 1.0f / (float)Trows, lengths,
-                     c->d, c->d_p, sc.rowpart, sc.dimpart);
-}
-
-static void recon_launch_fold(sae_ctx* c, const ReconScratch& sc, int nrb_lat, int nrb_dim, int64_t n_files, int Trows, const int* lengths,
-                              const ReconOut& o, double* file_out, hipStream_t s) {
-  const int nb_lat = (c->n + 255) / 256, nb_dim = (c->d + 255) / 256, nb_files = (int)((n_files + 3) / 4);
-  hipLaunchKernelGGL(recon_fold_kernel, dim3((unsigned)(nb_lat + nb_dim + nb_files)), dim3(256), 0, s, sc.slab_p, sc.slab_q, nrb_lat, c->n,
-                     c->n_p, sc.dimpart, nrb_dim, c->d, c->d_p, sc.rowpart, c->d_p / RC_CW, (int)n_files, Trows, lengths, o, file_out, nb_lat,
-                     nb_dim);
-}
-
-// L1: the stored latent of file_pass_l1_encode; x_hat by decode_l1_latent on that latent; the residual sweep writes r_b into c->dxh
-// (free in a file pass) and zeroes the latent rows that do not count;
-// the attribution is the backward's dpre-shaped GEMM r_b [M_p][d_p] x Wt [n_p][d_p] with EpiAttr: in the streaming form where
-// launch_gemm would take it (gemm_streams), in the tile forms elsewhere and with `unfused` (SAE_RECON_UNFUSED).
-template <typename T>
-static int recon_l1_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
-                         double* file_out, float* resid, bool unfused, hipStream_t s) {
-  const int n_p = c->n_p;
-  int64_t Mp;
-  if (int rc = file_pass_l1_encode(c, x, M, s, nullptr, &Mp)) return rc;
-  const ReconScratch sc = recon_scratch(c);
-
-  ev_begin(c, KID_RECON_DECODE, s);
-  int rc = decode_l1_latent(c, c->c, round_up(M, c->row_pad) / 128, M, sc.xr, s);      // (sae_decode's M_p)
-  ev_end(c, KID_RECON_DECODE, s);
-  if (rc) return rc;
-
-  ev_begin(c, KID_RECON_RESID, s);
-  recon_launch_resid(c, x, sc, resid, c->dxh, c->c, Mp, M, Trows, lengths, s);
-  hipLaunchKernelGGL(recon_wnorm_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->Wb, (int64_t)1, (int64_t)n_p, c->d, c->n,
-                     o.wnorm);
-  ev_end(c, KID_RECON_RESID, s);
-
-  const GemmArgs ga = enc_gemm_args(c, c->dxh, Mp);
-  EpiAttr ea{};
-  ea.c = c->c; ea.slab_p = sc.slab_p; ea.slab_q = sc.slab_q; ea.n_p = n_p;
-  const bool no_stream_was = g_no_stream;
-  if (unfused) g_no_stream = true;                 // (the tile forms for this launch only)
-  const int kid = gemm_streams<OP_ROW, OP_ROW, EpiAttr>(ga) ? KID_RECON_ATTR_STREAM : KID_RECON_ATTR;
-  ev_begin(c, kid, s);
-  rc = launch_gemm<OP_ROW, OP_ROW>(ga, ea, s);
-  g_no_stream = no_stream_was;
-  if (!rc) recon_launch_fold(c, sc, (int)(Mp / STATS_RB), (int)(Mp / STATS_RB), n_files, Trows, lengths, o, file_out, s);
-  ev_end(c, kid, s);
-  if (rc) return rc;
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-template <typename T>
-static int recon_topk_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
-                           double* file_out, float* resid, hipStream_t s) {
-  const ReconScratch sc = recon_scratch(c);
-  const int64_t rows_cover = round_up(M, STATS_RB);
-  ev_begin(c, KID_RECON_DECODE, s);
-  manip_decode_topk(c, M, sc.xr, s);
-  ev_end(c, KID_RECON_DECODE, s);
-
-  ev_begin(c, KID_RECON_RESID, s);
-  recon_launch_resid(c, x, sc, resid, (bf16_t*)nullptr, (bf16_t*)nullptr, rows_cover, M, Trows, lengths, s);
-  hipLaunchKernelGGL(recon_wnorm_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->Wd_b, (int64_t)c->d_p, (int64_t)1, c->d,
-                     c->n, o.wnorm);
-  ev_end(c, KID_RECON_RESID, s);
-
-  ev_begin(c, KID_RECON_ATTR, s);
-  {
-    const dim3 grid((unsigned)((M + 3) / 4));
-    with_np(c->d_p, [&](auto np_tag) {
-      constexpr int NP = decltype(np_tag)::value;
-      hipLaunchKernelGGL(recon_topk_attr_kernel<NP>, grid, dim3(256), 0, s, sc.xr, c->top_vals, c->top_idx, c->k, c->Wd_b, sc.p, M, c->d,
-                         c->d_p, c->n_p);
-    });
-  }
-  const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
-  hipLaunchKernelGGL(recon_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
-                     c->top_idx, (const unsigned short*)c->top_vals, sc.p, c->k, M, Trows, lengths, c->n, c->n_p, sc.slab_p, sc.slab_q);
-  recon_launch_fold(c, sc, nrb, (int)(rows_cover / STATS_RB), n_files, Trows, lengths, o, file_out, s);
-  ev_end(c, KID_RECON_ATTR, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
-                               int flags, void* block, double* file_out, float* resid, void* stream) {
-  int64_t M;
-  if (!file_out) return fail(SAE_ERR_INVALID, "null argument");
-  if (int rc = file_pass_begin(kReconPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (misaligned(block, 8) || misaligned(file_out, 8) || misaligned(resid, 4))
-    return fail(SAE_ERR_INVALID, "the report block and file_out must be 8-byte aligned, resid 4-byte aligned");
-  if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_recon_files: the TopK decode serves d_model <= 1536");
-  if ((c->max_rows_p / STATS_RB) * (int64_t)c->n_p >= ((int64_t)1 << 31))
-    return fail(SAE_ERR_INVALID, "sae_recon_files: max_rows / 128 x n_dict = %lld slab entries >= 2^31", (long long)((c->max_rows_p / STATS_RB) * (int64_t)c->n_p));
-  if (int rc = recon_ensure(c)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int Trows = (int)rows_per_file;
-  const ReconOut o = recon_out(block, c->n, c->d);
-  if (c->topk) {
-    // the sparse decode and the attribution of encode()'s selection
-    if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_topk_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, s); }))
-      return rc;
-  } else {
-    const bool unfused = (flags & SAE_RECON_UNFUSED) != 0;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_l1_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, unfused, s); }))
-      return rc;
-  }
-  file_pass_end(kReconPass, c);
-  return SAE_OK;
-}
-
-// ---- feature collection (collect.h): every row's K slots of the latent encode() returns, in the reference's indexed form
-static_assert(SAE_COLLECT_IDX32 == CL_IDX32 && SAE_COLLECT_MAX_K == CL_MAX_K, "freud_sae.h and collect.h disagree");
-// Grids of what is resident at once, the kernels stride over the rest of the rows: collect_l1_kernel holds 98 VGPRs (4 waves per SIMD:
-// 4 workgroups of 256 threads per CU), collect_topk_kernel 32 KiB of LDS (5 per CU); 256 CUs
-constexpr int COLLECT_L1_WGS = 256 * 4, COLLECT_TOPK_WGS = 256 * 5;
-
-template <typename IdxT>
-static void collect_launch(sae_ctx* c, int64_t M, int K, float* values, IdxT* indices, int64_t* stats, hipStream_t s) {
-  unsigned long long* st = reinterpret_cast<unsigned long long*>(stats);
-  if (c->topk)
-    hipLaunchKernelGGL(collect_topk_kernel<IdxT>, dim3(grid_for(M, COLLECT_TOPK_WGS, 4)), dim3(CL_THREADS), 0, s, c->top_idx,
-                       (const unsigned short*)c->top_vals, c->k, M, K, values, indices, st);
-  else
-    hipLaunchKernelGGL(collect_l1_kernel<IdxT>, dim3(grid_for(M, COLLECT_L1_WGS, 1)), dim3(CL_THREADS), 0, s, (const unsigned short*)c->c,
-                       (int64_t)c->n_p, c->n, M, K, values, indices, st);
-}
-
-extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, int K, int flags,
-                                 float* values, void* indices, int64_t* stats, void* stream) {
-  int64_t M;
-  if (!indices || !stats) return fail(SAE_ERR_INVALID, "null argument");
-  if (int rc = file_pass_begin(kCollectPass, c, x, values, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  const bool idx32 = (flags & SAE_COLLECT_IDX32) != 0;
-  if (misaligned(stats, 8) || misaligned(values, 4) || misaligned(indices, idx32 ? 4 : 8))
-    return fail(SAE_ERR_INVALID, "stats must be 8-byte aligned, values 4-byte aligned, indices aligned to their type");
-  const int k_max = c->topk ? c->k : std::min(c->n, (int)SAE_COLLECT_MAX_K);
-  if (K < 1 || K > k_max)
-    return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max, c->topk ? "the context's k" : "min(n_dict, SAE_COLLECT_MAX_K)");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-  ev_begin(c, KID_COLLECT, s);
-  if (idx32) collect_launch(c, M, K, values, (int32_t*)indices, stats, s);
-  else collect_launch(c, M, K, values, (int64_t*)indices, stats, s);
-  ev_end(c, KID_COLLECT, s);
-  HIP_TRY(hipGetLastError());
-  file_pass_end(kCollectPass, c);
-  return SAE_OK;
-}
-
-// ---- feature index (findex.h): the latent-major postings of an indexed store; context-free, like sae_search_merge
-static_assert(SAE_FINDEX_IDX32 == FI_IDX32 && SAE_FINDEX_NSTATS == FI_NSTATS && SAE_COLLECT_MAX_K == FI_MAX_K, "freud_sae.h and findex.h disagree");
-
-static int64_t findex_blocks(int64_t rows) { return (rows + FI_ROWS - 1) / FI_ROWS; }
-
-static int findex_batch_check(const void* values, const void* indices, int64_t rows, int K, int flags, int64_t n_dict) {
-  if (!values || !indices) return fail(SAE_ERR_INVALID, "null argument");
-  if (flags & ~SAE_FINDEX_IDX32) return fail(SAE_ERR_INVALID, "unknown feature-index flags 0x%x", flags);
-  if (rows < 1 || findex_blocks(rows) > 0x7FFFFFFFll) return fail(SAE_ERR_INVALID, "rows=%lld outside [1, 2^31 * %d)", (long long)rows, FI_ROWS);
-  if (K < 1 || K > FI_MAX_K) return fail(SAE_ERR_INVALID, "K=%d outside [1, %d]", K, FI_MAX_K);
-  if (n_dict < 1 || n_dict > FI_MAX_N) return fail(SAE_ERR_INVALID, "n_dict=%lld outside [1, 2^30]", (long long)n_dict);
-  if (misaligned(values, 4) || misaligned(indices, (flags & SAE_FINDEX_IDX32) ? 4 : 8))
-    return fail(SAE_ERR_INVALID, "values must be 4-byte aligned, indices aligned to their type");
-  return SAE_OK;
-}
-
-extern "C" int64_t sae_findex_workspace_bytes(int64_t max_rows, int64_t n_range) {
-  if (max_rows < 1 || n_range < 1 || n_range > FI_MAX_N) return -1;
-  return findex_blocks(max_rows) * n_range * 4;
-}
-
-template <typename IdxT>
-static void findex_count_launch(const uint32_t* vb, const IdxT* idx, int64_t rows, int K, int64_t n_dict, int j0, int j1,
-                                unsigned long long* totals, unsigned int* counts, unsigned long long* stats, hipStream_t s) {
-  const dim3 grid((unsigned)findex_blocks(rows), (unsigned)((j1 - j0 + FI_SEG - 1) / FI_SEG));
-  const size_t lds = (size_t)std::min(j1 - j0, FI_SEG) * 4;
-  if (K <= 64) hipLaunchKernelGGL((fi_count_kernel<IdxT, true>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, totals, counts, stats);
-  else hipLaunchKernelGGL((fi_count_kernel<IdxT, false>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, totals, counts, stats);
-}
-
-template <typename IdxT>
-static void findex_fill_launch(const uint32_t* vb, const IdxT* idx, int64_t rows, int K, int64_t n_dict, int j0, int j1, uint64_t pos0,
-                               const unsigned int* block_off, uint32_t* positions, uint32_t* values, uint64_t capacity,
-                               unsigned long long* err, hipStream_t s) {
-  const dim3 grid((unsigned)findex_blocks(rows), (unsigned)((j1 - j0 + FI_SEG - 1) / FI_SEG));
-  const size_t lds = (size_t)std::min(j1 - j0, FI_SEG) * 4;
-  if (K <= 64)
-    hipLaunchKernelGGL((fi_fill_kernel<IdxT, true>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, (unsigned long long)pos0, block_off,
-                       positions, values, (unsigned long long)capacity, err);
-  else
-    hipLaunchKernelGGL((fi_fill_kernel<IdxT, false>), grid, dim3(64), lds, s, vb, idx, rows, K, n_dict, j0, j1, (unsigned long long)pos0, block_off,
-                       positions, values, (unsigned long long)capacity, err);
-}
-
-extern "C" int sae_findex_count(const float* values, const void* indices, int64_t rows, int K, int flags, int64_t n_dict, int64_t* totals,
-                                int64_t* stats, void* stream) {
-  if (!totals || !stats) return fail(SAE_ERR_INVALID, "null argument");
-  if (int rc = findex_batch_check(values, indices, rows, K, flags, n_dict)) return rc;
-  if (misaligned(totals, 8) || misaligned(stats, 8)) return fail(SAE_ERR_INVALID, "totals and stats must be 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t* vb = reinterpret_cast<const uint32_t*>(values);
-  unsigned long long *tt = reinterpret_cast<unsigned long long*>(totals), *st = reinterpret_cast<unsigned long long*>(stats);
-  if (flags & SAE_FINDEX_IDX32) findex_count_launch(vb, (const int32_t*)indices, rows, K, n_dict, 0, (int)n_dict, tt, nullptr, st, s);
-  else findex_count_launch(vb, (const int64_t*)indices, rows, K, n_dict, 0, (int)n_dict, tt, nullptr, st, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_findex_fill(const float* values, const void* indices, int64_t rows, int K, int flags, int64_t n_dict, int64_t j0, int64_t j1,
-                               int64_t pos0, int64_t* cursor, int64_t out_base, uint32_t* positions_out, float* values_out,
-                               int64_t capacity, void* workspace, int64_t workspace_bytes, int64_t* err, void* stream) {
-  if (!cursor || !positions_out || !values_out || !workspace || !err) return fail(SAE_ERR_INVALID, "null argument");
-  if (int rc = findex_batch_check(values, indices, rows, K, flags, n_dict)) return rc;
-  if (j0 < 0 || j1 <= j0 || j1 > n_dict) return fail(SAE_ERR_INVALID, "latent range [%lld, %lld) outside [0, %lld)", (long long)j0, (long long)j1, (long long)n_dict);
-  if (pos0 < 0 || pos0 + rows > 0x100000000ll) return fail(SAE_ERR_INVALID, "positions [%lld, %lld) do not fit 32 bits", (long long)pos0, (long long)(pos0 + rows));
-  if (out_base < 0 || capacity < 0 || capacity >= 0xFFFFFFFFll)
-    return fail(SAE_ERR_INVALID, "out_base=%lld, capacity=%lld: a range holds fewer than 2^32 - 1 slots", (long long)out_base, (long long)capacity);
-  if (workspace_bytes < sae_findex_workspace_bytes(rows, j1 - j0))
-    return fail(SAE_ERR_INVALID, "workspace of %lld bytes < sae_findex_workspace_bytes(%lld, %lld)", (long long)workspace_bytes, (long long)rows, (long long)(j1 - j0));
-  if (misaligned(cursor, 8) || misaligned(err, 8) || misaligned(workspace, 4) || misaligned(positions_out, 4) || misaligned(values_out, 4))
-    return fail(SAE_ERR_INVALID, "cursor and err must be 8-byte aligned, workspace and the outputs 4-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t* vb = reinterpret_cast<const uint32_t*>(values);
-  unsigned int* counts = reinterpret_cast<unsigned int*>(workspace);
-  unsigned long long* er = reinterpret_cast<unsigned long long*>(err);
-  uint32_t* vout = reinterpret_cast<uint32_t*>(values_out);
-  const bool i32 = (flags & SAE_FINDEX_IDX32) != 0;
-  if (i32) findex_count_launch(vb, (const int32_t*)indices, rows, K, n_dict, (int)j0, (int)j1, nullptr, counts, nullptr, s);
-  else findex_count_launch(vb, (const int64_t*)indices, rows, K, n_dict, (int)j0, (int)j1, nullptr, counts, nullptr, s);
-  hipLaunchKernelGGL(fi_scan_kernel, dim3((unsigned)((j1 - j0 + 63) / 64)), dim3(1024), 0, s, counts, (int)findex_blocks(rows), (int)j0, (int)j1,
-                     reinterpret_cast<long long*>(cursor), (long long)out_base);
-  if (i32) findex_fill_launch(vb, (const int32_t*)indices, rows, K, n_dict, (int)j0, (int)j1, (uint64_t)pos0, counts, positions_out, vout, (uint64_t)capacity, er, s);
-  else findex_fill_launch(vb, (const int64_t*)indices, rows, K, n_dict, (int)j0, (int)j1, (uint64_t)pos0, counts, positions_out, vout, (uint64_t)capacity, er, s);
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
-
-extern "C" int sae_findex_verify(const int64_t* starts, int64_t n_dict, int64_t j0, int64_t j1, int64_t out_base, const uint32_t* positions,
-                                 int64_t capacity, int64_t limit, int64_t* err, void* stream) {
-  if (!starts || !positions || !err) return fail(SAE_ERR_INVALID, "null argument");
-  if (n_dict < 1 || n_dict > FI_MAX_N || j0 < 0 || j1 <= j0 || j1 > n_dict)
-    return fail(SAE_ERR_INVALID, "latent range [%lld, %lld) outside [0, n_dict=%lld)", (long long)j0, (long long)j1, (long long)n_dict);
-  if (limit < 1 || limit > 0x100000000ll || out_base < 0 || capacity < 0) return fail(SAE_ERR_INVALID, "limit=%lld outside [1, 2^32], or out_base or capacity < 0", (long long)limit);
-  if (misaligned(starts, 8) || misaligned(err, 8) || misaligned(positions, 4)) return fail(SAE_ERR_INVALID, "starts and err must be 8-byte aligned");
-  hipLaunchKernelGGL(fi_verify_kernel, dim3((unsigned)((j1 - j0 + FI_VERIFY_WAVES - 1) / FI_VERIFY_WAVES)), dim3(64 * FI_VERIFY_WAVES), 0,
-                     (hipStream_t)stream, reinterpret_cast<const long long*>(starts), (int)j0, (int)j1, (long long)out_base, positions,
-                     (long long)capacity, (unsigned long long)limit, reinterpret_cast<unsigned long long*>(err));
-  HIP_TRY(hipGetLastError());
-  return SAE_OK;
-}
+int launch_encoder_l1(sae_ctx* c, const GemmArgs& g, int64_t M, hipStream_t s) { return launch_encoder<float>(c, g, M, s); }
 
 extern "C" int sae_profile(sae_ctx* c, int level) {
   if (!c) return fail(SAE_ERR_INVALID, "null argument");

@@ -272,14 +272,17 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
         if (i / 2 + 4 <= 23) ring[(i / 2 + 4) % RING] = enc_frag(SLOT_E, i / 2 + 4);
         ring[(i / 2 + 3) % RING] = enc_frag(SLOT_E, i / 2 + 3);
       }
-      if (i == 42 || i == 44 || i == 46) ring[(i - 42) / 2] = enc_frag(SLOT_EN, (i - 42) / 2);      // k = 0..2 of the NEXT iteration
-      if (i == 15 || i == 16 || i == 17) Afr[i - 12] = dec_a(SLOT_D, i - 12);                       // k-step 1 (decoder MFMAs 12..23)
-      if (i == 45 || i == 46 || i == 47) Afr[i - 45] = dec_a(SLOT_DN, i - 45);                      // k-step 0 of the next phase
+      // (if constexpr on the slot index where the branch indexes an array: a plain `if` still instantiates the branch not taken, with
+      // its constant index out of range.  The other slot branches of this body stay plain `if` on purpose: they fold the same, and the
+      // least edit is what kept the compiled code of every instantiation as it was.)
+      if constexpr (i == 42 || i == 44 || i == 46) ring[(i - 42) / 2] = enc_frag(SLOT_EN, (i - 42) / 2);      // k = 0..2 of the NEXT iteration
+      if constexpr (i == 15 || i == 16 || i == 17) Afr[i - 12] = dec_a(SLOT_D, i - 12);                       // k-step 1 (decoder MFMAs 12..23)
+      if constexpr (i == 45 || i == 46 || i == 47) Afr[i - 45] = dec_a(SLOT_DN, i - 45);                      // k-step 0 of the next phase
       // c^T fragment b feeds decoder MFMAs 3 b .. 3 b + 2 (slots 6 b .. 6 b + 4): requested at slot 6 b - 7
-      if (i >= 5 && i <= 35 && (i - 5) % 6 == 0) Bq[((i + 7) / 6) & 3] = dec_b(PB_D, HF_D, (i + 7) / 6);
-      if (i == 41) Bq[0] = dec_b(PB_W, HF_W, 0);                                                    // next phase, after the barrier
-      if (i == 47) Bq[1] = dec_b(PB_W, HF_W, 1);
-      if (i < 4) bq[i] = *reinterpret_cast<const f32x4*>(bj + 8 * i + 4 * ah);
+      if constexpr (i >= 5 && i <= 35 && (i - 5) % 6 == 0) Bq[((i + 7) / 6) & 3] = dec_b(PB_D, HF_D, (i + 7) / 6);
+      if constexpr (i == 41) Bq[0] = dec_b(PB_W, HF_W, 0);                                                    // next phase, after the barrier
+      if constexpr (i == 47) Bq[1] = dec_b(PB_W, HF_W, 1);
+      if constexpr (i < 4) bq[i] = *reinterpret_cast<const f32x4*>(bj + 8 * i + 4 * ah);
       if (i == 40) {
         // <= 1 VMEM operation outstanding (this iteration's first latent store): the six DMA pieces of tile j+2 are done;
         // <= 2 LDS operations outstanding (four fragment reads follow the staging write of gap 34): that write is done
@@ -328,7 +331,7 @@ __global__ __launch_bounds__(256, 1) void fwd_fused2_d384_kernel(FwdFusedArgs a)
       // The L1 additions are opaque instructions: written as `l1_it += cv`, LLVM SANK the sixteen additions of three of the four unrolled
       // bodies to the loop latch -- 51 dependent v_add_f32 back to back at the back edge with no MFMA between them (~200 cycles per four
       // iterations with the matrix pipe idle).  As asm the additions stay in their MFMA gap; same operands, same order, same sum.
-      if (i >= 4 && i <= 35) {
+      if constexpr (i >= 4 && i <= 35) {
         const int p = (i - 4) >> 2, ph = (i - 4) & 3, e0 = 2 * p;       // pair p = elements e0, e0 + 1 (S register e <-> column n = (e&3) + 8 (e>>2) + 4 h)
         if (ph == 0) {
           se_u = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{S[e0], S[e0 + 1]}, bf16x2));      // rounded to bf16 BEFORE the fp32 bias add (CPU autocast)

@@ -199,6 +199,15 @@ struct epi_prefetch_batch { static constexpr int value = 16; };
 template <class E>
 struct epi_prefetch_batch<E, std::void_t<decltype(E::PREFETCH_BATCH)>> { static constexpr int value = E::PREFETCH_BATCH; };
 
+// (what the epilogue functors of every unit share -- l1_kernels.h's and the file passes': here, next to the kernels that run them)
+// Store of a large output that is next read only after it has left every cache (the [M x n] latent / pre / dpre
+// streams): non-temporal, so that it does not evict the operand tiles the co-resident workgroups share (same-box A/B at
+// d=1280 n=40960: encoder GEMM 7.1 -> 6.4 ms, dpre 7.85 -> 7.55; TopK encoder at d=768 3.03 -> 2.55 ms)
+constexpr int EPI_BATCH_HEAVY = 8;      // prefetch batch of the functors with a large Pre (epi_prefetch_batch)
+#define EPI_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
+// ... and the matching read of such a stream inside an epilogue (dpre GEMM reading the latent: 7.6 -> 7.1 ms)
+#define EPI_LOAD(ptr) __builtin_nontemporal_load(ptr)
+
 // Epi requirements:
 //   __device__ void tile_begin(int row0, int col0, int split);
 //   struct Pre;  __device__ Pre prefetch(int row, int col) const;      // the global loads of apply(), issued early

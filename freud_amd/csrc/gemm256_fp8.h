@@ -251,8 +251,6 @@ __global__ __launch_bounds__(512, 2) void gemm256s_fp8_kernel(Gemm8Args g, Epi e
       if (more) tile_coords(xcd_remap(nblk, ntiles), g.nbm, g.nbn, bm2, bn2);
       const unsigned char* a_nxt = more ? g.A + (int64_t)(bm2 * G2_BM) * g.lda : a_cur + (int64_t)(nk - 2) * 128;
       const unsigned char* b_nxt = more ? g.B + (int64_t)(bn2 * G2_BN) * g.ldb : b_cur + (int64_t)(nk - 2) * 128;
-      auto pa = [&](int j) { return j < nk ? a_cur + (int64_t)j * 128 : a_nxt + (int64_t)(j - nk) * 128; };
-      auto pb = [&](int j) { return j < nk ? b_cur + (int64_t)j * 128 : b_nxt + (int64_t)(j - nk) * 128; };
       if (nk == 2) { q2a = a_nxt; q2b = b_nxt; }      // (two K tiles per output tile: stream tile 2 is the NEXT output tile's first, known only now)
       const int row_w = bm * G2_BM + 128 * wm, col_l = bn * G2_BN + 64 * wn + c8;
       typename Epi::SPre pre0[4];

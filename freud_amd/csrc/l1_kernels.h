@@ -78,9 +78,7 @@ __global__ __launch_bounds__(256) void normalize_cast_kernel(float* __restrict__
 // prep_x: activation rows (fp32 / fp16 / bf16, [M][d]) -> zero-padded bf16 GEMM operand
 // xb[M_p][d_p]; counts the entries equal to -1 (mse_loss's ignored_index, l1autoencoder.py:31).
 // ------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ float load_as_float(const T* p) { return (float)*p; }
-
+// (load_as_float: common.h)
 template <typename T> struct Vec8;
 template <> struct Vec8<float> { typedef __attribute__((ext_vector_type(8))) float type; };
 template <> struct Vec8<_Float16> { typedef __attribute__((ext_vector_type(8))) _Float16 type; };
@@ -148,14 +146,7 @@ __global__ __launch_bounds__(256) void finalize_count_kernel(const unsigned int*
 }
 
 // ------------------------------------------------------------------------------------------
-// Store of a large output that is next read only after it has left every cache (the [M x n] latent / pre / dpre
-// streams): non-temporal, so that it does not evict the operand tiles the co-resident workgroups share (same-box A/B at
-// d=1280 n=40960: encoder GEMM 7.1 -> 6.4 ms, dpre 7.85 -> 7.55; TopK encoder at d=768 3.03 -> 2.55 ms)
-constexpr int EPI_BATCH_HEAVY = 8;      // prefetch batch of the functors with a large Pre (gemm.h: epi_prefetch_batch)
-#define EPI_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-// ... and the matching read of such a stream inside an epilogue (dpre GEMM reading the latent: 7.6 -> 7.1 ms)
-#define EPI_LOAD(ptr) __builtin_nontemporal_load(ptr)
-
+// (EPI_STORE / EPI_LOAD, the non-temporal accesses of the large streams, and EPI_BATCH_HEAVY: gemm.h)
 // GEMM epilogues (row-major over the fp32 tile, 4 consecutive columns per call).  Two phases per thread and tile:
 // prefetch(row, col) -> Pre issues every global LOAD the element needs (all of a thread's 16 prefetches are in flight
 // before the first apply, so an epilogue pass costs about one memory latency instead of 16), apply() computes and stores.

@@ -45,11 +45,9 @@
 #include "common.h"
 #include "p2p_index.h"
 
-constexpr int P2P_MAX_WORLD = 8;
 constexpr int P2P_MAX_BLOCKS = 64;
 constexpr int P2P_MAX_SEGS = 4;
 constexpr int P2P_THREADS = 512;
-constexpr int P2P_CHANNELS = 2;                        // 0: statistics, 1: gradients (each its own flags and epoch)
 constexpr int P2P_SIG_WORDS = P2P_CHANNELS * 3 * P2P_MAX_BLOCKS * P2P_MAX_WORLD;    // 64-bit words per rank
 enum { P2P_F32 = 0, P2P_F64 = 1, P2P_BF16 = 2 };
 

@@ -11,6 +11,10 @@
 #define P2P_HD inline
 #endif
 
+// (here, not in p2p_exchange.h, because the context of engine_internal.h is sized by them in units that do not hold the kernels)
+constexpr int P2P_MAX_WORLD = 8;
+constexpr int P2P_CHANNELS = 2;                        // 0: statistics, 1: gradients (each its own flags and epoch)
+
 // Vectors [v0, v1) of slice (shard q, workgroup b) of a segment of `total` 16-byte vectors cut into `world` shards of `nblocks`
 // slices.  Shards are ceil(total / world) vectors (the last ones may be short or empty), slices ceil(shard / nblocks).
 P2P_HD void p2p_slice_of(unsigned total, unsigned world, unsigned nblocks, unsigned q, unsigned b, unsigned& v0, unsigned& v1) {

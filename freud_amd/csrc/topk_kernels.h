@@ -554,7 +554,7 @@ __global__ __launch_bounds__(256, (COMPACT && MAXV <= 12) ? SEL_OCC : 1) void to
   // cand (264 dwords at MAXV = 44) made hipcc leave all three on the stack (1072 bytes of scratch per lane)
   constexpr bool CBITS_AHEAD = COMPACT && MAXV <= 12;
   unsigned cbits[CBITS_AHEAD ? MAXV : 1];
-  if (CBITS_AHEAD) {
+  if constexpr (CBITS_AHEAD) {
     // the thread's bytes of vec_bits (vectors t, t + 256, ...) are the same for every row: dead_compact_kernel keeps them transposed
     // behind the table ([256 threads][16 bytes], zeros past the row's end) -- one 16-byte load instead of twelve predicated byte
     // loads (with their branches ~180 of the ~800 instructions this phase issued per thread; the phase is issue-bound)

@@ -51,7 +51,12 @@ def build(force: bool = False) -> str:
     """Compile the HIP engine for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.run(["make", "-C", CSRC_DIR], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    # one compile job per translation unit (csrc/Makefile: SRCS)
+    jobs = os.environ.get("MAX_JOBS") or str(min(16, os.cpu_count() or 1))
+    done = subprocess.run(["make", "-C", CSRC_DIR, "-j", jobs], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if done.returncode != 0:
+        sys.stderr.write(done.stdout)
+        raise EngineError(f"`make -C {CSRC_DIR} -j {jobs}` failed with status {done.returncode}: the compiler's output is above")
     if not os.path.exists(LIB_PATH):
         raise EngineError(f"build did not produce {LIB_PATH}")
     return LIB_PATH

@@ -47,7 +47,7 @@ def resolve_sae(sae):
 
 def default_batch_files(T: int, n: Optional[int], n_total: int) -> int:
     """Files per batch when the caller gives none: 16, or for an L1 / TopK SAE the fewest files at which the encoder GEMM has the
-    2048 output tiles of 256 x 256 that its streaming form (gemm256s.h: engine.hip gemm_streams, 4 x G2_PERSIST_STATIC) needs, so
+    2048 output tiles of 256 x 256 that its streaming form (gemm256s.h: gemm_launch.h gemm_streams, 4 x G2_PERSIST_STATIC) needs, so
     that an L1 pass takes the fused epilogue (n = 3072, T = 1500: 30 files; n = 40 960: 16).  Dictionaries whose padded size is
     no multiple of 256 never stream; above 512 files the batch stays at 16 (n < 1024) and the latent is stored and reduced."""
     B = 16

@@ -152,7 +152,7 @@ def same(a, b):
 @pytest.mark.parametrize("T,F,batch,n", [(50, 9, 4, 1000), (50, 9, 4, 4352), (1500, 3, 2, 1024), (8, 300, 128, 4352)])
 def test_l1_exact_against_encode(tmp_path, T, F, batch, n):
     """n = 1000: padded columns; n = 4352: 17 column blocks; batches of 4 + 4 + 1 and 2 + 1 files: a last partial batch.  128 files
-    at 17 column blocks: the launcher forms chunks of two files (engine.hip, hist_launch_l1), the last batch of 44 chunks of one."""
+    at 17 column blocks: the launcher forms chunks of two files (passes.hip, hist_launch_l1), the last batch of 44 chunks of one."""
     d = 256
     g = np.random.default_rng(T + n)
     x = g.normal(0, 1, (F, T, d)).astype(np.float32)
@@ -468,7 +468,7 @@ def test_fp8_context_is_rejected():
 def test_narrow_lds_counters_do_not_wrap(tmp_path):
     """The L1 kernel counts in 16-bit LDS counters.  Its bound (hist.h, HIST_FLUSH_ROWS): a thread flushes its counters before the
     rows since its last flush would exceed 65 535, so a column that stays in one bin brings a counter to 65 535 and no further.  A
-    chunk is whole files (engine.hip, hist_launch_l1: at n = 256 one column block, so one file per chunk up to 1024 files), hence
+    chunk is whole files (passes.hip, hist_launch_l1: at n = 256 one column block, so one file per chunk up to 1024 files), hence
     the largest chunk at d = 256, n = 256 is one file as long as the context allows: here 65 536 + 64 rows, more than a 16-bit
     counter holds, with zero input and a bias of 1.5 -- every latent is 1.5 on every frame.  Counters that wrapped would lose
     65 536 frames per column."""

@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import build_units
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MEASURES = {"jaccard": 0, "cond": 1, "count": 2}
 
@@ -153,8 +155,7 @@ def test_boundary_has_the_entry_points():
     for name, code in MEASURES.items():
         assert int(re.search(r"SAE_COACT_" + name.upper() + r"\s*=\s*(\d+)", hdr).group(1)) == code == E.COACT_MEASURES[name]
     assert "2^31 - 1" in hdr
-    assert '#include "coact.h"' in open(os.path.join(ROOT, "freud_amd", "csrc", "engine.hip")).read()
-    assert " coact.h " in open(os.path.join(ROOT, "freud_amd", "csrc", "Makefile")).read()
+    assert build_units.assert_one_unit_builds("coact.h") == "passes.hip"
     assert callable(E.coact_neighbor_keys) and callable(E.SaeEngine.coact_files)
 
 

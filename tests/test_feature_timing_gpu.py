@@ -238,7 +238,7 @@ def test_l1_contract_two_runs_batches_and_geometry(l1_setup):
 
 def test_l1_many_bins_take_the_narrow_workgroups(tmp_path):
     """T = 300 at sub_bits = 3 has 49 bins: more LDS per column than 256 columns may take, so the launcher forms workgroups of 128
-    columns (engine.hip, timing_launch_l1) -- n = 300 is then three column blocks, the last one partly padded.  The always-on column
+    columns (passes.hip, timing_launch_l1) -- n = 300 is then three column blocks, the last one partly padded.  The always-on column
     puts a run into the last bin."""
     T, F, s = 300, 2, 3
     L = np.array([T, 123])
@@ -258,7 +258,7 @@ def test_l1_many_bins_take_the_narrow_workgroups(tmp_path):
 
 def test_l1_launcher_chunks_of_several_files(tmp_path):
     """n = 4352 is 17 column blocks, so a batch of 127 files of 8 frames goes out in chunks of two files, the last chunk holding one
-    (engine.hip, timing_launch_l1); the second batch, 23 files, in chunks of one.  The state of a run must not leak from a file into
+    (passes.hip, timing_launch_l1); the second batch, 23 files, in chunks of one.  The state of a run must not leak from a file into
     the next one of its chunk: most runs here touch a file end."""
     T, F, n = 8, 150, 4352
     g = np.random.default_rng(8)

@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import build_units
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 TIMESTEP_S = 30 / 1500
@@ -136,7 +138,7 @@ def test_boundary_has_the_entry_point():
     assert int(re.search(r"SAE_FILE_TOP_POSITIVE\s*=\s*(\d+)", hdr).group(1)) == E.FILE_TOP_POSITIVE
     top = open(os.path.join(ROOT, "freud_amd", "csrc", "file_top.h")).read()
     assert int(re.search(r"#define\s+FT_MAX_TOP\s+(\d+)", top).group(1)) == E.FILE_TOP_MAX
-    assert '#include "file_top.h"' in open(os.path.join(ROOT, "freud_amd", "csrc", "engine.hip")).read()
+    assert build_units.assert_one_unit_builds("file_top.h") == "passes.hip"
     assert callable(E.file_top_features)
 
 

@@ -46,11 +46,19 @@ def disasm():
         so = os.path.join(tmp, "lib.so")
         shutil.copy(LIB, so)
         subprocess.run([OBJDUMP, "--offloading", so], check=True, cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-        cos = [f for f in os.listdir(tmp) if "gfx950" in f]
-        assert len(cos) == 1, f"expected one gfx950 code object, found {cos}"
+        # one gfx950 code object per translation unit of the library: every kernel is defined by exactly one of them
+        cos = sorted(f for f in os.listdir(tmp) if "gfx950" in f)
+        assert cos, "no gfx950 code object in the library"
+        defined = {}
+        for co in cos:
+            r = subprocess.run([OBJDUMP, "-t", os.path.join(tmp, co)], check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+            # symbol-table lines of functions: "<address> <binding> F <section> <size> [<visibility>] <name>"
+            defined[co] = set(re.findall(r"^[0-9a-f]+\s+\S+\s+F\s+\S+\s+[0-9a-f]+\s+(?:\.\w+\s+)?(\S+)\s*$", r.stdout, flags=re.M))
         out = {}
         for key, sym in KERNELS.items():
-            r = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", f"--disassemble-symbols={sym}", os.path.join(tmp, cos[0])],
+            owners = [co for co in cos if sym in defined[co]]
+            assert len(owners) == 1, f"{sym}: defined by {owners or 'no code object'} of {cos}, expected exactly one (renamed? update KERNELS)"
+            r = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", f"--disassemble-symbols={sym}", os.path.join(tmp, owners[0])],
                                check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             ins = []
             for line in r.stdout.splitlines():
@@ -166,18 +174,22 @@ def test_no_kernel_spills_to_scratch():
         so = os.path.join(tmp, "lib.so")
         shutil.copy(LIB, so)
         subprocess.run([OBJDUMP, "--offloading", so], check=True, cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-        co = [f for f in os.listdir(tmp) if "gfx950" in f][0]
-        r = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", os.path.join(tmp, co)], check=True, stdout=subprocess.PIPE,
-                           stderr=subprocess.PIPE, text=True)
-        counts, cur = {}, None
-        for line in r.stdout.splitlines():
-            m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
-            if m:
-                cur = m.group(1)
-                continue
-            if cur and re.search(r"\bscratch_(load|store)", line):
-                counts[cur] = counts.get(cur, 0) + 1
-        assert len(r.stdout) > 1_000_000, "disassembly suspiciously short"
+        cos = sorted(f for f in os.listdir(tmp) if "gfx950" in f)      # one code object per translation unit: all of them
+        assert cos, "no gfx950 code object in the library"
+        counts, total = {}, 0
+        for co in cos:
+            r = subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", os.path.join(tmp, co)], check=True, stdout=subprocess.PIPE,
+                               stderr=subprocess.PIPE, text=True)
+            total += len(r.stdout)
+            cur = None
+            for line in r.stdout.splitlines():
+                m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
+                if m:
+                    cur = m.group(1)
+                    continue
+                if cur and re.search(r"\bscratch_(load|store)", line):
+                    counts[cur] = counts.get(cur, 0) + 1
+        assert total > 1_000_000, "disassembly suspiciously short"
         bad = {k: v for k, v in counts.items() if v > SCRATCH_ALLOWED.get(k, 0)}
         assert not bad, f"kernels with scratch (spill) instructions: {bad}"
     finally:
