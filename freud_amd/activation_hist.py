@@ -39,7 +39,7 @@ import torch
 
 from . import feature_labels as FL
 from .engine import HIST_MAX_SEL, hist_nbins
-from .file_pass import FilePass, is_raw, keep_rng
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
 
 _ARRAYS = ("frame_hist", "file_max_hist", "label_hist", "label_latents", "label_count")
 
@@ -48,6 +48,18 @@ def _prev_bf16(v: np.ndarray) -> np.ndarray:
     """The largest bf16 value below each positive bf16 value of v (float32; +inf -> the largest finite one), as float64."""
     bits = (np.asarray(v, np.float32).view(np.uint32) >> 16) - 1
     return (bits << 16).astype(np.uint32).view(np.float32).astype(np.float64)
+
+
+def quantile_bounds(h: np.ndarray, q: float, lo_b: np.ndarray, hi_b: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Per row of the histograms h (int64 [n, NB]) the bounds (lo_b[b], hi_b[b]), float64 [n], of the bin b that holds the q-th order
+    statistic by the inverted-CDF rank -- the max(1, ceil(q N))-th smallest of the row's N values: the first bin whose cumulative
+    count reaches the rank.  NaN where N = 0."""
+    total = h.sum(1)
+    rank = np.maximum(1, np.ceil(q * total.astype(np.float64)).astype(np.int64))
+    b = (np.cumsum(h, 1) < rank[:, None]).sum(1)
+    ok = total > 0
+    b = np.where(ok, b, 0)
+    return np.where(ok, lo_b[b].astype(np.float64), np.nan), np.where(ok, hi_b[b].astype(np.float64), np.nan)
 
 
 @dataclasses.dataclass
@@ -96,13 +108,7 @@ class ActivationHistograms:
         if active_only:
             h = h.copy()
             h[:, 0] = 0
-        total = h.sum(1)
-        rank = np.maximum(1, np.ceil(q * total.astype(np.float64)).astype(np.int64))
-        b = (np.cumsum(h, 1) < rank[:, None]).sum(1)
-        lo_b, hi_b = self.bin_bounds()
-        ok = total > 0
-        b = np.where(ok, b, 0)
-        return np.where(ok, lo_b[b], np.nan), np.where(ok, hi_b[b], np.nan)
+        return quantile_bounds(h, q, *self.bin_bounds())
 
     def files_in_range(self, min_val: Optional[float] = None, max_val: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Per latent the number of files whose maximum m passes the feature search's filter min_val <= m <= max_val (None: no
@@ -222,39 +228,31 @@ def activation_histograms(sae, data_path: str, layer_name: str, *, lo_exp: int =
         res = ActivationHistograms(fp.n_frames, fp.n_total, spec, frame_hist.cpu().numpy(), file_max_hist.cpu().numpy(),
                                    None if sel is None else lhist.cpu().numpy(), sel, None if sel is None else lcount.cpu().numpy(),
                                    None if class_names is None else [str(s) for s in class_names])
-    if counted != fp.n_frames:
-        raise RuntimeError(f"the engine counted {counted} frames, the pass holds {fp.n_frames}")
+    fp.check_counted(counted)
     return res
 
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Value histograms of every latent of an SAE over a shard directory.")
-    ap.add_argument("--sae", required=True, help="checkpoint path")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+    add_pass_arguments(ap)
     ap.add_argument("--lo_exp", type=int, default=-12)
     ap.add_argument("--octaves", type=int, default=24)
     ap.add_argument("--sub_bits", type=int, default=2)
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
     ap.add_argument("--label_latents", default=None, help="comma-separated latent indices whose histogram is split by label")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--file_labels", default=None, help=".npy of int class ids [n_files] or [n_files, S] (-1 = none)")
     g.add_argument("--frame_labels", default=None, help=".npy of int class ids [n_files, T] or [n_files, T, S] (-1 = none)")
     ap.add_argument("--class_names", default=None, help=".json list of the class names")
-    ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     names = None
     if a.class_names:
         with open(a.class_names) as f:
             names = json.load(f)
-    ah = activation_histograms(a.sae, a.data_path, a.layer_name, lo_exp=a.lo_exp, octaves=a.octaves, sub_bits=a.sub_bits,
-                               lengths=np.load(a.lengths) if a.lengths else None, batch_files=a.batch_files,
-                               label_latents=[int(v) for v in a.label_latents.split(",")] if a.label_latents else None,
-                               file_labels=np.load(a.file_labels, mmap_mode="r") if a.file_labels else None,
-                               frame_labels=np.load(a.frame_labels, mmap_mode="r") if a.frame_labels else None, class_names=names)
-    ah.to_npz(a.out)
-    print(json.dumps({"out": a.out, **ah.summary()}))
+    run_pass_cli(a, lambda lengths: activation_histograms(
+        a.sae, a.data_path, a.layer_name, lo_exp=a.lo_exp, octaves=a.octaves, sub_bits=a.sub_bits, lengths=lengths,
+        batch_files=a.batch_files, label_latents=[int(v) for v in a.label_latents.split(",")] if a.label_latents else None,
+        file_labels=np.load(a.file_labels, mmap_mode="r") if a.file_labels else None,
+        frame_labels=np.load(a.frame_labels, mmap_mode="r") if a.frame_labels else None, class_names=names))
 
 
 if __name__ == "__main__":

@@ -24,7 +24,6 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
-import json
 from typing import Optional
 
 import numpy as np
@@ -32,7 +31,7 @@ import torch
 
 from .engine import COACT_MEASURES, FILE_TOP_MAX, FILE_TOP_POSITIVE
 from .feature_search import unord
-from .file_pass import FilePass, is_raw, keep_rng
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
 
 MAX_FRAMES = 2 ** 31 - 1          # int32 counts
 KEY_BLOCK = 1 << 25               # keys per neighbour-selection block (256 MiB of 64-bit keys)
@@ -155,21 +154,13 @@ def feature_coactivation(sae, data_path: str, layer_name: str, *, n_neighbors: i
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Which latents of an SAE fire together over a shard directory.")
-    ap.add_argument("--sae", required=True, help="checkpoint path")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+    add_pass_arguments(ap)
     ap.add_argument("--n_neighbors", type=int, default=16)
     ap.add_argument("--measure", default="jaccard", choices=sorted(COACT_MEASURES))
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
     ap.add_argument("--counts", action="store_true", help="also store the full int32 count matrix")
-    ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
-    lengths = np.load(a.lengths) if a.lengths else None
-    co = feature_coactivation(a.sae, a.data_path, a.layer_name, n_neighbors=a.n_neighbors, measure=a.measure, lengths=lengths,
-                              batch_files=a.batch_files, return_counts=a.counts)
-    co.to_npz(a.out)
-    print(json.dumps({"out": a.out, **co.summary()}))
+    run_pass_cli(a, lambda lengths: feature_coactivation(a.sae, a.data_path, a.layer_name, n_neighbors=a.n_neighbors, measure=a.measure,
+                                                         lengths=lengths, batch_files=a.batch_files, return_counts=a.counts))
 
 
 if __name__ == "__main__":

@@ -39,7 +39,7 @@ from typing import Iterable, List, Optional, Tuple
 
 import numpy as np
 
-from .engine import COLLECT_MAX_K
+from .engine import COLLECT_MAX_K, _alias
 
 STAT_NAMES = ("rows", "stored", "dropped", "rows_dropped", "max_active", "largest_dropped_bits", "reserved6", "reserved7")
 _INDEX_DTYPES = {"int64": np.int64, "int32": np.int32}
@@ -232,12 +232,7 @@ def _latent_batches(fp):
     for x, file0, nb, _lens in fp:
         fp.eng.eval(x.reshape(nb * fp.T, fp.d))
         ptr, ld = fp.eng.latent_buffer()
-        rows = nb * fp.T
-
-        class _Alias:
-            __cuda_array_interface__ = {"shape": (rows, ld), "typestr": "<i2", "data": (ptr, False), "version": 2}
-
-        lat = torch.as_tensor(_Alias(), device=fp.device).view(torch.bfloat16)[:, :n]
+        lat = _alias(ptr, (nb * fp.T, ld), "<i2", fp.device).view(torch.bfloat16)[:, :n]
         yield file0, lat.float().reshape(nb, fp.T, n).cpu().numpy(), None
 
 

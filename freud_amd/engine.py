@@ -65,6 +65,86 @@ def build(force: bool = False) -> str:
 GRAD_READY_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)   # sae_grad_ready_fn
 
 
+# Every entry point of include/freud_sae.h, once: name -> (restype, argtypes).  load() declares them, EXPORTED_SYMBOLS lists them.
+_vp, _i32, _i64, _dbl, _fptr = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_float)
+_SIGNATURES = {
+    "sae_last_error": (C.c_char_p, []),
+    "sae_version": (C.c_int, []),
+    "sae_create": (C.c_int, [C.POINTER(SaeConfig), C.POINTER(_vp)]),
+    "sae_destroy": (None, [_vp]),
+    "sae_set_params": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "sae_get_params": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "sae_set_opt_state": (C.c_int, [_vp, _i64, C.POINTER(_vp), C.POINTER(_vp), C.c_int]),
+    "sae_get_opt_state": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_vp), C.POINTER(_vp), C.c_int]),
+    "sae_forward_backward": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
+    "sae_grad_buffer": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "sae_optimizer_step": (C.c_int, [_vp, _dbl, _dbl, _vp]),
+    "sae_batch_stats": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
+    "sae_stats_buffer": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "sae_set_dp_world": (C.c_int, [_vp, C.c_int]),
+    "sae_dist_unique_id": (C.c_int, [_vp, _i64]),
+    "sae_dist_init": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int]),
+    "sae_dist_world": (C.c_int, [_vp]),
+    "sae_dist_set_payload": (C.c_int, [_vp, C.c_int]),
+    "sae_p2p_blob_bytes": (C.c_int, []),
+    "sae_p2p_export": (C.c_int, [_vp, _vp, _i64]),
+    "sae_p2p_init": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int]),
+    "sae_p2p_leave": (C.c_int, [_vp]),
+    "sae_dist_set_overlap": (C.c_int, [_vp, C.c_int]),
+    "sae_dist_check": (C.c_int, [_vp]),
+    "sae_dist_poll": (C.c_int, [_vp]),
+    "sae_dist_audit": (C.c_int, [_vp, _vp]),
+    "sae_grad_layout": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sae_param_checksum": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "sae_set_grad_ready_callback": (C.c_int, [_vp, GRAD_READY_FN, _vp]),
+    "sae_get_topk_state": (C.c_int, [_vp, C.POINTER(C.c_int64), _i64]),
+    "sae_set_topk_state": (C.c_int, [_vp, C.POINTER(C.c_int64), _i64]),
+    "sae_set_topk_options": (C.c_int, [_vp, _dbl, _i64]),
+    "sae_step": (C.c_int, [_vp, _vp, _i64, C.c_int, _dbl, _vp]),
+    "sae_eval": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
+    "sae_eval_into": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
+    "sae_set_eval_precision": (C.c_int, [_vp, C.c_int]),
+    "sae_latent_buffer": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "sae_topk_indices": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_int)]),
+    "sae_decode": (C.c_int, [_vp, _vp, C.c_int, _i64, _i64, _vp, _vp]),
+    "sae_multi_topk_buffers": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_vp), C.POINTER(C.c_int)]),
+    "sae_read_metrics": (C.c_int, [_vp, _fptr, _vp]),
+    "sae_latent_colmax": (C.c_int, [_vp, _fptr, _i64, _vp]),
+    "sae_debug_read": (C.c_int, [_vp, C.c_int, _fptr, _i64]),
+    "sae_search_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "sae_search_raw_files": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "sae_search_merge": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int, C.c_int, _dbl, _dbl, _vp, _vp, _vp]),
+    "sae_search_file_values": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "sae_file_top_features": (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "sae_stats_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "sae_coact_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "sae_coact_neighbor_keys": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp]),
+    "sae_label_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "sae_label_keys": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, _i64, _i64, _vp, _vp]),
+    "sae_hist_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
+                                 C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "sae_timing_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "sae_dict_pack_bytes": (_i64, [_i64, _i64]),
+    "sae_dict_pack": (C.c_int, [_vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp]),
+    "sae_dict_sim_keys": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, C.c_int, _vp, _vp]),
+    "sae_manipulate_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.POINTER(_i32), C.POINTER(_i32), C.c_int, _fptr, C.c_int, C.c_int,
+                                       _vp, _vp, _vp, _vp]),
+    "sae_recon_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "sae_collect_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sae_findex_workspace_bytes": (_i64, [_i64, _i64]),
+    "sae_findex_count": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _vp, _vp, _vp]),
+    "sae_findex_fill": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp,
+                                  _vp]),
+    "sae_findex_verify": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "sae_profile": (C.c_int, [_vp, C.c_int]),
+    "sae_profile_period": (C.c_int, [_vp, C.c_int]),
+    "sae_kernel_times": (C.c_int, [_vp, _fptr, C.POINTER(_i32), C.c_int]),
+    "sae_kernel_name": (C.c_char_p, [C.c_int]),
+    "sae_dominant_kernel": (C.c_int, [_vp]),
+}
+EXPORTED_SYMBOLS = list(_SIGNATURES)
+
+
 def load() -> C.CDLL:
     """dlopen the engine and declare every symbol of include/freud_sae.h."""
     global _lib
@@ -76,84 +156,8 @@ def load() -> C.CDLL:
             f"(run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C {CSRC_DIR}`). "
             "There is no CPU fallback for the train step.")
     lib = C.CDLL(LIB_PATH)
-    vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-    fptr = C.POINTER(C.c_float)
-    sig = {
-        "sae_last_error": (C.c_char_p, []),
-        "sae_version": (C.c_int, []),
-        "sae_create": (C.c_int, [C.POINTER(SaeConfig), C.POINTER(vp)]),
-        "sae_destroy": (None, [vp]),
-        "sae_set_params": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
-        "sae_get_params": (C.c_int, [vp, vp, vp, vp, vp, C.c_int]),
-        "sae_set_opt_state": (C.c_int, [vp, i64, C.POINTER(vp), C.POINTER(vp), C.c_int]),
-        "sae_get_opt_state": (C.c_int, [vp, C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.c_int]),
-        "sae_forward_backward": (C.c_int, [vp, vp, i64, C.c_int, vp]),
-        "sae_grad_buffer": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i64)]),
-        "sae_optimizer_step": (C.c_int, [vp, dbl, dbl, vp]),
-        "sae_batch_stats": (C.c_int, [vp, vp, i64, C.c_int, vp]),
-        "sae_stats_buffer": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i64)]),
-        "sae_set_dp_world": (C.c_int, [vp, C.c_int]),
-        "sae_dist_unique_id": (C.c_int, [vp, i64]),
-        "sae_dist_init": (C.c_int, [vp, vp, i64, C.c_int, C.c_int]),
-        "sae_dist_world": (C.c_int, [vp]),
-        "sae_dist_set_payload": (C.c_int, [vp, C.c_int]),
-        "sae_p2p_blob_bytes": (C.c_int, []),
-        "sae_p2p_export": (C.c_int, [vp, vp, i64]),
-        "sae_p2p_init": (C.c_int, [vp, vp, i64, C.c_int, C.c_int]),
-        "sae_p2p_leave": (C.c_int, [vp]),
-        "sae_dist_set_overlap": (C.c_int, [vp, C.c_int]),
-        "sae_dist_check": (C.c_int, [vp]),
-        "sae_dist_poll": (C.c_int, [vp]),
-        "sae_dist_audit": (C.c_int, [vp, vp]),
-        "sae_grad_layout": (C.c_int, [vp, C.POINTER(i64)]),
-        "sae_param_checksum": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
-        "sae_set_grad_ready_callback": (C.c_int, [vp, GRAD_READY_FN, vp]),
-        "sae_get_topk_state": (C.c_int, [vp, C.POINTER(C.c_int64), i64]),
-        "sae_set_topk_state": (C.c_int, [vp, C.POINTER(C.c_int64), i64]),
-        "sae_set_topk_options": (C.c_int, [vp, dbl, i64]),
-        "sae_step": (C.c_int, [vp, vp, i64, C.c_int, dbl, vp]),
-        "sae_eval": (C.c_int, [vp, vp, i64, C.c_int, vp]),
-        "sae_eval_into": (C.c_int, [vp, vp, i64, C.c_int, vp, vp, vp]),
-        "sae_set_eval_precision": (C.c_int, [vp, C.c_int]),
-        "sae_latent_buffer": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i64)]),
-        "sae_topk_indices": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_int)]),
-        "sae_decode": (C.c_int, [vp, vp, C.c_int, i64, i64, vp, vp]),
-        "sae_multi_topk_buffers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), C.POINTER(C.c_int)]),
-        "sae_read_metrics": (C.c_int, [vp, fptr, vp]),
-        "sae_latent_colmax": (C.c_int, [vp, fptr, i64, vp]),
-        "sae_debug_read": (C.c_int, [vp, C.c_int, fptr, i64]),
-        "sae_search_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
-        "sae_search_raw_files": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp]),
-        "sae_search_merge": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, dbl, dbl, vp, vp, vp]),
-        "sae_search_file_values": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, i64, i64, i64, vp, vp]),
-        "sae_file_top_features": (C.c_int, [vp, i64, i64, C.c_int, C.c_int, vp, vp, vp]),
-        "sae_stats_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
-        "sae_coact_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp]),
-        "sae_coact_neighbor_keys": (C.c_int, [vp, i64, i64, i64, C.c_int, vp, vp]),
-        "sae_label_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
-        "sae_label_keys": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, i64, i64, vp, vp]),
-        "sae_hist_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int,
-                                     vp, C.c_int, vp, vp, vp]),
-        "sae_timing_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp, vp]),
-        "sae_dict_pack_bytes": (i64, [i64, i64]),
-        "sae_dict_pack": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, vp, vp]),
-        "sae_dict_sim_keys": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, C.c_int, vp, vp]),
-        "sae_manipulate_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.POINTER(i32), C.POINTER(i32), C.c_int, fptr, C.c_int, C.c_int,
-                                           vp, vp, vp, vp]),
-        "sae_recon_files": (C.c_int, [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp]),
-        "sae_collect_files": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
-        "sae_findex_workspace_bytes": (i64, [i64, i64]),
-        "sae_findex_count": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, i64, vp, vp, vp]),
-        "sae_findex_fill": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, i64, i64, i64, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp]),
-        "sae_findex_verify": (C.c_int, [vp, i64, i64, i64, i64, vp, i64, i64, vp, vp]),
-        "sae_profile": (C.c_int, [vp, C.c_int]),
-        "sae_profile_period": (C.c_int, [vp, C.c_int]),
-        "sae_kernel_times": (C.c_int, [vp, fptr, C.POINTER(i32), C.c_int]),
-        "sae_kernel_name": (C.c_char_p, [C.c_int]),
-        "sae_dominant_kernel": (C.c_int, [vp]),
-    }
     skipped = []
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _SIGNATURES.items():
         try:
             fn = getattr(lib, name)      # AttributeError here = header / library mismatch
         except AttributeError:
@@ -173,28 +177,6 @@ def load() -> C.CDLL:
     return lib
 
 
-EXPORTED_SYMBOLS = [
-    "sae_last_error", "sae_version", "sae_create", "sae_destroy", "sae_set_params", "sae_get_params",
-    "sae_set_opt_state", "sae_get_opt_state", "sae_forward_backward", "sae_grad_buffer", "sae_optimizer_step",
-    "sae_set_grad_ready_callback", "sae_batch_stats", "sae_stats_buffer", "sae_set_dp_world", "sae_dist_unique_id",
-    "sae_dist_init", "sae_dist_world", "sae_dist_set_payload", "sae_p2p_blob_bytes", "sae_p2p_export", "sae_p2p_init", "sae_p2p_leave",
-    "sae_dist_set_overlap", "sae_dist_check", "sae_dist_poll", "sae_dist_audit", "sae_grad_layout", "sae_param_checksum", "sae_set_topk_options", "sae_get_topk_state", "sae_set_topk_state",
-    "sae_latent_buffer", "sae_topk_indices", "sae_decode", "sae_multi_topk_buffers",
-    "sae_step", "sae_eval", "sae_eval_into", "sae_set_eval_precision", "sae_read_metrics", "sae_latent_colmax", "sae_debug_read", "sae_profile", "sae_profile_period", "sae_kernel_times",
-    "sae_kernel_name", "sae_dominant_kernel",
-    "sae_search_files", "sae_search_raw_files", "sae_search_merge", "sae_search_file_values",
-    "sae_stats_files",
-    "sae_file_top_features",
-    "sae_coact_files", "sae_coact_neighbor_keys",
-    "sae_label_files", "sae_label_keys",
-    "sae_hist_files",
-    "sae_timing_files",
-    "sae_dict_pack_bytes", "sae_dict_pack", "sae_dict_sim_keys",
-    "sae_manipulate_files",
-    "sae_recon_files",
-    "sae_collect_files",
-    "sae_findex_workspace_bytes", "sae_findex_count", "sae_findex_fill", "sae_findex_verify",
-]
 SEARCH_ABS, SEARCH_MIN, SEARCH_MAX, SEARCH_UNFUSED = 1, 2, 4, 8     # include/freud_sae.h: SAE_SEARCH_*
 SEARCH_MAX_TOP = 4096
 FILE_TOP_POSITIVE = 1                                               # include/freud_sae.h: SAE_FILE_TOP_POSITIVE
@@ -241,11 +223,24 @@ def recon_layout(n: int, d: int) -> dict:
             "bytes": (8 + 20 * n + 24 * d + 7) // 8 * 8}
 
 
+def unpack_block(block, layout: dict) -> Dict[str, np.ndarray]:
+    """The arrays of a block read back from the device (uint8 bytes) by its stats_layout / recon_layout: name -> a copy."""
+    b = np.ascontiguousarray(block).view(np.uint8)
+    return {name: np.frombuffer(b, dtype=at[1], count=at[2], offset=at[0]).copy() for name, at in layout.items() if name != "bytes"}
+
+
+def check_sub_bits(sub_bits) -> int:
+    """sub_bits (2^sub_bits bins per octave: freud_amd/csrc/hist_bins.h, timing_bins.h) as an int; ValueError outside [0, 3]."""
+    sub_bits = int(sub_bits)
+    if sub_bits < 0 or sub_bits > 3:
+        raise ValueError(f"sub_bits={sub_bits} outside [0, 3]")
+    return sub_bits
+
+
 def hist_nbins(spec) -> int:
     """Bins of a histogram spec (lo_exp, octaves, sub_bits) -- freud_amd/csrc/hist_bins.h; ValueError for a spec outside its limits."""
     lo_exp, octaves, sub_bits = (int(v) for v in spec)
-    if sub_bits < 0 or sub_bits > 3:
-        raise ValueError(f"sub_bits={sub_bits} outside [0, 3]")
+    check_sub_bits(sub_bits)
     if lo_exp < -126 or octaves < 1 or lo_exp + octaves > 128:
         raise ValueError(f"lo_exp={lo_exp}, octaves={octaves}: -126 <= lo_exp, octaves >= 1 and lo_exp + octaves <= 128")
     if (octaves << sub_bits) > HIST_MAX_REGULAR:
@@ -264,9 +259,7 @@ def timing_index(L: int, sub_bits: int) -> int:
 
 def timing_nbins(sub_bits: int, T: int) -> int:
     """Bins of the feature timing for files of T frames -- freud_amd/csrc/timing_bins.h; ValueError for a spec outside its limits."""
-    sub_bits, T = int(sub_bits), int(T)
-    if sub_bits < 0 or sub_bits > 3:
-        raise ValueError(f"sub_bits={sub_bits} outside [0, 3]")
+    sub_bits, T = check_sub_bits(sub_bits), int(T)
     if T < 1 or T > TIMING_MAX_ROWS:
         raise ValueError(f"T={T} frames per file outside [1, {TIMING_MAX_ROWS}]")
     return timing_index(T, sub_bits)
@@ -288,6 +281,12 @@ def _shaped(name: str, a, shape) -> np.ndarray:
     if arr.size != int(np.prod(shape)):
         raise EngineError(f"{name}: got {arr.shape} ({arr.size} elements), the engine expects {tuple(shape)}")
     return arr.reshape(shape)
+
+
+def _quad(arrays):
+    """The four pointer slots of the parameter and optimizer-state calls: the arrays' host pointers in parameter order, then nulls."""
+    ptrs = [a.ctypes.data for a in arrays]
+    return (C.c_void_p * 4)(*(ptrs + [None] * (4 - len(ptrs))))
 
 
 class SaeEngine:
@@ -345,31 +344,25 @@ class SaeEngine:
 
     def set_params(self, params: Dict[str, np.ndarray]) -> None:
         arrs = [_shaped(k, params[k], shape) for k, shape in self.param_shapes().items()]
-        ptrs = [a.ctypes.data_as(C.c_void_p) for a in arrs] + [None] * (4 - len(arrs))
-        _check(self._lib.sae_set_params(self._ctx, *ptrs, 0))
+        _check(self._lib.sae_set_params(self._ctx, *_quad(arrs), 0))
 
     def get_params(self) -> Dict[str, np.ndarray]:
         out = {k: np.empty(shape, dtype=np.float32) for k, shape in self.param_shapes().items()}
-        ptrs = [a.ctypes.data_as(C.c_void_p) for a in out.values()] + [None] * (4 - len(out))
-        _check(self._lib.sae_get_params(self._ctx, *ptrs, 0))
+        _check(self._lib.sae_get_params(self._ctx, *_quad(out.values()), 0))
         return out
 
     def set_opt_state(self, step: int, exp_avg: Dict[str, np.ndarray], exp_avg_sq: Dict[str, np.ndarray]) -> None:
         shapes = self.param_shapes()
         a = [_shaped(f"exp_avg[{k}]", exp_avg[k], s) for k, s in shapes.items()]
         b = [_shaped(f"exp_avg_sq[{k}]", exp_avg_sq[k], s) for k, s in shapes.items()]
-        pa = (C.c_void_p * 4)(*([x.ctypes.data for x in a] + [None] * (4 - len(a))))
-        pb = (C.c_void_p * 4)(*([x.ctypes.data for x in b] + [None] * (4 - len(b))))
-        _check(self._lib.sae_set_opt_state(self._ctx, int(step), pa, pb, 0))
+        _check(self._lib.sae_set_opt_state(self._ctx, int(step), _quad(a), _quad(b), 0))
 
     def get_opt_state(self):
         shapes = self.param_shapes()
         a = {k: np.empty(s, dtype=np.float32) for k, s in shapes.items()}
         b = {k: np.empty(s, dtype=np.float32) for k, s in shapes.items()}
-        pa = (C.c_void_p * 4)(*([x.ctypes.data for x in a.values()] + [None] * (4 - len(a))))
-        pb = (C.c_void_p * 4)(*([x.ctypes.data for x in b.values()] + [None] * (4 - len(b))))
         step = C.c_int64(0)
-        _check(self._lib.sae_get_opt_state(self._ctx, C.byref(step), pa, pb, 0))
+        _check(self._lib.sae_get_opt_state(self._ctx, C.byref(step), _quad(a.values()), _quad(b.values()), 0))
         return int(step.value), a, b
 
     def set_topk_options(self, dead_feature_threshold: float, rows_per_file: int) -> None:
@@ -410,9 +403,15 @@ class SaeEngine:
         if self.variant == "topk" and x.dim() == 3 and getattr(self, "_rows_per_file", None) != x.shape[1]:
             self.set_topk_options(getattr(self, "_dead_threshold", 1e300), x.shape[1])
 
+    def _x(self, x):
+        """The front of every hot-path call: _note_shape, then what _x_args returns.  (The variant is tested here and the tuple is
+        passed on as it is, so that an L1 step makes the two calls it made before and nothing else.)"""
+        if self.variant == "topk":
+            self._note_shape(x)
+        return self._x_args(x)
+
     def forward_backward(self, x, stream=None) -> None:
-        self._note_shape(x)
-        x, ptr, rows, dt = self._x_args(x)
+        x, ptr, rows, dt = self._x(x)
         _check(self._lib.sae_forward_backward(self._ctx, C.c_void_p(ptr), rows, dt, _stream_ptr(stream)))
         err, self._cb_error = getattr(self, "_cb_error", None), None
         if err is not None:
@@ -421,21 +420,15 @@ class SaeEngine:
     # -- data parallel (include/freud_sae.h, "data-parallel exactness") ------------------------------------
     def batch_stats(self, x, stream=None) -> None:
         """This rank's statistics of batch x (what the losses normalise by) into the statistics buffer."""
-        self._note_shape(x)
-        x, ptr, rows, dt = self._x_args(x)
+        x, ptr, rows, dt = self._x(x)
         _check(self._lib.sae_batch_stats(self._ctx, C.c_void_p(ptr), rows, dt, _stream_ptr(stream)))
 
     def stats_tensor(self):
         """The statistics of the last batch_stats() as a float64 torch CUDA tensor aliasing the engine's buffer:
         all-reduce (sum) it over the ranks before forward_backward()."""
-        import torch
         p, n = C.c_void_p(), C.c_int64()
         _check(self._lib.sae_stats_buffer(self._ctx, C.byref(p), C.byref(n)))
-
-        class _Alias:
-            __cuda_array_interface__ = {"shape": (int(n.value),), "typestr": "<f8", "data": (int(p.value), False), "version": 2}
-
-        return torch.as_tensor(_Alias(), device=f"cuda:{self.device_id}")
+        return _alias(int(p.value), (int(n.value),), "<f8", f"cuda:{self.device_id}")
 
     def set_dp_world(self, world: int) -> None:
         _check(self._lib.sae_set_dp_world(self._ctx, int(world)))
@@ -517,13 +510,11 @@ class SaeEngine:
         _check(self._lib.sae_optimizer_step(self._ctx, float(lr), float(grad_scale), _stream_ptr(stream)))
 
     def step(self, x, lr: float, stream=None) -> None:
-        self._note_shape(x)
-        x, ptr, rows, dt = self._x_args(x)
+        x, ptr, rows, dt = self._x(x)
         _check(self._lib.sae_step(self._ctx, C.c_void_p(ptr), rows, dt, float(lr), _stream_ptr(stream)))
 
     def eval(self, x, stream=None) -> None:
-        self._note_shape(x)
-        x, ptr, rows, dt = self._x_args(x)
+        x, ptr, rows, dt = self._x(x)
         _check(self._lib.sae_eval(self._ctx, C.c_void_p(ptr), rows, dt, _stream_ptr(stream)))
 
     def set_eval_precision(self, precision: str) -> None:
@@ -540,15 +531,13 @@ class SaeEngine:
     def eval_into(self, x, metrics_row, colmax_row=None, stream=None) -> None:
         """eval() of one file with its 8 loss scalars (and per-feature latent maxima) left in the given fp32 CUDA rows:
         no host synchronisation (validate() reads all rows once at the end)."""
-        self._note_shape(x)
-        x, ptr, rows, dt = self._x_args(x)
+        x, ptr, rows, dt = self._x(x)
         assert metrics_row.is_cuda and metrics_row.is_contiguous() and metrics_row.numel() >= NUM_METRICS
         cm = None
         if colmax_row is not None:
             assert colmax_row.is_cuda and colmax_row.is_contiguous() and colmax_row.numel() >= self.n
             cm = C.c_void_p(colmax_row.data_ptr())
-        _check(self._lib.sae_eval_into(self._ctx, C.c_void_p(ptr), rows, dt, C.c_void_p(metrics_row.data_ptr()), cm,
-                                       _stream_ptr(stream)))
+        _check(self._lib.sae_eval_into(self._ctx, C.c_void_p(ptr), rows, dt, C.c_void_p(metrics_row.data_ptr()), cm, _stream_ptr(stream)))
 
     # -- inference (SURVEY section 8 row f3) ---------------------------------------------------------
     def latent_buffer(self):
@@ -559,14 +548,9 @@ class SaeEngine:
 
     def topk_indices_tensor(self, rows: int, device):
         """int32 [rows][k] torch view of the top-k indices of the last forward (TopK contexts; EngineError after an fp32 evaluation)."""
-        import torch
         ptr, k = C.c_void_p(), C.c_int()
         _check(self._lib.sae_topk_indices(self._ctx, C.byref(ptr), C.byref(k)))
-
-        class _Alias:
-            __cuda_array_interface__ = {"shape": (rows, k.value), "typestr": "<i4", "data": (ptr.value, False), "version": 2}
-
-        return torch.as_tensor(_Alias(), device=device)
+        return _alias(ptr.value, (rows, k.value), "<i4", device)
 
     def multi_topk_buffers(self, rows: int, device):
         """TopK with multi_topk: (bf16 [rows][n_dict] dense 4k activations, int32 [rows][4k] indices) of the last forward
@@ -574,15 +558,8 @@ class SaeEngine:
         import torch
         dptr, ld, iptr, k4 = C.c_void_p(), C.c_int64(), C.c_void_p(), C.c_int()
         _check(self._lib.sae_multi_topk_buffers(self._ctx, C.byref(dptr), C.byref(ld), C.byref(iptr), C.byref(k4)))
-
-        class _D:
-            __cuda_array_interface__ = {"shape": (rows, ld.value), "typestr": "<i2", "data": (dptr.value, False), "version": 2}
-
-        class _I:
-            __cuda_array_interface__ = {"shape": (rows, k4.value), "typestr": "<i4", "data": (iptr.value, False), "version": 2}
-
-        dense = torch.as_tensor(_D(), device=device).view(torch.bfloat16)[:, : self.n]
-        return dense, torch.as_tensor(_I(), device=device)
+        dense = _alias(dptr.value, (rows, ld.value), "<i2", device).view(torch.bfloat16)[:, : self.n]
+        return dense, _alias(iptr.value, (rows, k4.value), "<i4", device)
 
     def decode(self, latent, out, stream=None) -> None:
         """out[rows][d_model] (fp32 CUDA tensor) = decode(latent[rows][>= n_dict]) (fp32 or bf16 CUDA tensor, row-major)."""
@@ -635,35 +612,25 @@ class SaeEngine:
 
     def grad_tensor(self):
         """The gradient buffer as a torch CUDA tensor aliasing the engine's HBM (no copy)."""
-        import torch
         ptr, n = self.grad_buffer()
-
-        class _Alias:
-            __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False), "version": 2}
-
-        return torch.as_tensor(_Alias(), device=f"cuda:{self.device_id}")
+        return _alias(ptr, (n,), "<f4", f"cuda:{self.device_id}")
 
     # -- feature search (include/freud_sae.h: sae_search_*; freud_amd/feature_search.py) ------------------
     def search_files(self, x, file_keys, lengths=None, unfused: bool = False, stream=None) -> None:
         """Per-(file, latent) keys of x [n_files, T, d] (CUDA) into file_keys (int64 CUDA tensor [n_files, n_dict]); lengths: int32
         CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
         x, xp, B, T, _d, dt, lp = _files_args(x, "search_files", lengths)
-        _check_search_out(file_keys, B * self.n)
-        _check(self._lib.sae_search_files(self._ctx, xp, B, T, dt, lp, SEARCH_UNFUSED if unfused else 0,
-                                          C.c_void_p(file_keys.data_ptr()), _stream_ptr(stream)))
+        keys = _dev("file_keys", file_keys, "int64", B * self.n, at_least=True)
+        _check(self._lib.sae_search_files(self._ctx, xp, B, T, dt, lp, SEARCH_UNFUSED if unfused else 0, keys, _stream_ptr(stream)))
 
     # -- feature statistics (include/freud_sae.h: sae_stats_files; freud_amd/feature_stats.py) -----------------------------
     def stats_files(self, x, stats_block, lengths=None, unfused: bool = False, stream=None) -> None:
         """Add the statistics of x [n_files, T, d] (CUDA) to stats_block (a zero-initialised uint8 CUDA tensor of
         stats_layout(n)["bytes"] bytes); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward
         getters fail until the next eval() / step()."""
-        import torch
         x, xp, B, T, _d, dt, lp = _files_args(x, "stats_files", lengths)
-        nbytes = stats_layout(self.n)["bytes"]
-        if not (stats_block.is_cuda and stats_block.dtype == torch.uint8 and stats_block.is_contiguous() and stats_block.numel() >= nbytes):
-            raise EngineError(f"stats_block must be a contiguous uint8 CUDA tensor of >= {nbytes} bytes")
-        _check(self._lib.sae_stats_files(self._ctx, xp, B, T, dt, lp, STATS_UNFUSED if unfused else 0,
-                                         C.c_void_p(stats_block.data_ptr()), _stream_ptr(stream)))
+        block = _dev("stats_block", stats_block, "uint8", stats_layout(self.n)["bytes"], at_least=True)
+        _check(self._lib.sae_stats_files(self._ctx, xp, B, T, dt, lp, STATS_UNFUSED if unfused else 0, block, _stream_ptr(stream)))
 
     # -- feature co-activation (include/freud_sae.h: sae_coact_files; freud_amd/coactivation.py) ---------------------------
     def coact_files(self, x, counts, lengths=None, stream=None) -> None:
@@ -671,8 +638,8 @@ class SaeEngine:
         [n_dict, n_dict]); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail
         until the next eval() / step()."""
         x, xp, B, T, _d, dt, lp = _files_args(x, "coact_files", lengths)
-        _check_coact_table(counts, self.n)
-        _check(self._lib.sae_coact_files(self._ctx, xp, B, T, dt, lp, 0, C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+        table = _dev("counts", counts, "int32", self.n * self.n)
+        _check(self._lib.sae_coact_files(self._ctx, xp, B, T, dt, lp, 0, table, _stream_ptr(stream)))
 
     # -- feature labels (include/freud_sae.h: sae_label_files; freud_amd/feature_labels.py) ---------------------------------
     def label_files(self, x, labels, n_classes: int, counts, label_count, lengths=None, stream=None) -> None:
@@ -680,14 +647,10 @@ class SaeEngine:
         ids in [0, n_classes), -1 = empty) to counts (zero-initialised contiguous int32 CUDA [n_classes + 1, n_dict]) and label_count
         (zero-initialised int64 CUDA [n_classes + 1]); lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards
         the last-forward getters fail until the next eval() / step()."""
-        import torch
         x, xp, B, T, _d, dt, lp = _files_args(x, "label_files", lengths)
-        if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3
-                and tuple(labels.shape[:2]) == (B, T)):
-            raise EngineError(f"labels must be a contiguous int32 CUDA tensor [{B}, {T}, n_slots]")
-        _check_label_table(counts, label_count, n_classes, self.n)
-        _check(self._lib.sae_label_files(self._ctx, xp, B, T, dt, lp, C.c_void_p(labels.data_ptr()), int(labels.shape[2]), int(n_classes),
-                                         0, C.c_void_p(counts.data_ptr()), C.c_void_p(label_count.data_ptr()), _stream_ptr(stream)))
+        lab, n_slots = _labels_arg(labels, B, T)
+        table, lc = _label_table(counts, label_count, n_classes, self.n)
+        _check(self._lib.sae_label_files(self._ctx, xp, B, T, dt, lp, lab, n_slots, int(n_classes), 0, table, lc, _stream_ptr(stream)))
 
     # -- activation histograms (include/freud_sae.h: sae_hist_files; freud_amd/activation_hist.py) ------------------------------
     def hist_files(self, x, spec, frame_hist, file_max_hist, n_frames, lengths=None, labels=None, n_classes: int = 0, sel_latents=None,
@@ -698,32 +661,21 @@ class SaeEngine:
         int32 CUDA [n_files, T, n_slots], as label_files) also to label_hist (int64 CUDA [n_sel, n_classes + 1, NB]) and label_count
         (int64 CUDA [n_classes + 1]).  The same arrays go to every call of one pass.  Asynchronous.  Afterwards the last-forward
         getters fail until the next eval() / step()."""
-        import torch
         x, xp, B, T, _d, dt, lp = _files_args(x, "hist_files", lengths)
         lo_exp, octaves, sub_bits = (int(v) for v in spec)
         nb = hist_nbins(spec)
-
-        def i64(t, numel, name):
-            if not (t is not None and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == numel):
-                raise EngineError(f"{name} must be a contiguous int64 CUDA tensor of {numel} elements")
-            return C.c_void_p(t.data_ptr())
-
-        fh, mh, nf = i64(frame_hist, self.n * nb, "frame_hist"), i64(file_max_hist, self.n * nb, "file_max_hist"), i64(n_frames, 1, "n_frames")
+        fh, mh = _dev("frame_hist", frame_hist, "int64", self.n * nb), _dev("file_max_hist", file_max_hist, "int64", self.n * nb)
+        nf = _dev("n_frames", n_frames, "int64", 1)
         n_sel = 0 if sel_latents is None else int(sel_latents.numel())
         lab = sel = lh = lc = None
         n_slots = 0
         if n_sel:
             if n_sel > HIST_MAX_SEL:
                 raise EngineError(f"{n_sel} chosen latents > {HIST_MAX_SEL}")
-            if not (sel_latents.is_cuda and sel_latents.dtype == torch.int32 and sel_latents.is_contiguous()):
-                raise EngineError("sel_latents must be a contiguous int32 CUDA tensor")
-            if not (labels is not None and labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3
-                    and tuple(labels.shape[:2]) == (B, T)):
-                raise EngineError(f"labels must be a contiguous int32 CUDA tensor [{B}, {T}, n_slots]")
-            n_slots = int(labels.shape[2])
-            lab, sel = C.c_void_p(labels.data_ptr()), C.c_void_p(sel_latents.data_ptr())
-            lh = i64(label_hist, n_sel * (int(n_classes) + 1) * nb, "label_hist")
-            lc = i64(label_count, int(n_classes) + 1, "label_count")
+            sel = _dev("sel_latents", sel_latents, "int32", n_sel)      # (its own size: n_sel is read off it)
+            lab, n_slots = _labels_arg(labels, B, T)
+            lh = _dev("label_hist", label_hist, "int64", n_sel * (int(n_classes) + 1) * nb)
+            lc = _dev("label_count", label_count, "int64", int(n_classes) + 1)
         _check(self._lib.sae_hist_files(self._ctx, xp, B, T, dt, lp, lo_exp, octaves, sub_bits, 0, fh, mh, nf, lab, n_slots, int(n_classes),
                                         sel, n_sel, lh, lc, _stream_ptr(stream)))
 
@@ -736,24 +688,16 @@ class SaeEngine:
         of its value exceed threshold_bits; lengths: int32 CUDA tensor [n_files] or None.  The same arrays go to every call of one
         pass.  one_chunk: an L1 context walks all files of the call in one chunk per column block (another launch geometry, the same
         arrays; slower).  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
-        import torch
         x, xp, B, T, _d, dt, lp = _files_args(x, "timing_files", lengths)
         nb = timing_nbins(sub_bits, T)
-
-        def i64(t, numel, name):
-            if not (t is not None and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == numel):
-                raise EngineError(f"{name} must be a contiguous int64 CUDA tensor of {numel} elements")
-            return C.c_void_p(t.data_ptr())
-
-        rh, gh = i64(run_hist, self.n * nb, "run_hist"), i64(gap_hist, self.n * nb, "gap_hist")
-        tt, nf = i64(totals, self.n * TIMING_NTOTALS, "totals"), i64(n_frames, 1, "n_frames")
+        rh, gh = _dev("run_hist", run_hist, "int64", self.n * nb), _dev("gap_hist", gap_hist, "int64", self.n * nb)
+        tt, nf = _dev("totals", totals, "int64", self.n * TIMING_NTOTALS), _dev("n_frames", n_frames, "int64", 1)
         if not 0 <= int(bridge) <= TIMING_MAX_BRIDGE:
             raise EngineError(f"bridge={bridge} outside [0, {TIMING_MAX_BRIDGE}]")
         if not 0 <= int(threshold_bits) <= 0x7F80:
             raise EngineError(f"threshold_bits={threshold_bits} outside [0, 0x7F80]")
         _check(self._lib.sae_timing_files(self._ctx, xp, B, T, dt, lp, int(sub_bits), int(bridge), int(threshold_bits),
-                                          TIMING_ONE_CHUNK if one_chunk else 0, rh, gh, tt, nf,
-                                          _stream_ptr(stream)))
+                                          TIMING_ONE_CHUNK if one_chunk else 0, rh, gh, tt, nf, _stream_ptr(stream)))
 
     # -- feature manipulation (include/freud_sae.h: sae_manipulate_files; freud_amd/manipulate.py) -------------------------
     def manipulate_files(self, x, latents, ops, values, standard, manipulated, series, stream=None) -> None:
@@ -761,7 +705,6 @@ class SaeEngine:
         values [V, E] and decode both ways, into contiguous fp32 CUDA tensors: standard (n_files * T * d elements), manipulated
         (V times that) and series (E * n_files * T: the edited latents' own values per frame).  Asynchronous.  Afterwards the
         context is as after eval(x)."""
-        import torch
         x, xp, B, T, d, dt, _lp = _files_args(x, "manipulate_files", None)
         lat = np.ascontiguousarray(np.asarray(latents, dtype=np.int32).reshape(-1))
         op = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(-1))
@@ -772,14 +715,12 @@ class SaeEngine:
         if val.ndim != 2 or val.shape[1] != E or not 1 <= val.shape[0] <= MANIP_MAX_VARIANTS:
             raise EngineError(f"manipulate_files: values must be [1..{MANIP_MAX_VARIANTS}, {E}], got {val.shape}")
         V, M = int(val.shape[0]), B * T
-        for name, t, numel in (("standard", standard, M * d), ("manipulated", manipulated, V * M * d), ("series", series, E * M)):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel):
-                raise EngineError(f"{name} must be a contiguous float32 CUDA tensor of {numel} elements")
+        std, man = _dev("standard", standard, "float32", M * d), _dev("manipulated", manipulated, "float32", V * M * d)
+        ser = _dev("series", series, "float32", E * M)
         self._note_shape(x)
         _check(self._lib.sae_manipulate_files(self._ctx, xp, B, T, dt, lat.ctypes.data_as(C.POINTER(C.c_int32)),
                                               op.ctypes.data_as(C.POINTER(C.c_int32)), E, val.ctypes.data_as(C.POINTER(C.c_float)), V, 0,
-                                              C.c_void_p(standard.data_ptr()), C.c_void_p(manipulated.data_ptr()),
-                                              C.c_void_p(series.data_ptr()), _stream_ptr(stream)))
+                                              std, man, ser, _stream_ptr(stream)))
 
     # -- reconstruction report (include/freud_sae.h: sae_recon_files; freud_amd/reconstruction.py) -------------------------
     def recon_files(self, x, block, file_out, lengths=None, resid=None, unfused: bool = False, stream=None) -> None:
@@ -787,19 +728,11 @@ class SaeEngine:
         recon_layout(n, d)["bytes"] bytes) and write file_out (float64 CUDA [n_files, 2]: sum r^2, sum x^2 per file) and, if given,
         resid (float32 CUDA, n_files * T * d elements: r = x - x_hat, 0 on frames that do not count); lengths: int32 CUDA tensor
         [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
-        import torch
         x, xp, B, T, d, dt, lp = _files_args(x, "recon_files", lengths)
-        nbytes = recon_layout(self.n, self.d)["bytes"]
-        if not (block.is_cuda and block.dtype == torch.uint8 and block.is_contiguous() and block.numel() >= nbytes):
-            raise EngineError(f"block must be a contiguous uint8 CUDA tensor of >= {nbytes} bytes")
-        if not (file_out.is_cuda and file_out.dtype == torch.float64 and file_out.is_contiguous() and file_out.numel() == 2 * B):
-            raise EngineError(f"file_out must be a contiguous float64 CUDA tensor of {2 * B} elements")
-        if resid is not None and not (resid.is_cuda and resid.dtype == torch.float32 and resid.is_contiguous()
-                                      and resid.numel() == B * T * d):
-            raise EngineError(f"resid must be a contiguous float32 CUDA tensor of {B * T * d} elements")
-        _check(self._lib.sae_recon_files(self._ctx, xp, B, T, dt, lp, RECON_UNFUSED if unfused else 0, C.c_void_p(block.data_ptr()),
-                                         C.c_void_p(file_out.data_ptr()), C.c_void_p(resid.data_ptr()) if resid is not None else None,
-                                         _stream_ptr(stream)))
+        blk = _dev("block", block, "uint8", recon_layout(self.n, self.d)["bytes"], at_least=True)
+        fo = _dev("file_out", file_out, "float64", 2 * B)
+        res = _dev("resid", resid, "float32", B * T * d, optional=True)
+        _check(self._lib.sae_recon_files(self._ctx, xp, B, T, dt, lp, RECON_UNFUSED if unfused else 0, blk, fo, res, _stream_ptr(stream)))
 
     # -- feature collection (include/freud_sae.h: sae_collect_files; freud_amd/collect_features.py) ------------------------------
     def collect_files(self, x, K: int, values, indices, stats, stream=None) -> None:
@@ -810,15 +743,10 @@ class SaeEngine:
         import torch
         x, xp, B, T, _d, dt, _lp = _files_args(x, "collect_files", None)
         numel = B * T * int(K)
-        if not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.numel() == numel):
-            raise EngineError(f"values must be a contiguous float32 CUDA tensor of {numel} elements")
-        if not (indices.is_cuda and indices.dtype in (torch.int64, torch.int32) and indices.is_contiguous() and indices.numel() == numel):
-            raise EngineError(f"indices must be a contiguous int64 or int32 CUDA tensor of {numel} elements")
-        if not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() == 8):
-            raise EngineError("stats must be a contiguous int64 CUDA tensor of 8 elements")
+        val, idx = _dev("values", values, "float32", numel), _dev("indices", indices, ("int64", "int32"), numel)
+        st = _dev("stats", stats, "int64", 8)
         _check(self._lib.sae_collect_files(self._ctx, xp, B, T, dt, int(K), COLLECT_IDX32 if indices.dtype == torch.int32 else 0,
-                                           C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), C.c_void_p(stats.data_ptr()),
-                                           _stream_ptr(stream)))
+                                           val, idx, st, _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:
@@ -849,20 +777,53 @@ class SaeEngine:
         return self._lib.sae_kernel_name(self._lib.sae_dominant_kernel(self._ctx)).decode()
 
 
-# -- feature search without a context (raw mode, merge, per-file values) ---------------------------------------------------
-def _check_search_out(t, numel: int) -> None:
-    import torch
-    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= numel):
-        raise EngineError(f"key buffers must be contiguous int64 CUDA tensors of >= {numel} elements")
+# -- the device-tensor arguments, and feature search without a context (raw mode, merge, per-file values) ------------------------------
+_TORCH_DTYPES = {}      # _dev's dtype argument -> the torch dtypes it names, filled on first use (torch is not imported up here)
 
 
-def _lengths_ptr(lengths, n_files: int):
+def _torch_dtypes(dtype) -> tuple:
     import torch
-    if lengths is None:
+    _TORCH_DTYPES[dtype] = tuple(getattr(torch, s) for s in (dtype if isinstance(dtype, tuple) else (dtype,)))
+    return _TORCH_DTYPES[dtype]
+
+
+def _dev(name: str, t, dtype, numel: int, *, at_least: bool = False, optional: bool = False):
+    """The one check of a device-tensor argument: t must be a contiguous CUDA tensor of `dtype` (a torch dtype's name, or a tuple of
+    names) with exactly numel elements (at_least: numel or more) -> its pointer as void*.  optional: None passes, as None.  A size
+    rule that lets a short tensor through is a device over-write, so every caller states here which of the two it means."""
+    if t is None and optional:
         return None
-    if not (lengths.is_cuda and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == n_files):
-        raise EngineError(f"lengths must be a contiguous int32 CUDA tensor of {n_files} elements")
-    return C.c_void_p(lengths.data_ptr())
+    want = _TORCH_DTYPES.get(dtype) or _torch_dtypes(dtype)
+    if not (t is not None and t.is_cuda and t.dtype in want and t.is_contiguous()
+            and (t.numel() >= numel if at_least else t.numel() == numel)):
+        names = " or ".join(dtype if isinstance(dtype, tuple) else (dtype,))
+        raise EngineError(f"{name} must be a contiguous {names} CUDA tensor of {'>= ' if at_least else ''}{numel} elements")
+    return C.c_void_p(t.data_ptr())
+
+
+def _labels_arg(labels, B: int, T: int):
+    """The labels of label_files / hist_files, a contiguous int32 CUDA tensor [B, T, n_slots] -> (its pointer, n_slots)."""
+    import torch
+    if not (labels is not None and labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 3
+            and tuple(labels.shape[:2]) == (B, T)):
+        raise EngineError(f"labels must be a contiguous int32 CUDA tensor [{B}, {T}, n_slots]")
+    return C.c_void_p(labels.data_ptr()), int(labels.shape[2])
+
+
+def _label_table(counts, label_count, n_classes: int, n: int):
+    """The label table of label_files / label_keys -> (counts pointer, label_count pointer)."""
+    rows = int(n_classes) + 1
+    return _dev("counts", counts, "int32", rows * n), _dev("label_count", label_count, "int64", rows)
+
+
+def _alias(ptr: int, shape: tuple, typestr: str, device):
+    """A torch CUDA tensor over `shape` elements of `typestr` (as in __cuda_array_interface__) of the engine's HBM at ptr: no copy."""
+    import torch
+
+    class _View:
+        __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2}
+
+    return torch.as_tensor(_View(), device=device)
 
 
 def _stream_ptr(stream=None):
@@ -876,7 +837,7 @@ def _files_args(x, who: str, lengths):
     if x.dim() != 3:
         raise EngineError(f"{who} expects x as [n_files, T, d], got {tuple(x.shape)}")
     B, T, d = (int(v) for v in x.shape)
-    lp = _lengths_ptr(lengths, B)
+    lp = _dev("lengths", lengths, "int32", B, optional=True)
     x, ptr, _rows, dt = SaeEngine._x_args(x)
     return x, C.c_void_p(ptr), B, T, d, dt, lp
 
@@ -884,33 +845,22 @@ def _files_args(x, who: str, lengths):
 def search_raw_files(x, file_keys, aux=None, lengths=None, absolute: bool = False, stream=None) -> None:
     """Raw mode (no SAE): per-(file, column) keys of x [n_files, T, d] itself; with absolute, aux gets the abs-mode side words."""
     x, xp, B, T, d, dt, lp = _files_args(x, "search_raw_files", lengths)
-    _check_search_out(file_keys, B * d)
-    if absolute:
-        _check_search_out(aux, B * d)
-    _check(load().sae_search_raw_files(xp, B, T, d, dt, lp, int(absolute), C.c_void_p(file_keys.data_ptr()),
-                                       C.c_void_p(aux.data_ptr()) if absolute else None, _stream_ptr(stream)))
+    keys = _dev("file_keys", file_keys, "int64", B * d, at_least=True)
+    side = _dev("aux", aux, "int64", B * d, at_least=True) if absolute else None
+    _check(load().sae_search_raw_files(xp, B, T, d, dt, lp, int(absolute), keys, side, _stream_ptr(stream)))
 
 
 def search_merge(file_keys, aux, n_files: int, ncols: int, file0: int, n_top: int, flags: int, min_val: float, max_val: float,
                  top_keys, top_frames, stream=None) -> None:
-    import torch
-    _check_search_out(file_keys, n_files * ncols)
-    if aux is not None:
-        _check_search_out(aux, n_files * ncols)
-    _check_search_out(top_keys, n_top * ncols)
-    if not (top_frames.is_cuda and top_frames.dtype == torch.int32 and top_frames.is_contiguous() and top_frames.numel() >= n_top * ncols):
-        raise EngineError(f"top_frames must be a contiguous int32 CUDA tensor of >= {n_top * ncols} elements")
-    _check(load().sae_search_merge(C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if aux is not None else None,
-                                   int(n_files), int(ncols), int(file0), int(n_top), int(flags), float(min_val), float(max_val),
-                                   C.c_void_p(top_keys.data_ptr()), C.c_void_p(top_frames.data_ptr()), _stream_ptr(stream)))
+    keys = _dev("file_keys", file_keys, "int64", n_files * ncols, at_least=True)
+    side = _dev("aux", aux, "int64", n_files * ncols, at_least=True, optional=True)
+    tk = _dev("top_keys", top_keys, "int64", n_top * ncols, at_least=True)
+    tf = _dev("top_frames", top_frames, "int32", n_top * ncols, at_least=True)
+    _check(load().sae_search_merge(keys, side, int(n_files), int(ncols), int(file0), int(n_top), int(flags), float(min_val), float(max_val),
+                                   tk, tf, _stream_ptr(stream)))
 
 
 # -- feature index (include/freud_sae.h: sae_findex_*; freud_amd/feature_index.py) ---------------------------------------------------
-def _findex_dev(name: str, t, dtype, numel: int, exact: bool = False) -> None:
-    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and (t.numel() == numel if exact else t.numel() >= numel)):
-        raise EngineError(f"{name} must be a contiguous {dtype} CUDA tensor of {'' if exact else '>= '}{numel} elements")
-
-
 def _findex_batch(values, indices):
     import torch
     if not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.dim() == 2):
@@ -934,12 +884,10 @@ def findex_workspace_bytes(max_rows: int, n_range: int) -> int:
 def findex_count(values, indices, n_dict: int, totals, stats, stream=None) -> None:
     """Sweep 1 of the feature index: totals int64 [n_dict] += the batch's posted slots per latent, stats int64 [FINDEX_NSTATS] += the
     tallies (FINDEX_STAT_NAMES)."""
-    import torch
     rows, K, flags = _findex_batch(values, indices)
-    _findex_dev("totals", totals, torch.int64, int(n_dict), exact=True)
-    _findex_dev("stats", stats, torch.int64, FINDEX_NSTATS, exact=True)
-    _check(load().sae_findex_count(C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), rows, K, flags, int(n_dict),
-                                   C.c_void_p(totals.data_ptr()), C.c_void_p(stats.data_ptr()), _stream_ptr(stream)))
+    tot, st = _dev("totals", totals, "int64", int(n_dict)), _dev("stats", stats, "int64", FINDEX_NSTATS)
+    _check(load().sae_findex_count(C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), rows, K, flags, int(n_dict), tot, st,
+                                   _stream_ptr(stream)))
 
 
 def findex_fill(values, indices, n_dict: int, j0: int, j1: int, pos0: int, cursor, out_base: int, positions_out, values_out, workspace,
@@ -949,17 +897,15 @@ def findex_fill(values, indices, n_dict: int, j0: int, j1: int, pos0: int, curso
     workspace: a uint8 tensor of >= findex_workspace_bytes(rows, j1 - j0); err int64 [2]."""
     import torch
     rows, K, flags = _findex_batch(values, indices)
-    _findex_dev("cursor", cursor, torch.int64, int(n_dict), exact=True)
-    _findex_dev("err", err, torch.int64, 2, exact=True)
+    cur, er = _dev("cursor", cursor, "int64", int(n_dict)), _dev("err", err, "int64", 2)
     if not (positions_out.is_cuda and positions_out.dtype == torch.int32 and positions_out.is_contiguous() and positions_out.dim() == 1):
         raise EngineError("positions_out must be a contiguous 1-D int32 CUDA tensor (it holds the uint32 position words)")
-    _findex_dev("values_out", values_out, torch.float32, positions_out.numel(), exact=True)
+    vo = _dev("values_out", values_out, "float32", positions_out.numel())
     need = findex_workspace_bytes(rows, int(j1) - int(j0)) if 0 <= int(j0) < int(j1) else 0
-    _findex_dev("workspace", workspace, torch.uint8, need)
-    _check(load().sae_findex_fill(C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), rows, K, flags, int(n_dict), int(j0), int(j1),
-                                  int(pos0), C.c_void_p(cursor.data_ptr()), int(out_base), C.c_void_p(positions_out.data_ptr()),
-                                  C.c_void_p(values_out.data_ptr()), int(positions_out.numel()), C.c_void_p(workspace.data_ptr()),
-                                  int(workspace.numel()), C.c_void_p(err.data_ptr()), _stream_ptr(stream)))
+    ws = _dev("workspace", workspace, "uint8", need, at_least=True)
+    _check(load().sae_findex_fill(C.c_void_p(values.data_ptr()), C.c_void_p(indices.data_ptr()), rows, K, flags, int(n_dict), int(j0),
+                                  int(j1), int(pos0), cur, int(out_base), C.c_void_p(positions_out.data_ptr()), vo,
+                                  int(positions_out.numel()), ws, int(workspace.numel()), er, _stream_ptr(stream)))
 
 
 def findex_verify(starts, j0: int, j1: int, out_base: int, positions, limit: int, err, stream=None) -> None:
@@ -968,59 +914,38 @@ def findex_verify(starts, j0: int, j1: int, out_base: int, positions, limit: int
     import torch
     if not (starts.is_cuda and starts.dtype == torch.int64 and starts.is_contiguous() and starts.dim() == 1 and starts.numel() >= 2):
         raise EngineError("starts must be a contiguous 1-D int64 CUDA tensor [n_dict + 1]")
-    _findex_dev("err", err, torch.int64, 2, exact=True)
+    er = _dev("err", err, "int64", 2)
     if not (positions.is_cuda and positions.dtype == torch.int32 and positions.is_contiguous() and positions.dim() == 1):
         raise EngineError("positions must be a contiguous 1-D int32 CUDA tensor")
     _check(load().sae_findex_verify(C.c_void_p(starts.data_ptr()), int(starts.numel()) - 1, int(j0), int(j1), int(out_base),
-                                    C.c_void_p(positions.data_ptr()), int(positions.numel()), int(limit), C.c_void_p(err.data_ptr()),
-                                    _stream_ptr(stream)))
+                                    C.c_void_p(positions.data_ptr()), int(positions.numel()), int(limit), er, _stream_ptr(stream)))
 
 
 def file_top_features(file_keys, n_files: int, ncols: int, n_top: int, flags: int, top_latents, top_keys, stream=None) -> None:
     """Per file the n_top best latents of file_keys [n_files, ncols] (as search_files / search_raw_files leave them) into
     top_latents (int32, -1 = empty) and top_keys (int64 holding the uint64 file keys, 0 = empty), both [n_files, n_top]."""
-    import torch
-    _check_search_out(file_keys, n_files * ncols)
-    _check_search_out(top_keys, n_files * n_top)
-    if not (top_latents.is_cuda and top_latents.dtype == torch.int32 and top_latents.is_contiguous()
-            and top_latents.numel() >= n_files * n_top):
-        raise EngineError(f"top_latents must be a contiguous int32 CUDA tensor of >= {n_files * n_top} elements")
-    _check(load().sae_file_top_features(C.c_void_p(file_keys.data_ptr()), int(n_files), int(ncols), int(n_top), int(flags),
-                                        C.c_void_p(top_latents.data_ptr()), C.c_void_p(top_keys.data_ptr()), _stream_ptr(stream)))
-
-
-def _check_coact_table(counts, n: int) -> None:
-    import torch
-    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == n * n):
-        raise EngineError(f"counts must be a contiguous int32 CUDA tensor of {n} x {n} elements")
+    keys = _dev("file_keys", file_keys, "int64", n_files * ncols, at_least=True)
+    tk = _dev("top_keys", top_keys, "int64", n_files * n_top, at_least=True)
+    tl = _dev("top_latents", top_latents, "int32", n_files * n_top, at_least=True)
+    _check(load().sae_file_top_features(keys, int(n_files), int(ncols), int(n_top), int(flags), tl, tk, _stream_ptr(stream)))
 
 
 def coact_neighbor_keys(counts, n: int, row0: int, n_rows: int, measure: int, keys, stream=None) -> None:
     """keys [n_rows, n] (int64 holding uint64) = the neighbour keys of rows [row0, row0 + n_rows) of the count table counts [n, n]
     for file_top_features(keys, n_rows, n, n_top, FILE_TOP_POSITIVE, ...); measure: a COACT_MEASURES value."""
-    _check_coact_table(counts, n)
-    _check_search_out(keys, max(int(n_rows), 0) * n)
-    _check(load().sae_coact_neighbor_keys(C.c_void_p(counts.data_ptr()), int(n), int(row0), int(n_rows), int(measure),
-                                          C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
-
-
-def _check_label_table(counts, label_count, n_classes: int, n: int) -> None:
-    import torch
-    rows = int(n_classes) + 1
-    if not (counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == rows * n):
-        raise EngineError(f"counts must be a contiguous int32 CUDA tensor of {rows} x {n} elements")
-    if not (label_count.is_cuda and label_count.dtype == torch.int64 and label_count.is_contiguous() and label_count.numel() == rows):
-        raise EngineError(f"label_count must be a contiguous int64 CUDA tensor of {rows} elements")
+    table = _dev("counts", counts, "int32", n * n)
+    out = _dev("keys", keys, "int64", max(int(n_rows), 0) * n, at_least=True)
+    _check(load().sae_coact_neighbor_keys(table, int(n), int(row0), int(n_rows), int(measure), out, _stream_ptr(stream)))
 
 
 def label_keys(counts, label_count, n_classes: int, n: int, measure: int, by_latent: int, row0: int, n_rows: int, keys, stream=None) -> None:
     """keys (int64 holding uint64) = the keys of rows [row0, row0 + n_rows) of the label table counts [n_classes + 1, n] /
     label_count [n_classes + 1]: [n_rows, n] (by_latent 0: a row is a label) or [n_rows, n_classes] (1: a row is a latent), for
     file_top_features(keys, n_rows, columns, n_top, FILE_TOP_POSITIVE, ...); measure: a LABEL_MEASURES value."""
-    _check_label_table(counts, label_count, n_classes, n)
-    _check_search_out(keys, max(int(n_rows), 0) * (int(n_classes) if by_latent else n))
-    _check(load().sae_label_keys(C.c_void_p(counts.data_ptr()), C.c_void_p(label_count.data_ptr()), int(n_classes), int(n), int(measure),
-                                 int(by_latent), int(row0), int(n_rows), C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
+    table, lc = _label_table(counts, label_count, n_classes, n)
+    out = _dev("keys", keys, "int64", max(int(n_rows), 0) * (int(n_classes) if by_latent else n), at_least=True)
+    _check(load().sae_label_keys(table, lc, int(n_classes), int(n), int(measure), int(by_latent), int(row0), int(n_rows), out,
+                                 _stream_ptr(stream)))
 
 
 def dict_pack_bytes(n: int, d: int) -> int:
@@ -1029,6 +954,13 @@ def dict_pack_bytes(n: int, d: int) -> int:
     if b <= 0:
         raise EngineError(f"n={n} outside [1, 2^24] or d={d} outside [1, {DICT_MAX_D}]")
     return b
+
+
+def _packed(name: str, t, n: int, d: int):
+    """A packed dictionary operand: a contiguous CUDA tensor of any dtype that holds dict_pack_bytes(n, d) bytes -> its pointer."""
+    if not (t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= dict_pack_bytes(n, d)):
+        raise EngineError(f"{name} must be a contiguous CUDA tensor of >= {dict_pack_bytes(n, d)} bytes")
+    return C.c_void_p(t.data_ptr())
 
 
 def dict_pack(w, n: int, d: int, dir_stride: int, elem_stride: int, side: int, packed, norms, stream=None) -> None:
@@ -1042,34 +974,25 @@ def dict_pack(w, n: int, d: int, dir_stride: int, elem_stride: int, side: int, p
         last = w.storage_offset() + (n - 1) * dir_stride + (d - 1) * elem_stride
         if last >= w.untyped_storage().nbytes() // 4:
             raise EngineError(f"{n} directions of length {d} with strides ({dir_stride}, {elem_stride}) reach past the tensor's storage")
-    if not (packed.is_cuda and packed.is_contiguous() and packed.numel() * packed.element_size() >= dict_pack_bytes(n, d)):
-        raise EngineError(f"packed must be a contiguous CUDA tensor of >= {dict_pack_bytes(n, d)} bytes")
-    if not (norms.is_cuda and norms.dtype == torch.float32 and norms.is_contiguous() and norms.numel() >= n):
-        raise EngineError(f"norms must be a contiguous float32 CUDA tensor of >= {n} elements")
-    _check(load().sae_dict_pack(C.c_void_p(w.data_ptr()), n, d, dir_stride, elem_stride, int(side), C.c_void_p(packed.data_ptr()),
-                                C.c_void_p(norms.data_ptr()), _stream_ptr(stream)))
+    pk, nr = _packed("packed", packed, n, d), _dev("norms", norms, "float32", n, at_least=True)
+    _check(load().sae_dict_pack(C.c_void_p(w.data_ptr()), n, d, dir_stride, elem_stride, int(side), pk, nr, _stream_ptr(stream)))
 
 
 def dict_sim_keys(packed_a, n_a: int, packed_b, n_b: int, d: int, row0: int, n_rows: int, self_mode: bool, keys, stream=None) -> None:
     """keys [n_rows, n_b] (int64 holding uint64) = the cosine keys of the directions [row0, row0 + n_rows) of A against all of B, from
     their packed operands (dict_pack with DICT_LEFT / DICT_RIGHT), for file_top_features(keys, n_rows, n_b, n_top, 0, ...)."""
-    for t, n in ((packed_a, n_a), (packed_b, n_b)):
-        if not (t.is_cuda and t.is_contiguous() and t.numel() * t.element_size() >= dict_pack_bytes(n, d)):
-            raise EngineError(f"a packed operand must be a contiguous CUDA tensor of >= {dict_pack_bytes(n, d)} bytes")
-    _check_search_out(keys, max(int(n_rows), 0) * int(n_b))
-    _check(load().sae_dict_sim_keys(C.c_void_p(packed_a.data_ptr()), int(n_a), C.c_void_p(packed_b.data_ptr()), int(n_b), int(d), int(row0),
-                                    int(n_rows), int(bool(self_mode)), C.c_void_p(keys.data_ptr()), _stream_ptr(stream)))
+    pa, pb = _packed("packed_a", packed_a, n_a, d), _packed("packed_b", packed_b, n_b, d)
+    out = _dev("keys", keys, "int64", max(int(n_rows), 0) * int(n_b), at_least=True)
+    _check(load().sae_dict_sim_keys(pa, int(n_a), pb, int(n_b), int(d), int(row0), int(n_rows), int(bool(self_mode)), out,
+                                    _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:
     import torch
-    _check_search_out(file_keys, n_files * ncols)
-    if aux is not None:
-        _check_search_out(aux, n_files * ncols)
-    if not (latents.is_cuda and latents.dtype == torch.int32 and latents.is_contiguous()):
-        raise EngineError("latents must be a contiguous int32 CUDA tensor")
+    keys = _dev("file_keys", file_keys, "int64", n_files * ncols, at_least=True)
+    side = _dev("aux", aux, "int64", n_files * ncols, at_least=True, optional=True)
+    lat = _dev("latents", latents, "int32", int(latents.numel()))       # (its own size: the call takes the count from it)
     if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous() and out.shape[0] >= latents.numel()):
         raise EngineError(f"out must be a contiguous float32 CUDA tensor [>= {latents.numel()}, files]")
-    _check(load().sae_search_file_values(C.c_void_p(file_keys.data_ptr()), C.c_void_p(aux.data_ptr()) if aux is not None else None,
-                                         int(n_files), int(ncols), int(flags), C.c_void_p(latents.data_ptr()), int(latents.numel()),
-                                         int(file0), int(out.shape[1]), C.c_void_p(out.data_ptr()), _stream_ptr(stream)))
+    _check(load().sae_search_file_values(keys, side, int(n_files), int(ncols), int(flags), lat, int(latents.numel()), int(file0),
+                                         int(out.shape[1]), C.c_void_p(out.data_ptr()), _stream_ptr(stream)))

@@ -37,6 +37,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from .collect_features import store_paths
+from .file_pass import check_lengths
 
 TIMESTEP_S = 30 / 1500          # src/utils/constants.py:17
 _PARTIAL = ".partial"
@@ -303,20 +304,6 @@ def build_feature_index(data_path: str, layer_name: str, *, subset_size: Optiona
                               build["longest_latent"], build["empty_lists"], 1 + len(ranges), [tuple(r) for r in ranges], dict(writer.paths), int(nbytes))
 
 
-def _check_lengths(lengths, n_total: int, T: int) -> Optional[np.ndarray]:
-    """file_pass.check_lengths (kept importable without torch: the reader needs numpy only)."""
-    if lengths is None:
-        return None
-    a = np.asarray(lengths)
-    if a.ndim != 1 or a.shape[0] != n_total:
-        raise ValueError(f"lengths must hold one entry per file ({n_total}), got shape {a.shape}")
-    if not np.issubdtype(a.dtype, np.integer):
-        raise ValueError(f"lengths must be integers, got {a.dtype}")
-    if a.size and int(a.min()) < 1:
-        raise ValueError(f"lengths must be >= 1 (file {int(np.argmin(a))} has {int(a.min())}): an empty series has no maximum")
-    return np.minimum(a.astype(np.int64), T).astype(np.int32)
-
-
 class FeatureIndex:
     """Reader of the index; numpy only (no GPU, no engine library).  A stale index -- one whose store has other file sizes or other
     filenames than the store it was built from -- is refused."""
@@ -378,7 +365,7 @@ class FeatureIndex:
         p, v = self.postings(latent)
         p, v = np.asarray(p, dtype=np.int64), np.asarray(v)
         file, frame = p // self.T, p % self.T
-        L = _check_lengths(lengths, self.n_files, self.T)
+        L = check_lengths(lengths, self.n_files, self.T)
         L = np.full(self.n_files, self.T, np.int64) if L is None else L.astype(np.int64)
         keep = frame < L[file]
         return file[keep], frame[keep], v[keep], L
@@ -415,7 +402,7 @@ class FeatureIndex:
         with pq = [(filename, trimmed series, max value, max time)], value descending then file ascending, filtered by
         min_val <= signed value <= max_val; absolute_magnitude ranks |value| and, as the reference does, reports the time of the
         SIGNED argmax (freud_amd/feature_search.py).  max_per_file (signed values, every file) or None."""
-        L = _check_lengths(lengths, self.n_files, self.T)
+        L = check_lengths(lengths, self.n_files, self.T)
         signed, sframes = self.file_max(latent, lengths, False)
         if absolute_magnitude:
             value, _ = self.file_max(latent, lengths, True)

@@ -41,7 +41,7 @@ import torch
 from . import coactivation as CO
 from . import engine as E
 from .engine import FILE_TOP_MAX, LABEL_MAX_CLASSES, LABEL_MAX_SLOTS, LABEL_MEASURES
-from .file_pass import FilePass, is_raw, keep_rng
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
 
 MAX_FRAMES = 2 ** 31 - 1          # int32 counts
 _SCAN_ELEMS = 1 << 24             # label ids checked per slice of a (possibly memory-mapped) label array
@@ -211,39 +211,31 @@ def feature_labels(sae, data_path: str, layer_name: str, *, file_labels=None, fr
         counts = lcount.cpu().numpy()
         fire = table[C].to(torch.int64).cpu().numpy()
         matrix = table[:C].cpu().numpy() if return_counts else None
-    if int(counts[C]) != fp.n_frames:
-        raise RuntimeError(f"the engine counted {int(counts[C])} frames, the pass holds {fp.n_frames}")
+    fp.check_counted(counts[C])
     return FeatureLabels(fp.n_frames, counts[:C].copy(), fire, *by_label, *by_latent, matrix, measure,
                          None if class_names is None else [str(s) for s in class_names])
 
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Which latents of an SAE detect which labels over a shard directory.")
-    ap.add_argument("--sae", required=True, help="checkpoint path")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+    add_pass_arguments(ap)
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument("--file_labels", default=None, help=".npy of int class ids [n_files] or [n_files, S] (-1 = none)")
     g.add_argument("--frame_labels", default=None, help=".npy of int class ids [n_files, T] or [n_files, T, S] (-1 = none)")
     ap.add_argument("--class_names", default=None, help=".json list of the class names")
     ap.add_argument("--n_top", type=int, default=16)
     ap.add_argument("--measure", default="f1", choices=sorted(LABEL_MEASURES))
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
     ap.add_argument("--counts", action="store_true", help="also store the int32 count matrix [C, n]")
-    ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     names = None
     if a.class_names:
         with open(a.class_names) as f:
             names = json.load(f)
-    fl = feature_labels(a.sae, a.data_path, a.layer_name,
-                        file_labels=np.load(a.file_labels, mmap_mode="r") if a.file_labels else None,
-                        frame_labels=np.load(a.frame_labels, mmap_mode="r") if a.frame_labels else None,
-                        class_names=names, n_top=a.n_top, measure=a.measure, lengths=np.load(a.lengths) if a.lengths else None,
-                        batch_files=a.batch_files, return_counts=a.counts)
-    fl.to_npz(a.out)
-    print(json.dumps({"out": a.out, **fl.summary()}))
+    run_pass_cli(a, lambda lengths: feature_labels(a.sae, a.data_path, a.layer_name,
+                                                   file_labels=np.load(a.file_labels, mmap_mode="r") if a.file_labels else None,
+                                                   frame_labels=np.load(a.frame_labels, mmap_mode="r") if a.frame_labels else None,
+                                                   class_names=names, n_top=a.n_top, measure=a.measure, lengths=lengths,
+                                                   batch_files=a.batch_files, return_counts=a.counts))
 
 
 if __name__ == "__main__":

@@ -26,7 +26,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .file_pass import FilePass, check_lengths, default_batch_files, keep_rng, resolve_sae     # noqa: F401 (re-exported)
+from .file_pass import FilePass, add_pass_arguments, check_lengths, default_batch_files, keep_rng, resolve_sae    # noqa: F401 (re-exported)
 
 TIMESTEP_S = 30 / 1500          # src/utils/constants.py:17
 
@@ -182,16 +182,11 @@ def top_activations(sae, data_path: str, layer_name: str, feature_idx: int, n_fi
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Top-N files of every latent in one pass (the reference's top_activations).")
-    ap.add_argument("--sae", required=True, help="checkpoint path, or 'none' for the activations' own columns")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+    add_pass_arguments(ap, "checkpoint path, or 'none' for the activations' own columns")
     ap.add_argument("--n_files", type=int, required=True)
     ap.add_argument("--absolute", action="store_true")
     ap.add_argument("--min_val", type=float, default=None)
     ap.add_argument("--max_val", type=float, default=None)
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
-    ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     lengths = np.load(a.lengths) if a.lengths else None
     atlas = search_features(None if a.sae.lower() == "none" else a.sae, a.data_path, a.layer_name, a.n_files,

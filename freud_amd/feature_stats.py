@@ -16,13 +16,12 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
-import json
 from typing import Optional
 
 import numpy as np
 import torch
 
-from .file_pass import FilePass, is_raw, keep_rng
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
 
 _FIELDS = ("fire_count", "act_sum", "act_sq_sum", "act_max", "l0_hist")
 
@@ -83,14 +82,9 @@ class FeatureStats:
     @classmethod
     def from_block(cls, block: np.ndarray, n: int) -> "FeatureStats":
         """The arrays of an sae_stats_files block (uint8 bytes, engine.stats_layout)."""
-        from .engine import stats_layout
-        lay = stats_layout(n)
-        b = np.ascontiguousarray(block).view(np.uint8)
-
-        def get(name):
-            off, dt, cnt = lay[name]
-            return np.frombuffer(b, dtype=dt, count=cnt, offset=off).copy()
-        return cls(int(get("n_frames")[0]), get("fire_count"), get("act_sum"), get("act_sq_sum"), get("act_max"), get("l0_hist"))
+        from .engine import stats_layout, unpack_block
+        a = unpack_block(block, stats_layout(n))
+        return cls(int(a["n_frames"][0]), *(a[k] for k in _FIELDS))
 
 
 @keep_rng
@@ -116,17 +110,9 @@ def feature_stats(sae, data_path: str, layer_name: str, *, lengths=None, subset_
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Per-latent firing rates and the L0 histogram of an SAE over a shard directory.")
-    ap.add_argument("--sae", required=True, help="checkpoint path")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
-    ap.add_argument("--out", required=True)
+    add_pass_arguments(ap)
     a = ap.parse_args(argv)
-    lengths = np.load(a.lengths) if a.lengths else None
-    st = feature_stats(a.sae, a.data_path, a.layer_name, lengths=lengths, batch_files=a.batch_files)
-    st.to_npz(a.out)
-    print(json.dumps({"out": a.out, **st.summary()}))
+    run_pass_cli(a, lambda lengths: feature_stats(a.sae, a.data_path, a.layer_name, lengths=lengths, batch_files=a.batch_files))
 
 
 if __name__ == "__main__":

@@ -32,7 +32,6 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
-import json
 import math
 from typing import Optional, Tuple
 
@@ -40,8 +39,9 @@ import numpy as np
 import torch
 
 from .engine import (TIMING_ACTIVE, TIMING_CENSORED, TIMING_FILES, TIMING_LONGEST, TIMING_MAX_BRIDGE, TIMING_NTOTALS, TIMING_RUNS, TIMING_SPAN,
-                     timing_nbins)
-from .file_pass import FilePass, is_raw, keep_rng
+                     check_sub_bits, timing_nbins)
+from .activation_hist import quantile_bounds
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
 
 _ARRAYS = ("run_hist", "gap_hist", "totals")
 
@@ -63,9 +63,7 @@ def threshold_bits(threshold) -> int:
 
 
 def _check_args(sae, sub_bits, bridge, threshold) -> Tuple[int, int, int]:
-    sub_bits, bridge = int(sub_bits), int(bridge)
-    if sub_bits < 0 or sub_bits > 3:
-        raise ValueError(f"sub_bits={sub_bits} outside [0, 3]")
+    sub_bits, bridge = check_sub_bits(sub_bits), int(bridge)
     if bridge < 0 or bridge > TIMING_MAX_BRIDGE:
         raise ValueError(f"bridge={bridge} outside [0, {TIMING_MAX_BRIDGE}]")
     thr = threshold_bits(threshold)
@@ -156,14 +154,7 @@ class FeatureTiming:
             raise ValueError(f"which={which!r} is neither 'run' nor 'gap'")
         if not 0.0 <= q <= 1.0:
             raise ValueError(f"q={q} outside [0, 1]")
-        h = (self.run_hist if which == "run" else self.gap_hist).astype(np.int64)
-        total = h.sum(1)
-        rank = np.maximum(1, np.ceil(q * total.astype(np.float64)).astype(np.int64))
-        b = (np.cumsum(h, 1) < rank[:, None]).sum(1)
-        lo_b, hi_b = self.bin_bounds()
-        ok = total > 0
-        b = np.where(ok, b, 0)
-        return np.where(ok, lo_b[b].astype(np.float64), np.nan), np.where(ok, hi_b[b].astype(np.float64), np.nan)
+        return quantile_bounds((self.run_hist if which == "run" else self.gap_hist).astype(np.int64), q, *self.bin_bounds())
 
     @staticmethod
     def seconds(frames, frame_ms: float = 20.0):
@@ -250,28 +241,20 @@ def feature_timing(sae, data_path: str, layer_name: str, *, sub_bits: int = 2, b
         counted = int(n_frames.item())
         res = FeatureTiming(fp.n_frames, fp.n_total, T, (sub_bits, bridge, thr), run_hist.cpu().numpy(), gap_hist.cpu().numpy(),
                             totals.cpu().numpy())
-    if counted != fp.n_frames:
-        raise RuntimeError(f"the engine counted {counted} frames, the pass holds {fp.n_frames}")
+    fp.check_counted(counted)
     res.check()
     return res
 
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Run-length and gap histograms of every latent of an SAE over a shard directory.")
-    ap.add_argument("--sae", required=True, help="checkpoint path")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+    add_pass_arguments(ap)
     ap.add_argument("--sub_bits", type=int, default=2)
     ap.add_argument("--bridge", type=int, default=0, help="inactive frames a run may span (0..15)")
     ap.add_argument("--threshold", type=float, default=0.0, help="a frame is active above this bf16 value")
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
-    ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
-    ft = feature_timing(a.sae, a.data_path, a.layer_name, sub_bits=a.sub_bits, bridge=a.bridge, threshold=a.threshold,
-                        lengths=np.load(a.lengths) if a.lengths else None, batch_files=a.batch_files)
-    ft.to_npz(a.out)
-    print(json.dumps({"out": a.out, **ft.summary()}))
+    run_pass_cli(a, lambda lengths: feature_timing(a.sae, a.data_path, a.layer_name, sub_bits=a.sub_bits, bridge=a.bridge,
+                                                   threshold=a.threshold, lengths=lengths, batch_files=a.batch_files))
 
 
 if __name__ == "__main__":

@@ -27,9 +27,8 @@ import numpy as np
 import torch
 
 from .feature_search import TIMESTEP_S, _series, unord
-from .file_pass import FilePass, keep_rng, resolve_sae
-
-FILE_TOP_MAX = 1024             # include/freud_sae.h: SAE_FILE_TOP_MAX (engine.FILE_TOP_MAX)
+from .engine import FILE_TOP_MAX
+from .file_pass import FilePass, add_pass_arguments, keep_rng, resolve_sae
 
 
 @dataclasses.dataclass
@@ -166,13 +165,8 @@ def top_activations_for_file(sae, x, top_n: int, length: Optional[int] = None):
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="Top-N latents of every file in one pass (the reference's top_activations_for_audio).")
-    ap.add_argument("--sae", required=True, help="checkpoint path, or 'none' for the activations' own columns")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+    add_pass_arguments(ap, "checkpoint path, or 'none' for the activations' own columns")
     ap.add_argument("--n_top", type=int, required=True)
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
-    ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     lengths = np.load(a.lengths) if a.lengths else None
     ff = file_features(None if a.sae.lower() == "none" else a.sae, a.data_path, a.layer_name, a.n_top, lengths=lengths,

@@ -1,13 +1,15 @@
 """One GPU pass over a shard directory in batches of files: what the feature search (feature_search.py) and the feature statistics
 (feature_stats.py) share.  Both encode batches of files with the training kernels and keep a reduction instead of the latent; this
-module owns the argument rules, the choice of the batch size and the walk over the shard loader."""
+module owns the argument rules, the choice of the batch size, the walk over the shard loader and the front and tail of the passes'
+command lines.  It imports without torch (the feature index's reader takes check_lengths from here): torch is imported where a pass
+runs."""
 from __future__ import annotations
 
 import functools
+import json
 from typing import Optional
 
 import numpy as np
-import torch
 
 
 def check_lengths(lengths, n_total: int, T: int) -> Optional[np.ndarray]:
@@ -66,6 +68,7 @@ def keep_rng(fn):
     building a model from a checkpoint runs the reference modules' random initialisations before the weights are loaded."""
     @functools.wraps(fn)
     def wrapped(*a, **k):
+        import torch
         state = torch.get_rng_state()
         try:
             return fn(*a, **k)
@@ -85,6 +88,7 @@ class FilePass:
 
     def __init__(self, sae, data_path: str, layer_name: str, *, what: str, lengths=None, subset_size: Optional[int] = None,
                  batch_files: Optional[int] = None, max_frames: Optional[int] = None):
+        import torch
         from .loader import MemoryMappedActivationsDataset
 
         if batch_files is not None and int(batch_files) < 1:
@@ -133,7 +137,13 @@ class FilePass:
         self.filenames = list(ds.metadata["filenames"])
         self._loader_args = (data_path, layer_name, subset_size)
 
+    def check_counted(self, counted: int) -> None:
+        """The frames the engine counted on the device must be the frames of the pass."""
+        if int(counted) != self.n_frames:
+            raise RuntimeError(f"the engine counted {int(counted)} frames, the pass holds {self.n_frames}")
+
     def __iter__(self):
+        import torch
         from .loader import MemoryMappedActivationDataLoader
 
         data_path, layer_name, subset_size = self._loader_args
@@ -150,3 +160,21 @@ class FilePass:
             file0 += nb
         if file0 != self.n_total:
             raise RuntimeError(f"the loader delivered {file0} of {self.n_total} files")
+
+
+def add_pass_arguments(ap, sae_help: str = "checkpoint path") -> None:
+    """The arguments that every pass's command line takes."""
+    ap.add_argument("--sae", required=True, help=sae_help)
+    ap.add_argument("--data_path", required=True)
+    ap.add_argument("--layer_name", required=True)
+    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
+    ap.add_argument("--batch_files", type=int, default=None)
+    ap.add_argument("--out", required=True)
+
+
+def run_pass_cli(a, run) -> None:
+    """The tail of a pass's command line over its parsed arguments: result = run(the --lengths array or None), stored as a.out, and
+    one JSON line of its summary()."""
+    result = run(np.load(a.lengths) if a.lengths else None)
+    result.to_npz(a.out)
+    print(json.dumps({"out": a.out, **result.summary()}))

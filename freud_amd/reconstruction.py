@@ -25,13 +25,12 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
-import json
 from typing import List, Optional
 
 import numpy as np
 import torch
 
-from .file_pass import FilePass, is_raw, keep_rng
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
 
 _FIELDS = ("attr_sum", "act_sq_sum", "dec_norm_sq", "sum_x", "sum_x_sq", "sum_r_sq", "file_sse", "file_energy")
 
@@ -126,16 +125,11 @@ class ReconstructionReport:
     @classmethod
     def from_block(cls, block: np.ndarray, n: int, d: int, file_out: np.ndarray, filenames=()) -> "ReconstructionReport":
         """The arrays of an sae_recon_files block (uint8 bytes, engine.recon_layout) and the per-file rows [n_files][2]."""
-        from .engine import recon_layout
-        lay = recon_layout(n, d)
-        b = np.ascontiguousarray(block).view(np.uint8)
-
-        def get(name):
-            off, dt, cnt = lay[name]
-            return np.frombuffer(b, dtype=dt, count=cnt, offset=off).copy()
+        from .engine import recon_layout, unpack_block
+        a = unpack_block(block, recon_layout(n, d))
         fo = np.asarray(file_out, dtype=np.float64).reshape(-1, 2)
-        return cls(int(get("n_frames")[0]), get("attr_sum"), get("act_sq_sum"), get("dec_norm_sq"), get("sum_x"), get("sum_x_sq"),
-                   get("sum_r_sq"), fo[:, 0].copy(), fo[:, 1].copy(), list(filenames))
+        # (_FIELDS' last two are the per-file columns)
+        return cls(int(a["n_frames"][0]), *(a[k] for k in _FIELDS[:-2]), fo[:, 0].copy(), fo[:, 1].copy(), list(filenames))
 
 
 @keep_rng
@@ -162,17 +156,9 @@ def reconstruction_report(sae, data_path: str, layer_name: str, *, lengths=None,
 
 def main(argv=None) -> None:
     ap = argparse.ArgumentParser(description="FVU, per-file error and per-latent ablation effect of an SAE over a shard directory.")
-    ap.add_argument("--sae", required=True, help="checkpoint path")
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
-    ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
-    ap.add_argument("--out", required=True)
+    add_pass_arguments(ap)
     a = ap.parse_args(argv)
-    lengths = np.load(a.lengths) if a.lengths else None
-    rep = reconstruction_report(a.sae, a.data_path, a.layer_name, lengths=lengths, batch_files=a.batch_files)
-    rep.to_npz(a.out)
-    print(json.dumps({"out": a.out, **rep.summary()}))
+    run_pass_cli(a, lambda lengths: reconstruction_report(a.sae, a.data_path, a.layer_name, lengths=lengths, batch_files=a.batch_files))
 
 
 if __name__ == "__main__":

@@ -87,3 +87,52 @@ def test_dp_mode_selection_from_environment(monkeypatch):
         dp.requested_mode()
     monkeypatch.setenv("FREUD_DP_HOST", "1")
     assert dp.requested_mode() == "host"
+
+
+def test_symbol_table_is_the_export_list():
+    from freud_amd import engine
+    assert engine.EXPORTED_SYMBOLS == list(engine._SIGNATURES)
+    assert len(set(engine.EXPORTED_SYMBOLS)) == len(engine.EXPORTED_SYMBOLS)
+
+
+class _Tensor:
+    """What engine._dev reads of a torch tensor."""
+
+    def __init__(self, numel, dtype, cuda=True, contiguous=True):
+        self.is_cuda, self.dtype, self._numel, self._contiguous = cuda, dtype, numel, contiguous
+
+    def is_contiguous(self):
+        return self._contiguous
+
+    def numel(self):
+        return self._numel
+
+    def data_ptr(self):
+        return 0x1000
+
+
+def test_dev_checks_every_condition_and_names_the_argument():
+    import torch
+    from freud_amd.engine import EngineError, _dev
+    i64, i32 = torch.int64, torch.int32
+    assert _dev("totals", _Tensor(8, i64), "int64", 8).value == 0x1000
+    for bad in (_Tensor(8, i64, cuda=False), _Tensor(8, i32), _Tensor(8, i64, contiguous=False), _Tensor(7, i64), _Tensor(9, i64)):
+        with pytest.raises(EngineError, match="totals must be a contiguous int64 CUDA tensor of 8 elements"):
+            _dev("totals", bad, "int64", 8)
+    # at least: more passes, less does not; the three other conditions hold as before
+    assert _dev("keys", _Tensor(8, i64), "int64", 8, at_least=True).value == 0x1000
+    assert _dev("keys", _Tensor(9, i64), "int64", 8, at_least=True).value == 0x1000
+    for bad in (_Tensor(7, i64), _Tensor(9, i64, cuda=False), _Tensor(9, i32), _Tensor(9, i64, contiguous=False)):
+        with pytest.raises(EngineError, match="keys must be a contiguous int64 CUDA tensor of >= 8 elements"):
+            _dev("keys", bad, "int64", 8, at_least=True)
+    # a tuple of dtypes takes each member and nothing else
+    for dt in (i64, i32):
+        assert _dev("indices", _Tensor(4, dt), ("int64", "int32"), 4).value == 0x1000
+    with pytest.raises(EngineError, match="indices must be a contiguous int64 or int32 CUDA tensor of 4 elements"):
+        _dev("indices", _Tensor(4, torch.int16), ("int64", "int32"), 4)
+    # None passes only where the argument is optional
+    assert _dev("resid", None, "float32", 4, optional=True) is None
+    with pytest.raises(EngineError, match="resid must be"):
+        _dev("resid", None, "float32", 4)
+    with pytest.raises(EngineError, match="resid must be"):
+        _dev("resid", _Tensor(3, torch.float32), "float32", 4, optional=True)
