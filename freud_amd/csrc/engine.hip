@@ -584,7 +584,7 @@ static int xfer_flat_topk(sae_ctx* c, float* internal, float* const ext[4], int 
 // Brings the fp32 master of an L1 context to what the reference holds at this point (see sae_ctx::wn_pending): if a forward
 // has run since the last update, the in-place normalisation it stands for is carried out.  Afterwards the next forward takes
 // the plain path (column norms + normalize_cast), exactly as if the folded update had never been used.
-static void settle_weights(sae_ctx* c, hipStream_t s) {
+void settle_weights(sae_ctx* c, hipStream_t s) {
   if (!c->wn_pending) return;
   if (c->wn_fwd_seen) {
     const int64_t n4 = c->nW / 4;

@@ -132,7 +132,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE };
 
 // A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
 // of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
@@ -151,8 +151,9 @@ static const FilePassKind kManipPass = {"sae_manipulate_files", "manipulate in a
 static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruction report in a bf16 context", "reconstruction", SAE_RECON_UNFUSED, LAST_RECON, "a reconstruction report"};
 static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32, LAST_COLLECT, "a feature collection"};
 static const FilePassKind kTimingPass = {"sae_timing_files", "time the features in a bf16 context", "timing", SAE_TIMING_ONE_CHUNK, LAST_TIMING, "a feature timing pass"};
+static const FilePassKind kResamplePass = {"sae_resample_files", "resample in a bf16 context", "resample", 0, LAST_RESAMPLE, "a resampling pass"};
 static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
-                                                  &kTimingPass};
+                                                  &kTimingPass, &kResamplePass};
 
 struct sae_ctx {
   sae_config cfg;
@@ -382,6 +383,7 @@ static void ev_end(sae_ctx* c, int kid, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 #pragma GCC visibility push(hidden)
 void prep_weights_l1(sae_ctx* c, hipStream_t s);
+void settle_weights(sae_ctx* c, hipStream_t s);
 GemmArgs enc_gemm_args(const sae_ctx* c, const bf16_t* xb, int64_t Mp);
 int dispatch_fwd_bwd(sae_ctx* c, const void* x, int64_t M, int x_dtype, void* stream, bool backward);
 int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s);

@@ -22,6 +22,7 @@
 #include "manip.h"
 #include "dict_match.h"
 #include "recon.h"
+#include "resample.h"
 
 // ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
 static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
@@ -1032,3 +1033,152 @@ extern "C" int sae_findex_verify(const int64_t* starts, int64_t n_dict, int64_t 
   return SAE_OK;
 }
 
+// ---- dead-latent resampling (resample.h, resample_draw.h): the row losses and firing counts of one batch of files, the selection of
+// (dead latent, high-loss row) pairs, and the rewrite of the chosen columns inside the engine
+static int resample_refuse(const sae_ctx* c, const char* fn) {
+  if (c->topk) return fail(SAE_ERR_INVALID, "%s: resampling serves L1 contexts; a TopK dictionary revives its dead latents with AuxK (auxk_alpha)", fn);
+  if (c->fp8) return fail(SAE_ERR_INVALID, "%s: fp8 contexts are not supported (resample in a bf16 context)", fn);
+  return SAE_OK;
+}
+
+template <typename T>
+static int resample_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, float* row_loss, unsigned long long* fire,
+                            hipStream_t s) {
+  if (int rc = file_pass_l1_encode(c, x, M, s)) return rc;
+  // the firing counts of the stored latent: the unfused statistics path's column reduction, folded for the counts alone
+  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
+  const StatsSlab sl = stats_slab(c);
+  hipLaunchKernelGGL(stats_colreduce_kernel, dim3((unsigned)((c->n + 255) / 256), (unsigned)nrb), dim3(256), 0, s, (const unsigned short*)c->c,
+                     (int64_t)c->n_p, c->n, M, Trows, lengths, sl);
+  hipLaunchKernelGGL(rs_fire_fold_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, sl.cnt, nrb, c->n, fire);
+  // x_hat of exactly that latent and the residual sweep, as sae_recon_files runs them -- and no attribution GEMM
+  const ReconScratch sc = recon_scratch(c);
+  ev_begin(c, KID_RECON_DECODE, s);
+  const int rc = decode_l1_latent(c, c->c, round_up(M, c->row_pad) / 128, M, sc.xr, s);
+  ev_end(c, KID_RECON_DECODE, s);
+  if (rc) return rc;
+  ev_begin(c, KID_RECON_RESID, s);
+  recon_launch_resid(c, x, sc, (float*)nullptr, (bf16_t*)nullptr, (bf16_t*)nullptr, round_up(M, STATS_RB), M, Trows, lengths, s);
+  hipLaunchKernelGGL(rs_rowloss_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, sc.rowpart, c->d_p / RC_CW, M, row_loss);
+  ev_end(c, KID_RECON_RESID, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_resample_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                                  float* row_loss, int64_t* fire_count, void* stream) {
+  int64_t M;
+  if (!fire_count) return fail(SAE_ERR_INVALID, "null argument");
+  if (c)
+    if (int rc = resample_refuse(c, "sae_resample_files")) return rc;
+  if (int rc = file_pass_begin(kResamplePass, c, x, row_loss, n_files, rows_per_file, x_dtype, 0, &M)) return rc;
+  if (misaligned(row_loss, 4) || misaligned(fire_count, 8)) return fail(SAE_ERR_INVALID, "row_loss must be 4-byte aligned, fire_count 8-byte aligned");
+  if ((c->max_rows_p / STATS_RB) * (int64_t)c->n_p >= ((int64_t)1 << 31))
+    return fail(SAE_ERR_INVALID, "sae_resample_files: max_rows / 128 x n_dict = %lld slab entries >= 2^31", (long long)((c->max_rows_p / STATS_RB) * (int64_t)c->n_p));
+  if (int rc = stats_ensure(c)) return rc;
+  if (int rc = recon_ensure(c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = with_x_type(x_dtype, x, [&](auto* xt) {
+        return resample_l1_impl(c, xt, M, (int)rows_per_file, lengths, row_loss, reinterpret_cast<unsigned long long*>(fire_count), s);
+      }))
+    return rc;
+  file_pass_end(kResamplePass, c);
+  return SAE_OK;
+}
+
+// the workspace of sae_resample_select: RsHeader | c [rows] u64 | block sums [blocks] u64 | owner [rows] u32 | dead [n] i32 | draw [n] i32
+struct ResampleWs {
+  RsHeader* hdr;
+  unsigned long long *c, *blocksum;
+  uint32_t* owner;
+  int *dead, *draw;
+  int64_t nblk, bytes;
+};
+
+static ResampleWs resample_ws(void* base, int64_t rows, int64_t n) {
+  ResampleWs w;
+  char* p = (char*)base;
+  w.nblk = (rows + RS_SCAN_ROWS - 1) / RS_SCAN_ROWS;
+  w.hdr = (RsHeader*)p; p += RS_HDR_BYTES;
+  w.c = (unsigned long long*)p; p += rows * 8;
+  w.blocksum = (unsigned long long*)p; p += w.nblk * 8;
+  w.owner = (uint32_t*)p; p += round_up(rows * 4, 8);
+  w.dead = (int*)p; p += round_up(n * 4, 8);
+  w.draw = (int*)p; p += round_up(n * 4, 8);
+  w.bytes = p - (char*)base;
+  return w;
+}
+
+static bool resample_dims_ok(int64_t rows, int64_t n) { return rows >= 1 && rows <= RS_MAX_ROWS && n >= 1 && n <= RS_MAX_N; }
+
+extern "C" int64_t sae_resample_workspace_bytes(int64_t rows, int64_t n) {
+  return resample_dims_ok(rows, n) ? resample_ws(nullptr, rows, n).bytes : -1;
+}
+
+static_assert(sizeof(RsHeader) <= RS_HDR_BYTES && SAE_RESAMPLE_NCOUNTS == RS_NCOUNTS && SAE_RESAMPLE_DEAD == RS_DEAD && SAE_RESAMPLE_PAIRS == RS_PAIRS &&
+              SAE_RESAMPLE_SKIPPED_DUPLICATE == RS_SKIPPED_DUPLICATE && SAE_RESAMPLE_TOTAL == RS_TOTAL && SAE_RESAMPLE_LMAX_BITS == RS_LMAX_BITS,
+              "freud_sae.h, resample_draw.h and resample.h disagree");
+
+extern "C" int sae_resample_select(const float* row_loss, int64_t rows, const int64_t* fire_count, int64_t n, uint64_t seed, uint64_t round,
+                                   int32_t* latents_out, int64_t* rows_out, int64_t* counts_out, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  if (!row_loss || !fire_count || !latents_out || !rows_out || !counts_out || !workspace) return fail(SAE_ERR_INVALID, "null argument");
+  if (!resample_dims_ok(rows, n)) return fail(SAE_ERR_INVALID, "rows=%lld outside [1, 2^31) or n=%lld outside [1, 2^24]", (long long)rows, (long long)n);
+  if (workspace_bytes < sae_resample_workspace_bytes(rows, n))
+    return fail(SAE_ERR_INVALID, "workspace of %lld bytes < sae_resample_workspace_bytes(%lld, %lld)", (long long)workspace_bytes, (long long)rows, (long long)n);
+  if (misaligned(row_loss, 4) || misaligned(latents_out, 4) || misaligned(fire_count, 8) || misaligned(rows_out, 8) || misaligned(counts_out, 8) ||
+      misaligned(workspace, 8))
+    return fail(SAE_ERR_INVALID, "row_loss and latents_out must be 4-byte aligned, fire_count, rows_out, counts_out and the workspace 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const ResampleWs w = resample_ws(workspace, rows, n);
+  const uint32_t* bits = reinterpret_cast<const uint32_t*>(row_loss);
+  HIP_TRY(hipMemsetAsync(w.hdr, 0, RS_HDR_BYTES, s));
+  HIP_TRY(hipMemsetAsync(w.owner, 0xFF, (size_t)rows * 4, s));
+  hipLaunchKernelGGL(rs_max_kernel, dim3(grid_for(rows, 1024)), dim3(256), 0, s, bits, rows, w.hdr);
+  hipLaunchKernelGGL(rs_blocksum_kernel, dim3((unsigned)w.nblk), dim3(RS_SCAN_ROWS), 0, s, bits, rows, w.hdr, w.blocksum);
+  hipLaunchKernelGGL(rs_blockscan_kernel, dim3(1), dim3(RS_SCAN_ROWS), 0, s, w.blocksum, w.nblk, w.hdr);
+  hipLaunchKernelGGL(rs_prefix_kernel, dim3((unsigned)w.nblk), dim3(RS_SCAN_ROWS), 0, s, bits, rows, w.hdr, w.blocksum, w.c);
+  hipLaunchKernelGGL(rs_dead_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(fire_count), (int)n, w.dead, w.hdr);
+  hipLaunchKernelGGL(rs_draw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.hdr, w.c, rows, (unsigned long long)seed,
+                     (unsigned long long)round, w.draw, w.owner);
+  hipLaunchKernelGGL(rs_emit_kernel, dim3(1), dim3(256), 0, s, w.hdr, w.dead, w.draw, w.owner, latents_out, reinterpret_cast<long long*>(rows_out),
+                     reinterpret_cast<long long*>(counts_out));
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_resample_apply(sae_ctx* c, const int32_t* latents, int64_t n_latents, const float* x_rows, double alpha, int64_t* out_stats,
+                                  void* stream) {
+  if (!c || !latents || !x_rows || !out_stats) return fail(SAE_ERR_INVALID, "null argument");
+  if (int rc = resample_refuse(c, "sae_resample_apply")) return rc;
+  if (n_latents < 1 || n_latents > c->n) return fail(SAE_ERR_INVALID, "n_latents=%lld outside [1, n_dict=%d]", (long long)n_latents, c->n);
+  if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(SAE_ERR_INVALID, "alpha=%g outside [0, 1]", alpha);
+  if (misaligned(latents, 4) || misaligned(x_rows, 4) || misaligned(out_stats, 8))
+    return fail(SAE_ERR_INVALID, "latents and x_rows must be 4-byte aligned, out_stats 8-byte aligned");
+  USE_DEVICE(c);
+  hipStream_t s = (hipStream_t)stream;
+  // the latents are read back and checked before anything is enqueued that writes
+  int32_t* host = new int32_t[(size_t)n_latents];
+  unsigned char* seen = new unsigned char[(size_t)c->n]();
+  int rc = SAE_OK;
+  hipError_t e = hipMemcpyAsync(host, latents, (size_t)n_latents * 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) rc = fail(SAE_ERR_HIP, "reading the latents failed: %s", hipGetErrorString(e));
+  for (int64_t i = 0; i < n_latents && !rc; ++i) {
+    if (host[i] < 0 || host[i] >= c->n) rc = fail(SAE_ERR_INVALID, "pair %lld: latent %d outside [0, %d)", (long long)i, host[i], c->n);
+    else if (seen[host[i]]) rc = fail(SAE_ERR_INVALID, "pair %lld repeats latent %d", (long long)i, host[i]);
+    else seen[host[i]] = 1;
+  }
+  delete[] host;
+  delete[] seen;
+  if (rc) return rc;
+  // the master as the reference holds it (d_p <= 384: the folded update may have left it un-normalised), then the columns; every
+  // derived copy (Wb, Wt, cnorm, cn_part) is rebuilt by the next forward, as after sae_set_params
+  settle_weights(c, s);
+  c->cn_valid = false;
+  HIP_TRY(hipMemsetAsync(out_stats, 0, (size_t)(2 + n_latents) * 8, s));
+  hipLaunchKernelGGL(rs_apply_kernel, dim3((unsigned)n_latents), dim3(256), 0, s, latents, x_rows, c->d, c->d_p, c->n_p, (float)alpha, c->P, c->Mom,
+                     c->Var, reinterpret_cast<unsigned long long*>(out_stats));
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}

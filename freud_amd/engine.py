@@ -131,6 +131,10 @@ _SIGNATURES = {
                                        _vp, _vp, _vp, _vp]),
     "sae_recon_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_collect_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sae_resample_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp]),
+    "sae_resample_workspace_bytes": (_i64, [_i64, _i64]),
+    "sae_resample_select": (C.c_int, [_vp, _i64, _vp, _i64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sae_resample_apply": (C.c_int, [_vp, _vp, _i64, _vp, _dbl, _vp, _vp]),
     "sae_findex_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_findex_count": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _vp, _vp, _vp]),
     "sae_findex_fill": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp,
@@ -204,6 +208,8 @@ MANIP_OPS = {"scale": 0, "set": 1}                                  # include/fr
 MANIP_MAX_EDITS = 16                                                # include/freud_sae.h: SAE_MANIP_MAX_EDITS
 MANIP_MAX_VARIANTS = 16                                             # include/freud_sae.h: SAE_MANIP_MAX_VARIANTS
 RECON_UNFUSED = 1                                                   # include/freud_sae.h: SAE_RECON_UNFUSED
+RESAMPLE_DEAD, RESAMPLE_PAIRS, RESAMPLE_SKIPPED_DUPLICATE, RESAMPLE_TOTAL, RESAMPLE_LMAX_BITS = range(5)   # include/freud_sae.h: SAE_RESAMPLE_*
+RESAMPLE_NCOUNTS = 8                                                # include/freud_sae.h: SAE_RESAMPLE_NCOUNTS
 
 
 def stats_layout(n: int) -> dict:
@@ -734,6 +740,35 @@ class SaeEngine:
         res = _dev("resid", resid, "float32", B * T * d, optional=True)
         _check(self._lib.sae_recon_files(self._ctx, xp, B, T, dt, lp, RECON_UNFUSED if unfused else 0, blk, fo, res, _stream_ptr(stream)))
 
+    # -- dead-latent resampling (include/freud_sae.h: sae_resample_*; freud_amd/resample.py) ---------------------------------------
+    def resample_files(self, x, row_loss, row0: int, fire_count, lengths=None, stream=None) -> None:
+        """The row losses of x [n_files, T, d] (CUDA) into row_loss[row0 : row0 + n_files * T] (a contiguous float32 CUDA tensor over
+        all rows of the pass) and its firing counts added to fire_count (zero-initialised int64 CUDA [n_dict]); lengths: int32 CUDA
+        tensor [n_files] or None.  L1 contexts in bf16 precision.  Asynchronous.  Afterwards the last-forward getters fail until the
+        next eval() / step()."""
+        x, xp, B, T, _d, dt, lp = _files_args(x, "resample_files", lengths)
+        row0 = int(row0)
+        if row0 < 0:
+            raise EngineError(f"row0={row0} is negative")
+        _dev("row_loss", row_loss, "float32", row0 + B * T, at_least=True)
+        fc = _dev("fire_count", fire_count, "int64", self.n)
+        _check(self._lib.sae_resample_files(self._ctx, xp, B, T, dt, lp, C.c_void_p(row_loss.data_ptr() + 4 * row0), fc, _stream_ptr(stream)))
+
+    def resample_apply(self, latents, x_rows, alpha: float, out_stats, stream=None) -> None:
+        """Rewrite the columns `latents` (int32 CUDA [P]) of W, b and both Adam moments from x_rows (contiguous float32 CUDA [P, d]:
+        the drawn shard rows) inside the engine; out_stats: int64 CUDA [2 + P], written ([0] revived, [1] skipped_degenerate,
+        [2 + i] = 1 iff pair i was applied).  Synchronises the stream (the latents are checked on the host first)."""
+        P = int(latents.numel())
+        lat = _dev("latents", latents, "int32", P)                      # (its own size: the call takes the count from it)
+        xr = _dev("x_rows", x_rows, "float32", P * self.d)
+        st = _dev("out_stats", out_stats, "int64", 2 + P)
+        _check(self._lib.sae_resample_apply(self._ctx, lat, P, xr, float(alpha), st, _stream_ptr(stream)))
+
+    def resample_dead_latents(self, data_path: str, layer_name: str, **kw):
+        """freud_amd.resample.resample_dead_latents on this engine (what train() calls for a "resample" round)."""
+        from .resample import resample_dead_latents
+        return resample_dead_latents(self, data_path, layer_name, **kw)
+
     # -- feature collection (include/freud_sae.h: sae_collect_files; freud_amd/collect_features.py) ------------------------------
     def collect_files(self, x, K: int, values, indices, stats, stream=None) -> None:
         """Write the K slots of every row of x [n_files, T, d] (CUDA) -- the first K entries of the stable descending sort of the
@@ -858,6 +893,29 @@ def search_merge(file_keys, aux, n_files: int, ncols: int, file0: int, n_top: in
     tf = _dev("top_frames", top_frames, "int32", n_top * ncols, at_least=True)
     _check(load().sae_search_merge(keys, side, int(n_files), int(ncols), int(file0), int(n_top), int(flags), float(min_val), float(max_val),
                                    tk, tf, _stream_ptr(stream)))
+
+
+# -- dead-latent resampling without a context (include/freud_sae.h: sae_resample_select) ------------------------------------------------
+def resample_workspace_bytes(rows: int, n: int) -> int:
+    """Bytes of workspace that resample_select needs for `rows` row losses and n latents."""
+    nbytes = int(load().sae_resample_workspace_bytes(int(rows), int(n)))
+    if nbytes < 0:
+        raise EngineError(f"resample_workspace_bytes: rows={rows} outside [1, 2^31) or n={n} outside [1, 2^24]")
+    return nbytes
+
+
+def resample_select(row_loss, rows: int, fire_count, n: int, seed: int, round: int, latents_out, rows_out, counts_out, workspace,
+                    stream=None) -> None:
+    """The applying (dead latent, row) pairs of row_loss (float32 CUDA, >= rows) and fire_count (int64 CUDA [n]) for (seed, round), in
+    ascending latent order into latents_out (int32 CUDA [n]) / rows_out (int64 CUDA [n]); counts_out: int64 CUDA [RESAMPLE_NCOUNTS];
+    workspace: a uint8 CUDA tensor of >= resample_workspace_bytes(rows, n).  Asynchronous."""
+    rl = _dev("row_loss", row_loss, "float32", int(rows), at_least=True)
+    fc = _dev("fire_count", fire_count, "int64", int(n))
+    lo, ro = _dev("latents_out", latents_out, "int32", int(n)), _dev("rows_out", rows_out, "int64", int(n))
+    co = _dev("counts_out", counts_out, "int64", RESAMPLE_NCOUNTS)
+    ws = _dev("workspace", workspace, "uint8", resample_workspace_bytes(rows, n), at_least=True)
+    _check(load().sae_resample_select(rl, int(rows), fc, int(n), int(seed) & (2 ** 64 - 1), int(round) & (2 ** 64 - 1), lo, ro, co, ws,
+                                      int(workspace.numel()), _stream_ptr(stream)))
 
 
 # -- feature index (include/freud_sae.h: sae_findex_*; freud_amd/feature_index.py) ---------------------------------------------------

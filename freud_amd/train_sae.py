@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from freud_amd.config import L1AutoEncoderConfig, TopKAutoEncoderConfig, get_n_dict_components
+from freud_amd.file_pass import keep_rng
 from freud_amd.loader import MemoryMappedActivationDataLoader
 
 EXIT_EXCHANGE_FAILED = 3      # main(): the data-parallel exchange failed mid-run; restart fresh processes from the last good checkpoint
@@ -277,15 +278,30 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
           steps: int, clip_thresh: float, batch_size: int, dl_max_workers: int, log_tb_every: int, save_every: int,
           val_every: int, start_checkpoint: Optional[str], whisper_config: dict, optimizer: str, scheduler: str,
           scheduler_params: dict, from_disk: bool, autoencoder_variant: str, autoencoder_config: dict, *,
-          eval_precision: Optional[str] = None, engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
+          eval_precision: Optional[str] = None, resample: Optional[dict] = None, engine_factory: Optional[Callable] = None,
+          dist_backend: Optional[str] = None):
     """Same keyword arguments as the reference's train() (train_sae.py:297-320).  One OPTIONAL key beyond them: "eval_precision":
     "fp32" makes validate() -- and with it the choice of bestval.pth -- compute what the reference's validate() computes on
     device='cpu' (no autocast: fp32 end to end, train_sae.py:162-166); "bf16" (default; also FREUD_EVAL_PRECISION) keeps the training
-    kernels' arithmetic, which agrees with that to ~1e-2.  A config file without the key is a reference config file.  The two trailing
-    keyword-only arguments are test hooks and are never present in a config file."""
+    kernels' arithmetic, which agrees with that to ~1e-2.  And "resample": {"every": E, "until": U, "files": F, "activation_scale": a}
+    (L1 only; U defaults to steps, F to 512, a to 0.2): at every step s with s % E == 0 and s <= U the dead latents are resampled from
+    the high-loss frames of the first F training files (freud_amd/resample.py; round = s // E, seed = the run's seed) -- after the
+    logging block, before the checkpoint and validation blocks, so that stepN.pth holds the revived state.  A config file without
+    these keys is a reference config file and trains bit for bit as before.  The two trailing keyword-only arguments are test hooks
+    and are never present in a config file."""
     eval_precision = eval_precision or os.environ.get("FREUD_EVAL_PRECISION") or "bf16"
     if eval_precision not in ("bf16", "fp32"):
         raise ValueError(f"Invalid eval_precision: {eval_precision}, must be 'bf16' or 'fp32'")
+    if resample is not None:
+        if autoencoder_variant == "topk":
+            raise ValueError("\"resample\" serves L1 dictionaries; a TopK dictionary revives its dead latents with AuxK (auxk_alpha)")
+        unknown = set(resample) - {"every", "until", "files", "activation_scale"}
+        if unknown or "every" not in resample or int(resample["every"]) < 1:
+            raise ValueError(f"\"resample\" takes every (>= 1), until, files, activation_scale; got {dict(resample)}")
+        from freud_amd.resample import check_resample_args
+        rs_every, rs_until = int(resample["every"]), int(resample.get("until", steps))
+        rs_files, rs_scale = int(resample.get("files", 512)), float(resample.get("activation_scale", 0.2))
+        check_resample_args(rs_files, rs_scale)
     device = torch.device(device)
     rank, local_rank, world = _dist_env()
     # FREUD_FORCE_DIST=1 (test hook, like bench.py --force-dist): take the data-parallel code path - process group,
@@ -331,6 +347,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         "whisper_config": whisper_config, "activation_size": feat_dim, "train_folder": train_folder,
         "val_folder": val_folder, "optimizer": optimizer, "scheduler": scheduler, "scheduler_params": scheduler_params,
     }
+    if resample is not None:
+        hparam_dict["resample"] = dict(resample)
     assert autoencoder_variant in ["l1", "topk"], \
         f"Invalid autoencoder variant: {autoencoder_variant}, must be 'l1' or 'topk'"
     if optimizer not in ("radam", "adam"):
@@ -500,6 +518,18 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
                 logger.add_scalar("train/lr", lr_at(state["step"], lr, scheduler, steps, scheduler_params), state["step"])
                 logger.add_scalar("train/grad_norm", m[3], state["step"])
                 logger.add_scalar("train/activations_per_sec", rows_done / max(time.time() - t_start, 1e-9), state["step"])
+
+            if resample is not None and state["step"] % rs_every == 0 and state["step"] <= rs_until:
+                # (after the logging block: a file pass leaves no metrics to read; before the checkpoint: stepN.pth holds the revived
+                # state and a resume needs nothing else.  Every rank runs the identical, unsharded pass on its own replica.)
+                guard("resample")
+                report = keep_rng(eng.resample_dead_latents)(train_folder, whisper_config["layer_name"], files=rs_files, seed=seed,
+                                                             round=state["step"] // rs_every, activation_scale=rs_scale)
+                guard("resample")                           # the replicas must still agree to the bit
+                if use_dist:
+                    dist.barrier()
+                logger.add_scalar("resample/dead", report.dead, state["step"])
+                logger.add_scalar("resample/revived", report.revived, state["step"])
 
             if state["step"] % save_every == 0:
                 guard("checkpoint")                         # nothing is written from a failed or diverged run

@@ -800,6 +800,57 @@ int sae_findex_fill(const float* values_dev, const void* indices_dev, int64_t ro
 int sae_findex_verify(const int64_t* starts_dev, int64_t n_dict, int64_t j0, int64_t j1, int64_t out_base, const uint32_t* positions_dev,
                       int64_t capacity, int64_t limit, int64_t* err_dev, void* stream);
 
+/* ---- Dead-latent resampling for L1 training: revive latents that never fire from the inputs the dictionary reconstructs worst
+ * (Bricken et al. 2023, "Towards Monosemanticity", neuron resampling; freud_amd/resample.py; kernels: freud_amd/csrc/resample.h, the
+ * arithmetic: freud_amd/csrc/resample_draw.h).  L1 contexts in bf16 precision only: a TopK context is refused (it has AuxK,
+ * auxk_alpha), an fp8 context is refused as by every file pass.
+ *
+ * The rule.  Over the rows i = file * T + frame of a set of files:
+ *   dead set   latent j < n_dict is dead iff its firing count over the counted frames is 0 (firing as in sae_stats_files: the bf16
+ *              latent's magnitude bits are non-zero); padding columns are never in the set;
+ *   row loss   l_i = sum_k r_k^2, r = float(x) - x_hat with x_hat the decode of the forward's own latent, exactly as sae_recon_files
+ *              defines it (an element equal to -1 is data): the fp32 sum, in ascending order, of the residual sweep's partials per 64
+ *              columns; l_i = 0 on rows that do not count;
+ *   weights    l_max = the maximum row loss (the losses are non-negative: the maximum of the bit patterns), e = its frexp exponent,
+ *              q_i = floor(l_i 2^(16 - e)) in [0, 65535], w_i = q_i^2 (uint64): p proportional to the loss squared; c_i = the inclusive
+ *              uint64 prefix, total = c_last (rows < 2^31: no overflow); total == 0: nothing is resampled;
+ *   draw       dead latents in ascending order r = 0 .. |D| - 1: h = rs_hash(seed, round, r) (three splitmix64 finalisers), t =
+ *              mulhi64(h, total), row = the first i with c_i > t.  Nothing depends on how the rows were batched or on a rank;
+ *   distinct   of the latents that drew one row the lowest r owns it; the others stay dead this round (skipped_duplicate);
+ *   column     x = the drawn shard row widened to fp32: s = fmaf-accumulated sum x_k^2 (k ascending), nrm = sqrt(s), W[:, j] = x / nrm,
+ *              b_j = -((1 - alpha) nrm), each one correctly rounded fp32 operation: the seed frame then activates at alpha |x|.
+ *              s == 0 or not finite: the pair is skipped (skipped_degenerate);
+ *   optimizer  exp_avg and exp_avg_sq of column j of W and of b_j are set to 0; the step count is untouched.
+ *
+ * sae_resample_files: one batch (x_dev [n_files][rows_per_file][d], x_dtype; lengths_dev or null) -- the encoder with the stored
+ *   latent, the count reduction of sae_stats_files' stored-latent path, the decoder GEMM and the residual sweep of sae_recon_files,
+ *   and NOT its attribution GEMM.  Writes the batch's row losses to row_loss_dev [n_files * rows_per_file] (the caller passes its
+ *   array + the batch's first row) and adds the firing counts to fire_count_dev int64 [n_dict] (zeroed by the caller before the
+ *   first batch).  Argument rules, limits, scratch, the state it leaves and what it does not touch: as sae_recon_files.  Two runs
+ *   give the same bytes.
+ * sae_resample_select: context-free, like sae_search_merge; all pointers caller-owned device memory.  From row_loss_dev [rows]
+ *   (1 <= rows < 2^31) and fire_count_dev [n] (1 <= n <= 2^24): the applying pairs in ascending latent order in latents_out_dev
+ *   int32 [n] / rows_out_dev int64 [n] (the first counts[SAE_RESAMPLE_PAIRS] entries), and counts_out_dev int64
+ *   [SAE_RESAMPLE_NCOUNTS]: DEAD, PAIRS, SKIPPED_DUPLICATE, TOTAL (the uint64 total), LMAX_BITS (the fp32 bits of l_max).
+ *   workspace_dev: sae_resample_workspace_bytes(rows, n) bytes (-1: arguments out of range), 8-byte aligned scratch.  Integer
+ *   arithmetic only; the atomics are an integer maximum and an integer minimum whose results do not depend on order.
+ * sae_resample_apply: rewrites column latents_dev[i] (int32 [n_latents], device) of W, b and both moments from x_rows_dev
+ *   [n_latents][d] fp32, inside the engine: the fp32 master is settled first (d_model <= 384: a training step may have left it
+ *   un-normalised), every derived copy is rebuilt by the next forward exactly as after sae_set_params, and nothing else of the
+ *   training state changes.  A latent outside [0, n_dict), a repeated latent, a TopK or fp8 context, alpha outside [0, 1]:
+ *   SAE_ERR_INVALID before anything is written (the latents are read back first: the call synchronises `stream`).  out_stats_dev
+ *   int64 [2 + n_latents], written: [0] revived, [1] skipped_degenerate, [2 + i] = 1 iff pair i was applied. */
+enum { SAE_RESAMPLE_DEAD = 0, SAE_RESAMPLE_PAIRS = 1, SAE_RESAMPLE_SKIPPED_DUPLICATE = 2, SAE_RESAMPLE_TOTAL = 3, SAE_RESAMPLE_LMAX_BITS = 4,
+       SAE_RESAMPLE_NCOUNTS = 8 };
+int sae_resample_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                       float* row_loss_dev, int64_t* fire_count_dev, void* stream);
+int64_t sae_resample_workspace_bytes(int64_t rows, int64_t n);
+int sae_resample_select(const float* row_loss_dev, int64_t rows, const int64_t* fire_count_dev, int64_t n, uint64_t seed, uint64_t round,
+                        int32_t* latents_out_dev, int64_t* rows_out_dev, int64_t* counts_out_dev, void* workspace_dev, int64_t workspace_bytes,
+                        void* stream);
+int sae_resample_apply(sae_ctx* ctx, const int32_t* latents_dev, int64_t n_latents, const float* x_rows_dev, double alpha,
+                       int64_t* out_stats_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
