@@ -30,6 +30,7 @@
 #include "topk_sparse.h"
 #include "topk_aux.h"
 #include "eval_fp32.h"
+#include "dec_norm.h"
 #include "engine_internal.h"
 #include "gemm_launch.h"
 
@@ -594,6 +595,49 @@ void settle_weights(sae_ctx* c, hipStream_t s) {
   c->cn_valid = false;
 }
 
+// ---- decoder-norm constraint of TopK training (dec_norm.h; topkautoencoder.py:153-175)
+static void launch_dec_project(sae_ctx* c, hipStream_t s) {
+  float* const gWd = c->G + c->nW + c->n_p;
+  const float* const Wd = c->P + c->nW + c->n_p;
+  with_dec_nv(c->d_p, [&](auto nv) {
+    hipLaunchKernelGGL(topk_dec_project_kernel<decltype(nv)::value>, dim3(c->n_p / 4), dim3(256), 0, s, gWd, Wd, c->d_p);
+  });
+}
+static void launch_dec_renorm(sae_ctx* c, hipStream_t s) {
+  float* const Wd = c->P + c->nW + c->n_p;
+  with_dec_nv(c->d_p, [&](auto nv) {
+    hipLaunchKernelGGL(topk_dec_renorm_kernel<decltype(nv)::value>, dim3(c->n_p / 4), dim3(256), 0, s, Wd, c->Wd_b, c->d_p);
+  });
+}
+// the renorm on its own (the constraint is switched on; sae_set_params while it is on).  Synchronous, like its callers.
+static int dec_renorm_now(sae_ctx* c) {
+  HIP_TRY(hipDeviceSynchronize());
+  launch_dec_renorm(c, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  c->wb_valid = false;          // (W_enc's copy is not this kernel's: the next forward casts both)
+  return SAE_OK;
+}
+
+extern "C" int sae_set_decoder_constraint(sae_ctx* c, int on) {
+  if (!c) return fail(SAE_ERR_INVALID, "null argument");
+  if (!c->topk) return fail(SAE_ERR_STATE, "the decoder-norm constraint is a TopK option: an L1 forward normalises its columns itself");
+  if (c->fp8) return fail(SAE_ERR_STATE, "the decoder-norm constraint needs a bf16 context");
+  if (c->d_p > 256 * DEC_NORM_MAX_NV) return fail(SAE_ERR_STATE, "the decoder-norm kernels hold rows of at most %d columns", 256 * DEC_NORM_MAX_NV);
+  USE_DEVICE(c);
+  if (on != 0 && on != SAE_DEC_CONSTRAINT_ON && on != SAE_DEC_CONSTRAINT_ON_KEEP_ROWS)
+    return fail(SAE_ERR_INVALID, "Invalid decoder constraint: %d, must be 0, SAE_DEC_CONSTRAINT_ON or SAE_DEC_CONSTRAINT_ON_KEEP_ROWS", on);
+  const bool was = c->dec_constraint;
+  c->dec_constraint = on != 0;
+  if (on == SAE_DEC_CONSTRAINT_ON && !was) return dec_renorm_now(c);
+  return SAE_OK;
+}
+
+extern "C" int sae_get_decoder_constraint(sae_ctx* c) {
+  if (!c) return fail(SAE_ERR_INVALID, "null argument");
+  return c->dec_constraint ? 1 : 0;
+}
+
 extern "C" int sae_set_params(sae_ctx* c, const float* p0, const float* p1, const float* p2, const float* p3, int is_device) {
   if (!c || !p0 || !p1) return fail(SAE_ERR_INVALID, "null argument");
   USE_DEVICE(c);
@@ -605,7 +649,9 @@ extern "C" int sae_set_params(sae_ctx* c, const float* p0, const float* p1, cons
   if (c->topk) {
     if (!p2 || !p3) return fail(SAE_ERR_INVALID, "topk needs 4 parameter tensors");
     float* const ext[4] = {const_cast<float*>(p0), const_cast<float*>(p1), const_cast<float*>(p2), const_cast<float*>(p3)};
-    return xfer_flat_topk(c, c->P, ext, 1, is_device);
+    int rc = xfer_flat_topk(c, c->P, ext, 1, is_device);
+    if (!rc && c->dec_constraint) rc = dec_renorm_now(c);     // the rows are unit before the first projection
+    return rc;
   }
   return xfer_flat(c, c->P, const_cast<float*>(p0), const_cast<float*>(p1), 1, is_device);
 }
@@ -2379,9 +2425,19 @@ extern "C" int sae_optimizer_step(sae_ctx* c, double lr, double grad_scale, void
   int gblocks = grid_for(n4, 1024);
   // the reduction kernel already left the local sum of squares; it is only valid when nothing (no all-reduce, no
   // rescaling) touched the gradient buffer in between, i.e. for the single-GPU sae_step path
+  // decoder-norm constraint (TopK): the projection changes the gradient, so no sum of squares that was left before it -- by the
+  // backward, by the peer exchange, or by the bf16 conversion below -- is the clip norm: it is formed from the projected buffer
+  const bool constrained = c->topk && c->dec_constraint;
   if (c->grads_in_bf16) {     // data parallel, bf16 payload: the summed gradient comes back to fp32 in the same pass
     hipLaunchKernelGGL(gnorm_from_bf16_kernel, dim3(gblocks), dim3(256), 0, s, c->Gb, c->G, n4, a.grad_scale, c->gn_part);
     c->grads_in_bf16 = false;
+    if (constrained) {
+      launch_dec_project(c, s);
+      hipLaunchKernelGGL(gnorm_partial_kernel, dim3(gblocks), dim3(256), 0, s, c->G, n4, a.grad_scale, c->gn_part);
+    }
+  } else if (constrained) {
+    launch_dec_project(c, s);
+    hipLaunchKernelGGL(gnorm_partial_kernel, dim3(gblocks), dim3(256), 0, s, c->G, n4, a.grad_scale, c->gn_part);
   } else if (c->gn_valid && grad_scale == 1.0 && c->step_fused_call) {
     gblocks = c->gn_blocks;
   } else {
@@ -2409,9 +2465,11 @@ extern "C" int sae_optimizer_step(sae_ctx* c, double lr, double grad_scale, void
     if (c->topk) {       // the bf16 copies of W_enc and W_dec leave with the update: no cast pass in the next step
       cast.off4[0] = 0; cast.len4[0] = c->nW / 4; cast.dst[0] = c->We_b;
       cast.off4[1] = (c->nW + c->n_p) / 4; cast.len4[1] = c->nW / 4; cast.dst[1] = c->Wd_b;
+      if (constrained) cast.dst[1] = nullptr;      // Wd_b is taken from the renormalised rows below
     }
     hipLaunchKernelGGL(optimizer_kernel, dim3(oblocks), dim3(256), 0, s, c->P, c->Mom, c->Var, c->G, n4, c->gn_part, gblocks,
                        a, c->G + c->nparams, cast);
+    if (constrained) launch_dec_renorm(c, s);
     c->cn_valid = false;
     c->wb_valid = c->topk;
   }

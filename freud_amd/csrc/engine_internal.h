@@ -216,6 +216,9 @@ struct sae_ctx {
   bool topk = false;
   int k = 0, k_aux_cap = 0;
   int64_t rows_per_file = 0;          // T: x is [B][T][d] for x.mean(0); 0 = the whole batch is one file
+  // decoder-norm constraint (sae_set_decoder_constraint; dec_norm.h): every optimizer step projects the gradient of W_dec off its
+  // rows before the clip norm and renormalises the rows after the update (topkautoencoder.py:153-175)
+  bool dec_constraint = false;
   double dead_threshold = 1e300;
   bf16_t *We_b = nullptr, *Wd_b = nullptr, *xs = nullptr, *pre = nullptr, *dense = nullptr, *aux_dense = nullptr;
   bf16_t *de_b = nullptr, *dh_b = nullptr;

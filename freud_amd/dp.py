@@ -155,6 +155,14 @@ class Auditor:
         n_par, n_met, _ = eng.grad_layout()
         self.cmp = torch.ones(self.grads.numel(), dtype=torch.bool, device=self.grads.device)
         self.cmp[n_par:n_par + n_met] = False
+        # ... and so is W_dec's gradient while the decoder-norm constraint is on: the optimizer step projects it in place after the
+        # exchange (sae_set_decoder_constraint).  TopK layout: W_enc [n_p][d_p] | b_enc [n_p] | W_dec [n_p][d_p] | b_dec [d_p]
+        if getattr(eng, "decoder_constraint", False):
+            n_p = eng.grad_layout()[2]
+            d_p, rest = divmod(n_par - n_p, 2 * n_p + 1)               # n_par = 2 n_p d_p + n_p + d_p
+            assert rest == 0 and n_p > 0, (n_par, n_p)
+            nW = n_p * d_p
+            self.cmp[nW + n_p:2 * nW + n_p] = False
         self.tol = 2e-2 if payload == "bfloat16" else 1e-5
         self.armed = False
         self.passed = 0

@@ -100,6 +100,8 @@ _SIGNATURES = {
     "sae_get_topk_state": (C.c_int, [_vp, C.POINTER(C.c_int64), _i64]),
     "sae_set_topk_state": (C.c_int, [_vp, C.POINTER(C.c_int64), _i64]),
     "sae_set_topk_options": (C.c_int, [_vp, _dbl, _i64]),
+    "sae_set_decoder_constraint": (C.c_int, [_vp, C.c_int]),
+    "sae_get_decoder_constraint": (C.c_int, [_vp]),
     "sae_step": (C.c_int, [_vp, _vp, _i64, C.c_int, _dbl, _vp]),
     "sae_eval": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp]),
     "sae_eval_into": (C.c_int, [_vp, _vp, _i64, C.c_int, _vp, _vp, _vp]),
@@ -375,6 +377,19 @@ class SaeEngine:
         """TopK only: autoencoder_config["dead_feature_threshold"] (train_sae.py:438) and T of the [B][T][d] batch."""
         self._dead_threshold, self._rows_per_file = float(dead_feature_threshold), int(rows_per_file)
         _check(self._lib.sae_set_topk_options(self._ctx, float(dead_feature_threshold), int(rows_per_file)))
+
+    def set_decoder_constraint(self, on: bool, keep_rows: bool = False) -> None:
+        """TopK, bf16 contexts only (EngineError otherwise).  While on, every optimizer_step() / step() projects the gradient of W_dec
+        off its rows before the clip norm and renormalises the rows after the update (the reference model's
+        remove_gradient_parallel_to_decoder_directions / set_decoder_norm_to_unit_norm, topkautoencoder.py:153-175, which its train()
+        never calls).  Switching it on, and set_params() while it is on, renormalise the rows at once: loading weights that were
+        trained without the constraint changes the model.  keep_rows: switch it on without that renorm -- for rows a constrained
+        run left (its own checkpoint, loaded before the switch), which a second renorm would move by an ulp."""
+        _check(self._lib.sae_set_decoder_constraint(self._ctx, (2 if keep_rows else 1) if on else 0))
+
+    @property
+    def decoder_constraint(self) -> bool:
+        return self._lib.sae_get_decoder_constraint(self._ctx) == 1
 
     def get_topk_state(self) -> np.ndarray:
         """TopK only: num_frames_since_fired[n_dict] (int64) - train_sae.py:412-415 keeps it in the live process only."""

@@ -278,15 +278,20 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
           steps: int, clip_thresh: float, batch_size: int, dl_max_workers: int, log_tb_every: int, save_every: int,
           val_every: int, start_checkpoint: Optional[str], whisper_config: dict, optimizer: str, scheduler: str,
           scheduler_params: dict, from_disk: bool, autoencoder_variant: str, autoencoder_config: dict, *,
-          eval_precision: Optional[str] = None, resample: Optional[dict] = None, engine_factory: Optional[Callable] = None,
-          dist_backend: Optional[str] = None):
+          eval_precision: Optional[str] = None, resample: Optional[dict] = None, decoder_constraint: Optional[bool] = None,
+          engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
     """Same keyword arguments as the reference's train() (train_sae.py:297-320).  One OPTIONAL key beyond them: "eval_precision":
     "fp32" makes validate() -- and with it the choice of bestval.pth -- compute what the reference's validate() computes on
     device='cpu' (no autocast: fp32 end to end, train_sae.py:162-166); "bf16" (default; also FREUD_EVAL_PRECISION) keeps the training
     kernels' arithmetic, which agrees with that to ~1e-2.  And "resample": {"every": E, "until": U, "files": F, "activation_scale": a}
     (L1 only; U defaults to steps, F to 512, a to 0.2): at every step s with s % E == 0 and s <= U the dead latents are resampled from
     the high-loss frames of the first F training files (freud_amd/resample.py; round = s // E, seed = the run's seed) -- after the
-    logging block, before the checkpoint and validation blocks, so that stepN.pth holds the revived state.  A config file without
+    logging block, before the checkpoint and validation blocks, so that stepN.pth holds the revived state.  And
+    "decoder_constraint": true (TopK with autoencoder_config.normalize_decoder only): every optimizer step removes the component of
+    W_dec's gradient along each row and renormalises the rows after the update -- the reference model's
+    remove_gradient_parallel_to_decoder_directions / set_decoder_norm_to_unit_norm (topkautoencoder.py:153-175), which its train()
+    never calls.  The rows are renormalised when the key takes effect: resuming a checkpoint that was trained without it changes the
+    model at step 0 (a checkpoint of a constrained run is continued bit for bit).  A config file without
     these keys is a reference config file and trains bit for bit as before.  The two trailing keyword-only arguments are test hooks
     and are never present in a config file."""
     eval_precision = eval_precision or os.environ.get("FREUD_EVAL_PRECISION") or "bf16"
@@ -302,6 +307,13 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         rs_every, rs_until = int(resample["every"]), int(resample.get("until", steps))
         rs_files, rs_scale = int(resample.get("files", 512)), float(resample.get("activation_scale", 0.2))
         check_resample_args(rs_files, rs_scale)
+    if decoder_constraint is not None and not isinstance(decoder_constraint, bool):
+        raise ValueError(f"\"decoder_constraint\" is true or false; got {decoder_constraint!r}")
+    if decoder_constraint:
+        if autoencoder_variant != "topk":
+            raise ValueError("\"decoder_constraint\" serves TopK dictionaries; an L1 forward normalises its decoder columns itself")
+        if not TopKAutoEncoderConfig.from_dict(autoencoder_config).normalize_decoder:
+            raise ValueError("\"decoder_constraint\" keeps the decoder rows at unit norm: autoencoder_config.normalize_decoder is false")
     device = torch.device(device)
     rank, local_rank, world = _dist_env()
     # FREUD_FORCE_DIST=1 (test hook, like bench.py --force-dist): take the data-parallel code path - process group,
@@ -349,6 +361,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
     }
     if resample is not None:
         hparam_dict["resample"] = dict(resample)
+    if decoder_constraint:
+        hparam_dict["decoder_constraint"] = True
     assert autoencoder_variant in ["l1", "topk"], \
         f"Invalid autoencoder variant: {autoencoder_variant}, must be 'l1' or 'topk'"
     if optimizer not in ("radam", "adam"):
@@ -403,6 +417,11 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         if not hasattr(eng, "set_eval_precision"):
             raise RuntimeError("eval_precision='fp32' needs the HIP engine (sae_set_eval_precision)")
         eng.set_eval_precision("fp32")
+    if decoder_constraint:
+        if not hasattr(eng, "set_decoder_constraint"):
+            raise RuntimeError("decoder_constraint needs the HIP engine (sae_set_decoder_constraint)")
+        if start_checkpoint is None:
+            eng.set_decoder_constraint(True)
 
     is_main = rank == 0
     checkpoint_out_dir = run_dir + "/checkpoints"
@@ -423,6 +442,13 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         if is_main:
             print(f"Checkpoint: {start_checkpoint}")
         load_checkpoint(state, start_checkpoint, device=device)
+        if decoder_constraint:
+            # re-applied after the parameters are in place.  A checkpoint of a constrained run holds rows the renorm already left, and
+            # the renorm is not idempotent in fp32: keep them, so that the resumed run continues bit for bit.  Any other checkpoint
+            # is renormalised here -- the model changes at step 0.
+            own = bool(state["hparams"].get("decoder_constraint"))
+            eng.set_decoder_constraint(True, keep_rows=own)
+            state["hparams"]["decoder_constraint"] = True
 
     # Data parallel: (a) in-engine -- the context gets its own RCCL communicator and step() runs statistics, gradient
     # all-reduces (overlapped with the backward) and the optimizer without returning to Python; (b) host-driven -- the

@@ -247,6 +247,25 @@ int sae_optimizer_step(sae_ctx* ctx, double lr, double grad_scale, void* stream)
  * (topkautoencoder.py:104); 0 = treat the batch as one file. */
 int sae_set_topk_options(sae_ctx* ctx, double dead_feature_threshold, int64_t rows_per_file);
 
+/* TopK, bf16 contexts only (anything else: SAE_ERR_STATE).  The decoder-norm constraint: what the reference model defines as
+ * remove_gradient_parallel_to_decoder_directions() and set_decoder_norm_to_unit_norm() (topkautoencoder.py:153-175) and its train()
+ * never calls.  Off by default: the rows of W_dec are unit at initialisation only and drift afterwards, as in the reference.
+ * While it is on, every sae_optimizer_step (and so sae_step)
+ *   1. projects the gradient of W_dec off its rows, g_j <- g_j - (g_j . w_j) w_j (no division by |w_j|^2), in the gradient buffer,
+ *      after any data-parallel sum and before the clip norm, which is then formed from the projected buffer;
+ *   2. clips and updates every parameter exactly as without the constraint (the Adam moments are neither projected nor rescaled);
+ *   3. renormalises the rows, w_j <- w_j / (||w_j||_2 + eps) with eps = 2^-23, in the fp32 master; the bf16 copy the next forward
+ *      multiplies by is taken from the renormalised rows.  A zero row, and the padding, stay exactly zero.
+ * Switching it on (SAE_DEC_CONSTRAINT_ON), and sae_set_params while it is on, run step 3 once (synchronous), so that the rows are unit
+ * before the first projection: loading weights that were trained without the constraint changes the model at step 0.  Step 3 is not
+ * idempotent in fp32 (w / (||w|| + eps) of a row it produced moves most rows by an ulp again), so a run that resumes ITS OWN
+ * checkpoint -- rows that step 3 already left -- loads the parameters first and then switches the constraint on with
+ * SAE_DEC_CONSTRAINT_ON_KEEP_ROWS, which skips the renorm at the switch: the resumed run then continues bit for bit.  0 switches it
+ * off; any other value: SAE_ERR_INVALID.  sae_get_decoder_constraint: 1 / 0. */
+enum { SAE_DEC_CONSTRAINT_ON = 1, SAE_DEC_CONSTRAINT_ON_KEEP_ROWS = 2 };
+int sae_set_decoder_constraint(sae_ctx* ctx, int on);
+int sae_get_decoder_constraint(sae_ctx* ctx);
+
 /* TopK bookkeeping state num_frames_since_fired[n_dict] (int64, train_sae.py:412-415,443-446).  The reference keeps
  * it only in the live process and restarts it from zero on resume (train_sae.py:396-415 never saves it); these two
  * calls let the host persist it next to the checkpoint.  Host buffers of n_dict int64.
