@@ -23,6 +23,7 @@
 #include "dict_match.h"
 #include "recon.h"
 #include "resample.h"
+#include "input_stats.h"
 
 // ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
 static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
@@ -1179,6 +1180,134 @@ extern "C" int sae_resample_apply(sae_ctx* c, const int32_t* latents, int64_t n_
   HIP_TRY(hipMemsetAsync(out_stats, 0, (size_t)(2 + n_latents) * 8, s));
   hipLaunchKernelGGL(rs_apply_kernel, dim3((unsigned)n_latents), dim3(256), 0, s, latents, x_rows, c->d, c->d_p, c->n_p, (float)alpha, c->P, c->Mom,
                      c->Var, reinterpret_cast<unsigned long long*>(out_stats));
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- input statistics (input_stats.h): moments and the geometric median of a resident sample, no context
+static_assert(SAE_INPUT_MAX_D == IN_MAX_D && SAE_INPUT_MAX_ITERATIONS == 1024 && IN_MAX_NV * 64 * 4 >= IN_MAX_D, "freud_sae.h and input_stats.h disagree");
+
+// the workspace: the frame count | the folded sums [4 d + 2] | the units' partials [U][max(4 d, d + 2)]
+struct InputWs {
+  int64_t* n_frames;
+  double *folded, *part;
+  int64_t units_per_file, U, bytes;
+};
+
+static InputWs input_ws(void* base, int64_t n_files, int64_t rows_per_file, int64_t d) {
+  InputWs w;
+  char* p = (char*)base;
+  w.units_per_file = (rows_per_file + IN_UNIT - 1) / IN_UNIT;
+  w.U = n_files * w.units_per_file;
+  w.n_frames = (int64_t*)p; p += 64;
+  w.folded = (double*)p; p += round_up((4 * d + 2) * 8, 64);
+  w.part = (double*)p; p += w.U * std::max<int64_t>(4 * d, d + 2) * 8;
+  w.bytes = p - (char*)base;
+  return w;
+}
+
+static bool input_dims_ok(int64_t n_files, int64_t rows_per_file, int64_t d) {
+  return n_files >= 1 && n_files <= 65535 && rows_per_file >= 1 && rows_per_file <= 65535ll * 128 && d >= 1 && d <= IN_MAX_D;
+}
+
+extern "C" int64_t sae_input_stats_workspace_bytes(int64_t n_files, int64_t rows_per_file, int64_t d) {
+  return input_dims_ok(n_files, rows_per_file, d) ? input_ws(nullptr, n_files, rows_per_file, d).bytes : -1;
+}
+
+// the checks that sae_input_moments and sae_input_median share; nothing is enqueued when one fails
+static int input_check(const char* fn, const void* x, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const void* out,
+                       const void* workspace, int64_t workspace_bytes) {
+  if (!x || !out || !workspace) return fail(SAE_ERR_INVALID, "%s: null argument", fn);
+  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
+  if (d < 1 || d > IN_MAX_D) return fail(SAE_ERR_INVALID, "%s: d=%lld outside [1, %d]", fn, (long long)d, IN_MAX_D);
+  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  if (workspace_bytes < sae_input_stats_workspace_bytes(n_files, rows_per_file, d))
+    return fail(SAE_ERR_INVALID, "%s: workspace of %lld bytes < sae_input_stats_workspace_bytes(%lld, %lld, %lld)", fn, (long long)workspace_bytes,
+                (long long)n_files, (long long)rows_per_file, (long long)d);
+  if (misaligned(x, x_dtype == SAE_DTYPE_F32 ? 4 : 2) || misaligned(out, 8) || misaligned(workspace, 8))
+    return fail(SAE_ERR_INVALID, "%s: x must be aligned to its element, the outputs and the workspace to 8 bytes", fn);
+  return SAE_OK;
+}
+
+template <int MODE>
+static void input_launch_fold(const InputWs& w, int ncols, int d, double* m_next, double* objective, hipStream_t s) {
+  const int cols = MODE == IN_FOLD_WEISZFELD ? d : ncols;
+  hipLaunchKernelGGL(in_fold_kernel<MODE>, dim3((unsigned)((cols + IN_FOLD_COLS - 1) / IN_FOLD_COLS)), dim3(256), 0, s, w.part, w.U, ncols, d,
+                     w.folded, m_next, objective, w.n_frames);
+}
+
+extern "C" int sae_input_moments(const void* x, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths,
+                                 double* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = input_check("sae_input_moments", x, n_files, rows_per_file, d, x_dtype, out, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const InputWs w = input_ws(workspace, n_files, rows_per_file, d);
+  const int T = (int)rows_per_file, di = (int)d, upf = (int)w.units_per_file;
+  hipLaunchKernelGGL(in_count_kernel, dim3(1), dim3(256), 0, s, lengths, n_files, T, w.n_frames);
+  int rc = with_x_type(x_dtype, x, [&](auto* xt) {
+    using XT = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+    hipLaunchKernelGGL((in_moments_kernel<XT, 0>), dim3((unsigned)w.U), dim3(256), 0, s, xt, T, di, upf, lengths, (const double*)nullptr, w.part);
+    input_launch_fold<IN_FOLD_MOMENTS0>(w, 4 * di, di, nullptr, nullptr, s);
+    hipLaunchKernelGGL(in_finish_kernel<0>, dim3(1), dim3(256), 0, s, w.folded, di, w.n_frames, out);
+    // the centred sweep reads the mean that the first one left in out
+    hipLaunchKernelGGL((in_moments_kernel<XT, 1>), dim3((unsigned)w.U), dim3(256), 0, s, xt, T, di, upf, lengths, (const double*)out, w.part);
+    input_launch_fold<IN_FOLD_SUM>(w, di, di, nullptr, nullptr, s);
+    hipLaunchKernelGGL(in_finish_kernel<1>, dim3(1), dim3(256), 0, s, w.folded, di, w.n_frames, out);
+    return (int)SAE_OK;
+  });
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// one sweep at the estimate m: the units' partials, then the fold into m_next (null: the objective alone) and *objective
+template <typename XT>
+static int input_launch_step(const XT* x, int T, int d, const InputWs& w, const int32_t* lengths, const double* m, float floor_w,
+                             double* m_next, double* objective, hipStream_t s) {
+  constexpr int EPV = 16 / (int)sizeof(XT);
+  // the register form needs 16-byte aligned rows; NV = its vectors per lane
+  const bool vec = d % EPV == 0 && !misaligned(x, 16);
+  const int nv = vec ? (d / EPV + 63) / 64 : 0;
+  int rc = SAE_OK;
+  const bool known = with_in_nv(nv, [&](auto NV) {
+    // (d <= IN_MAX_D: a 2-byte dtype never has more than 4 vectors per lane, and those forms are not compiled)
+    constexpr int KNV = (decltype(NV)::value - 1) * 64 * EPV < IN_MAX_D ? decltype(NV)::value : 0;
+    auto kern = in_weiszfeld_kernel<XT, KNV>;
+    const size_t lds = (size_t)(nv ? d : 4 * d) * 8;
+    if (lds > 48 * 1024) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) { rc = fail(SAE_ERR_HIP, "hipFuncSetAttribute(%zu bytes of LDS) failed: %s", lds, hipGetErrorString(e)); return; }
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)w.U), dim3(256), lds, s, x, T, d, (int)w.units_per_file, lengths, m, floor_w, w.part);
+  });
+  if (!known) return fail(SAE_ERR_INVALID, "no Weiszfeld kernel for %d vectors per lane", nv);
+  if (rc) return rc;
+  input_launch_fold<IN_FOLD_WEISZFELD>(w, d + 2, d, m_next, objective, s);
+  return SAE_OK;
+}
+
+extern "C" int sae_input_median(const void* x, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths,
+                                const double* start, double floor, int iterations, double* path, double* objective, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  if (!start || !objective) return fail(SAE_ERR_INVALID, "sae_input_median: null argument");
+  if (int rc = input_check("sae_input_median", x, n_files, rows_per_file, d, x_dtype, path, workspace, workspace_bytes)) return rc;
+  if (iterations < 1 || iterations > SAE_INPUT_MAX_ITERATIONS)
+    return fail(SAE_ERR_INVALID, "iterations=%d outside [1, %d]", iterations, SAE_INPUT_MAX_ITERATIONS);
+  if (!(floor >= (double)FLT_MIN && floor <= (double)FLT_MAX)) return fail(SAE_ERR_INVALID, "floor=%g outside [FLT_MIN, FLT_MAX]", floor);
+  if (misaligned(start, 8) || misaligned(objective, 8)) return fail(SAE_ERR_INVALID, "start and objective must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const InputWs w = input_ws(workspace, n_files, rows_per_file, d);
+  const int T = (int)rows_per_file, di = (int)d;
+  hipLaunchKernelGGL(in_count_kernel, dim3(1), dim3(256), 0, s, lengths, n_files, T, w.n_frames);
+  HIP_TRY(hipMemcpyAsync(path, start, (size_t)d * 8, hipMemcpyDeviceToDevice, s));
+  // sweep k at m_k gives J_k and m_{k+1}; the last sweep, at m_I, gives J_I alone.  No host synchronisation in between.
+  int rc = with_x_type(x_dtype, x, [&](auto* xt) {
+    for (int k = 0; k <= iterations; ++k)
+      if (int r = input_launch_step(xt, T, di, w, lengths, path + (int64_t)k * d, (float)floor, k < iterations ? path + (int64_t)(k + 1) * d : nullptr,
+                                    objective + k, s))
+        return r;
+    return (int)SAE_OK;
+  });
+  if (rc) return rc;
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

@@ -137,6 +137,9 @@ _SIGNATURES = {
     "sae_resample_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_resample_select": (C.c_int, [_vp, _i64, _vp, _i64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sae_resample_apply": (C.c_int, [_vp, _vp, _i64, _vp, _dbl, _vp, _vp]),
+    "sae_input_stats_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "sae_input_moments": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, _i64, _vp]),
+    "sae_input_median": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _dbl, C.c_int, _vp, _vp, _vp, _i64, _vp]),
     "sae_findex_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_findex_count": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _vp, _vp, _vp]),
     "sae_findex_fill": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp,
@@ -212,6 +215,7 @@ MANIP_MAX_VARIANTS = 16                                             # include/fr
 RECON_UNFUSED = 1                                                   # include/freud_sae.h: SAE_RECON_UNFUSED
 RESAMPLE_DEAD, RESAMPLE_PAIRS, RESAMPLE_SKIPPED_DUPLICATE, RESAMPLE_TOTAL, RESAMPLE_LMAX_BITS = range(5)   # include/freud_sae.h: SAE_RESAMPLE_*
 RESAMPLE_NCOUNTS = 8                                                # include/freud_sae.h: SAE_RESAMPLE_NCOUNTS
+INPUT_MAX_D, INPUT_MAX_ITERATIONS = 2048, 1024                      # include/freud_sae.h: SAE_INPUT_MAX_*
 
 
 def stats_layout(n: int) -> dict:
@@ -931,6 +935,45 @@ def resample_select(row_loss, rows: int, fire_count, n: int, seed: int, round: i
     ws = _dev("workspace", workspace, "uint8", resample_workspace_bytes(rows, n), at_least=True)
     _check(load().sae_resample_select(rl, int(rows), fc, int(n), int(seed) & (2 ** 64 - 1), int(round) & (2 ** 64 - 1), lo, ro, co, ws,
                                       int(workspace.numel()), _stream_ptr(stream)))
+
+
+# -- input statistics without a context (include/freud_sae.h: sae_input_*; freud_amd/input_stats.py) --------------------------------
+def input_stats_workspace_bytes(n_files: int, T: int, d: int) -> int:
+    """Bytes of workspace that input_moments / input_median need for a sample [n_files, T, d]."""
+    nbytes = int(load().sae_input_stats_workspace_bytes(int(n_files), int(T), int(d)))
+    if nbytes < 0:
+        raise EngineError(f"input_stats_workspace_bytes: n_files={n_files}, T={T} or d={d} (1 <= d <= {INPUT_MAX_D}) out of range")
+    return nbytes
+
+
+def _input_args(x, who: str, lengths, workspace):
+    x, xp, B, T, d, dt, lp = _files_args(x, who, lengths)
+    if d > INPUT_MAX_D:
+        raise EngineError(f"{who}: d={d} > {INPUT_MAX_D}")
+    ws = _dev("workspace", workspace, "uint8", input_stats_workspace_bytes(B, T, d), at_least=True)
+    return x, xp, B, T, d, dt, lp, ws
+
+
+def input_moments(x, out, workspace, lengths=None, stream=None) -> None:
+    """The moments of the sample x [n_files, T, d]: out (float64 CUDA [4 d + 2]) = mean | centred sum of squares | min | max |
+    sum |x|^2 | N.  workspace: a uint8 CUDA tensor of >= input_stats_workspace_bytes(n_files, T, d).  Asynchronous."""
+    x, xp, B, T, d, dt, lp, ws = _input_args(x, "input_moments", lengths, workspace)
+    o = _dev("out", out, "float64", 4 * d + 2)
+    _check(load().sae_input_moments(xp, B, T, d, dt, lp, o, ws, int(workspace.numel()), _stream_ptr(stream)))
+
+
+def input_median(x, start, floor: float, iterations: int, path, objective, workspace, lengths=None, stream=None) -> None:
+    """Weiszfeld's iteration on the sample x [n_files, T, d] from start (float64 CUDA [d]): path (float64 CUDA [iterations + 1, d]) =
+    m_0 .. m_I, objective (float64 CUDA [iterations + 1]) = J_0 .. J_I.  Asynchronous."""
+    x, xp, B, T, d, dt, lp, ws = _input_args(x, "input_median", lengths, workspace)
+    iterations = int(iterations)
+    if iterations < 1 or iterations > INPUT_MAX_ITERATIONS:
+        raise EngineError(f"input_median: iterations={iterations} outside [1, {INPUT_MAX_ITERATIONS}]")
+    st = _dev("start", start, "float64", d)
+    pa = _dev("path", path, "float64", (iterations + 1) * d)
+    ob = _dev("objective", objective, "float64", iterations + 1)
+    _check(load().sae_input_median(xp, B, T, d, dt, lp, st, float(floor), iterations, pa, ob, ws, int(workspace.numel()),
+                                   _stream_ptr(stream)))
 
 
 # -- feature index (include/freud_sae.h: sae_findex_*; freud_amd/feature_index.py) ---------------------------------------------------

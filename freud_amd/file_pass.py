@@ -162,19 +162,23 @@ class FilePass:
             raise RuntimeError(f"the loader delivered {file0} of {self.n_total} files")
 
 
-def add_pass_arguments(ap, sae_help: str = "checkpoint path") -> None:
-    """The arguments that every pass's command line takes."""
-    ap.add_argument("--sae", required=True, help=sae_help)
-    ap.add_argument("--data_path", required=True)
-    ap.add_argument("--layer_name", required=True)
+def add_pass_arguments(ap, sae_help: str = "checkpoint path", *, sae: bool = True, out_required: bool = True) -> None:
+    """The arguments that every pass's command line takes (--data-path and --layer-name are also spelled with an underscore).
+    sae=False: a pass without a dictionary takes neither --sae nor --batch_files; out_required=False: --out is optional."""
+    if sae:
+        ap.add_argument("--sae", required=True, help=sae_help)
+    ap.add_argument("--data_path", "--data-path", dest="data_path", required=True)
+    ap.add_argument("--layer_name", "--layer-name", dest="layer_name", required=True)
     ap.add_argument("--lengths", default=None, help=".npy of int frames per file (file order); default: the full T")
-    ap.add_argument("--batch_files", type=int, default=None)
-    ap.add_argument("--out", required=True)
+    if sae:
+        ap.add_argument("--batch_files", type=int, default=None)
+    ap.add_argument("--out", required=out_required, default=None)
 
 
 def run_pass_cli(a, run) -> None:
-    """The tail of a pass's command line over its parsed arguments: result = run(the --lengths array or None), stored as a.out, and
-    one JSON line of its summary()."""
+    """The tail of a pass's command line over its parsed arguments: result = run(the --lengths array or None), stored as a.out
+    (where one is given), and one JSON line of its summary()."""
     result = run(np.load(a.lengths) if a.lengths else None)
-    result.to_npz(a.out)
+    if a.out:
+        result.to_npz(a.out)
     print(json.dumps({"out": a.out, **result.summary()}))

@@ -274,12 +274,33 @@ def _dist_env():
 # ------------------------------------------------------------------------------------------------
 # train()
 # ------------------------------------------------------------------------------------------------
+def parse_init_b_dec(init_b_dec, autoencoder_variant: str) -> Optional[dict]:
+    """The optional train() key "init_b_dec" -> None or {"method", "files", "iterations"}; ValueError for a form it does not take.
+    Needs no device."""
+    if init_b_dec is None:
+        return None
+    from freud_amd.input_stats import DEFAULT_FILES, DEFAULT_ITERATIONS, check_input_stats_args
+    if autoencoder_variant == "l1":
+        raise ValueError("\"init_b_dec\" serves TopK dictionaries: the tied L1 model has no decoder bias to initialise")
+    spec = {"method": init_b_dec} if isinstance(init_b_dec, str) else init_b_dec
+    if not isinstance(spec, dict):
+        raise ValueError(f"\"init_b_dec\" is a method name or an object; got {init_b_dec!r}")
+    unknown = set(spec) - {"method", "files", "iterations"}
+    if unknown or spec.get("method") not in ("geometric_median", "mean"):
+        raise ValueError("\"init_b_dec\" takes method (\"geometric_median\" or \"mean\"), files, iterations; "
+                         f"got {init_b_dec!r}")
+    out = {"method": spec["method"], "files": int(spec.get("files", DEFAULT_FILES)),
+           "iterations": int(spec.get("iterations", DEFAULT_ITERATIONS))}
+    check_input_stats_args(out["files"], out["iterations"])
+    return out
+
+
 def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, lr: float, weight_decay: float,
           steps: int, clip_thresh: float, batch_size: int, dl_max_workers: int, log_tb_every: int, save_every: int,
           val_every: int, start_checkpoint: Optional[str], whisper_config: dict, optimizer: str, scheduler: str,
           scheduler_params: dict, from_disk: bool, autoencoder_variant: str, autoencoder_config: dict, *,
           eval_precision: Optional[str] = None, resample: Optional[dict] = None, decoder_constraint: Optional[bool] = None,
-          engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
+          init_b_dec=None, engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
     """Same keyword arguments as the reference's train() (train_sae.py:297-320).  One OPTIONAL key beyond them: "eval_precision":
     "fp32" makes validate() -- and with it the choice of bestval.pth -- compute what the reference's validate() computes on
     device='cpu' (no autocast: fp32 end to end, train_sae.py:162-166); "bf16" (default; also FREUD_EVAL_PRECISION) keeps the training
@@ -291,7 +312,11 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
     W_dec's gradient along each row and renormalises the rows after the update -- the reference model's
     remove_gradient_parallel_to_decoder_directions / set_decoder_norm_to_unit_norm (topkautoencoder.py:153-175), which its train()
     never calls.  The rows are renormalised when the key takes effect: resuming a checkpoint that was trained without it changes the
-    model at step 0 (a checkpoint of a constrained run is continued bit for bit).  A config file without
+    model at step 0 (a checkpoint of a constrained run is continued bit for bit).  And "init_b_dec": "geometric_median" | "mean" |
+    {"method": ..., "files": F, "iterations": I} (TopK only; F defaults to 256, I to 32): b_dec starts at that statistic of the first F
+    training files in file order (freud_amd/input_stats.py) instead of at zero; the other initial parameters, the loader's shuffles
+    and the global RNG are what they are without the key, every rank computes the same bytes, and with start_checkpoint the key is
+    recorded and the checkpoint's b_dec stands.  A config file without
     these keys is a reference config file and trains bit for bit as before.  The two trailing keyword-only arguments are test hooks
     and are never present in a config file."""
     eval_precision = eval_precision or os.environ.get("FREUD_EVAL_PRECISION") or "bf16"
@@ -314,6 +339,7 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
             raise ValueError("\"decoder_constraint\" serves TopK dictionaries; an L1 forward normalises its decoder columns itself")
         if not TopKAutoEncoderConfig.from_dict(autoencoder_config).normalize_decoder:
             raise ValueError("\"decoder_constraint\" keeps the decoder rows at unit norm: autoencoder_config.normalize_decoder is false")
+    ib = parse_init_b_dec(init_b_dec, autoencoder_variant)
     device = torch.device(device)
     rank, local_rank, world = _dist_env()
     # FREUD_FORCE_DIST=1 (test hook, like bench.py --force-dist): take the data-parallel code path - process group,
@@ -363,6 +389,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         hparam_dict["resample"] = dict(resample)
     if decoder_constraint:
         hparam_dict["decoder_constraint"] = True
+    if ib is not None:
+        hparam_dict["init_b_dec"] = init_b_dec if isinstance(init_b_dec, str) else dict(init_b_dec)
     assert autoencoder_variant in ["l1", "topk"], \
         f"Invalid autoencoder variant: {autoencoder_variant}, must be 'l1' or 'topk'"
     if optimizer not in ("radam", "adam"):
@@ -412,6 +440,13 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         param_order = ["W_dec", "b_dec", "encoder.weight", "encoder.bias"]
         state_dict_order = ["W_dec", "b_dec", "encoder.weight", "encoder.bias"]
         eng.set_topk_options(float(autoencoder_config["dead_feature_threshold"]), T)   # raw key (:438); T for x.mean(0)
+    ib_stats = None
+    if ib is not None and start_checkpoint is None:
+        # (keep_rng inside: the loader's shuffles and everything drawn after this point are those of a run without the key; every
+        # rank computes the same bytes from the same files, which the replica guard checks)
+        from freud_amd.input_stats import input_statistics
+        ib_stats = input_statistics(train_folder, whisper_config["layer_name"], files=ib["files"], iterations=ib["iterations"])
+        init["b_dec"] = (ib_stats.geometric_median if ib["method"] == "geometric_median" else ib_stats.mean.astype(np.float32)).copy()
     eng.set_params(init)
     if eval_precision == "fp32":
         if not hasattr(eng, "set_eval_precision"):
@@ -430,6 +465,10 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         os.makedirs(checkpoint_out_dir, exist_ok=True)
     logger = _Logger(run_dir, is_main)
     logger.add_text("hparams", json.dumps(hparam_dict, indent=4))
+    if ib_stats is not None:
+        logger.add_scalar("init/b_dec_norm", float(np.linalg.norm(init["b_dec"].astype(np.float64))), 0)
+        logger.add_scalar("init/mean_energy_fraction", ib_stats.mean_energy_fraction, 0)
+        logger.add_scalar("init/median_shift", ib_stats.shift, 0)
     n_params = sum(int(np.prod(s)) for s in eng.param_shapes().values())
     if is_main:
         print("Model: %.2fM" % (n_params / 1.0e6))
@@ -449,6 +488,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
             own = bool(state["hparams"].get("decoder_constraint"))
             eng.set_decoder_constraint(True, keep_rows=own)
             state["hparams"]["decoder_constraint"] = True
+        if ib is not None:
+            state["hparams"]["init_b_dec"] = hparam_dict["init_b_dec"]      # recorded, not applied: the checkpoint's b_dec stands
 
     # Data parallel: (a) in-engine -- the context gets its own RCCL communicator and step() runs statistics, gradient
     # all-reduces (overlapped with the backward) and the optimizer without returning to Python; (b) host-driven -- the

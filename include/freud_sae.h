@@ -870,6 +870,35 @@ int sae_resample_select(const float* row_loss_dev, int64_t rows, const int64_t* 
 int sae_resample_apply(sae_ctx* ctx, const int32_t* latents_dev, int64_t n_latents, const float* x_rows_dev, double alpha,
                        int64_t* out_stats_dev, void* stream);
 
+/* ---- Input statistics: the moments and the geometric median of a sample of activation rows, before any dictionary exists
+ * (freud_amd/input_stats.py; kernels: freud_amd/csrc/input_stats.h).  Context-free like sae_search_raw_files: no SAE, the current
+ * device, all pointers caller-owned device memory.  The sample is resident as x_dev [n_files][rows_per_file][d] (x_dtype); lengths_dev
+ * as for the file passes (int32 [n_files] or NULL = T; only the first min(length, T) frames of a file count, a length below 1 counts
+ * as 1).  N = the counted frames.  1 <= d <= SAE_INPUT_MAX_D, n_files and rows_per_file within the file passes' limits.
+ *
+ * sae_input_stats_workspace_bytes: the scratch both calls need (-1: arguments out of range); 8-byte aligned.
+ * sae_input_moments: two sweeps.  out_dev, double [4 d + 2]: mean [d] | the centred sum of squares sum_i (x_i - mean)^2 [d] (a second
+ *   sweep with the fp64 mean, not E[x^2] - mean^2) | min [d] | max [d] (exact) | sum_i |x_i|^2 | N.  All sums are fp64.
+ * sae_input_median: Weiszfeld's iteration with a fixed count, from start_dev (double [d]; the mean, for the documented rule):
+ *   dist_i = |x_i - m_k|, w_i = 1 / max(dist_i, floor), m_{k+1} = sum w_i x_i / sum w_i, J_k = sum dist_i / N.  x_i - m_k is formed from
+ *   the fp64 estimate with one rounding to fp32; the squared distance, its root and w are fp32 (a fixed summation order); the three
+ *   sums are fp64.  path_dev, double [iterations + 1][d]: m_0 (= start) .. m_I; objective_dev, double [iterations + 1]: J_0 .. J_I
+ *   (iterations + 1 sweeps: the last one evaluates J at m_I).  FLT_MIN <= floor <= FLT_MAX, 1 <= iterations <=
+ *   SAE_INPUT_MAX_ITERATIONS.  No convergence test and no host synchronisation between the iterations: asynchronous on `stream`.
+ *
+ * Every partial sum belongs to a fixed unit (a file and a block of 256 of its frames) and the units are added in ascending order on
+ * the device: the results are a function of (x, lengths, iterations) alone, not of the grid or the device's size; no atomics; two
+ * calls give the same bytes.  Null pointers, a shape, d, dtype, floor or iteration count out of range, a short or misaligned
+ * workspace: SAE_ERR_INVALID before anything is enqueued. */
+#define SAE_INPUT_MAX_D 2048
+#define SAE_INPUT_MAX_ITERATIONS 1024
+int64_t sae_input_stats_workspace_bytes(int64_t n_files, int64_t rows_per_file, int64_t d);
+int sae_input_moments(const void* x_dev, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths_dev,
+                      double* out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
+int sae_input_median(const void* x_dev, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths_dev,
+                     const double* start_dev, double floor, int iterations, double* path_dev, double* objective_dev, void* workspace_dev,
+                     int64_t workspace_bytes, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
