@@ -2528,19 +2528,21 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
   if (!c || !out) return fail(SAE_ERR_INVALID, "null argument");
   USE_DEVICE(c);
   HIP_TRY(hipDeviceSynchronize());
-  if (which == 0 || which == 1 || which == 3 || which == 8 || which == 9)      // tensors of the last bf16 forward
+  if (which == 14 && !(c->topk && c->multi)) return fail(SAE_ERR_INVALID, "debug tensor 14: not a TopK context with multi_topk");
+  if (which == 0 || which == 1 || which == 3 || which == 8 || which == 9 || which == 14)      // tensors of the last bf16 forward
     if (int rc = no_bf16_forward_left(c)) return rc;
   if (which == 0) {
     int rc_d = ensure_dense(c);
     if (rc_d) return rc_d;
   }
   const int64_t M = c->last_M;
-  if (which == 0 || which == 1) {
+  if (which == 0 || which == 1 || which == 14) {   // 14 = dm_b, the multi-TopK pass's d (decoder output) of the last training forward
     const int cols = which == 0 ? c->n : c->d, ld = which == 0 ? c->n_p : c->d_p;
     if (cap < M * cols) return fail(SAE_ERR_INVALID, "capacity too small");
     std::vector<uint16_t> tmp((size_t)M * ld);
-    HIP_TRY(hipMemcpy(tmp.data(), which == 0 ? (c->topk ? (void*)c->dense : (void*)c->c) : (c->topk ? (void*)c->de_b : (void*)c->dxh),
-                      tmp.size() * 2, hipMemcpyDeviceToHost));
+    const void* src = which == 14 ? (void*)c->dm_b
+                                  : which == 0 ? (c->topk ? (void*)c->dense : (void*)c->c) : (c->topk ? (void*)c->de_b : (void*)c->dxh);
+    HIP_TRY(hipMemcpy(tmp.data(), src, tmp.size() * 2, hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < M; ++r)
       for (int j = 0; j < cols; ++j) {
         uint32_t u = (uint32_t)tmp[(size_t)r * ld + j] << 16;

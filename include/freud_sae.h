@@ -313,7 +313,7 @@ int sae_eval_into(sae_ctx* ctx, const void* x_dev, int64_t M, int x_dtype, float
  * the L1 weights happens first, exactly as in every other forward.  Training steps are not affected.  Any SAE_PREC_* other than
  * these two: SAE_ERR_INVALID.
  * The fp32 forward obeys M <= max_rows like every other forward and works in buffers of its own: it leaves no bf16 latent rows.
- * While it is the last forward, sae_latent_buffer, sae_topk_indices, sae_multi_topk_buffers and sae_debug_read(0, 1, 3, 8, 9)
+ * While it is the last forward, sae_latent_buffer, sae_topk_indices, sae_multi_topk_buffers and sae_debug_read(0, 1, 3, 8, 9, 14)
  * return SAE_ERR_STATE (run a bf16 sae_eval to read those); sae_read_metrics and sae_latent_colmax answer for the fp32 forward,
  * and sae_debug_read(2) (the gradients of the last training forward), sae_get_params, sae_get_opt_state, sae_get_topk_state and
  * sae_decode stay valid. */
@@ -901,7 +901,9 @@ int sae_input_median(const void* x_dev, int64_t n_files, int64_t rows_per_file, 
 
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
- * layouts, concatenated in parameter order.  Synchronising.  Not part of the hot path. */
+ * layouts, concatenated in parameter order; 14 = the multi-TopK pass's d (decoder output) [M][d] of the last training forward, as
+ * the sparse backward reads it (bf16 values; SAE_ERR_INVALID unless the context is TopK with multi_topk, SAE_ERR_STATE after an fp32
+ * evaluation, like 1).  Synchronising.  Not part of the hot path. */
 int sae_debug_read(sae_ctx* ctx, int which, float* out_host, int64_t capacity_floats);
 
 /* Timing hooks for bench.py / profiling.  level 0 = off, 1 = bracket only the dominant kernel of
