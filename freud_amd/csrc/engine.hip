@@ -103,7 +103,7 @@ extern "C" int sae_dominant_kernel(sae_ctx* c) { return c ? dominant_kid(c) : KI
 // launch runs in rounds of one workgroup per CU (256x256 kernel, both dimensions even) or two (128x128 kernel); pick
 // the factor that minimises rounds / factor (plus a small price per slab for the reduction pass).
 static int choose_splits(int r128, int c128, int64_t ktiles) {
-  const bool big = !g_force_gemm128 && r128 % 2 == 0 && c128 % 2 == 0;
+  const bool big = gemm_tile_edge(r128, c128) == 256;
   const int tiles = big ? (r128 / 2) * (c128 / 2) : r128 * c128, slots = big ? 256 : 512;
   int best = 1;
   double best_cost = 1e30;
@@ -279,7 +279,7 @@ static int topk_create(sae_ctx* c, int64_t Mp) {
 extern "C" void sae_destroy(sae_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device_id);   // teardown: nothing useful can be done about a failure here
-  void* ptrs[] = {c->P,    c->Mom,     c->Var,     c->G,       c->Wb,   c->Wt,      c->xb,    c->c, c->dxh, c->dxhT, c->xT,
+  void* ptrs[] = {c->P,    c->Mom,     c->Var,     c->G,       c->Wb,   c->Wt,      c->xb,    c->c, c->dxh,
                   c->dpre, c->slab,    c->db_part, c->l1_part, c->sq_part, c->scal, c->gn_part, c->masked, c->cn_part, c->cnt_part,
                   c->We_b, c->Wd_b, c->xs, c->pre, c->dense, c->aux_dense, c->de_b, c->dh_b, c->e, c->dh, c->e2_part,
                   c->a2_part, c->dbd_part, c->ds_part, c->tkf, c->top_idx, c->aux_idx, c->tk, c->tv_part, c->nfsf, c->dead, c->dbe_fx,
@@ -479,13 +479,6 @@ extern "C" int sae_create(const sae_config* cfg, sae_ctx** out) {
   ALLOC(c->c, Mp * c->n_p * 2 + 4096);   // + a dummy line the fused forward parks its first two stores on
   ALLOC(c->dxh, Mp * c->d_p * 2);
   ALLOC(c->dpre, Mp * c->n_p * 2);
-  // (opt-in, FREUD_DW_ROWA=1: measured SLOWER in the engine -- C4 weight gradient 9.70 -> 10.75 ms, profiles/r05_ab_dw_row_a.txt --
-  // although the stand-alone shape on random dense operands ran 10 % faster, profiles/r05_kbench_dw_row_a.txt)
-  if (!c->use_fused_bwd && !g_force_gemm128 && c->d_p % 256 == 0 && c->n_p % 256 == 0 && Mp % 64 == 0 &&
-      getenv("FREUD_DW_ROWA") && atoi(getenv("FREUD_DW_ROWA")) == 1) {
-    ALLOC(c->dxhT, Mp * c->d_p * 2);
-    ALLOC(c->xT, Mp * c->d_p * 2);
-  }
   ALLOC(c->slab, (int64_t)slab_splits * c->nW * 4);
   ALLOC(c->db_part, db_rows * c->n_p * 4);
   ALLOC(c->l1_part, (Mp / 128) * (c->n_p / 128) * 4);
@@ -1397,7 +1390,7 @@ GemmArgs enc_gemm_args(const sae_ctx* c, const bf16_t* xb, int64_t Mp) {
 }
 
 // c = relu(x W + b), stored: the ordinary encoder.  (T, the caller's activation type, is not used: as a template with a deduced
-// return type the helper is instantiated inside its first caller, forward_impl<float>, so the encoder's GEMM kernels keep their
+// return type the helper is instantiated inside its first caller, l1_forward_bf16<float>, so the encoder's GEMM kernels keep their
 // place in the code object and two builds stay comparable byte for byte)
 template <typename T>
 static auto launch_encoder(sae_ctx* c, const GemmArgs& g, int64_t M, hipStream_t s) {
@@ -1415,8 +1408,11 @@ static auto launch_encoder(sae_ctx* c, const GemmArgs& g, int64_t M, hipStream_t
 template <typename T> static constexpr bool x_dtype_is_bf16() { return false; }
 template <> constexpr bool x_dtype_is_bf16<bf16_t>() { return true; }
 
+// ---- the L1 forward in stages: l1_prepare, then ONE of l1_forward_fused / l1_forward_fp8 / l1_forward_bf16 (forward_impl)
+
+// weights (normalised, cast), the bf16 copy of x with its masked-entry count, and the fp8 scales and operands
 template <typename T>
-static int forward_impl(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s, bool need_backward) {
+static int l1_prepare(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s, bool need_backward) {
   const int d = c->d, d_p = c->d_p, n_p = c->n_p;
   const float alpha = (float)c->cfg.recon_alpha;
   float* W = c->P;
@@ -1449,373 +1445,465 @@ static int forward_impl(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream
     hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->xb, c->x8, n8, c->scal8);
   }
   ev_end(c, KID_PREP_X, s);
+  return SAE_OK;
+}
 
-  int rc;
-  if (c->use_fused_fwd) {
-    const int lds = FF_LDS_BYTES;
-    FwdFusedArgs a{};
-    a.xb = c->xb_cur; a.x = x; a.Wt = c->Wt; a.bias = b; a.cnt_part = c->cnt_part; a.c = c->c; a.dxh = c->dxh;
-    a.l1_part = c->l1_part; a.sq_part = c->sq_part; a.M = M; a.d = d; a.n_p = n_p; a.ntiles = n_p / FF_BN;
-    a.c_rows = c->max_rows_p;
-    // full workgroups (all 128 rows < M) run the mask-free instantiation; a ragged last workgroup the padded one
-    const int full_wgs = (int)(M / FF_BM), all_wgs = (int)(Mp / FF_BM);
-    auto launch = [&](auto kern, int blocks, int block_offset) -> int {
-      LDS_ATTR(kern, 160 * 1024, g_device);     // opt in to > 64 KiB dynamic LDS once per instantiation and device
-      a.block_offset = block_offset;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a);
-      return SAE_OK;
-    };
-    ev_begin(c, KID_FWD_FUSED, s);
-    int rcl = SAE_OK;
-    if (full_wgs > 0 && c->cfg.debug_flags == 65 && c->fwd_variant == 1) {   // diagnostic: stamps into the (unused here) dpre buffer
-      a.stamps = reinterpret_cast<unsigned long long*>(c->dpre);
-      rcl = launch(fwd_fused_d384_kernel<T, false, true>, full_wgs, 0);
-    } else if (c->fwd_variant == 2) {               // the second decomposition (fwd_fused2.h)
-      if (full_wgs > 0 && c->cfg.debug_flags == 65) {
-        a.stamps = reinterpret_cast<unsigned long long*>(c->dpre);
-        rcl = launch(fwd_fused2_d384_kernel<T, false, true>, full_wgs, 0);
-      } else if (full_wgs > 0) rcl = launch(fwd_fused2_d384_kernel<T, false>, full_wgs, 0);
-      if (!rcl && all_wgs > full_wgs) rcl = launch(fwd_fused2_d384_kernel<T, true>, all_wgs - full_wgs, full_wgs);
-      if (rcl) return rcl;
-      ev_end(c, KID_FWD_FUSED, s);
-      HIP_TRY(hipGetLastError());
-      return SAE_OK;
-    } else if (full_wgs > 0) {
-      rcl = launch(fwd_fused_d384_kernel<T, false, false>, full_wgs, 0);
-    }
-    if (!rcl && all_wgs > full_wgs) rcl = launch(fwd_fused_d384_kernel<T, true, false>, all_wgs - full_wgs, full_wgs);
-    if (rcl) return rcl;
-    ev_end(c, KID_FWD_FUSED, s);
-    HIP_TRY(hipGetLastError());
-    return SAE_OK;
+// One fused d = 384 forward over all rows: the full workgroups (all 128 rows < M) run the mask-free instantiation `full`, a ragged
+// last workgroup the padded one `ragged`
+using FwdFusedKernel = void (*)(FwdFusedArgs);
+static int launch_fwd_fused_pair(FwdFusedKernel full, FwdFusedKernel ragged, FwdFusedArgs a, int64_t M, int64_t Mp, hipStream_t s) {
+  const int full_wgs = (int)(M / FF_BM), all_wgs = (int)(Mp / FF_BM);
+  if (full_wgs > 0) {
+    LDS_ATTR(full, 160 * 1024, g_device);     // opt in to > 64 KiB dynamic LDS once per instantiation and device
+    a.block_offset = 0;
+    hipLaunchKernelGGL(full, dim3(full_wgs), dim3(256), FF_LDS_BYTES, s, a);
   }
-  if (c->fp8) {
-    {  // c = relu(bf16((x8 W8t) / (s_x s_w)) + b); also stored as c8 = e4m3(c s_c)
-      Gemm8Args g{};
-      g.A = c->x8; g.B = c->W8t; g.lda = d_p; g.ldb = d_p;
-      g.nbm = (int)(Mp / 256); g.nbn = n_p / 256; g.ktiles = d_p / 128;
-      EpiEnc8 e{};
-      e.c = c->c; e.c8 = c->c8; e.bias = b; e.scal8 = c->scal8; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = n_p / 128;
-      // (streaming form: one L1 partial per workgroup, the rest of the per-tile range zeroed -- as for EpiEnc below)
-      if (gemm8_streams<EpiEnc8>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)(Mp / 128) * (n_p / 128) * 4, s));
-      ev_begin(c, KID_ENC_FWD, s);
-      rc = launch_gemm8(g, e, s);
-      ev_end(c, KID_ENC_FWD, s);
-      if (rc) return rc;
-    }
-    {  // x_hat = bf16((c8 W8^T) / (s_c s_w)), residual, dx_hat
-      Gemm8Args g{};
-      g.A = c->c8; g.B = c->W8; g.lda = n_p; g.ldb = n_p;
-      g.nbm = (int)(Mp / 256); g.nbn = d_p / 256; g.ktiles = n_p / 128;
-      EpiDec<T> e{};
-      e.x = x; e.dxh = c->dxh; e.scal = c->scal; e.sq_part = c->sq_part; e.M = M; e.d = d; e.d_p = d_p; e.nbn = d_p / 128;
-      e.vec_all = (M == Mp && d == d_p && d % 4 == 0 && (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(T))) == 0) ? 1 : 0;
-      e.vscale = c->scal8 + S8_INV_DEC;
-      ev_begin(c, KID_DEC_FWD, s);
-      rc = launch_gemm8(g, e, s);
-      ev_end(c, KID_DEC_FWD, s);
-      if (rc) return rc;
-    }
-    if (need_backward && c->dxhT) {
-      hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)(Mp / 64), d_p / 64), dim3(256), 0, s, c->dxh, c->dxhT, Mp, d_p);
-      hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)(Mp / 64), d_p / 64), dim3(256), 0, s, c->xb_cur, c->xT, Mp, d_p);
-      HIP_TRY(hipGetLastError());
-    }
-    return SAE_OK;
-  }
-  rc = launch_encoder<T>(c, enc_gemm_args(c, c->xb_cur, Mp), M, s);       // c = relu(x W + b)
-  if (rc) return rc;
-  {  // x_hat = c W^T, residual, dx_hat
-    GemmArgs g{};
-    g.A0 = c->c; g.B0 = c->Wb; g.lda = n_p; g.ldb = n_p;
-    g.nbm = (int)(Mp / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
-    g.group_m = 4;       // (gemm.h: GemmArgs::group_m)
-    EpiDec<T> e{};
-    e.x = x; e.dxh = c->dxh; e.scal = c->scal; e.sq_part = c->sq_part; e.M = M; e.d = d; e.d_p = d_p; e.nbn = g.nbn;
-    e.vec_all = (M == Mp && d == d_p && d % 4 == 0 && (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(T))) == 0) ? 1 : 0;
-    ev_begin(c, KID_DEC_FWD, s);
-    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-    ev_end(c, KID_DEC_FWD, s);
-    if (rc) return rc;
-  }
-  if (need_backward && c->dxhT) {
-    // the weight-gradient GEMM's d-side operands K-contiguous: dx_hat^T and x^T, 2 x (M_p x d_p) bf16 read + written (section 4)
-    hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)(Mp / 64), d_p / 64), dim3(256), 0, s, c->dxh, c->dxhT, Mp, d_p);
-    hipLaunchKernelGGL(transpose_bf16_kernel, dim3((unsigned)(Mp / 64), d_p / 64), dim3(256), 0, s, c->xb_cur, c->xT, Mp, d_p);
-    HIP_TRY(hipGetLastError());
+  if (all_wgs > full_wgs) {
+    LDS_ATTR(ragged, 160 * 1024, g_device);
+    a.block_offset = full_wgs;
+    hipLaunchKernelGGL(ragged, dim3(all_wgs - full_wgs), dim3(256), FF_LDS_BYTES, s, a);
   }
   return SAE_OK;
 }
 
+// c = relu(x W + b), x_hat = c W^T, residual and dx_hat in one kernel (fwd_fused2.h; FREUD_FWD=1: fwd_fused.h)
 template <typename T>
-static int fwd_bwd_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool backward) {
-  const int d = c->d, d_p = c->d_p, n_p = c->n_p;
-  const int64_t Mp = round_up(M, c->row_pad);
-  const float alpha = (float)c->cfg.recon_alpha;
-  const double* gs = (backward && c->dp_world > 0) ? c->stats : nullptr;    // data parallel: global normalisers
-  ev_begin(c, KID_STEP_TOTAL, s);
-  int rc = forward_impl<T>(c, x, M, Mp, s, backward);
+static int l1_forward_fused(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s) {
+  FwdFusedArgs a{};
+  a.xb = c->xb_cur; a.x = x; a.Wt = c->Wt; a.bias = c->P + c->nW; a.cnt_part = c->cnt_part; a.c = c->c; a.dxh = c->dxh;
+  a.l1_part = c->l1_part; a.sq_part = c->sq_part; a.M = M; a.d = c->d; a.n_p = c->n_p; a.ntiles = c->n_p / FF_BN;
+  a.c_rows = c->max_rows_p;
+  // diagnostic (debug_flags 65): the full workgroups run the stamping instantiation, stamps into the (unused here) dpre buffer
+  const bool stamp = c->cfg.debug_flags == 65 && M >= FF_BM;
+  if (stamp) a.stamps = reinterpret_cast<unsigned long long*>(c->dpre);
+  FwdFusedKernel full, ragged;
+  if (c->fwd_variant == 2) {               // the second decomposition (fwd_fused2.h)
+    full = stamp ? fwd_fused2_d384_kernel<T, false, true> : fwd_fused2_d384_kernel<T, false>;
+    ragged = fwd_fused2_d384_kernel<T, true>;
+  } else {
+    full = stamp ? fwd_fused_d384_kernel<T, false, true> : fwd_fused_d384_kernel<T, false, false>;
+    ragged = fwd_fused_d384_kernel<T, true, false>;
+  }
+  ev_begin(c, KID_FWD_FUSED, s);
+  const int rc = launch_fwd_fused_pair(full, ragged, a, M, Mp, s);
   if (rc) return rc;
-  // single GPU, fused forward + fused backward in ONE launch: the backward takes alpha/count from the forward's counts itself and
-  // the loss scalars are finalised by reduce_grads_kernel's last block (5 us less between the forward and the backward)
-  const bool fold_finalize = c->use_fused_fwd && c->use_fused_bwd && backward && gs == nullptr && c->bwd_ranges == 1 &&
-                             c->cfg.debug_flags != 78;
-  if (c->use_fused_fwd && !fold_finalize) {  // the fused forward counted the masked entries itself: scal[] and the losses are due now
-    StatsPush push{};
-    if (gs && inline_stats(c)) {       // peer exchange: the statistics travel inside this kernel (no pass over x, no second stream)
-      for (int r = 0; r < c->dp_world; ++r) push.inbox[r] = c->p2p_sig[r] + P2P_SIG_WORDS;
-      push.rank = c->p2p_rank; push.world = c->dp_world; push.epoch = ++c->p2p_epoch_push;
-      push.timeout_ticks = c->p2p_timeout_ticks; push.status = c->p2p_status; push.status_host = c->p2p_status_hostdev; push.gstats_out = c->stats;
-    } else if (gs && c->dist) {
-      HIP_TRY(hipStreamWaitEvent(s, c->ev_stats, 0));      // the summed statistics have arrived
-    }
-    if (push.world > 0) ev_begin(c, KID_STATS_XCHG, s);
-    hipLaunchKernelGGL(finalize_losses_kernel, dim3(1), dim3(1024), 0, s, c->l1_part, (int)(Mp / 128), c->sq_part,
-                       (int)(Mp / 128), c->scal, c->G + c->nparams, M, d, alpha, c->cnt_part, (int)(Mp / 128),
-                       push.world > 0 ? (const double*)nullptr : gs, push);
-    if (push.world > 0) ev_end(c, KID_STATS_XCHG, s);
+  ev_end(c, KID_FWD_FUSED, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// the decoder GEMMs' epilogue: x_hat -> residual, dx_hat and the squared-error partials
+template <typename T>
+static EpiDec<T> dec_epilogue(const sae_ctx* c, const T* x, int64_t M, int64_t Mp) {
+  const int d = c->d, d_p = c->d_p;
+  EpiDec<T> e{};
+  e.x = x; e.dxh = c->dxh; e.scal = c->scal; e.sq_part = c->sq_part; e.M = M; e.d = d; e.d_p = d_p; e.nbn = d_p / 128;
+  e.vec_all = (M == Mp && d == d_p && d % 4 == 0 && (reinterpret_cast<uintptr_t>(x) % (4 * sizeof(T))) == 0) ? 1 : 0;
+  return e;
+}
+
+// encoder and decoder as two GEMMs on e4m3 operands (l1_fp8.h)
+template <typename T>
+static int l1_forward_fp8(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  int rc;
+  {  // c = relu(bf16((x8 W8t) / (s_x s_w)) + b); also stored as c8 = e4m3(c s_c)
+    Gemm8Args g{};
+    g.A = c->x8; g.B = c->W8t; g.lda = d_p; g.ldb = d_p;
+    g.nbm = (int)(Mp / 256); g.nbn = n_p / 256; g.ktiles = d_p / 128;
+    EpiEnc8 e{};
+    e.c = c->c; e.c8 = c->c8; e.bias = c->P + c->nW; e.scal8 = c->scal8; e.l1_part = c->l1_part; e.M = M; e.n_p = n_p; e.nbn = n_p / 128;
+    // (streaming form: one L1 partial per workgroup, the rest of the per-tile range zeroed -- as for EpiEnc in launch_encoder)
+    if (gemm8_streams<EpiEnc8>(g)) HIP_TRY(hipMemsetAsync(c->l1_part, 0, (size_t)(Mp / 128) * (n_p / 128) * 4, s));
+    ev_begin(c, KID_ENC_FWD, s);
+    rc = launch_gemm8(g, e, s);
+    ev_end(c, KID_ENC_FWD, s);
+    if (rc) return rc;
   }
-  bool dw_chunked_any = false;
-  if (backward) {
-    int splits = c->dw_splits;
-    int db_rows = (int)(Mp / 128);
-    bool dw_chunked = false;
-    if (c->use_fused_bwd) {
-      BwdFusedArgs a{};
-      a.dxh = c->dxh; a.xb = c->xb_cur; a.c = c->c; a.Wt = c->Wt; a.scal = c->scal; a.slab = c->slab; a.db_part = c->db_part;
-      a.unscaled = c->use_fused_fwd ? 1 : 0;
-      if (fold_finalize) { a.cnt_part = c->cnt_part; a.n_cnt = (int)(Mp / 128); a.alpha = alpha; a.M = M; a.d = d; }
-      a.n_p = n_p; a.steps_total = (int)(Mp / BF_BM);
-      // diagnostic clock stamps go to the second half of the (unused on this path) dpre buffer
-      a.clk = c->cfg.debug_flags == 66 ? reinterpret_cast<unsigned long long*>(c->dpre) + (1 << 16) : nullptr;
-      // Column-tile ranges (sae_dist_set_overlap; one range otherwise): each range is a launch of its own over ALL rows, split
-      // into enough row ranges to fill the chip; its slabs are reduced and the range's gradient exchanged on the communication
-      // stream while the next range's backward runs.
-      const int nranges = c->bwd_ranges, rtiles = (n_p / BF_BN) / nranges;
-      splits = nranges == 1 ? c->bwd_splits : c->bwd_range_splits;
-      if (splits > a.steps_total) splits = a.steps_total;
-      a.ntiles = rtiles; a.splits = splits;
-      db_rows = splits;
-      const bool balanced = nranges == 1 && c->bal_m > 0 && a.steps_total >= 64;
-      if (balanced) {
-        a.bal_m = c->bal_m;
-        a.bal_q = (a.steps_total + 31) / 32;
-        a.wg_map = c->bal_map;
-      }
-      const bool dp_now = c->dist && c->dp_world > 0;
-      bf16_t* gb = (dp_now && c->payload == SAE_DTYPE_BF16) ? c->Gb : (bf16_t*)nullptr;
-      ev_begin(c, KID_BWD_FUSED, s);
-      LDS_ATTR(bwd_fused_d384_kernel, BF_LDS_BYTES, g_device);
-      for (int r = 0; r < nranges; ++r) {
-        a.tile0 = r * rtiles;
-        hipLaunchKernelGGL(bwd_fused_d384_kernel, dim3(balanced ? c->bal_grid : a.ntiles * a.splits), dim3(256), BF_LDS_BYTES, s, a);
-        if (nranges > 1) {
-          const int c0 = a.tile0 * BF_BN, cols = rtiles * BF_BN;
-          hipLaunchKernelGGL(reduce_grads_range_kernel, dim3(256), dim3(256), 0, s, c->slab, c->nW, splits, c->db_part, db_rows, n_p,
-                             d_p, c0, cols, c->G, c->gn_part + 256 * r, gb);
-          if (dp_now && r + 1 < nranges) fused_exchange(c, r, nranges, c0, cols, false, s);
-        }
-      }
-      ev_end(c, KID_BWD_FUSED, s);
-      HIP_TRY(hipGetLastError());
+  {  // x_hat = bf16((c8 W8^T) / (s_c s_w)), residual, dx_hat
+    Gemm8Args g{};
+    g.A = c->c8; g.B = c->W8; g.lda = n_p; g.ldb = n_p;
+    g.nbm = (int)(Mp / 256); g.nbn = d_p / 256; g.ktiles = n_p / 128;
+    EpiDec<T> e = dec_epilogue(c, x, M, Mp);
+    e.vscale = c->scal8 + S8_INV_DEC;
+    ev_begin(c, KID_DEC_FWD, s);
+    rc = launch_gemm8(g, e, s);
+    ev_end(c, KID_DEC_FWD, s);
+  }
+  return rc;
+}
+
+// encoder and decoder as two bf16 GEMMs
+template <typename T>
+static int l1_forward_bf16(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s) {
+  int rc = launch_encoder<T>(c, enc_gemm_args(c, c->xb_cur, Mp), M, s);       // c = relu(x W + b)
+  if (rc) return rc;
+  // x_hat = c W^T, residual, dx_hat
+  GemmArgs g{};
+  g.A0 = c->c; g.B0 = c->Wb; g.lda = c->n_p; g.ldb = c->n_p;
+  g.nbm = (int)(Mp / 128); g.nbn = c->d_p / 128; g.ktiles0 = g.ktiles = c->n_p / 64; g.splits = 1;
+  g.group_m = 4;       // (gemm.h: GemmArgs::group_m)
+  ev_begin(c, KID_DEC_FWD, s);
+  rc = launch_gemm<OP_ROW, OP_ROW>(g, dec_epilogue(c, x, M, Mp), s);
+  ev_end(c, KID_DEC_FWD, s);
+  return rc;
+}
+
+template <typename T>
+static int forward_impl(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s, bool need_backward) {
+  int rc = l1_prepare(c, x, M, Mp, s, need_backward);
+  if (!rc) rc = c->use_fused_fwd ? l1_forward_fused(c, x, M, Mp, s) : c->fp8 ? l1_forward_fp8(c, x, M, Mp, s) : l1_forward_bf16(c, x, M, Mp, s);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// L1 backward.  The weight gradient dW = dx_hat^T c + x^T dpre takes one of seven launch forms; dw_plan decides once, at the top of
+// the backward, and every later stage (the form's own function, the reduction, the closing announcement) reads the plan.
+// ------------------------------------------------------------------------------------------
+enum DwForm {
+  DW_FUSED,         // fused d = 384 backward (bwd_fused.h), one launch over all columns
+  DW_FUSED_RANGES,  // ... in column-tile ranges, each reduced and exchanged behind its launch (sae_dist_set_overlap)
+  DW_DIRECT,        // one GEMM, whole tiles straight into the gradient, the tiles left over in K pieces through dw_tail
+  DW_UNIFORM,       // one GEMM, uniform split-K through the slabs
+  DW_ROW_CHUNKS,    // row chunks of dW (contiguous ranges of the gradient buffer): gradient-ready hook, host-driven exchange
+  DW_COL_ROUNDS,    // in-engine exchange, d >= 1024: column chunks of one launch round of whole 256x256 tiles each
+  DW_COL_EQUAL      // ... equal column chunks with split-K slabs (shapes the round form does not take)
+};
+struct DwPlan {
+  DwForm form;
+  int splits;               // slabs: split-K factor of the GEMM forms, row ranges of the fused ones
+  int db_rows;              // rows of db_part
+  int chunk;                // ROW_CHUNKS: rows of d_p per launch; COL_ROUNDS: 256-column tiles per chunk; COL_EQUAL: columns per chunk
+  int tail_tiles, tail_pieces;   // DIRECT (gemm_tail_plan)
+  bool staged;              // COL_*: RCCL sums a contiguous staging block (c->col_stage); false: the peer exchange, in place
+  bool balanced;            // FUSED: the balanced row partition (bwd_fused.h)
+  bool exchange;            // the engine's own communicator carries this step's gradient
+  bool slabs_pending;       // a reduce_slabs_kernel over all of dW is still due
+  bool announced_dw;        // dW was already handed to notify_grads / the exchange chunk by chunk
+};
+
+static DwPlan dw_plan(const sae_ctx* c, int64_t Mp) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  DwPlan p{};
+  p.exchange = c->dist && c->dp_world > 0;
+  if (c->use_fused_bwd) {
+    const int steps = (int)(Mp / BF_BM);
+    p.form = c->bwd_ranges == 1 ? DW_FUSED : DW_FUSED_RANGES;
+    p.splits = c->bwd_ranges == 1 ? c->bwd_splits : c->bwd_range_splits;
+    if (p.splits > steps) p.splits = steps;
+    p.db_rows = p.splits;
+    p.balanced = c->bwd_ranges == 1 && c->bal_m > 0 && steps >= 64;
+    return p;
+  }
+  const int ktiles = (int)(2 * Mp / 64);
+  p.db_rows = (int)(Mp / 128);
+  // In-engine exchange, d >= 1024: COLUMN chunks of dW.  Every chunk reads only its own columns of the latent / dpre streams, so
+  // chunking costs no extra HBM traffic -- row chunks re-read both 5.4 GB streams once per chunk: +1.5 ms of the 30 ms C4 step on one
+  // rank.  The peer exchange takes a [d_p x cols] block of the gradient as the strided 2-D segment it is; RCCL sums contiguous
+  // buffers, so each chunk goes into a contiguous staging block, is all-reduced there and copied back into its strided place on the
+  // communication stream (two passes over 52 MB per chunk at C4).
+  if (p.exchange && c->dw_col_chunks > 1) {
+    p.staged = !c->p2p;
+    p.announced_dw = true;
+    // A chunk of floor(256 / (d_p / 256)) tile columns is one round of whole 256x256 tiles: it needs no split-K, writes straight into
+    // the gradient (or the staging block) and costs what the same tiles cost in the plain launch; the columns left over run like the
+    // plain launch's tail.  Equal chunks were 0.78 of a round at C4, bought full with split-K slabs and a reduction pass: +2.8 % on one
+    // rank against +1.5 % (peer exchange) and +1.1 % (RCCL) for rounds (profiles/r04_ab_c4_forcedist_interleaved.txt).
+    const int nbm256 = d_p / 256, per_round = nbm256 > 0 ? 256 / nbm256 : 0;
+    if (d_p % 256 == 0 && n_p % 256 == 0 && per_round >= 1 && n_p / 256 > per_round && c->dw_tail != nullptr && !g_force_gemm128) {
+      p.form = DW_COL_ROUNDS;
+      p.chunk = per_round;
+      p.splits = 1;
     } else {
-      if (c->fp8_bwd) {  // dpre = (bf16((dxh8 W8t^T) / (s_g s_w)) + 1/M) [c > 0]: dx_hat quantised with a scale from its own maximum
-        const int sgrid = (int)((Mp / 4) < 1024 ? (Mp / 4) : 1024);
-        hipLaunchKernelGGL(fp8_x_stats_kernel, dim3(sgrid), dim3(256), 0, s, c->dxh, Mp, d_p, c->x8_part);
-        hipLaunchKernelGGL(fp8_g_scale_kernel, dim3(1), dim3(256), 0, s, c->x8_part, sgrid, c->scal8);
-        const int64_t n8 = Mp * (d_p / 8);
-        hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->dxh, c->dxh8, n8, c->scal8, (int)S8_SG);
-        Gemm8Args g{};
-        g.A = c->dxh8; g.B = c->W8t; g.lda = d_p; g.ldb = d_p;
-        g.nbm = (int)(Mp / 256); g.nbn = n_p / 256; g.ktiles = d_p / 128;
-        EpiDpre8 e{};
-        e.c = c->c; e.dpre = c->dpre; e.db_part = c->db_part; e.scal = c->scal; e.scal8 = c->scal8; e.n_p = n_p;
-        ev_begin(c, KID_DPRE, s);
-        rc = launch_gemm8(g, e, s);
-        ev_end(c, KID_DPRE, s);
-        if (rc) return rc;
-      } else {  // dpre = (dx_hat W + 1/M) [c > 0]
-        GemmArgs g{};
-        g.A0 = c->dxh; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
-        g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
-        EpiDpre e{};
-        e.c = c->c; e.dpre = c->dpre; e.db_part = c->db_part; e.scal = c->scal; e.n_p = n_p;
-        ev_begin(c, KID_DPRE, s);
-        rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-        ev_end(c, KID_DPRE, s);
-        if (rc) return rc;
-      }
-      // dW = dx_hat^T c + x^T dpre   (K = 2 M, split-K partial slabs).  With a gradient-ready hook the GEMM is issued in
-      // row chunks of dW (contiguous ranges of the gradient buffer): each chunk is reduced and announced as soon as it
-      // is enqueued, so its all-reduce runs under the GEMM of the next chunk.
-      // Peer exchange: COLUMN chunks of dW (a [d_p x cols] block of the gradient is a strided 2-D segment, which the exchange
-      // kernel takes as it is): every chunk reads only its own columns of the latent / dpre streams, so chunking costs no
-      // extra HBM traffic -- row chunks (the contiguous ranges RCCL and the host callback need) re-read both 5.4 GB streams
-      // once per chunk: +1.5 ms of the 30 ms C4 step on one rank.
-      // In-engine RCCL (round 4): the same column chunks, each summed over its split-K slabs into a CONTIGUOUS staging block,
-      // all-reduced there and copied back into its strided place on the communication stream (two passes over 52 MB per chunk
-      // at C4 against re-reading two 5.4 GB streams per row chunk).  Host-driven exchange: row chunks (the callback's contract
-      // is a contiguous range of the gradient buffer).
-      // dW = dx_hat^T c + x^T dpre (rows r0.. of d).  Round 5 experiment (FREUD_DW_ROWA=1, off by default): with transposed copies of
-      // the d-side operands (forward_impl) the A operand is row-major -- [d_p][M_p], K = the batch rows contiguous -- and its fragments
-      // come by ds_read_b128 instead of twice as many ds_read_b64_tr_b16.  The stand-alone shape on random dense operands ran 10.6
-      // against 11.7 ms (tools/kbench mode 6); in the engine, on the real latent (half zeros) the k-major x k-major form with its
-      // k-half ring is FASTER: 9.70 against 10.75 ms at C4 (profiles/r05_ab_dw_row_a.txt).  Kept as a switch for that record.
-      auto launch_dw = [&](GemmArgs g, const EpiSlab& e, int r0) -> int {
-        if (c->dxhT) {
-          g.A0 = c->dxhT + (int64_t)r0 * Mp; g.A1 = c->xT + (int64_t)r0 * Mp; g.lda = Mp;
-          return launch_gemm<OP_ROW, OP_KMAJOR>(g, e, s);
-        }
-        return launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, e, s);
-      };
-      const bool col_staged = c->dist && c->dp_world > 0 && !c->p2p && c->dw_col_chunks > 1 && c->cfg.debug_flags != 82;
-      if (col_staged && !c->col_stage) {
-        hipError_t e_ = hipMalloc((void**)&c->col_stage, (size_t)c->nW * 4);
-        if (e_ != hipSuccess) return fail(SAE_ERR_HIP, "staging buffer of the column chunks: %s", hipGetErrorString(e_));
-      }
-      const bool col_chunked = c->dist && c->dp_world > 0 && (c->p2p || col_staged) && c->dw_col_chunks > 1;
-      // Round 4: chunks sized by ROUNDS.  A chunk of floor(256 / (d_p / 256)) tile columns is one round of whole 256x256 tiles --
-      // it needs no split-K, writes straight into the gradient (or the staging block) and costs what the same tiles cost in the
-      // plain launch; the columns left over run like the plain launch's tail (K pieces through the overflow buffer).  Round 3's
-      // four equal chunks were 200 tiles each: 0.78 of a round, bought full with split-K slabs and a reduction pass (+2.8 % on
-      // one rank at C4; now +1.5 % with the peer exchange, +1.1 % with RCCL, section 5).  debug_flags 84 = the equal chunks.
-      const int nbm256 = d_p / 256, per_round = nbm256 > 0 ? 256 / nbm256 : 0;
-      const bool round_chunks = col_chunked && d_p % 256 == 0 && n_p % 256 == 0 && per_round >= 1 && n_p / 256 > per_round &&
-                                c->dw_tail != nullptr && c->cfg.debug_flags != 84 && !g_force_gemm128;
-      if (round_chunks) {
-        ev_begin(c, KID_DW, s);
-        const int nbn256 = n_p / 256;
-        for (int ct0 = 0; ct0 < nbn256;) {
-          const int nct = nbn256 - ct0 >= per_round ? per_round : nbn256 - ct0;
-          const int col0 = ct0 * 256, cols = nct * 256;
-          float* stage = c->p2p ? nullptr : c->col_stage + (int64_t)col0 * d_p;        // contiguous [d_p x cols] block (RCCL)
-          GemmArgs g{};
-          g.A0 = c->dxh; g.B0 = c->c + col0; g.A1 = c->xb_cur; g.B1 = c->dpre + col0; g.lda = d_p; g.ldb = n_p;
-          g.nbm = d_p / 128; g.nbn = cols / 128; g.ktiles0 = (int)(Mp / 64); g.ktiles = 2 * g.ktiles0;
-          g.splits = 1;
-          gemm_tail_plan(nbm256 * nct, g.ktiles, g.tail_tiles, g.tail_pieces);
-          if (nbm256 * nct >= 255) g.tail_tiles = g.tail_pieces = 0;      // (a full chunk: one round, nothing to split)
-          EpiSlab e{};
-          e.slab = c->p2p ? c->G + col0 : stage; e.slab_stride = 0; e.ld = c->p2p ? n_p : cols; e.tail = c->dw_tail;
-          rc = launch_dw(g, e, 0);
-          if (rc) return rc;
-          if (g.tail_tiles > 0)
-            hipLaunchKernelGGL(reduce_tail_kernel, dim3(g.tail_tiles, 16), dim3(256), 0, s, c->dw_tail, e.slab, e.ld, nbm256, nct,
-                               g.tail_tiles, g.tail_pieces);
-          if (c->p2p) exchange_block(c, col0, d_p, cols, n_p, s);
-          else exchange_staged(c, stage, col0, d_p, cols, n_p, s);
-          ct0 += nct;
-        }
-        ev_end(c, KID_DW, s);
-        dw_chunked = dw_chunked_any = true;
-      } else if (col_chunked) {
-        const int cols = n_p / c->dw_col_chunks;
-        ev_begin(c, KID_DW, s);
-        for (int q = 0; q < c->dw_col_chunks; ++q) {
-          const int col0 = q * cols;
-          GemmArgs g{};
-          g.A0 = c->dxh; g.B0 = c->c + col0; g.A1 = c->xb_cur; g.B1 = c->dpre + col0; g.lda = d_p; g.ldb = n_p;
-          g.nbm = d_p / 128; g.nbn = cols / 128; g.ktiles0 = (int)(Mp / 64); g.ktiles = 2 * g.ktiles0;
-          g.splits = c->dw_col_splits > g.ktiles ? g.ktiles : c->dw_col_splits;
-          EpiSlab e{};
-          e.slab = c->slab + col0; e.slab_stride = c->nW; e.ld = n_p;
-          rc = launch_dw(g, e, 0);
-          if (rc) return rc;
-          if (c->p2p) {
-            hipLaunchKernelGGL(reduce_slabs_range_kernel, dim3(512), dim3(256), 0, s, c->slab, c->nW, g.splits, n_p, d_p, col0, cols, c->G,
-                               (int64_t)n_p, col0);
-            exchange_block(c, col0, d_p, cols, n_p, s);
-          } else {
-            float* stage = c->col_stage + (int64_t)q * d_p * cols;
-            hipLaunchKernelGGL(reduce_slabs_range_kernel, dim3(512), dim3(256), 0, s, c->slab, c->nW, g.splits, n_p, d_p, col0, cols, stage,
-                               (int64_t)cols, 0);
-            exchange_staged(c, stage, col0, d_p, cols, n_p, s);
-          }
-        }
-        ev_end(c, KID_DW, s);
-        dw_chunked = dw_chunked_any = true;
-      }
-      const bool chunked = !col_chunked && (c->grad_ready != nullptr || (c->dist && c->dp_world > 0)) && c->dw_chunk_rows < d_p;
-      const int chunk_rows = chunked ? c->dw_chunk_rows : d_p;
-      if (chunked) splits = c->dw_chunk_splits;
-      // one launch, no exchange to feed: whole tiles go straight into the gradient buffer (no slabs, no reduction pass), the
-      // tiles left over after whole rounds of 256 workgroups in K pieces through the small overflow buffer
-      const bool direct = !col_chunked && !chunked && c->dw_tail_tiles != 0 && (int64_t)c->dw_tail_tiles * c->dw_tail_pieces <= 256 &&
-                          2 * Mp / 64 >= 16 * (c->dw_tail_pieces > 0 ? c->dw_tail_pieces : 1);
-      if (!col_chunked) ev_begin(c, KID_DW, s);
-      for (int r0 = 0; r0 < d_p && !col_chunked; r0 += chunk_rows) {
-        const int rows = d_p - r0 < chunk_rows ? d_p - r0 : chunk_rows;
-        GemmArgs g{};
-        g.A0 = c->dxh + r0; g.B0 = c->c; g.A1 = c->xb_cur + r0; g.B1 = c->dpre; g.lda = d_p; g.ldb = n_p;
-        g.nbm = rows / 128; g.nbn = n_p / 128; g.ktiles0 = (int)(Mp / 64); g.ktiles = 2 * g.ktiles0;
-        if (splits > g.ktiles) splits = g.ktiles;
-        g.splits = splits;
-        EpiSlab e{};
-        e.slab = c->slab + (int64_t)r0 * n_p; e.slab_stride = c->nW; e.ld = n_p;
-        if (direct) {
-          g.splits = 1;
-          g.tail_tiles = c->dw_tail_tiles > 0 ? c->dw_tail_tiles : 0;
-          g.tail_pieces = c->dw_tail_tiles > 0 ? c->dw_tail_pieces : 0;
-          e.slab = c->G; e.slab_stride = 0; e.tail = c->dw_tail;
-        }
-        rc = launch_dw(g, e, r0);
-        if (rc) return rc;
-        if (direct && g.tail_tiles > 0)
-          hipLaunchKernelGGL(reduce_tail_kernel, dim3(g.tail_tiles, 16), dim3(256), 0, s, c->dw_tail, c->G, n_p, d_p / 256, n_p / 256,
-                             g.tail_tiles, g.tail_pieces);
-        if (chunked) {
-          const int64_t off4 = (int64_t)r0 * n_p / 4, n4 = (int64_t)rows * n_p / 4;
-          hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab + 4 * off4,
-                             c->G + 4 * off4, n4, c->nW / 4, splits);
-          notify_grads(c, 4 * off4, 4 * n4, s);
-        }
-      }
-      if (!col_chunked) {
-        ev_end(c, KID_DW, s);
-        dw_chunked_any = chunked;
-        dw_chunked = chunked || direct;     // (direct: the gradient is already in place -- no slab reduction; nothing was announced)
-      }
+      p.form = DW_COL_EQUAL;
+      p.chunk = n_p / c->dw_col_chunks;
+      p.splits = c->dw_col_splits > ktiles ? ktiles : c->dw_col_splits;
     }
-    ev_begin(c, KID_REDUCE, s);
-    if (c->use_fused_bwd && c->bwd_ranges > 1) {   // (every range was reduced right behind its launch)
-      c->gn_blocks = 256 * c->bwd_ranges;
-      c->gn_valid = true;
-    } else if (c->use_fused_bwd) {   // one pass: slabs + db partials -> grads, plus the local gradient sum of squares
-      const int64_t nW4 = c->nW / 4, n4 = c->nparams / 4;
-      const int blocks = grid_for(n4, 1024);
-      LossFinalize fin{};
-      if (fold_finalize) {
-        fin.l1_part = c->l1_part; fin.sq_part = c->sq_part; fin.cnt_part = c->cnt_part; fin.n_parts = (int)(Mp / 128);
-        fin.scal = c->scal; fin.metrics = c->G + c->nparams; fin.M = M; fin.d = d; fin.alpha = alpha;
-      }
-      hipLaunchKernelGGL(reduce_grads_kernel, dim3(blocks), dim3(256), 0, s, c->slab, nW4, splits, c->db_part, db_rows, n_p,
-                         c->G, nW4, n4, c->gn_part,
-                         (c->dist && c->dp_world > 0 && c->payload == SAE_DTYPE_BF16) ? c->Gb : (bf16_t*)nullptr, fin,
-                         (c->bwd_ranges == 1 && c->bal_m > 0 && (int)(Mp / BF_BM) >= 64) ? c->bal_m : 0);
-      c->gn_blocks = blocks;
-      c->gn_valid = true;
+    return p;
+  }
+  // With a gradient-ready hook (the host-driven exchange: the callback's contract is a contiguous range of the gradient buffer), or an
+  // in-engine exchange whose shape has no column chunks, the GEMM is issued in row chunks of dW: each chunk is reduced and announced
+  // as soon as it is enqueued, so its all-reduce runs under the GEMM of the next chunk.
+  if ((c->grad_ready != nullptr || p.exchange) && c->dw_chunk_rows < d_p) {
+    p.form = DW_ROW_CHUNKS;
+    p.chunk = c->dw_chunk_rows;
+    p.splits = c->dw_chunk_splits > ktiles ? ktiles : c->dw_chunk_splits;
+    p.announced_dw = true;
+    return p;
+  }
+  // one launch, no exchange to feed: whole tiles go straight into the gradient buffer (no slabs, no reduction pass), the
+  // tiles left over after whole rounds of 256 workgroups in K pieces through the small overflow buffer
+  if (c->dw_tail_tiles != 0 && (int64_t)c->dw_tail_tiles * c->dw_tail_pieces <= 256 &&
+      ktiles >= 16 * (c->dw_tail_pieces > 0 ? c->dw_tail_pieces : 1)) {
+    p.form = DW_DIRECT;
+    p.splits = 1;
+    p.tail_tiles = c->dw_tail_tiles > 0 ? c->dw_tail_tiles : 0;       // (-1: whole rounds, no tail -- sae_create)
+    p.tail_pieces = c->dw_tail_tiles > 0 ? c->dw_tail_pieces : 0;
+    return p;
+  }
+  p.form = DW_UNIFORM;
+  p.splits = c->dw_splits > ktiles ? ktiles : c->dw_splits;
+  p.slabs_pending = true;
+  return p;
+}
+
+// the K = 2 M_p weight-gradient GEMM of rows r0 .. r0 + rows and columns col0 .. col0 + cols of dW (split-K, tail and output: the caller's)
+static GemmArgs dw_gemm_args(const sae_ctx* c, int64_t Mp, int r0, int rows, int col0, int cols) {
+  GemmArgs g{};
+  g.A0 = c->dxh + r0; g.B0 = c->c + col0; g.A1 = c->xb_cur + r0; g.B1 = c->dpre + col0; g.lda = c->d_p; g.ldb = c->n_p;
+  g.nbm = rows / 128; g.nbn = cols / 128; g.ktiles0 = (int)(Mp / 64); g.ktiles = 2 * g.ktiles0;
+  return g;
+}
+
+// a weight-gradient GEMM's output: split-K slabs `stride` floats apart (0: the output itself), tail pieces through `tail` (l1_kernels.h)
+static EpiSlab slab_epilogue(float* slab, int64_t stride, int ld, float* tail = nullptr) {
+  EpiSlab e{};
+  e.slab = slab; e.slab_stride = stride; e.ld = ld; e.tail = tail;
+  return e;
+}
+
+// what both fused forms pass to bwd_fused_d384_kernel (tile0: the range's)
+static BwdFusedArgs bwd_fused_args(const sae_ctx* c, const DwPlan& p, int64_t M, int64_t Mp, bool fold_finalize) {
+  BwdFusedArgs a{};
+  a.dxh = c->dxh; a.xb = c->xb_cur; a.c = c->c; a.Wt = c->Wt; a.scal = c->scal; a.slab = c->slab; a.db_part = c->db_part;
+  a.unscaled = c->use_fused_fwd ? 1 : 0;
+  if (fold_finalize) { a.cnt_part = c->cnt_part; a.n_cnt = (int)(Mp / 128); a.alpha = (float)c->cfg.recon_alpha; a.M = M; a.d = c->d; }
+  a.n_p = c->n_p; a.steps_total = (int)(Mp / BF_BM);
+  // diagnostic clock stamps go to the second half of the (unused on this path) dpre buffer
+  a.clk = c->cfg.debug_flags == 66 ? reinterpret_cast<unsigned long long*>(c->dpre) + (1 << 16) : nullptr;
+  a.ntiles = (c->n_p / BF_BN) / c->bwd_ranges; a.splits = p.splits;
+  if (p.balanced) {
+    a.bal_m = c->bal_m;
+    a.bal_q = (a.steps_total + 31) / 32;
+    a.wg_map = c->bal_map;
+  }
+  return a;
+}
+
+static int dw_fused(sae_ctx* c, const DwPlan& p, int64_t M, int64_t Mp, bool fold_finalize, hipStream_t s) {
+  const BwdFusedArgs a = bwd_fused_args(c, p, M, Mp, fold_finalize);
+  ev_begin(c, KID_BWD_FUSED, s);
+  LDS_ATTR(bwd_fused_d384_kernel, BF_LDS_BYTES, g_device);
+  hipLaunchKernelGGL(bwd_fused_d384_kernel, dim3(p.balanced ? c->bal_grid : a.ntiles * a.splits), dim3(256), BF_LDS_BYTES, s, a);
+  ev_end(c, KID_BWD_FUSED, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// Column-tile ranges: each range is a launch of its own over ALL rows, split into enough row ranges to fill the chip; its slabs are
+// reduced and the range's gradient exchanged on the communication stream while the next range's backward runs.
+static int dw_fused_ranges(sae_ctx* c, const DwPlan& p, int64_t M, int64_t Mp, hipStream_t s) {
+  BwdFusedArgs a = bwd_fused_args(c, p, M, Mp, false);
+  const int nranges = c->bwd_ranges, cols = a.ntiles * BF_BN;
+  bf16_t* gb = (p.exchange && c->payload == SAE_DTYPE_BF16) ? c->Gb : (bf16_t*)nullptr;
+  ev_begin(c, KID_BWD_FUSED, s);
+  LDS_ATTR(bwd_fused_d384_kernel, BF_LDS_BYTES, g_device);
+  for (int r = 0; r < nranges; ++r) {
+    a.tile0 = r * a.ntiles;
+    hipLaunchKernelGGL(bwd_fused_d384_kernel, dim3(a.ntiles * a.splits), dim3(256), BF_LDS_BYTES, s, a);
+    hipLaunchKernelGGL(reduce_grads_range_kernel, dim3(256), dim3(256), 0, s, c->slab, c->nW, p.splits, c->db_part, p.db_rows, c->n_p,
+                       c->d_p, r * cols, cols, c->G, c->gn_part + 256 * r, gb);
+    if (p.exchange && r + 1 < nranges) fused_exchange(c, r, nranges, r * cols, cols, false, s);
+  }
+  ev_end(c, KID_BWD_FUSED, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// dpre = (dx_hat W + 1/M) [c > 0] and the column sums of its row blocks (db_part): the generic backward's first GEMM
+static int l1_dpre(sae_ctx* c, int64_t Mp, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  int rc;
+  if (c->fp8_bwd) {  // dpre = (bf16((dxh8 W8t^T) / (s_g s_w)) + 1/M) [c > 0]: dx_hat quantised with a scale from its own maximum
+    const int sgrid = (int)((Mp / 4) < 1024 ? (Mp / 4) : 1024);
+    hipLaunchKernelGGL(fp8_x_stats_kernel, dim3(sgrid), dim3(256), 0, s, c->dxh, Mp, d_p, c->x8_part);
+    hipLaunchKernelGGL(fp8_g_scale_kernel, dim3(1), dim3(256), 0, s, c->x8_part, sgrid, c->scal8);
+    const int64_t n8 = Mp * (d_p / 8);
+    hipLaunchKernelGGL(fp8_quant_x_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->dxh, c->dxh8, n8, c->scal8, (int)S8_SG);
+    Gemm8Args g{};
+    g.A = c->dxh8; g.B = c->W8t; g.lda = d_p; g.ldb = d_p;
+    g.nbm = (int)(Mp / 256); g.nbn = n_p / 256; g.ktiles = d_p / 128;
+    EpiDpre8 e{};
+    e.c = c->c; e.dpre = c->dpre; e.db_part = c->db_part; e.scal = c->scal; e.scal8 = c->scal8; e.n_p = n_p;
+    ev_begin(c, KID_DPRE, s);
+    rc = launch_gemm8(g, e, s);
+    ev_end(c, KID_DPRE, s);
+  } else {
+    GemmArgs g{};
+    g.A0 = c->dxh; g.B0 = c->Wt; g.lda = d_p; g.ldb = d_p;
+    g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
+    EpiDpre e{};
+    e.c = c->c; e.dpre = c->dpre; e.db_part = c->db_part; e.scal = c->scal; e.n_p = n_p;
+    ev_begin(c, KID_DPRE, s);
+    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+    ev_end(c, KID_DPRE, s);
+  }
+  return rc;
+}
+
+static int dw_direct(sae_ctx* c, const DwPlan& p, int64_t Mp, hipStream_t s) {
+  GemmArgs g = dw_gemm_args(c, Mp, 0, c->d_p, 0, c->n_p);
+  g.splits = 1; g.tail_tiles = p.tail_tiles; g.tail_pieces = p.tail_pieces;
+  ev_begin(c, KID_DW, s);
+  const int rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(c->G, 0, c->n_p, c->dw_tail), s);
+  if (rc) return rc;
+  if (p.tail_tiles > 0)
+    hipLaunchKernelGGL(reduce_tail_kernel, dim3(p.tail_tiles, 16), dim3(256), 0, s, c->dw_tail, c->G, c->n_p, c->d_p / 256, c->n_p / 256,
+                       p.tail_tiles, p.tail_pieces);
+  ev_end(c, KID_DW, s);
+  return SAE_OK;
+}
+
+// split-K partial slabs; the step's reduction sums them (DwPlan::slabs_pending)
+static int dw_uniform(sae_ctx* c, const DwPlan& p, int64_t Mp, hipStream_t s) {
+  GemmArgs g = dw_gemm_args(c, Mp, 0, c->d_p, 0, c->n_p);
+  g.splits = p.splits;
+  ev_begin(c, KID_DW, s);
+  const int rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(c->slab, c->nW, c->n_p), s);
+  if (rc) return rc;
+  ev_end(c, KID_DW, s);
+  return SAE_OK;
+}
+
+static int dw_row_chunks(sae_ctx* c, const DwPlan& p, int64_t Mp, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  ev_begin(c, KID_DW, s);
+  for (int r0 = 0; r0 < d_p; r0 += p.chunk) {
+    const int rows = d_p - r0 < p.chunk ? d_p - r0 : p.chunk;
+    GemmArgs g = dw_gemm_args(c, Mp, r0, rows, 0, n_p);
+    g.splits = p.splits;
+    const int rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(c->slab + (int64_t)r0 * n_p, c->nW, n_p), s);
+    if (rc) return rc;
+    const int64_t off4 = (int64_t)r0 * n_p / 4, n4 = (int64_t)rows * n_p / 4;
+    hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab + 4 * off4, c->G + 4 * off4, n4,
+                       c->nW / 4, p.splits);
+    notify_grads(c, 4 * off4, 4 * n4, s);
+  }
+  ev_end(c, KID_DW, s);
+  return SAE_OK;
+}
+
+// the staging buffer of the column chunks, on first use by a staged form
+static int col_stage_ready(sae_ctx* c, const DwPlan& p) {
+  if (!p.staged || c->col_stage) return SAE_OK;
+  hipError_t e_ = hipMalloc((void**)&c->col_stage, (size_t)c->nW * 4);
+  if (e_ != hipSuccess) return fail(SAE_ERR_HIP, "staging buffer of the column chunks: %s", hipGetErrorString(e_));
+  return SAE_OK;
+}
+
+// the columns left over after whole rounds run like the plain launch's tail (K pieces through the overflow buffer)
+static int dw_col_rounds(sae_ctx* c, const DwPlan& p, int64_t Mp, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p, nbm256 = d_p / 256, nbn256 = n_p / 256;
+  if (const int rc = col_stage_ready(c, p)) return rc;
+  ev_begin(c, KID_DW, s);
+  for (int ct0 = 0; ct0 < nbn256; ct0 += p.chunk) {
+    const int nct = nbn256 - ct0 >= p.chunk ? p.chunk : nbn256 - ct0;
+    const int col0 = ct0 * 256, cols = nct * 256;
+    float* stage = p.staged ? c->col_stage + (int64_t)col0 * d_p : nullptr;        // contiguous [d_p x cols] block (RCCL)
+    GemmArgs g = dw_gemm_args(c, Mp, 0, d_p, col0, cols);
+    g.splits = 1;
+    gemm_tail_plan(nbm256 * nct, g.ktiles, g.tail_tiles, g.tail_pieces);
+    if (nbm256 * nct >= 255) g.tail_tiles = g.tail_pieces = 0;      // (a full chunk: one round, nothing to split)
+    const EpiSlab e = slab_epilogue(p.staged ? stage : c->G + col0, 0, p.staged ? cols : n_p, c->dw_tail);
+    const int rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, e, s);
+    if (rc) return rc;
+    if (g.tail_tiles > 0)
+      hipLaunchKernelGGL(reduce_tail_kernel, dim3(g.tail_tiles, 16), dim3(256), 0, s, c->dw_tail, e.slab, e.ld, nbm256, nct, g.tail_tiles,
+                         g.tail_pieces);
+    if (p.staged) exchange_staged(c, stage, col0, d_p, cols, n_p, s);
+    else exchange_block(c, col0, d_p, cols, n_p, s);
+  }
+  ev_end(c, KID_DW, s);
+  return SAE_OK;
+}
+
+// each chunk summed over its split-K slabs into its place in the gradient (peer exchange) or its staging block (RCCL)
+static int dw_col_equal(sae_ctx* c, const DwPlan& p, int64_t Mp, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p, cols = p.chunk;
+  if (const int rc = col_stage_ready(c, p)) return rc;
+  ev_begin(c, KID_DW, s);
+  for (int col0 = 0; col0 < n_p; col0 += cols) {
+    GemmArgs g = dw_gemm_args(c, Mp, 0, d_p, col0, cols);
+    g.splits = p.splits;
+    const int rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(c->slab + col0, c->nW, n_p), s);
+    if (rc) return rc;
+    if (p.staged) {
+      float* stage = c->col_stage + (int64_t)col0 * d_p;
+      hipLaunchKernelGGL(reduce_slabs_range_kernel, dim3(512), dim3(256), 0, s, c->slab, c->nW, g.splits, n_p, d_p, col0, cols, stage,
+                         (int64_t)cols, 0);
+      exchange_staged(c, stage, col0, d_p, cols, n_p, s);
     } else {
-      const int64_t n4 = c->nW / 4;
-      if (!dw_chunked)
-        hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab, c->G, n4, n4,
-                           splits);
-      hipLaunchKernelGGL(reduce_db_kernel, dim3(n_p / 32), dim3(256), 0, s, c->db_part, c->G + c->nW, db_rows, n_p);
-      c->gn_valid = false;
+      hipLaunchKernelGGL(reduce_slabs_range_kernel, dim3(512), dim3(256), 0, s, c->slab, c->nW, g.splits, n_p, d_p, col0, cols, c->G,
+                         (int64_t)n_p, col0);
+      exchange_block(c, col0, d_p, cols, n_p, s);
     }
-    ev_end(c, KID_REDUCE, s);
   }
-  if (!c->use_fused_fwd)
-    hipLaunchKernelGGL(finalize_losses_kernel, dim3(1), dim3(1024), 0, s, c->l1_part, (int)((Mp / 128) * (n_p / 128)),
-                       c->sq_part, (int)((Mp / 128) * (d_p / 128)), c->scal, c->G + c->nparams, M, d, alpha,
-                       (const float*)nullptr, 0, gs, StatsPush{});
-  if (backward) {   // everything that was not announced chunk by chunk: [dW] | db | loss scalars
-    const int64_t total = c->nparams + SAE_NUM_METRICS;
-    if (c->use_fused_bwd && c->dist && c->dp_world > 0) {      // the last (or only) column range, with the loss scalars
-      const int nr = c->bwd_ranges, cols = n_p / nr;
-      fused_exchange(c, nr - 1, nr, (nr - 1) * cols, cols, true, s);
-    } else if (dw_chunked_any) notify_grads(c, c->nW, total - c->nW, s);
-    else notify_grads(c, 0, total, s);
+  ev_end(c, KID_DW, s);
+  return SAE_OK;
+}
+
+// the fused forward counted the masked entries itself: scal[] and the losses from its partials (unless the backward folds them in)
+static int l1_finalize_fused_fwd(sae_ctx* c, int64_t M, int64_t Mp, const double* gs, hipStream_t s) {
+  StatsPush push{};
+  if (gs && inline_stats(c)) {       // peer exchange: the statistics travel inside this kernel (no pass over x, no second stream)
+    for (int r = 0; r < c->dp_world; ++r) push.inbox[r] = c->p2p_sig[r] + P2P_SIG_WORDS;
+    push.rank = c->p2p_rank; push.world = c->dp_world; push.epoch = ++c->p2p_epoch_push;
+    push.timeout_ticks = c->p2p_timeout_ticks; push.status = c->p2p_status; push.status_host = c->p2p_status_hostdev; push.gstats_out = c->stats;
+  } else if (gs && c->dist) {
+    HIP_TRY(hipStreamWaitEvent(s, c->ev_stats, 0));      // the summed statistics have arrived
   }
+  if (push.world > 0) ev_begin(c, KID_STATS_XCHG, s);
+  hipLaunchKernelGGL(finalize_losses_kernel, dim3(1), dim3(1024), 0, s, c->l1_part, (int)(Mp / 128), c->sq_part,
+                     (int)(Mp / 128), c->scal, c->G + c->nparams, M, c->d, (float)c->cfg.recon_alpha, c->cnt_part, (int)(Mp / 128),
+                     push.world > 0 ? (const double*)nullptr : gs, push);
+  if (push.world > 0) ev_end(c, KID_STATS_XCHG, s);
+  return SAE_OK;
+}
+
+// slabs and bias partials -> the gradient, as far as the plan's form left that to do
+static void l1_reduce_grads(sae_ctx* c, const DwPlan& p, int64_t M, int64_t Mp, bool fold_finalize, hipStream_t s) {
+  ev_begin(c, KID_REDUCE, s);
+  if (p.form == DW_FUSED_RANGES) {   // (every range was reduced right behind its launch)
+    c->gn_blocks = 256 * c->bwd_ranges;
+    c->gn_valid = true;
+  } else if (p.form == DW_FUSED) {   // one pass: slabs + db partials -> grads, plus the local gradient sum of squares
+    const int64_t nW4 = c->nW / 4, n4 = c->nparams / 4;
+    const int blocks = grid_for(n4, 1024);
+    LossFinalize fin{};
+    if (fold_finalize) {
+      fin.l1_part = c->l1_part; fin.sq_part = c->sq_part; fin.cnt_part = c->cnt_part; fin.n_parts = (int)(Mp / 128);
+      fin.scal = c->scal; fin.metrics = c->G + c->nparams; fin.M = M; fin.d = c->d; fin.alpha = (float)c->cfg.recon_alpha;
+    }
+    hipLaunchKernelGGL(reduce_grads_kernel, dim3(blocks), dim3(256), 0, s, c->slab, nW4, p.splits, c->db_part, p.db_rows, c->n_p, c->G, nW4,
+                       n4, c->gn_part, (p.exchange && c->payload == SAE_DTYPE_BF16) ? c->Gb : (bf16_t*)nullptr, fin,
+                       p.balanced ? c->bal_m : 0);
+    c->gn_blocks = blocks;
+    c->gn_valid = true;
+  } else {
+    const int64_t n4 = c->nW / 4;
+    if (p.slabs_pending)
+      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab, c->G, n4, n4, p.splits);
+    hipLaunchKernelGGL(reduce_db_kernel, dim3(c->n_p / 32), dim3(256), 0, s, c->db_part, c->G + c->nW, p.db_rows, c->n_p);
+    c->gn_valid = false;
+  }
+  ev_end(c, KID_REDUCE, s);
+}
+
+// everything that was not announced chunk by chunk: [dW] | db | loss scalars
+static void l1_announce_grads(sae_ctx* c, const DwPlan& p, hipStream_t s) {
+  const int64_t total = c->nparams + SAE_NUM_METRICS;
+  if ((p.form == DW_FUSED || p.form == DW_FUSED_RANGES) && p.exchange) {      // the last (or only) column range, with the loss scalars
+    const int nr = c->bwd_ranges, cols = c->n_p / nr;
+    fused_exchange(c, nr - 1, nr, (nr - 1) * cols, cols, true, s);
+  } else if (p.announced_dw) notify_grads(c, c->nW, total - c->nW, s);
+  else notify_grads(c, 0, total, s);
+}
+
+// data parallel: the global normalisers of a training step's losses (null: this rank's own batch)
+static const double* step_global_stats(const sae_ctx* c, bool backward) { return (backward && c->dp_world > 0) ? c->stats : nullptr; }
+
+// how both step functions end
+static int step_end(sae_ctx* c, int64_t M, int64_t Mp, hipStream_t s) {
   ev_end(c, KID_STEP_TOTAL, s);
   HIP_TRY(hipGetLastError());
   c->last_M = M;
@@ -1825,140 +1913,206 @@ static int fwd_bwd_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool b
   return SAE_OK;
 }
 
+template <typename T>
+static int fwd_bwd_impl(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool backward) {
+  const int64_t Mp = round_up(M, c->row_pad);
+  const double* gs = step_global_stats(c, backward);
+  ev_begin(c, KID_STEP_TOTAL, s);
+  int rc = forward_impl<T>(c, x, M, Mp, s, backward);
+  if (rc) return rc;
+  const DwPlan plan = dw_plan(c, Mp);
+  // single GPU, fused forward + fused backward in ONE launch: the backward takes alpha/count from the forward's counts itself and
+  // the loss scalars are finalised by reduce_grads_kernel's last block (5 us less between the forward and the backward)
+  const bool fold_finalize = c->use_fused_fwd && backward && plan.form == DW_FUSED && gs == nullptr && c->cfg.debug_flags != 78;
+  if (c->use_fused_fwd && !fold_finalize) {
+    rc = l1_finalize_fused_fwd(c, M, Mp, gs, s);
+    if (rc) return rc;
+  }
+  if (backward) {
+    if (plan.form != DW_FUSED && plan.form != DW_FUSED_RANGES) {
+      rc = l1_dpre(c, Mp, s);
+      if (rc) return rc;
+    }
+    switch (plan.form) {
+      case DW_FUSED: rc = dw_fused(c, plan, M, Mp, fold_finalize, s); break;
+      case DW_FUSED_RANGES: rc = dw_fused_ranges(c, plan, M, Mp, s); break;
+      case DW_DIRECT: rc = dw_direct(c, plan, Mp, s); break;
+      case DW_UNIFORM: rc = dw_uniform(c, plan, Mp, s); break;
+      case DW_ROW_CHUNKS: rc = dw_row_chunks(c, plan, Mp, s); break;
+      case DW_COL_ROUNDS: rc = dw_col_rounds(c, plan, Mp, s); break;
+      case DW_COL_EQUAL: rc = dw_col_equal(c, plan, Mp, s); break;
+    }
+    if (rc) return rc;
+    l1_reduce_grads(c, plan, M, Mp, fold_finalize, s);
+  }
+  if (!c->use_fused_fwd)
+    hipLaunchKernelGGL(finalize_losses_kernel, dim3(1), dim3(1024), 0, s, c->l1_part, (int)((Mp / 128) * (c->n_p / 128)), c->sq_part,
+                       (int)((Mp / 128) * (c->d_p / 128)), c->scal, c->G + c->nparams, M, c->d, (float)c->cfg.recon_alpha,
+                       (const float*)nullptr, 0, gs, StatsPush{});
+  if (backward) l1_announce_grads(c, plan, s);
+  return step_end(c, M, Mp, s);
+}
+
 // ------------------------------------------------------------------------------------------
 // TopK variant: one train step's forward + backward (topkautoencoder.py:93-151, train_sae.py:436-448)
 // ------------------------------------------------------------------------------------------
-template <typename T>
-static int topk_fwd_bwd(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool backward) {
-  const int d = c->d, n = c->n, d_p = c->d_p, n_p = c->n_p, k = c->k;
-  const int64_t Mp = round_up(M, 128);
-  const int64_t T_rows = (c->rows_per_file > 0 && M % c->rows_per_file == 0) ? c->rows_per_file : M;
-  const int B = (int)(M / T_rows);
-  const float alpha = (float)c->cfg.auxk_alpha;
-  float* We = c->P;
-  float* be = c->P + c->nW;
-  float* Wd = c->P + c->nW + n_p;
-  float* bd = c->P + 2 * c->nW + n_p;
-  float* gWe = c->G;
-  float* gbe = c->G + c->nW;
-  float* gWd = c->G + c->nW + n_p;
-  float* gbd = c->G + 2 * c->nW + n_p;
-  float* metrics = c->G + c->nparams;
-  float* did_fire = metrics + SAE_NUM_METRICS;
-  const double* gs = (backward && c->dp_world > 0) ? c->stats : nullptr;    // data parallel: global normalisers
-  int rc;
-  ev_begin(c, KID_STEP_TOTAL, s);
+// What the stages of one TopK step share, built once at its top (topk_step_begin).
+struct TopkStep {
+  int64_t M, Mp;
+  int64_t T_rows;          // x is [B][T_rows][d] for the variance of the file means (rows_per_file)
+  int B;
+  float alpha;             // auxk_alpha
+  float *We, *be, *Wd, *bd;             // the flat parameters' parts
+  float *gWe, *gbe, *gWd, *gbd;         // ... and the gradient's
+  float *metrics, *did_fire;
+  const double* gs;        // data parallel: global normalisers
+  bool aux;                // the AuxK branch is "possible": the device gates it on tk[0] > 0
+  bool auxc;               // AuxK as dense GEMMs over the compacted dead latents (topk_aux.h) next to the CSC backward of the main selection
+  bool use_csc;            // the CSC backward (topk_sparse.h), else the dense fallbacks
+  bool write_dense;        // the masked DENSE rows [M x n] are written
+  bool tile_select;        // tile-driven main select (topk_select_tiles_kernel)
+};
 
-  // dead mask from num_frames_since_fired.  Whether the AuxK branch runs (num_dead > 0, topkautoencoder.py:109) is decided
-  // ON THE DEVICE: the aux kernels are always enqueued and exit at once when tk[0] == 0, the weight-gradient GEMM drops its
-  // second K segment through GemmArgs::seg1_gate -- no device->host copy, no stream synchronisation in the step.
+static TopkStep topk_step_begin(sae_ctx* c, int64_t M, bool backward) {
+  const int n_p = c->n_p;
+  TopkStep st{};
+  st.M = M; st.Mp = round_up(M, 128);
+  st.T_rows = (c->rows_per_file > 0 && M % c->rows_per_file == 0) ? c->rows_per_file : M;
+  st.B = (int)(M / st.T_rows);
+  st.alpha = (float)c->cfg.auxk_alpha;
+  st.We = c->P; st.be = c->P + c->nW; st.Wd = c->P + c->nW + n_p; st.bd = c->P + 2 * c->nW + n_p;
+  st.gWe = c->G; st.gbe = c->G + c->nW; st.gWd = c->G + c->nW + n_p; st.gbd = c->G + 2 * c->nW + n_p;
+  st.metrics = c->G + c->nparams; st.did_fire = st.metrics + SAE_NUM_METRICS;
+  st.gs = step_global_stats(c, backward);
+  // Whether the AuxK branch runs (num_dead > 0, topkautoencoder.py:109) is decided ON THE DEVICE: the aux kernels are always enqueued
+  // and exit at once when tk[0] == 0, the weight-gradient GEMM drops its second K segment through GemmArgs::seg1_gate -- no
+  // device->host copy, no stream synchronisation in the step.
   // validate() passes no dead_mask (train_sae.py:168-171): without a backward the AuxK branch is off.
+  st.aux = st.alpha != 0.f && backward;
+  st.auxc = st.aux && c->aux_compact;
+  // Which backward: the CSC one wins by a wide margin while no latent is dead, the dense-GEMM one once the AuxK pass brings d/2 more
+  // entries per row.  Both are correct for any number of dead latents (each gates its AuxK part on the device), so the choice may
+  // rest on a STALE count: the last value of tk[0] that an asynchronous copy happened to land in pinned host memory (this step's
+  // copy is enqueued by topk_prepare and read by some later step; never waited for).
+  st.use_csc = c->topk_csc && backward && (st.auxc || !(st.aux && c->dead_hint[0] > 0));
+  // the dense rows are only written for those who read them: the dense fallbacks and validation / inference
+  st.write_dense = !st.use_csc;
+  // tile-driven main select: when no dense row is wanted, every column is a candidate and k fits (rows it cannot take -- too many
+  // qualifying tiles or candidates -- fall to the register kernel: n_p <= 2048 * 44)
+  st.tile_select = !st.write_dense && c->n == n_p && c->k <= n_p / TSEL_TILE && n_p / TSEL_TILE <= TSEL_MAX_TILES && n_p <= 2048 * 44 &&
+                   c->cfg.debug_flags != 75;
+  return st;
+}
+
+// dead mask from num_frames_since_fired, the bf16 copies of the weights, sae_in = x - b_dec and the variance of x
+template <typename T>
+static int topk_prepare(sae_ctx* c, const TopkStep& st, const T* x, hipStream_t s) {
+  const int d = c->d, n = c->n, d_p = c->d_p, n_p = c->n_p, B = st.B;
+  const int64_t M = st.M, Mp = st.Mp;
   if (c->aux_compact)
-    hipLaunchKernelGGL(dead_compact_kernel, dim3(1), dim3(1024), 0, s, c->nfsf, c->dead, did_fire, n, n_p, c->dead_threshold, d, c->tk,
+    hipLaunchKernelGGL(dead_compact_kernel, dim3(1), dim3(1024), 0, s, c->nfsf, c->dead, st.did_fire, n, n_p, c->dead_threshold, d, c->tk,
                        c->tkf, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits);
   else
-    hipLaunchKernelGGL(dead_mask_kernel, dim3(1), dim3(1024), 0, s, c->nfsf, c->dead, did_fire, n, n_p, c->dead_threshold, d, c->tk,
+    hipLaunchKernelGGL(dead_mask_kernel, dim3(1), dim3(1024), 0, s, c->nfsf, c->dead, st.did_fire, n, n_p, c->dead_threshold, d, c->tk,
                        c->tkf);
-  const bool aux = alpha != 0.f && backward;      // "possible": the device gates it on tk[0] > 0
-  // AuxK as dense GEMMs over the compacted dead latents (topk_aux.h) next to the CSC backward of the main selection
-  const bool auxc = aux && c->aux_compact;
-  // Which backward: the CSC one (topk_sparse.h) wins by a wide margin while no latent is dead, the dense-GEMM one once the
-  // AuxK pass brings d/2 more entries per row.  Both are correct for any number of dead latents (each gates its AuxK part
-  // on the device), so the choice may rest on a STALE count: the last value of tk[0] that an asynchronous copy happened to
-  // land in pinned host memory (this step's copy is enqueued now and read by some later step; never waited for).
-  const bool use_csc = c->topk_csc && backward && (auxc || !(aux && c->dead_hint[0] > 0));
   HIP_TRY(hipMemcpyAsync(c->dead_hint, c->tk, 4, hipMemcpyDeviceToHost, s));
-  // the masked DENSE rows [M x n] are only written for those who read them: the dense fallbacks and validation / inference
-  const bool write_dense = !use_csc;
-  c->dense_valid = write_dense;
-  c->multi_dense_valid = write_dense;
-  // tile-driven main select (topk_select_tiles_kernel): when no dense row is wanted, every column is a candidate and k fits
-  // (rows it cannot take -- too many qualifying tiles or candidates -- fall to the register kernel: n_p <= 2048 * 44)
-  const bool tile_select = !write_dense && n == n_p && k <= n_p / TSEL_TILE && n_p / TSEL_TILE <= TSEL_MAX_TILES && n_p <= 2048 * 44 &&
-                           c->cfg.debug_flags != 75;
-
-  {
-    const int64_t n8 = c->nW / 8;
-    const int grid = grid_for(n8, 4096);
-    if (!c->wb_valid) {        // (a training step's optimizer already wrote the bf16 copies of the weights it updated)
-      hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, s, We, c->We_b, n8);
-      hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, s, Wd, c->Wd_b, n8);
-    }
-    if (auxc) hipLaunchKernelGGL(aux_gather_rows_kernel, dim3(n_p / 4), dim3(256), 0, s, c->Wd_b, c->dead_cols, c->tkd, c->Wdd_b, d_p);
-    const int g2 = grid_for(Mp * (d_p / 8), 4096);
-    if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
-      hipLaunchKernelGGL((topk_prep_x_kernel<T, true>), dim3(g2), dim3(256), 0, s, x, bd, c->xs, M, d, Mp, d_p);
-    else
-      hipLaunchKernelGGL((topk_prep_x_kernel<T, false>), dim3(g2), dim3(256), 0, s, x, bd, c->xs, M, d, Mp, d_p);
-    const int64_t TD = T_rows * d;
-    if (!gs)   // (data parallel: the variance comes from the column statistics summed over the ranks, below)
-    {
-      bool vec = false;
-      if constexpr (std::is_same<T, bf16_t>::value) {
-        if (B <= TV_MAXB && TD % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-          vec = true;
-          if (B <= 32)
-            hipLaunchKernelGGL((total_variance_vec_kernel<32, 8>), dim3((unsigned)((TD + 2047) / 2048)), dim3(256), 0, s, x, B, TD, c->tv_part);
-          else
-            hipLaunchKernelGGL((total_variance_vec_kernel<64, 4>), dim3((unsigned)((TD + 1023) / 1024)), dim3(256), 0, s, x, B, TD, c->tv_part);
-        }
+  c->dense_valid = st.write_dense;
+  c->multi_dense_valid = st.write_dense;
+  const int64_t n8 = c->nW / 8;
+  const int grid = grid_for(n8, 4096);
+  if (!c->wb_valid) {        // (a training step's optimizer already wrote the bf16 copies of the weights it updated)
+    hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, s, st.We, c->We_b, n8);
+    hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid), dim3(256), 0, s, st.Wd, c->Wd_b, n8);
+  }
+  if (st.auxc) hipLaunchKernelGGL(aux_gather_rows_kernel, dim3(n_p / 4), dim3(256), 0, s, c->Wd_b, c->dead_cols, c->tkd, c->Wdd_b, d_p);
+  const int g2 = grid_for(Mp * (d_p / 8), 4096);
+  if (d % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
+    hipLaunchKernelGGL((topk_prep_x_kernel<T, true>), dim3(g2), dim3(256), 0, s, x, st.bd, c->xs, M, d, Mp, d_p);
+  else
+    hipLaunchKernelGGL((topk_prep_x_kernel<T, false>), dim3(g2), dim3(256), 0, s, x, st.bd, c->xs, M, d, Mp, d_p);
+  const int64_t TD = st.T_rows * d;
+  if (!st.gs) {   // (data parallel: the variance comes from the column statistics summed over the ranks, topk_decode)
+    bool vec = false;
+    if constexpr (std::is_same<T, bf16_t>::value) {
+      if (B <= TV_MAXB && TD % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+        vec = true;
+        if (B <= 32)
+          hipLaunchKernelGGL((total_variance_vec_kernel<32, 8>), dim3((unsigned)((TD + 2047) / 2048)), dim3(256), 0, s, x, B, TD, c->tv_part);
+        else
+          hipLaunchKernelGGL((total_variance_vec_kernel<64, 4>), dim3((unsigned)((TD + 1023) / 1024)), dim3(256), 0, s, x, B, TD, c->tv_part);
       }
-      if (!vec) hipLaunchKernelGGL(total_variance_kernel<T>, dim3((unsigned)((TD + 255) / 256)), dim3(256), 0, s, x, B, TD, c->tv_part);
     }
+    if (!vec) hipLaunchKernelGGL(total_variance_kernel<T>, dim3((unsigned)((TD + 255) / 256)), dim3(256), 0, s, x, B, TD, c->tv_part);
   }
-  {  // pre = relu(sae_in We^T + be)
-    GemmArgs g{};
-    g.A0 = c->xs; g.B0 = c->We_b; g.lda = d_p; g.ldb = d_p;
-    g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
-    hipLaunchKernelGGL(round_bias_kernel, dim3((n_p + 255) / 256), dim3(256), 0, s, be, c->be_r, n_p);
-    EpiTopkEnc e{};
-    e.pre = c->pre; e.bias = c->be_r; e.M = M; e.n_p = n_p;
-    e.tmax = c->tile_max;      // (always written: a null test per s_apply call would split the streaming epilogue into basic blocks)
-    ev_begin(c, KID_TK_ENC, s);
-    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-    ev_end(c, KID_TK_ENC, s);
-    if (rc) return rc;
+  return SAE_OK;
+}
+
+// pre = relu(sae_in We^T + be)
+static int topk_encode(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  GemmArgs g{};
+  g.A0 = c->xs; g.B0 = c->We_b; g.lda = d_p; g.ldb = d_p;
+  g.nbm = (int)(st.Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
+  hipLaunchKernelGGL(round_bias_kernel, dim3((n_p + 255) / 256), dim3(256), 0, s, st.be, c->be_r, n_p);
+  EpiTopkEnc e{};
+  e.pre = c->pre; e.bias = c->be_r; e.M = st.M; e.n_p = n_p;
+  e.tmax = c->tile_max;      // (always written: a null test per s_apply call would split the streaming epilogue into basic blocks)
+  ev_begin(c, KID_TK_ENC, s);
+  const int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+  ev_end(c, KID_TK_ENC, s);
+  return rc;
+}
+
+// the key vectors per thread a dictionary of n_p latents needs in topk_select_reg_kernel: 12 or 44; 0 = beyond it (topk_select_kernel)
+static int select_reg_vectors(int n_p) { return n_p <= 2048 * 12 ? 12 : n_p <= 2048 * 44 ? 44 : 0; }
+
+// one general selection over the rows of c->pre (only_flagged: just the rows the tile-driven select left over)
+static void launch_select(sae_ctx* c, const TopkStep& st, bf16_t* dense_out, int* idx_out, bf16_t* vals_out, float* fire,
+                          const unsigned char* dead_mask, const int* k_ptr, int k_fixed, int kcap, const unsigned char* only_flagged,
+                          hipStream_t s) {
+  const int n = c->n, n_p = c->n_p;
+  unsigned short* vo = reinterpret_cast<unsigned short*>(vals_out);
+  const int wd = st.write_dense ? 1 : 0;
+  switch (select_reg_vectors(n_p)) {
+    case 12:
+      hipLaunchKernelGGL(topk_select_reg_kernel<12>, dim3((unsigned)st.Mp), dim3(256), 0, s, c->pre, dense_out, idx_out, fire, dead_mask,
+                         k_ptr, k_fixed, kcap, n, n_p, st.M, vo, wd, only_flagged);
+      break;
+    case 44:
+      hipLaunchKernelGGL(topk_select_reg_kernel<44>, dim3((unsigned)st.Mp), dim3(256), 0, s, c->pre, dense_out, idx_out, fire, dead_mask,
+                         k_ptr, k_fixed, kcap, n, n_p, st.M, vo, wd, only_flagged);
+      break;
+    default:
+      hipLaunchKernelGGL(topk_select_kernel, dim3((unsigned)st.Mp), dim3(256), 0, s, c->pre, dense_out, idx_out, fire, dead_mask, k_ptr,
+                         k_fixed, kcap, n, n_p, st.M, vo, wd);
   }
+}
+
+// the main selection, the 4k one of multi-TopK and the AuxK one over the dead latents
+static int topk_select(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int n = c->n, n_p = c->n_p, k = c->k;
+  const int64_t M = st.M, Mp = st.Mp;
+  // did_fire follows out.encoded.top_indices (train_sae.py:442), which forward() re-binds to the 4k selection when
+  // cfg.multi_topk is set (topkautoencoder.py:135)
+  float* fire_main = c->multi ? (float*)nullptr : st.did_fire;
   ev_begin(c, KID_TK_SELECT, s);
-  {
-    const unsigned char* only_flagged = nullptr;
-    auto launch_select = [&](bf16_t* dense_out, int* idx_out, bf16_t* vals_out, float* fire, const unsigned char* dead_mask,
-                             const int* k_ptr, int k_fixed, int kcap) {
-      unsigned short* vo = reinterpret_cast<unsigned short*>(vals_out);
-      const int wd = write_dense ? 1 : 0;
-      if (n_p <= 2048 * 12)
-        hipLaunchKernelGGL(topk_select_reg_kernel<12>, dim3((unsigned)Mp), dim3(256), 0, s, c->pre, dense_out, idx_out, fire,
-                           dead_mask, k_ptr, k_fixed, kcap, n, n_p, M, vo, wd, only_flagged);
-      else if (n_p <= 2048 * 44)
-        hipLaunchKernelGGL(topk_select_reg_kernel<44>, dim3((unsigned)Mp), dim3(256), 0, s, c->pre, dense_out, idx_out, fire,
-                           dead_mask, k_ptr, k_fixed, kcap, n, n_p, M, vo, wd, only_flagged);
-      else
-        hipLaunchKernelGGL(topk_select_kernel, dim3((unsigned)Mp), dim3(256), 0, s, c->pre, dense_out, idx_out, fire, dead_mask,
-                           k_ptr, k_fixed, kcap, n, n_p, M, vo, wd);
-    };
-    // did_fire follows out.encoded.top_indices (train_sae.py:442), which forward() re-binds to the 4k selection when
-    // cfg.multi_topk is set (topkautoencoder.py:135)
-    if (tile_select) {
-      if (n_p <= 4096 * 8)
-        hipLaunchKernelGGL(topk_select_tiles_kernel<8>, dim3((unsigned)Mp), dim3(256), 0, s, c->pre, c->tile_max, c->top_idx,
-                           reinterpret_cast<unsigned short*>(c->top_vals), c->multi ? (float*)nullptr : did_fire, k, k, n_p, M, c->sel_flag);
-      else
-        hipLaunchKernelGGL(topk_select_tiles_kernel<32>, dim3((unsigned)Mp), dim3(256), 0, s, c->pre, c->tile_max, c->top_idx,
-                           reinterpret_cast<unsigned short*>(c->top_vals), c->multi ? (float*)nullptr : did_fire, k, k, n_p, M, c->sel_flag);
-      only_flagged = c->sel_flag;      // the general kernel below then only takes the rows flagged as left over
-    }
-    launch_select(c->dense, c->top_idx, c->top_vals, c->multi ? (float*)nullptr : did_fire, nullptr, nullptr, k, k);
-    only_flagged = nullptr;
-    if (c->multi) launch_select(c->multi_dense, c->multi_idx, c->multi_vals, did_fire, nullptr, nullptr, c->k4, c->k4);
-    if (auxc) {         // compact masked rows over the dead columns only
-      unsigned short* vo = reinterpret_cast<unsigned short*>(c->aux_vals);
-      if (n_p <= 2048 * 12)
+  if (st.tile_select)
+    hipLaunchKernelGGL(n_p <= 4096 * 8 ? topk_select_tiles_kernel<8> : topk_select_tiles_kernel<32>, dim3((unsigned)Mp), dim3(256), 0, s,
+                       c->pre, c->tile_max, c->top_idx, reinterpret_cast<unsigned short*>(c->top_vals), fire_main, k, k, n_p, M, c->sel_flag);
+  // (after the tile-driven select the general kernel only takes the rows flagged as left over)
+  launch_select(c, st, c->dense, c->top_idx, c->top_vals, fire_main, nullptr, nullptr, k, k, st.tile_select ? c->sel_flag : nullptr, s);
+  if (c->multi) launch_select(c, st, c->multi_dense, c->multi_idx, c->multi_vals, st.did_fire, nullptr, nullptr, c->k4, c->k4, nullptr, s);
+  if (st.auxc) {         // compact masked rows over the dead columns only
+    unsigned short* vo = reinterpret_cast<unsigned short*>(c->aux_vals);
+    switch (select_reg_vectors(n_p)) {
+      case 12:
         hipLaunchKernelGGL((topk_select_reg_kernel<12, true>), dim3((unsigned)Mp), dim3(256), 0, s, c->pre, c->aux_dense,
                            c->aux_idx, (float*)nullptr, c->dead, c->tk + 1, 0, c->k_aux_cap, n, n_p, M, vo, 0,
                            (const unsigned char*)nullptr, c->vec_rank, c->vec_bits, c->tkd, c->dead_cols);
-      else if (n_p <= 2048 * 44) {
-        // dictionaries above 24 576 latents (round 5): copy the dead columns into the compact rows, then the GENERAL select in
-        // place on those rows -- <12> for up to 24 576 dead latents, <44> beyond; the device-side count picks (topk_kernels.h:
+        break;
+      case 44:
+        // dictionaries above 24 576 latents: copy the dead columns into the compact rows, then the GENERAL select in place on
+        // those rows -- <12> for up to 24 576 dead latents, <44> beyond; the device-side count picks (topk_kernels.h:
         // compact_mode).  The one-kernel form needed 44 key vectors per thread: 7.8 ms per step at n = 40 960 with 4000 dead.
         hipLaunchKernelGGL((topk_select_reg_kernel<12, true>), dim3((unsigned)Mp), dim3(256), 0, s, c->pre, c->aux_dense,
                            c->aux_idx, (float*)nullptr, c->dead, c->tk + 1, 0, c->k_aux_cap, n, n_p, M, vo, 0,
@@ -1969,270 +2123,300 @@ static int topk_fwd_bwd(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool b
         hipLaunchKernelGGL((topk_select_reg_kernel<44>), dim3((unsigned)Mp), dim3(256), 0, s, c->aux_dense, c->aux_dense,
                            c->aux_idx, (float*)nullptr, (const unsigned char*)nullptr, c->tk + 1, 0, c->k_aux_cap, n, n_p, M, vo, 1,
                            (const unsigned char*)nullptr, (const int*)nullptr, (const unsigned char*)nullptr, c->tkd, (const int*)nullptr, 2);
-      } else {
+        break;
+      default:
         return fail(SAE_ERR_INVALID, "the compact AuxK path serves dictionaries up to %d latents", 2048 * 44);
-      }
-    } else if (aux) {
-      launch_select(c->aux_dense, c->aux_idx, c->aux_vals, nullptr, c->dead, c->tk + 1, 0, c->k_aux_cap);
     }
+  } else if (st.aux) {
+    launch_select(c, st, c->aux_dense, c->aux_idx, c->aux_vals, nullptr, c->dead, c->tk + 1, 0, c->k_aux_cap, nullptr, s);
   }
   ev_end(c, KID_TK_SELECT, s);
+  return SAE_OK;
+}
+
+// the residuals e = decode(selection) - x of every selection, then the loss scalars
+template <typename T>
+static int topk_decode(sae_ctx* c, const TopkStep& st, const T* x, hipStream_t s) {
+  const int d = c->d, d_p = c->d_p, n_p = c->n_p;
+  const int64_t M = st.M, Mp = st.Mp;
   ev_begin(c, KID_TK_DECODE, s);
-  {
-    auto launch_decode = [&](auto np_tag) {
-      constexpr int NP = decltype(np_tag)::value;
-      hipLaunchKernelGGL((topk_decode_kernel<T, NP>), dim3((unsigned)(Mp / 4)), dim3(256), 0, s, x, c->top_vals, c->top_idx, k, c->Wd_b,
-                         bd, c->e, c->dh, c->e2_part, M, d, d_p, n_p, 0, (const int*)nullptr);
-      if (aux && !auxc)
-        hipLaunchKernelGGL((topk_decode_kernel<T, NP>), dim3((unsigned)(Mp / 4)), dim3(256), 0, s, x, c->aux_vals, c->aux_idx,
-                           c->k_aux_cap, c->Wd_b, bd, c->e, c->dh, c->a2_part, M, d, d_p, n_p, 1, (const int*)c->tk);
-      if (c->multi)     // e_multi = decode(top-4k) - x into its own residual buffer
-        hipLaunchKernelGGL((topk_decode_kernel<T, NP>), dim3((unsigned)(Mp / 4)), dim3(256), 0, s, x, c->multi_vals, c->multi_idx,
-                           c->k4, c->Wd_b, bd, c->em, c->dh, c->m2_part, M, d, d_p, n_p, 0, (const int*)nullptr);
+  with_np(d_p, [&](auto np_tag) {
+    auto decode = [&](const bf16_t* vals, const int* idx, int kcap, float* e_out, float* sq_part, int is_aux, const int* gate) {
+      hipLaunchKernelGGL((topk_decode_kernel<T, decltype(np_tag)::value>), dim3((unsigned)(Mp / 4)), dim3(256), 0, s, x, vals, idx, kcap,
+                         c->Wd_b, st.bd, e_out, c->dh, sq_part, M, d, d_p, n_p, is_aux, gate);
     };
-    with_np(d_p, launch_decode);
-    if (auxc) {   // e_hat = A_aux W_dec[dead] over the compact dead set: K = ND_p (device side), e_hat - e and its squares in the epilogue
-      HIP_TRY(hipMemsetAsync(c->a2_part, 0, (size_t)Mp * 4, s));
-      GemmArgs g{};
-      g.A0 = c->aux_dense; g.B0 = c->Wdd_b; g.lda = n_p; g.ldb = d_p;
-      g.nbm = (int)(Mp / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
-      g.dyn = c->tkd; g.dyn_dim = GEMM_DYN_K;
-      EpiAuxDecode e{};
-      e.e = c->e; e.b_dec = bd; e.dh = c->dh; e.part = c->a2_part; e.M = M; e.d = d; e.d_p = d_p; e.nbn = d_p / 128;
-      rc = launch_gemm<OP_ROW, OP_KMAJOR>(g, e, s);
-      if (rc) return rc;
-    }
+    decode(c->top_vals, c->top_idx, c->k, c->e, c->e2_part, 0, nullptr);
+    if (st.aux && !st.auxc) decode(c->aux_vals, c->aux_idx, c->k_aux_cap, c->e, c->a2_part, 1, c->tk);
+    if (c->multi) decode(c->multi_vals, c->multi_idx, c->k4, c->em, c->m2_part, 0, nullptr);     // e_multi into its own residual buffer
+  });
+  if (st.auxc) {   // e_hat = A_aux W_dec[dead] over the compact dead set: K = ND_p (device side), e_hat - e and its squares in the epilogue
+    HIP_TRY(hipMemsetAsync(c->a2_part, 0, (size_t)Mp * 4, s));
+    GemmArgs g{};
+    g.A0 = c->aux_dense; g.B0 = c->Wdd_b; g.lda = n_p; g.ldb = d_p;
+    g.nbm = (int)(Mp / 128); g.nbn = d_p / 128; g.ktiles0 = g.ktiles = n_p / 64; g.splits = 1;
+    g.dyn = c->tkd; g.dyn_dim = GEMM_DYN_K;
+    EpiAuxDecode e{};
+    e.e = c->e; e.b_dec = st.bd; e.dh = c->dh; e.part = c->a2_part; e.M = M; e.d = d; e.d_p = d_p; e.nbn = d_p / 128;
+    const int rc = launch_gemm<OP_ROW, OP_KMAJOR>(g, e, s);
+    if (rc) return rc;
   }
-  const int64_t TD = T_rows * d;
-  if (gs) {
+  const int64_t TD = st.T_rows * d;
+  if (st.gs) {
     if (c->dist) HIP_TRY(hipStreamWaitEvent(s, c->ev_stats, 0));     // the summed statistics have arrived
-    hipLaunchKernelGGL(dp_topk_tv_kernel, dim3((unsigned)((TD + 255) / 256)), dim3(256), 0, s, gs, TD, c->tv_part);
+    hipLaunchKernelGGL(dp_topk_tv_kernel, dim3((unsigned)((TD + 255) / 256)), dim3(256), 0, s, st.gs, TD, c->tv_part);
   }
   hipLaunchKernelGGL(topk_finalize_kernel, dim3(1), dim3(1024), 0, s, c->tv_part, (int)((TD + 255) / 256), c->e2_part,
-                     aux ? c->a2_part : (const float*)nullptr, c->multi ? c->m2_part : (const float*)nullptr, Mp, M, d, alpha,
-                     c->tk, c->tkf, metrics, (float)n, gs, c->dp_world);
+                     st.aux ? c->a2_part : (const float*)nullptr, c->multi ? c->m2_part : (const float*)nullptr, Mp, M, d, st.alpha,
+                     c->tk, c->tkf, st.metrics, (float)c->n, st.gs, c->dp_world);
   ev_end(c, KID_TK_DECODE, s);
-  if (backward) {
-    const int rpb = 128;
-    const int nrb = (int)((Mp + rpb - 1) / rpb);
-    hipLaunchKernelGGL(topk_de_kernel, dim3((d_p + 255) / 256, nrb), dim3(256), 0, s, c->e, c->dh, c->tkf, c->de_b, c->dh_b,
-                       c->dbd_part, Mp, d_p, rpb, aux ? 1 : 0, c->tk, c->multi ? c->em : (const float*)nullptr, c->dm_b);
-    if (use_csc) {
-      // ---- CSC backward: selection sorted by latent, then d W_dec, d W_enc and d b_enc as gathered row sums (topk_sparse.h)
-      SparsePasses ps{};
-      if (c->multi) { ps.idx[0] = c->multi_idx; ps.vals[0] = c->multi_vals; ps.g[0] = c->dm_b; ps.kcap[0] = c->k4; }
-      if (aux && !auxc) { ps.idx[1] = c->aux_idx; ps.vals[1] = c->aux_vals; ps.g[1] = c->dh_b; ps.kcap[1] = c->k_aux_cap; ps.gated[1] = 1; }
-      ps.idx[2] = c->top_idx; ps.vals[2] = c->top_vals; ps.g[2] = c->de_b; ps.kcap[2] = k;
-      const int nb = (int)((M + CSC_ROWS - 1) / CSC_ROWS);
-      const int nseg = (n_p + CSC_MAX_NP - 1) / CSC_MAX_NP;            // dictionary segments of the counting kernels
-      const int lds = (n_p < CSC_MAX_NP ? n_p : CSC_MAX_NP) * 2;
-      ev_begin(c, KID_TK_DDENSE, s);
-      hipLaunchKernelGGL(csc_count_kernel, dim3(nb, nseg), dim3(64), lds, s, ps, c->tk, M, n_p, c->csc_counts);
-      hipLaunchKernelGGL(csc_scan_blocks_kernel, dim3((n_p + 63) / 64), dim3(1024), 0, s, c->csc_counts, nb, n_p, c->csc_block_off,
-                         c->csc_total);
-      hipLaunchKernelGGL(csc_scan_latents_kernel, dim3(1), dim3(1024), 0, s, c->csc_total, n_p, c->csc_start, c->csc_item_start);
-      HIP_TRY(hipMemsetAsync(c->csc_multi, 0, 16, s));
-      hipLaunchKernelGGL(csc_items_kernel, dim3((n_p + 255) / 256), dim3(256), 0, s, c->csc_item_start, n_p, c->csc_item_latent, c->csc_multi);
-      const int nseg_fill = (n_p + CSC_FILL_NP - 1) / CSC_FILL_NP;     // (32-bit position counters: 16 384 latents per 64 KiB)
-      hipLaunchKernelGGL(csc_fill_kernel, dim3(nb, nseg_fill), dim3(64), (n_p < CSC_FILL_NP ? n_p : CSC_FILL_NP) * 4, s, ps, c->tk, M, n_p,
-                         c->csc_block_off, c->csc_start, c->csc_entries);
-      ev_end(c, KID_TK_DDENSE, s);
-      ev_begin(c, KID_TK_DWD, s);
-      {
-        const unsigned blocks = (unsigned)((c->csc_max_items + SB_WAVES - 1) / SB_WAVES);
-        auto launch_sb = [&](auto np_tag) {
-          constexpr int NP = decltype(np_tag)::value;
-          hipLaunchKernelGGL(sparse_bwd_kernel<NP>, dim3(blocks), dim3(64 * SB_WAVES), 0, s, ps, c->xs, c->Wd_b, c->csc_entries, c->csc_start,
-                             c->csc_item_start, c->csc_item_latent, n_p, c->csc_part, c->csc_pbe, gWd, gWe, gbe, c->db_part);
-        };
-        if (d_p == 384) launch_sb(std::integral_constant<int, 3>{});
-        else if (d_p == 768) launch_sb(std::integral_constant<int, 6>{});
-        else launch_sb(std::integral_constant<int, 10>{});
-      }
-      ev_end(c, KID_TK_DWD, s);
-      ev_begin(c, KID_TK_DWE, s);
-      hipLaunchKernelGGL(sparse_combine_kernel, dim3(4096), dim3(256), 0, s, c->csc_part, c->csc_pbe, c->csc_item_start, n_p,
-                         d_p, gWd, gWe, gbe, c->db_part, c->csc_multi);
-      ev_end(c, KID_TK_DWE, s);
-      HIP_TRY(hipGetLastError());
-      if (auxc) {
-        // ---- AuxK backward over the compact dead set (every launch covers the static maximum and gates itself on the device)
-        ev_begin(c, KID_TK_AUX, s);
-        // launch sizes from the STALE dead count (pinned copy of an earlier step, never waited for) plus a margin: only an
-        // estimate is needed (GemmArgs::grid_hint), the kernels cover whatever the real extent is
-        const int nd_hint = c->dead_hint[0];
-        int ndp_hint = (nd_hint + nd_hint / 4 + 511) & ~255;
-        if (ndp_hint > n_p) ndp_hint = n_p;
-        const bool small_dead = (int64_t)ndp_hint * 8 <= n_p;      // estimated grids (persistent instantiation) only then
-        {   // d A = [selected, > 0] bf16(d e_hat W_dec[dead]^T), column sums
-          GemmArgs g{};
-          g.A0 = c->dh_b; g.B0 = c->Wdd_b; g.lda = d_p; g.ldb = d_p;
-          g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
-          g.dyn = c->tkd; g.dyn_dim = GEMM_DYN_N;
-          g.grid_hint = (int64_t)ndp_hint * 2 <= n_p ? (int)((Mp / 128) * (ndp_hint / 128)) : 0;   // (one exiting workgroup per
-                                                            // missing tile costs more than the persistent loop up to about there)
-          EpiTopkDpre e{};
-          e.sel = c->aux_dense; e.dpre = c->dpre; e.dbe_part = c->aux_dbe_part; e.n_p = n_p; e.accumulate = 0; e.last = 1;
-          rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-          if (rc) return rc;
-        }
-        for (int which = 0; which < 2; ++which) {   // d W_dec[dead] += A_aux^T d e_hat ; d W_enc[dead] += d A^T sae_in
-          GemmArgs g{};
-          g.A0 = which == 0 ? c->aux_dense : c->dpre; g.B0 = which == 0 ? c->dh_b : c->xs; g.lda = n_p; g.ldb = d_p;
-          g.nbm = n_p / 128; g.nbn = d_p / 128; g.ktiles0 = g.ktiles = (int)(Mp / 64);
-          // split-K on the DEVICE from the real dead count (gemm_dyn_splits): a few hundred dead latents are a handful of
-          // output tiles and K = M is long; between dw_splits and what the slab buffer holds
-          g.splits = c->slab_splits > g.ktiles / 8 ? (g.ktiles / 8 > 0 ? g.ktiles / 8 : 1) : c->slab_splits;
-          g.dyn_splits_min = 1;
-          // the launch only has to cover tiles x factor for the factor the device will choose: its maximum over every possible
-          // extent, not the static tile count times the largest factor (a workgroup that starts only to exit costs ~3 us of a
-          // CU: 8 700 of them were a quarter of these GEMMs' time)
-          {
-            const bool big_ = !g_force_gemm128 && g.nbm % 2 == 0 && g.nbn % 2 == 0;
-            const int tl = big_ ? 256 : 128, tn = d_p / tl, tm_max = n_p / tl;
-            int cover = 1;
-            for (int tmm = 1; tmm <= tm_max; ++tmm) {
-              const int need = tmm * tn * gemm_dyn_splits(tmm * tn, 1, g.splits, g.ktiles);
-              if (need > cover) cover = need;
-            }
-            g.grid_cover = cover;
-          }
-          g.dyn = c->tkd; g.dyn_dim = GEMM_DYN_M;
-          const bool big = !g_force_gemm128 && g.nbm % 2 == 0 && g.nbn % 2 == 0;       // launch_gemm's kernel choice
-          const int tile = big ? 256 : 128;
-          g.grid_hint = small_dead ? (ndp_hint / 128) * (d_p / 128) *
-                                         gemm_dyn_splits((ndp_hint / tile) * (d_p / tile), g.dyn_splits_min, g.splits, g.ktiles)
-                                   : 0;                                                                              // (sizing only)
-          EpiSlab e{};
-          e.slab = c->slab; e.slab_stride = c->nW; e.ld = d_p;
-          rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, e, s);
-          if (rc) return rc;
-          hipLaunchKernelGGL(aux_scatter_rows_kernel, dim3(n_p / 4), dim3(256), 0, s, c->slab, c->nW, g.dyn_splits_min, g.splits,
-                             g.ktiles, tile, c->dead_cols, c->tkd, which == 0 ? gWd : gWe, d_p);
-        }
-        hipLaunchKernelGGL(aux_scatter_dbe_kernel, dim3((n_p + 63) / 64), dim3(1024), 0, s, c->aux_dbe_part, (int)(Mp / 128), n_p,
-                           c->dead_cols, c->tkd, c->db_part, gbe);
-        ev_end(c, KID_TK_AUX, s);
-        HIP_TRY(hipGetLastError());
-      }
-      notify_grads(c, c->nW + c->n_p, c->nW, s);                 // d W_dec
-    } else {
-    if (c->topk_sparse_da) {   // dpre only where a latent was selected: k (+ k_aux) gathered dot products per row
-        ev_begin(c, KID_TK_DDENSE, s);
-        HIP_TRY(hipMemsetAsync(c->dpre, 0, (size_t)Mp * n_p * 2, s));
-        HIP_TRY(hipMemsetAsync(c->dbe_fx, 0, (size_t)n_p * 8, s));
-        DactsPasses ps{};
-        if (c->multi) { ps.g[0] = c->dm_b; ps.vals[0] = c->multi_vals; ps.idx[0] = c->multi_idx; ps.kcap[0] = c->k4; }
-        if (aux) { ps.g[1] = c->dh_b; ps.vals[1] = c->aux_vals; ps.idx[1] = c->aux_idx; ps.kcap[1] = c->k_aux_cap; ps.gated[1] = 1; }
-        ps.g[2] = c->de_b; ps.vals[2] = c->top_vals; ps.idx[2] = c->top_idx; ps.kcap[2] = k;
-        auto launch_dacts = [&](auto np_tag) {
-          constexpr int NP = decltype(np_tag)::value;
-          hipLaunchKernelGGL(topk_dacts_kernel<NP>, dim3((unsigned)(Mp / 4)), dim3(256), 0, s, ps, c->Wd_b, c->dpre, c->dbe_fx, M,
-                             n_p, c->tk);
-        };
-        if (d_p == 384) launch_dacts(std::integral_constant<int, 3>{});
-        else if (d_p == 768) launch_dacts(std::integral_constant<int, 6>{});
-        else launch_dacts(std::integral_constant<int, 10>{});
-        ev_end(c, KID_TK_DDENSE, s);
-      } else {  // dpre = [selected] (de W_dec^T)  (+ aux part) as a dense GEMM with a masking epilogue
-        // (A/B and test path only, topk_dense_backward: its second launch is a host decision, so this path reads num_dead back)
-        int num_dead = 0;
-        if (aux) {
-          HIP_TRY(hipMemcpyAsync(&num_dead, c->tk, 4, hipMemcpyDeviceToHost, s));
-          HIP_TRY(hipStreamSynchronize(s));
-        }
-        const bool aux_now = aux && num_dead > 0;
-        GemmArgs g{};
-        g.B0 = c->Wd_b; g.lda = d_p; g.ldb = d_p;
-        g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
-        // passes in autograd's execution order (multi-TopK, AuxK, main); each adds into dpre with one bf16 rounding
-        const bf16_t* gsrc[3] = {c->multi ? c->dm_b : nullptr, aux_now ? c->dh_b : nullptr, c->de_b};
-        const bf16_t* sel[3] = {c->multi_dense, c->aux_dense, c->dense};
-        ev_begin(c, KID_TK_DDENSE, s);
-        bool first = true;
-        rc = SAE_OK;
-        for (int pass = 0; pass < 3 && !rc; ++pass) {
-          if (!gsrc[pass]) continue;
-          g.A0 = gsrc[pass];
-          EpiTopkDpre e{};
-          e.sel = sel[pass]; e.dpre = c->dpre; e.dbe_part = c->db_part; e.n_p = n_p; e.accumulate = first ? 0 : 1; e.last = pass == 2;
-          rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
-          first = false;
-        }
-        ev_end(c, KID_TK_DDENSE, s);
-        if (rc) return rc;
-      }
-      const int splits = c->dw_splits;
-      {  // dW_dec[n][d] = dense^T de (+ aux_dense^T de_hat) (+ multi_dense^T dm as a second launch into its own slabs)
-        GemmArgs g{};
-        g.A0 = c->dense; g.B0 = c->de_b; g.A1 = c->aux_dense; g.B1 = c->dh_b; g.lda = n_p; g.ldb = d_p;
-        g.nbm = n_p / 128; g.nbn = d_p / 128; g.ktiles0 = (int)(Mp / 64); g.ktiles = aux ? 2 * g.ktiles0 : g.ktiles0;
-        g.seg1_gate = aux ? c->tk : nullptr;          // the AuxK pair joins only while latents are dead
-        g.splits = splits > g.ktiles0 ? g.ktiles0 : splits;
-        const bool slabs = g.splits > 1 || c->multi;
-        EpiSlab e{};
-        e.slab = slabs ? c->slab : gWd; e.slab_stride = c->nW; e.ld = d_p;
-        ev_begin(c, KID_TK_DWD, s);
-        rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, e, s);
-        int nslabs = g.splits;
-        if (!rc && c->multi) {
-          GemmArgs g2 = g;
-          g2.A0 = c->multi_dense; g2.B0 = c->dm_b; g2.A1 = nullptr; g2.B1 = nullptr; g2.ktiles = g2.ktiles0; g2.seg1_gate = nullptr;
-          EpiSlab e2 = e;
-          e2.slab = c->slab + (int64_t)g.splits * c->nW;
-          rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g2, e2, s);
-          nslabs = 2 * g.splits;
-        }
-        if (!rc && slabs) {
-          const int64_t n4 = c->nW / 4;
-          hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab, gWd, n4, n4, nslabs);
-        }
-        ev_end(c, KID_TK_DWD, s);
-        if (rc) return rc;
-        notify_grads(c, c->nW + c->n_p, c->nW, s);     // d W_dec is final: its all-reduce runs under the d W_enc GEMM
-      }
-      {  // dW_enc[n][d] = dpre^T sae_in
-        GemmArgs g{};
-        g.A0 = c->dpre; g.B0 = c->xs; g.lda = n_p; g.ldb = d_p;
-        g.nbm = n_p / 128; g.nbn = d_p / 128; g.ktiles0 = g.ktiles = (int)(Mp / 64);
-        g.splits = splits > g.ktiles ? g.ktiles : splits;
-        EpiSlab e{};
-        e.slab = g.splits > 1 ? c->slab : gWe; e.slab_stride = c->nW; e.ld = d_p;
-        ev_begin(c, KID_TK_DWE, s);
-        rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, e, s);
-        if (!rc && g.splits > 1) {
-          const int64_t n4 = c->nW / 4;
-          hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab, gWe, n4, n4, g.splits);
-        }
-        ev_end(c, KID_TK_DWE, s);
-        if (rc) return rc;
-      }
-    }
-    ev_begin(c, KID_REDUCE, s);
-    if (use_csc) {
-      // (d b_enc and its exact copy came out of sparse_combine_kernel)
-    } else if (c->topk_sparse_da)
-      hipLaunchKernelGGL(topk_dbe_from_fx_kernel, dim3((n_p + 255) / 256), dim3(256), 0, s, c->dbe_fx, gbe, c->db_part, n_p);
-    else
-      hipLaunchKernelGGL(reduce_db_kernel, dim3(n_p / 32), dim3(256), 0, s, c->db_part, gbe, (int)(Mp / 128), n_p);
-    // d b_dec also receives -sum_rows(dpre W_enc) through sae_in = x - b_dec; that row sum is a GEMV on d b_enc
-    ev_begin(c, KID_TK_DSAE, s);
-    const int nchunks = (n_p + 63) / 64;
-    hipLaunchKernelGGL(topk_dsae_colsum_kernel, dim3((d_p + 255) / 256, nchunks), dim3(256), 0, s,
-                       (use_csc || c->topk_sparse_da) ? c->db_part : gbe, c->We_b, c->ds_part, n_p, d_p);
-    ev_end(c, KID_TK_DSAE, s);
-    hipLaunchKernelGGL(topk_dbd_kernel, dim3((d_p + 63) / 64), dim3(1024), 0, s, c->dbd_part, nrb, c->ds_part, nchunks, gbd, d_p);
-    ev_end(c, KID_REDUCE, s);
-    notify_grads(c, 0, c->nW + c->n_p, s);                                                     // d W_enc | d b_enc
-    notify_grads(c, 2 * c->nW + c->n_p, c->d_p + SAE_NUM_METRICS + c->n_p, s);                 // d b_dec | scalars | did_fire
-  }
-  ev_end(c, KID_STEP_TOTAL, s);
-  HIP_TRY(hipGetLastError());
-  c->last_M = M;
-  c->last_M_p = Mp;
-  c->metrics_fresh = true;
-  c->prof_tick++;
   return SAE_OK;
+}
+
+constexpr int TK_DE_ROWS = 128;      // rows per block of topk_de_kernel's b_dec partials (dbd_part)
+
+// d e (and d e_hat, d e_multi) in bf16 for the backward's kernels, and the row-block partials of d b_dec
+static void topk_bwd_residuals(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int nrb = (int)((st.Mp + TK_DE_ROWS - 1) / TK_DE_ROWS);
+  hipLaunchKernelGGL(topk_de_kernel, dim3((c->d_p + 255) / 256, nrb), dim3(256), 0, s, c->e, c->dh, c->tkf, c->de_b, c->dh_b, c->dbd_part,
+                     st.Mp, c->d_p, TK_DE_ROWS, st.aux ? 1 : 0, c->tk, c->multi ? c->em : (const float*)nullptr, c->dm_b);
+}
+
+// CSC backward: selection sorted by latent, then d W_dec, d W_enc and d b_enc as gathered row sums (topk_sparse.h)
+static int topk_bwd_csc(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  const int64_t M = st.M;
+  SparsePasses ps{};
+  if (c->multi) { ps.idx[0] = c->multi_idx; ps.vals[0] = c->multi_vals; ps.g[0] = c->dm_b; ps.kcap[0] = c->k4; }
+  if (st.aux && !st.auxc) { ps.idx[1] = c->aux_idx; ps.vals[1] = c->aux_vals; ps.g[1] = c->dh_b; ps.kcap[1] = c->k_aux_cap; ps.gated[1] = 1; }
+  ps.idx[2] = c->top_idx; ps.vals[2] = c->top_vals; ps.g[2] = c->de_b; ps.kcap[2] = c->k;
+  const int nb = (int)((M + CSC_ROWS - 1) / CSC_ROWS);
+  const int nseg = (n_p + CSC_MAX_NP - 1) / CSC_MAX_NP;            // dictionary segments of the counting kernels
+  const int lds = (n_p < CSC_MAX_NP ? n_p : CSC_MAX_NP) * 2;
+  ev_begin(c, KID_TK_DDENSE, s);
+  hipLaunchKernelGGL(csc_count_kernel, dim3(nb, nseg), dim3(64), lds, s, ps, c->tk, M, n_p, c->csc_counts);
+  hipLaunchKernelGGL(csc_scan_blocks_kernel, dim3((n_p + 63) / 64), dim3(1024), 0, s, c->csc_counts, nb, n_p, c->csc_block_off,
+                     c->csc_total);
+  hipLaunchKernelGGL(csc_scan_latents_kernel, dim3(1), dim3(1024), 0, s, c->csc_total, n_p, c->csc_start, c->csc_item_start);
+  HIP_TRY(hipMemsetAsync(c->csc_multi, 0, 16, s));
+  hipLaunchKernelGGL(csc_items_kernel, dim3((n_p + 255) / 256), dim3(256), 0, s, c->csc_item_start, n_p, c->csc_item_latent, c->csc_multi);
+  const int nseg_fill = (n_p + CSC_FILL_NP - 1) / CSC_FILL_NP;     // (32-bit position counters: 16 384 latents per 64 KiB)
+  hipLaunchKernelGGL(csc_fill_kernel, dim3(nb, nseg_fill), dim3(64), (n_p < CSC_FILL_NP ? n_p : CSC_FILL_NP) * 4, s, ps, c->tk, M, n_p,
+                     c->csc_block_off, c->csc_start, c->csc_entries);
+  ev_end(c, KID_TK_DDENSE, s);
+  ev_begin(c, KID_TK_DWD, s);
+  const unsigned blocks = (unsigned)((c->csc_max_items + SB_WAVES - 1) / SB_WAVES);
+  with_np_trained(d_p, [&](auto np_tag) {      // (topk_csc implies topk_sparse_da: d_p is 384, 768 or 1280 -- topk_create)
+    constexpr int NP = decltype(np_tag)::value;
+    hipLaunchKernelGGL(sparse_bwd_kernel<NP>, dim3(blocks), dim3(64 * SB_WAVES), 0, s, ps, c->xs, c->Wd_b, c->csc_entries, c->csc_start,
+                       c->csc_item_start, c->csc_item_latent, n_p, c->csc_part, c->csc_pbe, st.gWd, st.gWe, st.gbe, c->db_part);
+  });
+  ev_end(c, KID_TK_DWD, s);
+  ev_begin(c, KID_TK_DWE, s);
+  hipLaunchKernelGGL(sparse_combine_kernel, dim3(4096), dim3(256), 0, s, c->csc_part, c->csc_pbe, c->csc_item_start, n_p, d_p, st.gWd,
+                     st.gWe, st.gbe, c->db_part, c->csc_multi);
+  ev_end(c, KID_TK_DWE, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// AuxK backward over the compact dead set (every launch covers the static maximum and gates itself on the device)
+static int topk_bwd_aux_compact(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  const int64_t Mp = st.Mp;
+  int rc;
+  ev_begin(c, KID_TK_AUX, s);
+  // launch sizes from the STALE dead count (pinned copy of an earlier step, never waited for) plus a margin: only an
+  // estimate is needed (GemmArgs::grid_hint), the kernels cover whatever the real extent is
+  const int nd_hint = c->dead_hint[0];
+  int ndp_hint = (nd_hint + nd_hint / 4 + 511) & ~255;
+  if (ndp_hint > n_p) ndp_hint = n_p;
+  const bool small_dead = (int64_t)ndp_hint * 8 <= n_p;      // estimated grids (persistent instantiation) only then
+  {   // d A = [selected, > 0] bf16(d e_hat W_dec[dead]^T), column sums
+    GemmArgs g{};
+    g.A0 = c->dh_b; g.B0 = c->Wdd_b; g.lda = d_p; g.ldb = d_p;
+    g.nbm = (int)(Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
+    g.dyn = c->tkd; g.dyn_dim = GEMM_DYN_N;
+    g.grid_hint = (int64_t)ndp_hint * 2 <= n_p ? (int)((Mp / 128) * (ndp_hint / 128)) : 0;   // (one exiting workgroup per
+                                                      // missing tile costs more than the persistent loop up to about there)
+    EpiTopkDpre e{};
+    e.sel = c->aux_dense; e.dpre = c->dpre; e.dbe_part = c->aux_dbe_part; e.n_p = n_p; e.accumulate = 0; e.last = 1;
+    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+    if (rc) return rc;
+  }
+  for (int which = 0; which < 2; ++which) {   // d W_dec[dead] += A_aux^T d e_hat ; d W_enc[dead] += d A^T sae_in
+    GemmArgs g{};
+    g.A0 = which == 0 ? c->aux_dense : c->dpre; g.B0 = which == 0 ? c->dh_b : c->xs; g.lda = n_p; g.ldb = d_p;
+    g.nbm = n_p / 128; g.nbn = d_p / 128; g.ktiles0 = g.ktiles = (int)(Mp / 64);
+    // split-K on the DEVICE from the real dead count (gemm_dyn_splits): a few hundred dead latents are a handful of
+    // output tiles and K = M is long; between dw_splits and what the slab buffer holds
+    g.splits = c->slab_splits > g.ktiles / 8 ? (g.ktiles / 8 > 0 ? g.ktiles / 8 : 1) : c->slab_splits;
+    g.dyn_splits_min = 1;
+    g.dyn = c->tkd; g.dyn_dim = GEMM_DYN_M;
+    const int tile = gemm_tile_edge(g), tn = d_p / tile, tm_max = n_p / tile;
+    // the launch only has to cover tiles x factor for the factor the device will choose: its maximum over every possible
+    // extent, not the static tile count times the largest factor (a workgroup that starts only to exit costs ~3 us of a
+    // CU: 8 700 of them were a quarter of these GEMMs' time)
+    g.grid_cover = 1;
+    for (int tmm = 1; tmm <= tm_max; ++tmm) {
+      const int need = tmm * tn * gemm_dyn_splits(tmm * tn, 1, g.splits, g.ktiles);
+      if (need > g.grid_cover) g.grid_cover = need;
+    }
+    g.grid_hint = small_dead ? (ndp_hint / 128) * (d_p / 128) *
+                                   gemm_dyn_splits((ndp_hint / tile) * (d_p / tile), g.dyn_splits_min, g.splits, g.ktiles)
+                             : 0;                                                                              // (sizing only)
+    rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(c->slab, c->nW, d_p), s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(aux_scatter_rows_kernel, dim3(n_p / 4), dim3(256), 0, s, c->slab, c->nW, g.dyn_splits_min, g.splits,
+                       g.ktiles, tile, c->dead_cols, c->tkd, which == 0 ? st.gWd : st.gWe, d_p);
+  }
+  hipLaunchKernelGGL(aux_scatter_dbe_kernel, dim3((n_p + 63) / 64), dim3(1024), 0, s, c->aux_dbe_part, (int)(Mp / 128), n_p,
+                     c->dead_cols, c->tkd, c->db_part, st.gbe);
+  ev_end(c, KID_TK_AUX, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// dpre only where a latent was selected: k (+ k_aux) gathered dot products per row
+static int topk_dpre_sparse(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int n_p = c->n_p;
+  ev_begin(c, KID_TK_DDENSE, s);
+  HIP_TRY(hipMemsetAsync(c->dpre, 0, (size_t)st.Mp * n_p * 2, s));
+  HIP_TRY(hipMemsetAsync(c->dbe_fx, 0, (size_t)n_p * 8, s));
+  DactsPasses ps{};
+  if (c->multi) { ps.g[0] = c->dm_b; ps.vals[0] = c->multi_vals; ps.idx[0] = c->multi_idx; ps.kcap[0] = c->k4; }
+  if (st.aux) { ps.g[1] = c->dh_b; ps.vals[1] = c->aux_vals; ps.idx[1] = c->aux_idx; ps.kcap[1] = c->k_aux_cap; ps.gated[1] = 1; }
+  ps.g[2] = c->de_b; ps.vals[2] = c->top_vals; ps.idx[2] = c->top_idx; ps.kcap[2] = c->k;
+  with_np_trained(c->d_p, [&](auto np_tag) {      // (topk_sparse_da: d_p is 384, 768 or 1280 -- topk_create)
+    constexpr int NP = decltype(np_tag)::value;
+    hipLaunchKernelGGL(topk_dacts_kernel<NP>, dim3((unsigned)(st.Mp / 4)), dim3(256), 0, s, ps, c->Wd_b, c->dpre, c->dbe_fx, st.M, n_p,
+                       c->tk);
+  });
+  ev_end(c, KID_TK_DDENSE, s);
+  return SAE_OK;
+}
+
+// dpre = [selected] (de W_dec^T)  (+ aux part) as a dense GEMM with a masking epilogue
+// (A/B and test path only, topk_dense_backward: its second launch is a host decision, so this path reads num_dead back)
+static int topk_dpre_gemm(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  int num_dead = 0;
+  if (st.aux) {
+    HIP_TRY(hipMemcpyAsync(&num_dead, c->tk, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  const bool aux_now = st.aux && num_dead > 0;
+  GemmArgs g{};
+  g.B0 = c->Wd_b; g.lda = d_p; g.ldb = d_p;
+  g.nbm = (int)(st.Mp / 128); g.nbn = n_p / 128; g.ktiles0 = g.ktiles = d_p / 64; g.splits = 1;
+  // passes in autograd's execution order (multi-TopK, AuxK, main); each adds into dpre with one bf16 rounding
+  const bf16_t* gsrc[3] = {c->multi ? c->dm_b : nullptr, aux_now ? c->dh_b : nullptr, c->de_b};
+  const bf16_t* sel[3] = {c->multi_dense, c->aux_dense, c->dense};
+  ev_begin(c, KID_TK_DDENSE, s);
+  bool first = true;
+  int rc = SAE_OK;
+  for (int pass = 0; pass < 3 && !rc; ++pass) {
+    if (!gsrc[pass]) continue;
+    g.A0 = gsrc[pass];
+    EpiTopkDpre e{};
+    e.sel = sel[pass]; e.dpre = c->dpre; e.dbe_part = c->db_part; e.n_p = n_p; e.accumulate = first ? 0 : 1; e.last = pass == 2;
+    rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+    first = false;
+  }
+  ev_end(c, KID_TK_DDENSE, s);
+  return rc;
+}
+
+// the dense fallbacks: dpre (sparse or as a GEMM), then both weight gradients as GEMMs over the masked dense rows
+static int topk_bwd_dense(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p, splits = c->dw_splits;
+  const int64_t Mp = st.Mp;
+  int rc = c->topk_sparse_da ? topk_dpre_sparse(c, st, s) : topk_dpre_gemm(c, st, s);
+  if (rc) return rc;
+  {  // dW_dec[n][d] = dense^T de (+ aux_dense^T de_hat) (+ multi_dense^T dm as a second launch into its own slabs)
+    GemmArgs g{};
+    g.A0 = c->dense; g.B0 = c->de_b; g.A1 = c->aux_dense; g.B1 = c->dh_b; g.lda = n_p; g.ldb = d_p;
+    g.nbm = n_p / 128; g.nbn = d_p / 128; g.ktiles0 = (int)(Mp / 64); g.ktiles = st.aux ? 2 * g.ktiles0 : g.ktiles0;
+    g.seg1_gate = st.aux ? c->tk : nullptr;          // the AuxK pair joins only while latents are dead
+    g.splits = splits > g.ktiles0 ? g.ktiles0 : splits;
+    const bool slabs = g.splits > 1 || c->multi;
+    ev_begin(c, KID_TK_DWD, s);
+    rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(slabs ? c->slab : st.gWd, c->nW, d_p), s);
+    int nslabs = g.splits;
+    if (!rc && c->multi) {
+      GemmArgs g2 = g;
+      g2.A0 = c->multi_dense; g2.B0 = c->dm_b; g2.A1 = nullptr; g2.B1 = nullptr; g2.ktiles = g2.ktiles0; g2.seg1_gate = nullptr;
+      rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g2, slab_epilogue(c->slab + (int64_t)g.splits * c->nW, c->nW, d_p), s);
+      nslabs = 2 * g.splits;
+    }
+    if (!rc && slabs) {
+      const int64_t n4 = c->nW / 4;
+      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab, st.gWd, n4, n4, nslabs);
+    }
+    ev_end(c, KID_TK_DWD, s);
+    if (rc) return rc;
+    notify_grads(c, c->nW + c->n_p, c->nW, s);     // d W_dec is final: its all-reduce runs under the d W_enc GEMM
+  }
+  {  // dW_enc[n][d] = dpre^T sae_in
+    GemmArgs g{};
+    g.A0 = c->dpre; g.B0 = c->xs; g.lda = n_p; g.ldb = d_p;
+    g.nbm = n_p / 128; g.nbn = d_p / 128; g.ktiles0 = g.ktiles = (int)(Mp / 64);
+    g.splits = splits > g.ktiles ? g.ktiles : splits;
+    ev_begin(c, KID_TK_DWE, s);
+    rc = launch_gemm<OP_KMAJOR, OP_KMAJOR>(g, slab_epilogue(g.splits > 1 ? c->slab : st.gWe, c->nW, d_p), s);
+    if (!rc && g.splits > 1) {
+      const int64_t n4 = c->nW / 4;
+      hipLaunchKernelGGL(reduce_slabs_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, c->slab, st.gWe, n4, n4, g.splits);
+    }
+    ev_end(c, KID_TK_DWE, s);
+  }
+  return rc;
+}
+
+// d b_enc where the backward left it in partials, d b_dec, and the announcement of everything but d W_dec
+static void topk_bias_grads(sae_ctx* c, const TopkStep& st, hipStream_t s) {
+  const int d_p = c->d_p, n_p = c->n_p;
+  ev_begin(c, KID_REDUCE, s);
+  if (st.use_csc) {
+    // (d b_enc and its exact copy came out of sparse_combine_kernel)
+  } else if (c->topk_sparse_da)
+    hipLaunchKernelGGL(topk_dbe_from_fx_kernel, dim3((n_p + 255) / 256), dim3(256), 0, s, c->dbe_fx, st.gbe, c->db_part, n_p);
+  else
+    hipLaunchKernelGGL(reduce_db_kernel, dim3(n_p / 32), dim3(256), 0, s, c->db_part, st.gbe, (int)(st.Mp / 128), n_p);
+  // d b_dec also receives -sum_rows(dpre W_enc) through sae_in = x - b_dec; that row sum is a GEMV on d b_enc
+  ev_begin(c, KID_TK_DSAE, s);
+  const int nchunks = (n_p + 63) / 64;
+  hipLaunchKernelGGL(topk_dsae_colsum_kernel, dim3((d_p + 255) / 256, nchunks), dim3(256), 0, s,
+                     (st.use_csc || c->topk_sparse_da) ? c->db_part : st.gbe, c->We_b, c->ds_part, n_p, d_p);
+  ev_end(c, KID_TK_DSAE, s);
+  const int nrb = (int)((st.Mp + TK_DE_ROWS - 1) / TK_DE_ROWS);      // (topk_bwd_residuals)
+  hipLaunchKernelGGL(topk_dbd_kernel, dim3((d_p + 63) / 64), dim3(1024), 0, s, c->dbd_part, nrb, c->ds_part, nchunks, st.gbd, d_p);
+  ev_end(c, KID_REDUCE, s);
+  notify_grads(c, 0, c->nW + c->n_p, s);                                                     // d W_enc | d b_enc
+  notify_grads(c, 2 * c->nW + c->n_p, c->d_p + SAE_NUM_METRICS + c->n_p, s);                 // d b_dec | scalars | did_fire
+}
+
+template <typename T>
+static int topk_fwd_bwd(sae_ctx* c, const T* x, int64_t M, hipStream_t s, bool backward) {
+  const TopkStep st = topk_step_begin(c, M, backward);
+  ev_begin(c, KID_STEP_TOTAL, s);
+  int rc = topk_prepare(c, st, x, s);
+  if (!rc) rc = topk_encode(c, st, s);
+  if (!rc) rc = topk_select(c, st, s);
+  if (!rc) rc = topk_decode(c, st, x, s);
+  if (rc) return rc;
+  if (backward) {
+    topk_bwd_residuals(c, st, s);
+    if (st.use_csc) {
+      rc = topk_bwd_csc(c, st, s);
+      if (!rc && st.auxc) rc = topk_bwd_aux_compact(c, st, s);
+      if (!rc) notify_grads(c, c->nW + c->n_p, c->nW, s);                 // d W_dec
+    } else {
+      rc = topk_bwd_dense(c, st, s);
+    }
+    if (rc) return rc;
+    topk_bias_grads(c, st, s);
+  }
+  return step_end(c, st.M, st.Mp, s);
 }
 
 static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dtype, hipStream_t s, bool backward);

@@ -79,6 +79,15 @@ static void with_np(int d_p, F&& f) {
   else f(std::integral_constant<int, 0>{});
 }
 
+// ... and of the two kernels of the TopK backward that exist for the three trained widths only (sparse_bwd_kernel, topk_dacts_kernel):
+// exactly <3>, <6> and <10> -- the caller guarantees d_p in {384, 768, 1280}
+template <class F>
+static void with_np_trained(int d_p, F&& f) {
+  if (d_p == 384) f(std::integral_constant<int, 3>{});
+  else if (d_p == 768) f(std::integral_constant<int, 6>{});
+  else f(std::integral_constant<int, 10>{});
+}
+
 // the entry points' test of a pointer argument against the alignment its kernels need (a null optional pointer passes)
 static bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
@@ -175,9 +184,6 @@ struct sae_ctx {
   bool use_fused_fwd = false;
   int fwd_variant = 2;          // fused forward: 2 = fwd_fused2.h (decoder split along d), 1 = fwd_fused.h (FREUD_FWD=1: A/B, stamps)
   bf16_t *xb = nullptr, *c = nullptr, *dxh = nullptr, *dpre = nullptr;
-  // generic L1 backward (round 5): dx_hat^T and x^T, [d_p][M_p] -- the weight-gradient GEMM's d-side operand K-contiguous, so that its
-  // fragments come by ds_read_b128 instead of twice as many transposing reads (null: the k-major x k-major form)
-  bf16_t *dxhT = nullptr, *xT = nullptr;
   float *slab = nullptr, *db_part = nullptr, *l1_part = nullptr, *sq_part = nullptr, *scal = nullptr;
   double* gn_part = nullptr;
   float* cn_part = nullptr;

@@ -8,12 +8,18 @@
 
 constexpr int G2_PERSIST_STATIC = 512;      // resident workgroups of the big static 256x256 GEMM launches (0: one workgroup per tile)
 
+// The output tile launch_gemm's tile form gives an [nbm x nbn] grid of 128x128 tiles: 256 (gemm256.h) when both output dimensions are
+// multiples of 256, else 128 (gemm.h).  The one statement of that rule: whoever sizes a grid, a split-K factor or a slab layout for a
+// launch_gemm call asks here.
+static int gemm_tile_edge(int nbm, int nbn) { return (!g_force_gemm128 && nbm % 2 == 0 && nbn % 2 == 0) ? 256 : 128; }
+static int gemm_tile_edge(const GemmArgs& g) { return gemm_tile_edge(g.nbm, g.nbn); }
+
 // true: launch_gemm runs this GEMM in the streaming form of gemm256s.h (the K = d GEMMs: row-major x row-major, one K segment,
 // thousands of static output tiles) -- callers that size a per-workgroup output of the functor ask first
 template <int AM, int BM_, class Epi>
 static bool gemm_streams(const GemmArgs& g) {
   if constexpr (!(epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW)) return false;
-  if (g_no_stream || g_force_gemm128 || g.nbm % 2 != 0 || g.nbn % 2 != 0) return false;
+  if (g_no_stream || gemm_tile_edge(g) != 256) return false;
   if (g.ktiles % 2 != 0) return false;                     // (the static-stage K loop walks the K tiles in pairs: gemm256s.h)
   return !g.dyn && g.splits == 1 && g.tail_tiles == 0 && g.ktiles == g.ktiles0 && g.ktiles >= 2 && g.seg1_gate == nullptr && g.lda == g.ldb &&
          (g.nbm / 2) * (g.nbn / 2) >= 4 * G2_PERSIST_STATIC;
@@ -44,7 +50,7 @@ static int launch_gemm(const GemmArgs& g, const Epi& epi, hipStream_t s) {
   if constexpr (epi_stream<Epi>::value && AM == OP_ROW && BM_ == OP_ROW) {
     if (gemm_streams<AM, BM_, Epi>(g)) return launch_gemm_stream(g, epi, s);
   }
-  if (!g_force_gemm128 && g.nbm % 2 == 0 && g.nbn % 2 == 0) {   // both output dimensions are multiples of 256
+  if (gemm_tile_edge(g) == 256) {
     auto kern256 = gemm256_bf16_kernel<AM, BM_, Epi>;
     constexpr bool a3 = epi_deep_a_ring<Epi>::value;     // (gemm256.h: three A slots + two B slots)
     constexpr int lds256 = a3 ? G2_A3_LDS_BYTES : (epi_rounds_first<Epi>::value && G2_BF16_LDS_BYTES > G2_LDS_BYTES) ? G2_BF16_LDS_BYTES : G2_LDS_BYTES;

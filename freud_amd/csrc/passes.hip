@@ -70,7 +70,7 @@ static int file_pass_begin(const FilePassKind& kind, sae_ctx* c, const void* x, 
   return SAE_OK;
 }
 
-// L1: forward_impl's weights preparation and bf16 copy of x, then the GEMM arguments of its encoder -- for the epilogue the pass
+// L1: the training forward's (l1_prepare) weights preparation and bf16 copy of x, then the GEMM arguments of its encoder -- for the epilogue the pass
 // brings (EpiSearch, EpiStats) where the GEMM streams, for file_pass_l1_encode and a reduction of the stored latent where it does not
 template <typename T>
 static GemmArgs file_pass_l1_front(sae_ctx* c, const T* x, int64_t M, hipStream_t s) {
