@@ -24,6 +24,8 @@
 #include "recon.h"
 #include "resample.h"
 #include "input_stats.h"
+#include "input_cov_plan.h"
+#include "input_cov.h"
 
 // ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
 static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
@@ -1308,6 +1310,51 @@ extern "C" int sae_input_median(const void* x, int64_t n_files, int64_t rows_per
     return (int)SAE_OK;
   });
   if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- input covariance (input_cov.h, input_cov_plan.h): the centred scatter of a resident sample, no context
+extern "C" int64_t sae_input_cov_workspace_bytes(int64_t n_files, int64_t rows_per_file, int64_t d) {
+  return input_dims_ok(n_files, rows_per_file, d) ? icv_partial_bytes(icv_plan(n_files, rows_per_file, d)) : -1;
+}
+
+extern "C" int sae_input_cov_plan(int64_t n_files, int64_t rows_per_file, int64_t d, int64_t out[4]) {
+  if (!out) return fail(SAE_ERR_INVALID, "sae_input_cov_plan: null argument");
+  if (!input_dims_ok(n_files, rows_per_file, d))
+    return fail(SAE_ERR_INVALID, "sae_input_cov_plan: n_files=%lld, rows_per_file=%lld or d=%lld out of range", (long long)n_files,
+                (long long)rows_per_file, (long long)d);
+  const IcvPlan p = icv_plan(n_files, rows_per_file, d);
+  out[0] = ICV_TILE;
+  out[1] = p.tiles;
+  out[2] = p.segments;
+  out[3] = p.units_per_seg;
+  return SAE_OK;
+}
+
+extern "C" int sae_input_cov(const void* x, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths,
+                             const double* center, double* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* const fn = "sae_input_cov";
+  if (!x || !out || !workspace) return fail(SAE_ERR_INVALID, "%s: null argument", fn);
+  if (int rc = search_shape_check(n_files, rows_per_file)) return rc;
+  if (d < 1 || d > IN_MAX_D) return fail(SAE_ERR_INVALID, "%s: d=%lld outside [1, %d]", fn, (long long)d, IN_MAX_D);
+  if (x_dtype != SAE_DTYPE_F32 && x_dtype != SAE_DTYPE_F16 && x_dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "unknown x_dtype %d", x_dtype);
+  if (workspace_bytes < sae_input_cov_workspace_bytes(n_files, rows_per_file, d))
+    return fail(SAE_ERR_INVALID, "%s: workspace of %lld bytes < sae_input_cov_workspace_bytes(%lld, %lld, %lld)", fn, (long long)workspace_bytes,
+                (long long)n_files, (long long)rows_per_file, (long long)d);
+  if (misaligned(x, x_dtype == SAE_DTYPE_F32 ? 4 : 2) || misaligned(out, 8) || misaligned(workspace, 8) || misaligned(center, 8))
+    return fail(SAE_ERR_INVALID, "%s: x must be aligned to its element, the centre, the output and the workspace to 8 bytes", fn);
+  hipStream_t s = (hipStream_t)stream;
+  const IcvPlan p = icv_plan(n_files, rows_per_file, d);
+  double* const part = (double*)workspace;
+  int rc = with_x_type(x_dtype, x, [&](auto* xt) {
+    using XT = std::remove_const_t<std::remove_pointer_t<decltype(xt)>>;
+    hipLaunchKernelGGL((icv_tile_kernel<XT>), dim3((unsigned)p.tiles, (unsigned)p.segments), dim3(256), 0, s, xt, (int)rows_per_file, (int)d, p,
+                       lengths, center, part);
+    return (int)SAE_OK;
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(icv_fold_kernel, dim3((unsigned)p.tiles, ICV_TILE * ICV_TILE / 256), dim3(256), 0, s, (const double*)part, p, (int)d, out);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

@@ -140,6 +140,9 @@ _SIGNATURES = {
     "sae_input_stats_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "sae_input_moments": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, _i64, _vp]),
     "sae_input_median": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _dbl, C.c_int, _vp, _vp, _vp, _i64, _vp]),
+    "sae_input_cov_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "sae_input_cov_plan": (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64)]),
+    "sae_input_cov": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sae_findex_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_findex_count": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _vp, _vp, _vp]),
     "sae_findex_fill": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp,
@@ -974,6 +977,35 @@ def input_median(x, start, floor: float, iterations: int, path, objective, works
     ob = _dev("objective", objective, "float64", iterations + 1)
     _check(load().sae_input_median(xp, B, T, d, dt, lp, st, float(floor), iterations, pa, ob, ws, int(workspace.numel()),
                                    _stream_ptr(stream)))
+
+
+# -- input covariance without a context (include/freud_sae.h: sae_input_cov*; freud_amd/input_pca.py) --------------------------------
+def input_cov_workspace_bytes(n_files: int, T: int, d: int) -> int:
+    """Bytes of workspace that input_cov needs for a sample [n_files, T, d]."""
+    nbytes = int(load().sae_input_cov_workspace_bytes(int(n_files), int(T), int(d)))
+    if nbytes < 0:
+        raise EngineError(f"input_cov_workspace_bytes: n_files={n_files}, T={T} or d={d} (1 <= d <= {INPUT_MAX_D}) out of range")
+    return nbytes
+
+
+def input_cov_plan(n_files: int, T: int, d: int) -> dict:
+    """The decomposition input_cov uses for a sample [n_files, T, d]: {"tile", "tiles", "segments", "units_per_segment"}."""
+    out = (_i64 * 4)()
+    _check(load().sae_input_cov_plan(int(n_files), int(T), int(d), out))
+    return dict(zip(("tile", "tiles", "segments", "units_per_segment"), (int(v) for v in out)))
+
+
+def input_cov(x, out, workspace, center=None, lengths=None, stream=None) -> None:
+    """The centred scatter of the sample x [n_files, T, d]: out (float64 CUDA [d, d]) = sum_k a_k a_k^T, a_k = double(x_k) - center
+    over the counted frames (center: float64 CUDA [d] or None = zeros), not divided by N.  workspace: a uint8 CUDA tensor of >=
+    input_cov_workspace_bytes(n_files, T, d).  Asynchronous."""
+    x, xp, B, T, d, dt, lp = _files_args(x, "input_cov", lengths)
+    if d > INPUT_MAX_D:
+        raise EngineError(f"input_cov: d={d} > {INPUT_MAX_D}")
+    ws = _dev("workspace", workspace, "uint8", input_cov_workspace_bytes(B, T, d), at_least=True)
+    o = _dev("out", out, "float64", d * d)
+    c = _dev("center", center, "float64", d) if center is not None else None
+    _check(load().sae_input_cov(xp, B, T, d, dt, lp, c, o, ws, int(workspace.numel()), _stream_ptr(stream)))
 
 
 # -- feature index (include/freud_sae.h: sae_findex_*; freud_amd/feature_index.py) ---------------------------------------------------

@@ -92,14 +92,16 @@ def check_input_stats_args(files, iterations, device_budget_bytes=DEFAULT_BUDGET
         raise ValueError(f"device_budget_bytes={device_budget_bytes} must be >= 1")
 
 
-def check_budget(n_files: int, T: int, d: int, itemsize: int, device_budget_bytes: int) -> None:
-    """A resident sample of n_files x T x d elements must fit the budget; the refusal names the largest `files` that does."""
+def check_budget(n_files: int, T: int, d: int, itemsize: int, device_budget_bytes: int, extra_bytes: int = 0) -> None:
+    """A resident sample of n_files x T x d elements (and extra_bytes of outputs and workspace beside it) must fit the budget; the
+    refusal names the largest `files` that does."""
     per_file = int(T) * int(d) * int(itemsize)
-    if int(n_files) * per_file > int(device_budget_bytes):
-        fits = int(device_budget_bytes) // per_file
+    if int(n_files) * per_file + int(extra_bytes) > int(device_budget_bytes):
+        fits = max(0, int(device_budget_bytes) - int(extra_bytes)) // per_file
         hint = f"files={fits} is the most that fits" if fits >= 1 else "not even one file fits"
+        beside = f" beside {int(extra_bytes)} bytes of output and workspace" if extra_bytes else ""
         raise ValueError(f"a resident sample of {n_files} files x {T} frames x d={d} ({itemsize} bytes each) takes "
-                         f"{int(n_files) * per_file} bytes, over device_budget_bytes={int(device_budget_bytes)}: {hint}")
+                         f"{int(n_files) * per_file} bytes{beside}, over device_budget_bytes={int(device_budget_bytes)}: {hint}")
 
 
 def derive(n_files: int, d: int, moments: np.ndarray, path: np.ndarray, objective: np.ndarray) -> InputStats:
@@ -146,24 +148,22 @@ def sample_statistics(x, lengths=None, iterations: int = DEFAULT_ITERATIONS):
         return moments, path.cpu().numpy(), obj.cpu().numpy()
 
 
-@keep_rng
-def input_statistics(data_path: str, layer_name: str, *, files: int = DEFAULT_FILES, lengths=None, iterations: int = DEFAULT_ITERATIONS,
-                     device_budget_bytes: int = DEFAULT_BUDGET) -> InputStats:
-    """The statistics of the first `files` files of a shard directory (fewer where it holds fewer).  lengths: frames per file for
-    those files.  The sample is loaded once and stays in device memory: one over device_budget_bytes is refused before the device is
-    touched.  The caller's global torch RNG is left as it was."""
+def load_resident_sample(data_path: str, layer_name: str, files: int, lengths, device_budget_bytes: int, what: str, extra_bytes=None):
+    """The first `files` files of a shard directory, loaded once into device memory -> (the FilePass, x [n_files, T, d] on its device
+    in the shards' dtype, the trimmed lengths as an int32 tensor there or None).  Every refusal that needs no device -- an empty
+    directory, d > MAX_D, a sample (plus extra_bytes(n_files, T, d), where given) over the budget, the lengths' rules -- comes before
+    the device is touched."""
     import torch
     from .loader import MemoryMappedActivationsDataset
 
-    check_input_stats_args(files, iterations, device_budget_bytes)
     ds = MemoryMappedActivationsDataset(data_path, layer_name, int(files))
     if len(ds) == 0:
         raise ValueError(f"{data_path}: no files")
     T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
     if d > MAX_D:
-        raise ValueError(f"the shards hold d={d}; the input statistics serve d <= {MAX_D}")
-    check_budget(len(ds), T, d, ds.mmap.dtype.itemsize, device_budget_bytes)
-    fp = FilePass(None, data_path, layer_name, what="input statistics", lengths=lengths, subset_size=int(files), max_frames=2 ** 31 - 1)
+        raise ValueError(f"the shards hold d={d}; the {what} serve{'' if what.endswith('s') else 's'} d <= {MAX_D}")
+    check_budget(len(ds), T, d, ds.mmap.dtype.itemsize, device_budget_bytes, extra_bytes(len(ds), T, d) if extra_bytes else 0)
+    fp = FilePass(None, data_path, layer_name, what=what, lengths=lengths, subset_size=int(files), max_frames=2 ** 31 - 1)
     with torch.cuda.device(fp.device):
         sample = None
         for x, file0, nb, _lb in fp:
@@ -171,6 +171,20 @@ def input_statistics(data_path: str, layer_name: str, *, files: int = DEFAULT_FI
                 sample = torch.empty((fp.n_total, fp.T, fp.d), dtype=x.dtype, device=fp.device)
             sample[file0:file0 + nb].copy_(x)
         lens = torch.from_numpy(fp._lens).to(fp.device) if fp._lens is not None else None
+    return fp, sample, lens
+
+
+@keep_rng
+def input_statistics(data_path: str, layer_name: str, *, files: int = DEFAULT_FILES, lengths=None, iterations: int = DEFAULT_ITERATIONS,
+                     device_budget_bytes: int = DEFAULT_BUDGET) -> InputStats:
+    """The statistics of the first `files` files of a shard directory (fewer where it holds fewer).  lengths: frames per file for
+    those files.  The sample is loaded once and stays in device memory: one over device_budget_bytes is refused before the device is
+    touched.  The caller's global torch RNG is left as it was."""
+    import torch
+
+    check_input_stats_args(files, iterations, device_budget_bytes)
+    fp, sample, lens = load_resident_sample(data_path, layer_name, files, lengths, device_budget_bytes, "input statistics")
+    with torch.cuda.device(fp.device):
         moments, path, objective = sample_statistics(sample, lens, int(iterations))
     stats = derive(fp.n_total, fp.d, moments, path, objective)
     fp.check_counted(stats.n_frames)

@@ -899,6 +899,29 @@ int sae_input_median(const void* x_dev, int64_t n_files, int64_t rows_per_file, 
                      const double* start_dev, double floor, int iterations, double* path_dev, double* objective_dev, void* workspace_dev,
                      int64_t workspace_bytes, void* stream);
 
+/* ---- Input covariance: the centred scatter of the same sample, the matrix whose diagonal sae_input_moments gives
+ * (freud_amd/input_pca.py; kernels: freud_amd/csrc/input_cov.h, the decomposition: freud_amd/csrc/input_cov_plan.h).  Context-free;
+ * x_dev, lengths_dev, the counted frames, N and the limits are those of sae_input_moments.
+ *
+ * The rule.  The operand of a counted frame k, column i is a_ki = double(x_ki) - c_i with c = center_dev (double [d]; NULL = zeros: the
+ * raw second moment): the conversion is exact and the subtraction rounds once.  A frame that is not counted contributes a zero
+ * operand, not 0 - c_i.  out_dev, double [d][d]: S_ij = sum_k a_ki a_kj, accumulated in fp64 (every product fused into its add),
+ * NOT divided by N; the whole matrix is written and the lower triangle is the bit-for-bit mirror of the upper.
+ *
+ * The work splits into the output tiles on or above the diagonal and into segments, fixed runs of consecutive 256-frame units; a
+ * workgroup adds its segment's frames in ascending order and a second kernel adds a tile's segments in ascending order.  So S is a
+ * function of (x, lengths, c) alone, not of the grid, the device's size, the stream or what the workspace held; no atomics; two calls
+ * give the same bytes.
+ * sae_input_cov_workspace_bytes: the segments' partials (-1: arguments out of range), at most 64 MiB; 8-byte aligned.
+ * sae_input_cov_plan: out[4] = the tile edge | the tiles computed | the segments | the units per segment: functions of
+ *   (n_files, rows_per_file, d) alone.
+ * sae_input_cov: asynchronous on `stream`, no host synchronisation.  Null x / out / workspace, a shape, d or dtype out of range, a
+ *   short or misaligned workspace: SAE_ERR_INVALID before anything is enqueued. */
+int64_t sae_input_cov_workspace_bytes(int64_t n_files, int64_t rows_per_file, int64_t d);
+int sae_input_cov_plan(int64_t n_files, int64_t rows_per_file, int64_t d, int64_t out[4]);
+int sae_input_cov(const void* x_dev, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths_dev,
+                  const double* center_dev, double* out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order; 14 = the multi-TopK pass's d (decoder output) [M][d] of the last training forward, as
