@@ -72,6 +72,7 @@ CL_H void cl_collect_serial(const uint16_t* row_bits, int64_t n, int K, float* v
 // ---- kernels.  Workgroups of CL_THREADS stride over the rows; entries live in LDS and a bitonic sort puts them in slot order, so
 // the compaction order (LDS counters) never shows: the selected set is exact and its order total -- two runs give the same bytes.
 // Row statistics stay in thread 0's registers until the workgroup is done: six integer atomics per workgroup, not per row.
+// row_nnz (or null): the number of active latents of every row, for the sparsity frontier (frontier.h).
 #define CL_THREADS 256
 #define CL_COLS_PER_IT (8 * CL_THREADS)   // one 16-byte load per thread
 
@@ -185,7 +186,7 @@ __device__ __forceinline__ void cl_find_bin(const uint32_t* hist, uint32_t need,
 template <typename IdxT>
 __global__ __launch_bounds__(CL_THREADS) void collect_l1_kernel(const unsigned short* __restrict__ lat, int64_t ld, int n, int64_t M, int K,
                                                                 float* __restrict__ vals, IdxT* __restrict__ idx,
-                                                                unsigned long long* __restrict__ stats) {
+                                                                unsigned long long* __restrict__ stats, uint32_t* __restrict__ row_nnz) {
   __shared__ uint64_t ent[CL_MAX_K];
   __shared__ uint64_t inact_mask[CL_MAX_K / 64];     // bit c: column c < K is inactive
   __shared__ uint32_t hist[256];
@@ -342,6 +343,7 @@ __global__ __launch_bounds__(CL_THREADS) void collect_l1_kernel(const unsigned s
 
     if (tid == 0) {
       const uint32_t stored = nnz < (uint32_t)K ? nnz : (uint32_t)K;
+      if (row_nnz) row_nnz[r] = nnz;
       st_rows += 1;
       st_stored += stored;
       st_dropped += nnz - stored;
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(CL_THREADS) void collect_l1_kernel(const unsigned s
 template <typename IdxT>
 __global__ __launch_bounds__(CL_THREADS) void collect_topk_kernel(const int* __restrict__ sel_idx, const unsigned short* __restrict__ sel_vals,
                                                                   int k, int64_t M, int K, float* __restrict__ vals, IdxT* __restrict__ idx,
-                                                                  unsigned long long* __restrict__ stats) {
+                                                                  unsigned long long* __restrict__ stats, uint32_t* __restrict__ row_nnz) {
   __shared__ uint64_t ent_all[4 * CL_MAX_K];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   uint64_t* ent = ent_all + wave * CL_MAX_K;
@@ -390,6 +392,7 @@ __global__ __launch_bounds__(CL_THREADS) void collect_topk_kernel(const int* __r
       cl_write_slots<IdxT>(ent, K, lane, 64, vals + r * K, idx + r * K);
       if (lane == 0) {
         const uint32_t stored = nnz < (uint32_t)K ? nnz : (uint32_t)K;
+        if (row_nnz) row_nnz[r] = nnz;
         const uint32_t cut = nnz > stored ? cl_entry_bits(ent[K]) : 0u;        // (nnz > K: K < k, the entry exists)
         st_rows += 1;
         st_stored += stored;

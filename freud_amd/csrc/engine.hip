@@ -75,7 +75,8 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "topk_dsaein_colsum", "topk_auxk_backward", "dp_exchange", "dp_stats_exchange",
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
-                                              "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing"};
+                                              "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing",
+                                              "frontier_sort", "frontier_walk", "frontier_fold"};
 
 // fused d = 384 L1 path with the peer exchange: the batch statistics are exchanged inside finalize_losses_kernel (StatsPush)
 // (FREUD_DP_STATS=stream: the statistics leave the critical path instead -- a pass over x and their exchange on the communication stream
@@ -286,7 +287,7 @@ extern "C" void sae_destroy(sae_ctx* c) {
                   c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
                   c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
                   c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->hs_fmax, c->mn_w, c->rc_buf};
+                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->hs_fmax, c->mn_w, c->rc_buf, c->fr_buf};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (c->dead_hint) (void)hipHostFree(c->dead_hint);

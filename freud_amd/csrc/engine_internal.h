@@ -130,6 +130,9 @@ enum KernelId {
   KID_RECON_ATTR_STREAM,   // ... the same bracket when the attribution GEMM ran in the streaming form (gemm256s.h)
   KID_COLLECT,         // feature collection (collect.h): the row collect kernel of sae_collect_files after the encoder
   KID_TIMING,          // feature timing (timing.h): every kernel of sae_timing_files after the encoder
+  KID_FRONTIER_SORT,   // sparsity frontier (frontier.h): the collect kernels into scratch, the walk alone, the dimension sums + the fold
+  KID_FRONTIER_WALK,
+  KID_FRONTIER_FOLD,
   KID_COUNT
 };
 constexpr int EV_RING = 64;
@@ -141,7 +144,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER };
 
 // A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
 // of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
@@ -161,8 +164,9 @@ static const FilePassKind kReconPass = {"sae_recon_files", "build the reconstruc
 static const FilePassKind kCollectPass = {"sae_collect_files", "collect the features in a bf16 context", "collect", SAE_COLLECT_IDX32, LAST_COLLECT, "a feature collection"};
 static const FilePassKind kTimingPass = {"sae_timing_files", "time the features in a bf16 context", "timing", SAE_TIMING_ONE_CHUNK, LAST_TIMING, "a feature timing pass"};
 static const FilePassKind kResamplePass = {"sae_resample_files", "resample in a bf16 context", "resample", 0, LAST_RESAMPLE, "a resampling pass"};
+static const FilePassKind kFrontierPass = {"sae_frontier_files", "build the sparsity frontier in a bf16 context", "frontier", 0, LAST_FRONTIER, "a sparsity frontier pass"};
 static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
-                                                  &kTimingPass, &kResamplePass};
+                                                  &kTimingPass, &kResamplePass, &kFrontierPass};
 
 struct sae_ctx {
   sae_config cfg;
@@ -323,6 +327,7 @@ struct sae_ctx {
   int64_t hs_files = 0;         // its files: the largest n_files asked for so far
   float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
   float* rc_buf = nullptr;      // sae_recon_files scratch (recon.h): x_hat / r, the slabs, the row and dimension partials, TopK's p
+  char* fr_buf = nullptr;       // sae_frontier_files scratch (frontier.h): the slots, the row records and the partials
   int64_t e32_rows = 0;
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;

@@ -22,6 +22,7 @@
 #include "manip.h"
 #include "dict_match.h"
 #include "recon.h"
+#include "frontier.h"
 #include "resample.h"
 #include "input_stats.h"
 #include "input_cov_plan.h"
@@ -902,15 +903,17 @@ static_assert(SAE_COLLECT_IDX32 == CL_IDX32 && SAE_COLLECT_MAX_K == CL_MAX_K, "f
 // 4 workgroups of 256 threads per CU), collect_topk_kernel 32 KiB of LDS (5 per CU); 256 CUs
 constexpr int COLLECT_L1_WGS = 256 * 4, COLLECT_TOPK_WGS = 256 * 5;
 
+// row_nnz (or null): every row's number of active latents, for sae_frontier_files
 template <typename IdxT>
-static void collect_launch(sae_ctx* c, int64_t M, int K, float* values, IdxT* indices, int64_t* stats, hipStream_t s) {
+static void collect_launch(sae_ctx* c, int64_t M, int K, float* values, IdxT* indices, int64_t* stats, hipStream_t s,
+                           uint32_t* row_nnz = nullptr) {
   unsigned long long* st = reinterpret_cast<unsigned long long*>(stats);
   if (c->topk)
     hipLaunchKernelGGL(collect_topk_kernel<IdxT>, dim3(grid_for(M, COLLECT_TOPK_WGS, 4)), dim3(CL_THREADS), 0, s, c->top_idx,
-                       (const unsigned short*)c->top_vals, c->k, M, K, values, indices, st);
+                       (const unsigned short*)c->top_vals, c->k, M, K, values, indices, st, row_nnz);
   else
     hipLaunchKernelGGL(collect_l1_kernel<IdxT>, dim3(grid_for(M, COLLECT_L1_WGS, 1)), dim3(CL_THREADS), 0, s, (const unsigned short*)c->c,
-                       (int64_t)c->n_p, c->n, M, K, values, indices, st);
+                       (int64_t)c->n_p, c->n, M, K, values, indices, st, row_nnz);
 }
 
 extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, int K, int flags,
@@ -932,6 +935,121 @@ extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int
   ev_end(c, KID_COLLECT, s);
   HIP_TRY(hipGetLastError());
   file_pass_end(kCollectPass, c);
+  return SAE_OK;
+}
+
+// ---- sparsity frontier (frontier.h): the squared error of every counted frame at every latent budget 0 .. K -- the slots of
+// sae_collect_files into context scratch, one walk of them per row, the fold into the caller's block
+static_assert(SAE_FRONTIER_MAX_K == FR_MAX_K && SAE_FRONTIER_MAX_TAU == FR_MAX_TAU && FR_MAX_K <= CL_MAX_K && FR_UNIT % 4 == 0,
+              "freud_sae.h, frontier.h and collect.h disagree");
+
+struct FrontierScratch {        // c->fr_buf carved up
+  float* vals;                  // [max_rows][kcap] the slots, kcap = min(FR_MAX_K, k or n)
+  int* idx;
+  int64_t* cstats;              // [8] the collect kernels' totals (not reported)
+  uint32_t *row_nnz, *rowinfo;  // [max_rows]
+  unsigned short* bud;          // [max_rows][FR_MAX_TAU]
+  float *part, *dimpart;        // [units][FR_PART_LD], [128-row blocks][2][d_p]
+  int64_t bytes;
+};
+
+static FrontierScratch frontier_scratch(const sae_ctx* c) {
+  const int64_t rows = c->cfg.max_rows, kcap = std::min<int64_t>(FR_MAX_K, c->topk ? c->k : c->n);
+  const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
+  char* p = c->fr_buf;
+  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
+  FrontierScratch f;
+  f.vals = (float*)take(rows * kcap * 4);
+  f.idx = (int*)take(rows * kcap * 4);
+  f.cstats = (int64_t*)take(64);
+  f.row_nnz = (uint32_t*)take(rows * 4);
+  f.rowinfo = (uint32_t*)take(rows * 4);
+  f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
+  f.part = (float*)take(units * FR_PART_LD * 4);
+  f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
+  f.bytes = p - c->fr_buf;
+  return f;
+}
+
+static int frontier_ensure(sae_ctx* c) {
+  if (c->fr_buf) return SAE_OK;
+  const int64_t bytes = frontier_scratch(c).bytes;        // (offsets from a null base: only their differences are used)
+  HIP_TRY(hipMalloc((void**)&c->fr_buf, (size_t)bytes));
+  HIP_TRY(hipMemset(frontier_scratch(c).cstats, 0, 64));       // (the collect kernels add to it on every call; it is never read)
+  return SAE_OK;
+}
+
+static FrOut frontier_out(void* block, int n_tau, int K, int d) {
+  char* b = (char*)block;
+  FrOut o;
+  o.n_frames = (unsigned long long*)(b + SAE_FRONTIER_N_FRAMES(n_tau, K, d));
+  o.rows_cut = (unsigned long long*)(b + SAE_FRONTIER_ROWS_CUT(n_tau, K, d));
+  o.active_cut = (unsigned long long*)(b + SAE_FRONTIER_ACTIVE_CUT(n_tau, K, d));
+  o.sse = (double*)(b + SAE_FRONTIER_SSE(n_tau, K, d));
+  o.sx = (double*)(b + SAE_FRONTIER_SUM_X(n_tau, K, d));
+  o.sxx = (double*)(b + SAE_FRONTIER_SUM_X_SQ(n_tau, K, d));
+  o.budget = (unsigned long long*)(b + SAE_FRONTIER_BUDGET(n_tau, K, d));
+  return o;
+}
+
+template <typename T>
+static int frontier_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const FrOut& o,
+                         hipStream_t s) {
+  const FrontierScratch f = frontier_scratch(c);
+  ev_begin(c, KID_FRONTIER_SORT, s);
+  collect_launch(c, M, K, f.vals, f.idx, f.cstats, s, f.row_nnz);
+  ev_end(c, KID_FRONTIER_SORT, s);
+
+  // the operand rows [n_p][d_p] and the bias: L1 -- the transposed copy of the normalised bf16 W, no bias; TopK -- W_dec and b_dec
+  const bf16_t* W = c->topk ? c->Wd_b : c->Wt;
+  const float* b = c->topk ? c->P + 2 * c->nW + c->n_p : nullptr;
+  const float inv_T = 1.0f / (float)Trows;
+  const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT);
+  ev_begin(c, KID_FRONTIER_WALK, s);
+  with_np(c->d_p, [&](auto np_tag) {
+    constexpr int NP = decltype(np_tag)::value;
+    hipLaunchKernelGGL((frontier_walk_kernel<T, NP>), dim3((unsigned)n_units), dim3(256), 0, s, x, b, f.vals, f.idx, f.row_nnz, K, W, M, Trows,
+                       inv_T, lengths, c->d, c->d_p, c->n_p, tau, f.part, f.rowinfo, f.bud);
+  });
+  ev_end(c, KID_FRONTIER_WALK, s);
+
+  ev_begin(c, KID_FRONTIER_FOLD, s);
+  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
+  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, inv_T, lengths, c->d,
+                     c->d_p, f.dimpart);
+  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
+  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
+  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (tau.n + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
+                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, tau.n, o, nb_s, nb_dim, n_chunks);
+  ev_end(c, KID_FRONTIER_FOLD, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_frontier_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                                  int K, const float* thresholds, int n_tau, int flags, void* block, void* stream) {
+  int64_t M;
+  if (int rc = file_pass_begin(kFrontierPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (misaligned(block, 8)) return fail(SAE_ERR_INVALID, "the frontier block must be 8-byte aligned");
+  const int k_max = std::min(c->topk ? c->k : c->n, (int)SAE_FRONTIER_MAX_K);
+  if (K < 1 || K > k_max)
+    return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max, c->topk ? "min(the context's k, SAE_FRONTIER_MAX_K)" : "min(n_dict, SAE_FRONTIER_MAX_K)");
+  if (n_tau < 0 || n_tau > SAE_FRONTIER_MAX_TAU) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, SAE_FRONTIER_MAX_TAU);
+  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
+  FrTau tau{};
+  tau.n = n_tau;
+  for (int t = 0; t < n_tau; ++t) {
+    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
+    tau.t[t] = thresholds[t];
+  }
+  if (c->d_p > FR_MAX_D) return fail(SAE_ERR_INVALID, "sae_frontier_files: the walk serves d_model <= %d", FR_MAX_D);
+  if (c->topk && c->k > CL_MAX_K) return fail(SAE_ERR_INVALID, "sae_frontier_files: k=%d > %d", c->k, CL_MAX_K);
+  if (int rc = frontier_ensure(c)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
+  const FrOut o = frontier_out(block, n_tau, K, c->d);
+  if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return frontier_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, s); })) return rc;
+  file_pass_end(kFrontierPass, c);
   return SAE_OK;
 }
 

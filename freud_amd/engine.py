@@ -133,6 +133,7 @@ _SIGNATURES = {
                                        _vp, _vp, _vp, _vp]),
     "sae_recon_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_collect_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "sae_frontier_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _fptr, C.c_int, C.c_int, _vp, _vp]),
     "sae_resample_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_resample_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_resample_select": (C.c_int, [_vp, _i64, _vp, _i64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -205,6 +206,7 @@ TIMING_ONE_CHUNK = 1                                                # include/fr
 TIMING_MAX_BINS, TIMING_MAX_BRIDGE, TIMING_MAX_ROWS = 111, 15, 65535  # include/freud_sae.h: SAE_TIMING_MAX_*; freud_amd/csrc/timing_bins.h: TB_MAX_ROWS
 COLLECT_IDX32 = 1                                                   # include/freud_sae.h: SAE_COLLECT_IDX32
 COLLECT_MAX_K = 1024                                                # include/freud_sae.h: SAE_COLLECT_MAX_K
+FRONTIER_MAX_K, FRONTIER_MAX_TAU = 256, 8                           # include/freud_sae.h: SAE_FRONTIER_MAX_K / SAE_FRONTIER_MAX_TAU
 FINDEX_IDX32 = 1                                                    # include/freud_sae.h: SAE_FINDEX_IDX32
 FINDEX_NSTATS = 8                                                   # include/freud_sae.h: SAE_FINDEX_NSTATS
 FINDEX_STAT_NAMES = ("slots", "zero_slots", "out_of_range", "posted")
@@ -236,6 +238,14 @@ def recon_layout(n: int, d: int) -> dict:
             "sum_x": (8 + 16 * n, "float64", d), "sum_x_sq": (8 + 16 * n + 8 * d, "float64", d),
             "sum_r_sq": (8 + 16 * n + 16 * d, "float64", d), "dec_norm_sq": (8 + 16 * n + 24 * d, "float32", n),
             "bytes": (8 + 20 * n + 24 * d + 7) // 8 * 8}
+
+
+def frontier_layout(n_tau: int, K: int, d: int) -> dict:
+    """Byte offsets of the sae_frontier_files block for n_tau thresholds, K slots and d model dimensions (include/freud_sae.h:
+    SAE_FRONTIER_*): name -> (offset, dtype, count), plus "bytes": the block's size."""
+    return {"n_frames": (0, "int64", 1), "rows_cut": (8, "int64", 1), "active_cut": (16, "int64", 1), "sse": (24, "float64", K + 1),
+            "sum_x": (32 + 8 * K, "float64", d), "sum_x_sq": (32 + 8 * K + 8 * d, "float64", d),
+            "budget": (32 + 8 * K + 16 * d, "int64", n_tau * (K + 2)), "bytes": 32 + 8 * K + 16 * d + 8 * n_tau * (K + 2)}
 
 
 def unpack_block(block, layout: dict) -> Dict[str, np.ndarray]:
@@ -804,6 +814,21 @@ class SaeEngine:
         st = _dev("stats", stats, "int64", 8)
         _check(self._lib.sae_collect_files(self._ctx, xp, B, T, dt, int(K), COLLECT_IDX32 if indices.dtype == torch.int32 else 0,
                                            val, idx, st, _stream_ptr(stream)))
+
+    # -- sparsity frontier (include/freud_sae.h: sae_frontier_files; freud_amd/sparsity_frontier.py) ------------------------------
+    def frontier_files(self, x, K: int, thresholds, block, lengths=None, stream=None) -> None:
+        """Add the sparsity frontier of x [n_files, T, d] (CUDA) -- per counted frame the squared error after its first s slots,
+        s = 0 .. K, and its budget at every threshold -- to block (a zero-initialised uint8 CUDA tensor of
+        frontier_layout(len(thresholds), K, d)["bytes"] bytes); thresholds: up to FRONTIER_MAX_TAU floats inside (0, 1); lengths:
+        int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
+        x, xp, B, T, _d, dt, lp = _files_args(x, "frontier_files", lengths)
+        tau = _np_f32(thresholds).reshape(-1)
+        if tau.size > FRONTIER_MAX_TAU:
+            raise EngineError(f"frontier_files: {tau.size} thresholds > {FRONTIER_MAX_TAU}")
+        K = int(K)
+        blk = _dev("block", block, "uint8", frontier_layout(tau.size, max(K, 0), self.d)["bytes"], at_least=True)
+        _check(self._lib.sae_frontier_files(self._ctx, xp, B, T, dt, lp, K, tau.ctypes.data_as(_fptr), int(tau.size), 0, blk,
+                                            _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:

@@ -781,6 +781,66 @@ enum { SAE_COLLECT_IDX32 = 1 };
 int sae_collect_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, int K, int flags,
                       float* values_dev, void* indices_dev, int64_t* stats_dev, void* stream);
 
+/* ---- Sparsity frontier: the squared reconstruction error of a dataset at EVERY per-frame latent budget s = 0 .. K, and per frame
+ * the budget that reaches a share of its energy -- the SAE's curve beside the PCA curve of sae_input_cov, and what a cut of the
+ * feature store to K' slots costs (freud_amd/sparsity_frontier.py; kernels: freud_amd/csrc/frontier.h).
+ *
+ * Semantics.  Counted frames as in sae_recon_files: the first min(lengths[f], rows_per_file) frames of file f when lengths_dev is
+ * given, all of them otherwise.  For a counted frame:
+ *   (v_s, i_s), s < K   exactly the slots sae_collect_files defines for the row (the same entry word, predicate and tie rule: the
+ *                       padding is +0.0 in column order, a multi_topk context uses its k selection), so the frontier's prefix at
+ *                       K' IS the content of a store cut to K';
+ *   w_j                 the bf16 decoder operand of the reconstruction report: the column of the normalised bf16 W for L1 (read
+ *                       as a row of the transposed copy), row j of the bf16 W_dec for TopK;
+ *   r_0     = float(x) - b, ONE fp32 subtraction on the delivered x; b = b_dec for TopK, 0 for L1;
+ *   r_{s+1} = fmaf(-v_s, w_{i_s}, r_s) elementwise in fp32, in slot order (a padding slot changes nothing);
+ *   e_s     = sum_i r_s[i]^2, s = 0 .. K, an fp32 sum in a fixed order that depends on the row alone (frontier.h: fr_lane_sq,
+ *             fr_wave_sum) -- not on K, the batch, the grid or the row's neighbours.
+ * An element of x equal to -1 is data, as in the reconstruction report.
+ * The frame's BUDGET at a threshold tau is the smallest s in 0 .. K with e_s <= tau * e_0 (one fp32 product, one fp32 compare),
+ * K + 1 if there is none; a frame with e_0 == 0 has budget 0.  Up to SAE_FRONTIER_MAX_TAU thresholds, a HOST array of floats, each
+ * finite and inside (0, 1).
+ *
+ * Output block: caller-owned device memory, 8-byte aligned, SAE_FRONTIER_BYTES(n_tau, K, d) bytes of running totals; zero it before
+ * the first batch, every call adds one batch (the same K and thresholds).  Byte offsets:
+ *   SAE_FRONTIER_N_FRAMES    int64                  frames counted
+ *   SAE_FRONTIER_ROWS_CUT    int64                  counted rows with more than K active latents   (sae_collect_files' stats [3])
+ *   SAE_FRONTIER_ACTIVE_CUT  int64                  their active latents beyond slot K             (sae_collect_files' stats [2])
+ *   SAE_FRONTIER_SSE         float64 [K + 1]        sum over the frames of e_s: the squared error with s latents per frame
+ *   SAE_FRONTIER_SUM_X       float64 [d]            with SUM_X_SQ the denominator of the reconstruction report's FVU
+ *   SAE_FRONTIER_SUM_X_SQ    float64 [d]
+ *   SAE_FRONTIER_BUDGET      int64 [n_tau][K + 2]   per threshold the histogram of the frames' budgets
+ *
+ * Limits: 1 <= K <= SAE_FRONTIER_MAX_K; L1 K <= n_dict, TopK K <= k; d_model <= 1536 (padded); n_files * rows_per_file <=
+ * max_rows; bf16 contexts only (fp8: SAE_ERR_INVALID).  Every shape and argument check -- K out of range, n_tau outside
+ * [0, SAE_FRONTIER_MAX_TAU], a threshold outside (0, 1), unknown flag bits (none are defined), null pointers, a misaligned block --
+ * fails before anything is enqueued.
+ *
+ * Determinism: every float sum is a fixed-order fp32 partial written with plain stores -- e_s per row, its sums per 32 consecutive
+ * rows of the batch, sum_x / sum_x_sq per (128-row block, column) -- folded in a fixed order into the fp64 totals.  No float
+ * atomics: two runs give the same bytes.  A frame's e_s depends on the frame alone, so the integer fields are the same for every
+ * split of the files into batches, and the first K' + 1 entries of sse equal those of a run at K' over the same batches.
+ *
+ * The call is the bf16 eval encoder, the collect kernels into context scratch (8 K bytes per row, allocated by the first call) and
+ * the walk, asynchronous on `stream`.  Training state (parameters, moments, num_frames_since_fired) is untouched; afterwards
+ * sae_latent_buffer, sae_topk_indices, sae_decode, sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return
+ * SAE_ERR_STATE until the next sae_eval / step, as after sae_collect_files.
+ *
+ * Out of scope: K above a TopK context's k (no wider re-selection); re-encoding under a budget (the latent is encode()'s, only cut);
+ * raw (no-SAE) activations; fp8 contexts; per-frame output arrays; NaN / Inf inputs. */
+#define SAE_FRONTIER_MAX_K 256
+#define SAE_FRONTIER_MAX_TAU 8
+#define SAE_FRONTIER_N_FRAMES(n_tau, K, d) ((int64_t)0)
+#define SAE_FRONTIER_ROWS_CUT(n_tau, K, d) ((int64_t)8)
+#define SAE_FRONTIER_ACTIVE_CUT(n_tau, K, d) ((int64_t)16)
+#define SAE_FRONTIER_SSE(n_tau, K, d) ((int64_t)24)
+#define SAE_FRONTIER_SUM_X(n_tau, K, d) ((int64_t)32 + 8 * (int64_t)(K))
+#define SAE_FRONTIER_SUM_X_SQ(n_tau, K, d) ((int64_t)32 + 8 * (int64_t)(K) + 8 * (int64_t)(d))
+#define SAE_FRONTIER_BUDGET(n_tau, K, d) ((int64_t)32 + 8 * (int64_t)(K) + 16 * (int64_t)(d))
+#define SAE_FRONTIER_BYTES(n_tau, K, d) ((int64_t)32 + 8 * (int64_t)(K) + 16 * (int64_t)(d) + 8 * (int64_t)(n_tau) * ((int64_t)(K) + 2))
+int sae_frontier_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                       int K, const float* thresholds /* host, [n_tau] */, int n_tau, int flags, void* block_dev, void* stream);
+
 /* ---- Feature index: the latent-major postings of an indexed feature store -- for every latent the (position, value) of the slots
  * that fire it, positions ascending (freud_amd/feature_index.py; kernels: freud_amd/csrc/findex.h).  The reference has no index:
  * it rebuilds one latent's series from the row-major store by scanning every slot of every file, per query
