@@ -140,10 +140,22 @@ static int fused_bwd_splits(int ntiles, int steps, int cols) {
   return best;
 }
 
-// allocation of a buffer the peers of a data-parallel run map (G, Gb, stats)
-static hipError_t peer_visible_malloc(const sae_ctx* c, void** p, size_t bytes) {
-  if (c->finegrained) return hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained);
-  return hipMalloc(p, bytes);
+// the memory kinds of the context's owner (dev_mem.h) on HIP
+static const char* mem_why(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
+static const char* mem_device(void** p, size_t bytes) { return mem_why(hipMalloc(p, bytes)); }
+static const char* mem_finegrained(void** p, size_t bytes) { return mem_why(hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained)); }
+static const char* mem_uncached(void** p, size_t bytes) { return mem_why(hipExtMallocWithFlags(p, bytes, hipDeviceMallocUncached)); }
+static const char* mem_pinned(void** p, size_t bytes) { return mem_why(hipHostMalloc(p, bytes, hipHostMallocDefault)); }
+static const char* mem_mapped(void** p, size_t bytes) { return mem_why(hipHostMalloc(p, bytes, hipHostMallocMapped)); }
+static void mem_free(void* p) { (void)hipFree(p); }
+static void mem_free_host(void* p) { (void)hipHostFree(p); }
+
+static void mem_kinds(sae_ctx* c) {
+  c->mem.kinds[DM_DEVICE] = {mem_device, mem_free};
+  c->mem.kinds[DM_PEER] = {c->finegrained ? mem_finegrained : mem_device, mem_free};
+  c->mem.kinds[DM_UNCACHED] = {mem_uncached, mem_free};
+  c->mem.kinds[DM_PINNED] = {mem_pinned, mem_free_host};
+  c->mem.kinds[DM_MAPPED] = {mem_mapped, mem_free_host};
 }
 
 static int create_events(sae_ctx* c) {
@@ -158,76 +170,64 @@ static int create_events(sae_ctx* c) {
   return SAE_OK;
 }
 
+// floats behind the gradient in G: the metrics, and TopK's did_fire flags, ride in the all-reduced buffer
+static int64_t grad_tail(const sae_ctx* c) { return SAE_NUM_METRICS + (c->topk ? c->n_p : 0); }
+
 static int topk_create(sae_ctx* c, int64_t Mp) {
   c->k = c->cfg.k;
   c->k_aux_cap = c->d / 2 > 0 ? c->d / 2 : 1;           // k_aux = x.shape[-1] // 2 (topkautoencoder.py:110)
   if (c->k_aux_cap > 1024) return fail(SAE_ERR_INVALID, "topk: d_model/2 = %d aux latents exceed the 1024 supported", c->k_aux_cap);
   c->nparams = 2 * c->nW + c->n_p + c->d_p;
-  const int64_t ntail = SAE_NUM_METRICS + c->n_p;       // metrics + did_fire flags ride in the all-reduced buffer
-  g_force_gemm128 = c->cfg.force_gemm128 == 1;
-  c->no_stream = g_no_stream = c->cfg.debug_flags == 86 || (getenv("FREUD_GEMM_STREAM") && atoi(getenv("FREUD_GEMM_STREAM")) == 0);
   const int splits = choose_splits(c->n_p / 128, c->d_p / 128, Mp / 64);
   c->dw_splits = splits;
-#define TALLOC(ptr, bytes)                                                                                   \
-  do {                                                                                                       \
-    hipError_t e_ = hipMalloc((void**)&(ptr), (size_t)(bytes));                                              \
-    if (e_ != hipSuccess)                                                                                    \
-      return fail(SAE_ERR_HIP, "hipMalloc(%lld bytes) for %s failed: %s", (long long)(bytes), #ptr, hipGetErrorString(e_)); \
-  } while (0)
-  TALLOC(c->P, c->nparams * 4);
-  TALLOC(c->Mom, c->nparams * 4);
-  TALLOC(c->Var, c->nparams * 4);
-  {
-    hipError_t e_ = peer_visible_malloc(c, (void**)&c->G, (size_t)(c->nparams + ntail) * 4);
-    if (e_ != hipSuccess) return fail(SAE_ERR_HIP, "allocation of the gradient buffer failed: %s", hipGetErrorString(e_));
-  }
-  TALLOC(c->We_b, c->nW * 2);
-  TALLOC(c->Wd_b, c->nW * 2);
-  TALLOC(c->xs, Mp * c->d_p * 2);
-  TALLOC(c->pre, Mp * c->n_p * 2);
-  TALLOC(c->dense, Mp * c->n_p * 2);
-  TALLOC(c->aux_dense, Mp * c->n_p * 2);
-  TALLOC(c->dpre, Mp * c->n_p * 2);
-  TALLOC(c->de_b, Mp * c->d_p * 2);
-  TALLOC(c->dh_b, Mp * c->d_p * 2);
-  TALLOC(c->e, Mp * c->d_p * 4);
-  TALLOC(c->dh, Mp * c->d_p * 4);
-  TALLOC(c->e2_part, Mp * 4);
-  TALLOC(c->a2_part, Mp * 4);
-  TALLOC(c->dbd_part, (Mp / 128 + 1) * c->d_p * 4);
-  TALLOC(c->ds_part, (int64_t)((c->n_p + 63) / 64) * c->d_p * 4);
-  TALLOC(c->db_part, (Mp / 128) * c->n_p * 4);
-  TALLOC(c->tkf, 64);
-  TALLOC(c->tk, 64);
-  TALLOC(c->top_idx, Mp * c->k * 4);
-  TALLOC(c->aux_idx, Mp * c->k_aux_cap * 4);
-  TALLOC(c->top_vals, Mp * c->k * 2);
-  TALLOC(c->tile_max, Mp * (c->n_p / TSEL_TILE) * 2);
-  TALLOC(c->sel_flag, Mp);
-  TALLOC(c->aux_vals, Mp * c->k_aux_cap * 2);
-  HIP_TRY(hipHostMalloc((void**)&c->dead_hint, 64, hipHostMallocDefault));
+  CTX_ALLOC(P, c->nparams * 4);
+  CTX_ALLOC(Mom, c->nparams * 4);
+  CTX_ALLOC(Var, c->nparams * 4);
+  CTX_MEM(alloc, G, (c->nparams + grad_tail(c)) * 4, DM_PEER);
+  CTX_ALLOC(We_b, c->nW * 2);
+  CTX_ALLOC(Wd_b, c->nW * 2);
+  CTX_ALLOC(xs, Mp * c->d_p * 2);
+  CTX_ALLOC(pre, Mp * c->n_p * 2);
+  CTX_ALLOC(dense, Mp * c->n_p * 2);
+  CTX_ALLOC(aux_dense, Mp * c->n_p * 2);
+  CTX_ALLOC(dpre, Mp * c->n_p * 2);
+  CTX_ALLOC(de_b, Mp * c->d_p * 2);
+  CTX_ALLOC(dh_b, Mp * c->d_p * 2);
+  CTX_ALLOC(e, Mp * c->d_p * 4);
+  CTX_ALLOC(dh, Mp * c->d_p * 4);
+  CTX_ALLOC(e2_part, Mp * 4);
+  CTX_ALLOC(a2_part, Mp * 4);
+  CTX_ALLOC(dbd_part, (Mp / 128 + 1) * c->d_p * 4);
+  CTX_ALLOC(ds_part, (int64_t)((c->n_p + 63) / 64) * c->d_p * 4);
+  CTX_ALLOC(db_part, (Mp / 128) * c->n_p * 4);
+  CTX_ALLOC(tkf, 64);
+  CTX_ALLOC(tk, 64);
+  CTX_ALLOC(top_idx, Mp * c->k * 4);
+  CTX_ALLOC(aux_idx, Mp * c->k_aux_cap * 4);
+  CTX_ALLOC(top_vals, Mp * c->k * 2);
+  CTX_ALLOC(tile_max, Mp * (c->n_p / TSEL_TILE) * 2);
+  CTX_ALLOC(sel_flag, Mp);
+  CTX_ALLOC(aux_vals, Mp * c->k_aux_cap * 2);
+  CTX_MEM(alloc, dead_hint, 64, DM_PINNED);
   c->dead_hint[0] = 0;
-  TALLOC(c->tv_part, ((Mp * c->d + 255) / 256 + 1) * 8);
-  TALLOC(c->nfsf, (size_t)c->n_p * 8);
-  TALLOC(c->dbe_fx, (size_t)c->n_p * 8);
+  CTX_ALLOC(tv_part, ((Mp * c->d + 255) / 256 + 1) * 8);
+  CTX_ALLOC(nfsf, (size_t)c->n_p * 8);
+  CTX_ALLOC(dbe_fx, (size_t)c->n_p * 8);
   c->stats_cap = DP_STATS_HEAD + 2 * (int64_t)c->cfg.max_rows * c->d;     // column sums / sums of squares: at most one file
-  {
-    hipError_t e_ = peer_visible_malloc(c, (void**)&c->stats, (size_t)c->stats_cap * 8);
-    if (e_ != hipSuccess) return fail(SAE_ERR_HIP, "allocation of the statistics buffer failed: %s", hipGetErrorString(e_));
-  }
+  CTX_MEM(alloc, stats, c->stats_cap * 8, DM_PEER);
   // topk_dense_backward keeps the dense ddense GEMM (tests cover both)
   c->topk_sparse_da = (c->d_p == 384 || c->d_p == 768 || c->d_p == 1280) && c->cfg.topk_dense_backward != 1;
-  TALLOC(c->dead, c->n_p);
-  TALLOC(c->be_r, (size_t)c->n_p * 4);
+  CTX_ALLOC(dead, c->n_p);
+  CTX_ALLOC(be_r, (size_t)c->n_p * 4);
   c->multi = c->cfg.multi_topk != 0;
   c->k4 = 4 * c->k;
   if (c->multi) {
-    TALLOC(c->multi_dense, Mp * c->n_p * 2);
-    TALLOC(c->multi_idx, Mp * c->k4 * 4);
-    TALLOC(c->multi_vals, Mp * c->k4 * 2);
-    TALLOC(c->em, Mp * c->d_p * 4);
-    TALLOC(c->dm_b, Mp * c->d_p * 2);
-    TALLOC(c->m2_part, Mp * 4);
+    CTX_ALLOC(multi_dense, Mp * c->n_p * 2);
+    CTX_ALLOC(multi_idx, Mp * c->k4 * 4);
+    CTX_ALLOC(multi_vals, Mp * c->k4 * 2);
+    CTX_ALLOC(em, Mp * c->d_p * 4);
+    CTX_ALLOC(dm_b, Mp * c->d_p * 2);
+    CTX_ALLOC(m2_part, Mp * 4);
   }
   // reserved switches: topk_dense_backward = 1 dense ddense GEMM, 2 = sparse d pre-activations + dense weight-gradient GEMMs
   c->topk_csc = c->topk_sparse_da && c->cfg.topk_dense_backward == 0;
@@ -237,68 +237,44 @@ static int topk_create(sae_ctx* c, int64_t Mp) {
     const bool auxc_will = c->cfg.auxk_alpha != 0.0 && c->n_p <= 2048 * 44 && c->cfg.debug_flags != 76;
     const int64_t emax = Mp * (int64_t)(c->k + (auxc_will ? 0 : c->k_aux_cap) + (c->multi ? c->k4 : 0));
     c->csc_max_items = c->n_p + emax / CSC_CHUNK + 1;
-    TALLOC(c->csc_counts, nb * c->n_p * 2);
-    TALLOC(c->csc_block_off, nb * c->n_p * 4);
-    TALLOC(c->csc_total, (size_t)c->n_p * 4);
-    TALLOC(c->csc_start, (size_t)(c->n_p + 1) * 4);
-    TALLOC(c->csc_item_start, (size_t)(c->n_p + 1) * 4);
-    TALLOC(c->csc_item_latent, (size_t)c->csc_max_items * 4);
-    TALLOC(c->csc_multi, (size_t)(c->n_p + 4) * 4);
-    TALLOC(c->csc_entries, (size_t)emax * sizeof(CscEntry));
-    TALLOC(c->csc_part, (size_t)c->csc_max_items * 2 * c->d_p * 4);
-    TALLOC(c->csc_pbe, (size_t)c->csc_max_items * 4);
+    CTX_ALLOC(csc_counts, nb * c->n_p * 2);
+    CTX_ALLOC(csc_block_off, nb * c->n_p * 4);
+    CTX_ALLOC(csc_total, (size_t)c->n_p * 4);
+    CTX_ALLOC(csc_start, (size_t)(c->n_p + 1) * 4);
+    CTX_ALLOC(csc_item_start, (size_t)(c->n_p + 1) * 4);
+    CTX_ALLOC(csc_item_latent, (size_t)c->csc_max_items * 4);
+    CTX_ALLOC(csc_multi, (size_t)(c->n_p + 4) * 4);
+    CTX_ALLOC(csc_entries, (size_t)emax * sizeof(CscEntry));
+    CTX_ALLOC(csc_part, (size_t)c->csc_max_items * 2 * c->d_p * 4);
+    CTX_ALLOC(csc_pbe, (size_t)c->csc_max_items * 4);
   }
   // AuxK as dense GEMMs over the compacted dead latents: with the CSC main path and the register select kernel
   c->aux_compact = c->topk_csc && c->cfg.auxk_alpha != 0.0 && c->n_p <= 2048 * 44 && c->cfg.debug_flags != 76;
   if (c->aux_compact) {
-    TALLOC(c->tkd, 64);
-    TALLOC(c->dead_cols, (size_t)c->n_p * 4);
-    TALLOC(c->vec_rank, (size_t)(c->n_p / 8) * 4);
-    TALLOC(c->vec_bits, (size_t)vec_bits_t_offset(c->n_p) + VEC_BITS_T_BYTES);     // the table + its transposed copy (topk_aux.h)
-    TALLOC(c->Wdd_b, c->nW * 2);
-    TALLOC(c->aux_dbe_part, (Mp / 128) * c->n_p * 4);
+    CTX_ALLOC(tkd, 64);
+    CTX_ALLOC(dead_cols, (size_t)c->n_p * 4);
+    CTX_ALLOC(vec_rank, (size_t)(c->n_p / 8) * 4);
+    CTX_ALLOC(vec_bits, (size_t)vec_bits_t_offset(c->n_p) + VEC_BITS_T_BYTES);     // the table + its transposed copy (topk_aux.h)
+    CTX_ALLOC(Wdd_b, c->nW * 2);
+    CTX_ALLOC(aux_dbe_part, (Mp / 128) * c->n_p * 4);
     HIP_TRY(hipMemset(c->tkd, 0, 64));
   }
   // the multi-TopK weight gradient is a second GEMM launch into its own split-K slabs
   // (the AuxK weight-gradient GEMMs over a SMALL dead set split K up to 32 times to fill the chip: slabs [split][n_p][d_p])
   c->slab_splits = (splits > 1 ? splits : 1) * (c->multi ? 2 : 1);
   if (c->aux_compact && c->slab_splits < 32) c->slab_splits = 32;
-  TALLOC(c->slab, (int64_t)c->slab_splits * c->nW * 4);
-  TALLOC(c->gn_part, 1024 * 8);
-#undef TALLOC
-  HIP_TRY(hipMemset(c->P, 0, c->nparams * 4));
-  HIP_TRY(hipMemset(c->Mom, 0, c->nparams * 4));
-  HIP_TRY(hipMemset(c->Var, 0, c->nparams * 4));
-  HIP_TRY(hipMemset(c->G, 0, (c->nparams + ntail) * 4));
+  CTX_ALLOC(slab, (int64_t)c->slab_splits * c->nW * 4);
+  CTX_ALLOC(gn_part, 1024 * 8);
   HIP_TRY(hipMemset(c->nfsf, 0, (size_t)c->n_p * 8));
-  int rc_ev = create_events(c);
-  if (rc_ev) return rc_ev;
-  HIP_TRY(hipDeviceSynchronize());
   return SAE_OK;
 }
 
 extern "C" void sae_destroy(sae_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device_id);   // teardown: nothing useful can be done about a failure here
-  void* ptrs[] = {c->P,    c->Mom,     c->Var,     c->G,       c->Wb,   c->Wt,      c->xb,    c->c, c->dxh,
-                  c->dpre, c->slab,    c->db_part, c->l1_part, c->sq_part, c->scal, c->gn_part, c->masked, c->cn_part, c->cnt_part,
-                  c->We_b, c->Wd_b, c->xs, c->pre, c->dense, c->aux_dense, c->de_b, c->dh_b, c->e, c->dh, c->e2_part,
-                  c->a2_part, c->dbd_part, c->ds_part, c->tkf, c->top_idx, c->aux_idx, c->tk, c->tv_part, c->nfsf, c->dead, c->dbe_fx,
-                  c->multi_dense, c->multi_idx, c->em, c->dm_b, c->m2_part, c->x8, c->c8, c->W8, c->W8t, c->scal8, c->x8_part, c->dxh8,
-                  c->stats, c->stats_part, c->Gb, c->top_vals, c->aux_vals, c->multi_vals, c->tile_max, c->sel_flag, c->csc_counts, c->csc_block_off, c->csc_total, c->csc_start, c->csc_item_start,
-                  c->csc_item_latent, c->csc_entries, c->csc_part, c->csc_pbe, c->tkd, c->dead_cols, c->vec_rank, c->vec_bits, c->Wdd_b,
-                  c->aux_dbe_part, c->be_r, c->cnorm, c->dw_tail, c->csc_multi, c->fs_slab, c->co_zt, c->lb_lt, c->hs_fmax, c->mn_w, c->rc_buf, c->fr_buf};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (c->dead_hint) (void)hipHostFree(c->dead_hint);
+  c->mem.free_all();
+  // what is not memory of the context's own: the peers' mappings, the communicator, the streams, the events
   for (int i = 0; i < c->p2p_nopened; ++i) (void)hipIpcCloseMemHandle(c->p2p_opened[i]);
-  if (c->sig) (void)hipFree(c->sig);
-  if (c->p2p_status) (void)hipFree(c->p2p_status);
-  if (c->p2p_status_host) (void)hipHostFree(c->p2p_status_host);
-  if (c->col_stage) (void)hipFree(c->col_stage);
-  if (c->bal_map) (void)hipFree(c->bal_map);
-  for (void* p : {(void*)c->e32_x, (void*)c->e32_pre, (void*)c->e32_sel, (void*)c->e32_xhat, (void*)c->e32_part, (void*)c->e32_colmax})
-    if (p) (void)hipFree(p);
   if (c->comm) (void)ncclCommDestroy(c->comm);
   if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
   for (hipEvent_t e : {c->ev_x, c->ev_stats, c->ev_done})
@@ -313,6 +289,8 @@ extern "C" void sae_destroy(sae_ctx* c) {
       }
   delete c;
 }
+
+static int l1_create(sae_ctx* c, int64_t Mp);
 
 extern "C" int sae_create(const sae_config* cfg, sae_ctx** out) {
   if (!cfg || !out) return fail(SAE_ERR_INVALID, "null argument");
@@ -360,18 +338,31 @@ extern "C" int sae_create(const sae_config* cfg, sae_ctx** out) {
   // non-coherently in a cache, so the peer exchange needs no cache maintenance to be correct.  The second in-engine option for a
   // node where the start-up self-test of the default (coarse-grained + fences) fails; costs local bandwidth.
   if (const char* fg = getenv("FREUD_P2P_FINEGRAINED")) c->finegrained = atoi(fg) == 1;
-  const int64_t Mp = c->max_rows_p;
-  if (c->topk) {
-    int rc_tk = topk_create(c, Mp);
-    if (rc_tk) {
-      sae_destroy(c);
-      return rc_tk;
-    }
-    *out = c;
-    return SAE_OK;
-  }
+  mem_kinds(c);
   g_force_gemm128 = cfg->force_gemm128 == 1;
   c->no_stream = g_no_stream = cfg->debug_flags == 86 || (getenv("FREUD_GEMM_STREAM") && atoi(getenv("FREUD_GEMM_STREAM")) == 0);
+  const int rc = [&]() -> int {
+    if (const int rc_v = c->topk ? topk_create(c, c->max_rows_p) : l1_create(c, c->max_rows_p)) return rc_v;
+    HIP_TRY(hipMemset(c->P, 0, c->nparams * 4));
+    HIP_TRY(hipMemset(c->Mom, 0, c->nparams * 4));
+    HIP_TRY(hipMemset(c->Var, 0, c->nparams * 4));
+    HIP_TRY(hipMemset(c->G, 0, (c->nparams + grad_tail(c)) * 4));
+    if (const int rc_ev = create_events(c)) return rc_ev;
+    // > 64 KiB dynamic LDS is opted in to lazily at the first launch of every kernel instantiation (LDS_ATTR)
+    HIP_TRY(hipDeviceSynchronize());
+    return SAE_OK;
+  }();
+  if (rc) {            // the one place a failed creation is torn down: whatever it got is the owner's or sae_destroy's
+    sae_destroy(c);
+    return rc;
+  }
+  *out = c;
+  return SAE_OK;
+}
+
+// the L1 variant's launch plan and buffers
+static int l1_create(sae_ctx* c, int64_t Mp) {
+  const sae_config* cfg = &c->cfg;
   c->dw_splits = choose_splits(c->d_p / 128, c->n_p / 128, 2 * Mp / 64);
   if (const char* ov = getenv("FREUD_DW_SPLITS")) {       // timing sweeps of the split-K factor of the weight-gradient GEMM
     const int v = atoi(ov);
@@ -435,13 +426,8 @@ extern "C" int sae_create(const sae_config* cfg, sae_ctx** out) {
         const int len = grid / 8 + (x < grid % 8 ? 1 : 0);
         for (int i = 0; i < len; ++i) map[8 * i + x] = (short)order[pos++];
       }
-      hipError_t e_ = hipMalloc((void**)&c->bal_map, (size_t)grid * 2);
-      if (e_ == hipSuccess) e_ = hipMemcpy(c->bal_map, map.data(), (size_t)grid * 2, hipMemcpyHostToDevice);
-      if (e_ != hipSuccess) {
-        int rc_ = fail(SAE_ERR_HIP, "balanced backward: workgroup table: %s", hipGetErrorString(e_));
-        sae_destroy(c);
-        return rc_;
-      }
+      CTX_ALLOC(bal_map, (size_t)grid * 2);
+      HIP_TRY(hipMemcpy(c->bal_map, map.data(), (size_t)grid * 2, hipMemcpyHostToDevice));
     }
   }
   {   // a chunk launch writes splits x (chunk rows x n_p) floats at the chunk's row offset of each slab
@@ -450,80 +436,42 @@ extern "C" int sae_create(const sae_config* cfg, sae_ctx** out) {
   }
   const int64_t db_rows = (Mp / 128) > 64 ? (Mp / 128) : 64;
 
-#define ALLOC(ptr, bytes)                                   \
-  do {                                                      \
-    hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));     \
-    if (e_ != hipSuccess) {                                 \
-      int rc_ = fail(SAE_ERR_HIP, "hipMalloc(%lld bytes) for %s failed: %s", (long long)(bytes), #ptr, \
-                     hipGetErrorString(e_));                \
-      sae_destroy(c);                                       \
-      return rc_;                                           \
-    }                                                       \
-  } while (0)
-  ALLOC(c->P, c->nparams * 4);
-  ALLOC(c->Mom, c->nparams * 4);
-  ALLOC(c->Var, c->nparams * 4);
-  if (c->finegrained) {
-    hipError_t e_ = peer_visible_malloc(c, (void**)&c->G, (size_t)(c->nparams + SAE_NUM_METRICS) * 4);
-    if (e_ == hipSuccess) e_ = peer_visible_malloc(c, (void**)&c->stats, (size_t)DP_STATS_HEAD * 8);
-    if (e_ != hipSuccess) {
-      int rc_ = fail(SAE_ERR_HIP, "fine-grained allocation of the gradient / statistics buffers failed: %s", hipGetErrorString(e_));
-      sae_destroy(c);
-      return rc_;
-    }
-  } else {
-    ALLOC(c->G, (c->nparams + SAE_NUM_METRICS) * 4);
-  }
-  ALLOC(c->Wb, c->nW * 2);
-  ALLOC(c->Wt, c->nW * 2);
-  ALLOC(c->xb, Mp * c->d_p * 2);
-  ALLOC(c->c, Mp * c->n_p * 2 + 4096);   // + a dummy line the fused forward parks its first two stores on
-  ALLOC(c->dxh, Mp * c->d_p * 2);
-  ALLOC(c->dpre, Mp * c->n_p * 2);
-  ALLOC(c->slab, (int64_t)slab_splits * c->nW * 4);
-  ALLOC(c->db_part, db_rows * c->n_p * 4);
-  ALLOC(c->l1_part, (Mp / 128) * (c->n_p / 128) * 4);
-  ALLOC(c->sq_part, (Mp / 128) * (c->d_p / 128) * 2 * 4);
-  ALLOC(c->scal, 16 * 4);
-  ALLOC(c->gn_part, 1024 * 8);
-  ALLOC(c->cn_part, (int64_t)(c->d_p / 32) * c->n_p * 4);
-  ALLOC(c->cnorm, (int64_t)c->n_p * 4);
+  c->stats_cap = DP_STATS_HEAD;
+  CTX_ALLOC(P, c->nparams * 4);
+  CTX_ALLOC(Mom, c->nparams * 4);
+  CTX_ALLOC(Var, c->nparams * 4);
+  CTX_MEM(alloc, G, (c->nparams + grad_tail(c)) * 4, DM_PEER);
+  if (c->finegrained) CTX_MEM(alloc, stats, c->stats_cap * 8, DM_PEER);      // (fine-grained: next to G; else in its place below)
+  CTX_ALLOC(Wb, c->nW * 2);
+  CTX_ALLOC(Wt, c->nW * 2);
+  CTX_ALLOC(xb, Mp * c->d_p * 2);
+  CTX_ALLOC(c, Mp * c->n_p * 2 + 4096);   // + a dummy line the fused forward parks its first two stores on
+  CTX_ALLOC(dxh, Mp * c->d_p * 2);
+  CTX_ALLOC(dpre, Mp * c->n_p * 2);
+  CTX_ALLOC(slab, (int64_t)slab_splits * c->nW * 4);
+  CTX_ALLOC(db_part, db_rows * c->n_p * 4);
+  CTX_ALLOC(l1_part, (Mp / 128) * (c->n_p / 128) * 4);
+  CTX_ALLOC(sq_part, (Mp / 128) * (c->d_p / 128) * 2 * 4);
+  CTX_ALLOC(scal, 16 * 4);
+  CTX_ALLOC(gn_part, 1024 * 8);
+  CTX_ALLOC(cn_part, (int64_t)(c->d_p / 32) * c->n_p * 4);
+  CTX_ALLOC(cnorm, (int64_t)c->n_p * 4);
   // overflow buffer of the tail-split weight-gradient launches: at most one round of pieces (256 tiles of 256 x 256 fp32); the
   // round-sized column chunks of the data-parallel form (below) use it for their last, partial chunk as well
-  if (c->dw_tail_tiles > 0 || (c->d_p >= 1024 && c->d_p % 256 == 0 && c->n_p % 256 == 0)) ALLOC(c->dw_tail, (int64_t)256 * 65536 * 4);
-  ALLOC(c->masked, 2048 * 4);
-  ALLOC(c->cnt_part, (Mp / 128 + 1) * 4);
-  c->stats_cap = DP_STATS_HEAD;
-  if (!c->stats) ALLOC(c->stats, c->stats_cap * 8);
-  ALLOC(c->stats_part, 1024 * 4);
+  if (c->dw_tail_tiles > 0 || (c->d_p >= 1024 && c->d_p % 256 == 0 && c->n_p % 256 == 0)) CTX_ALLOC(dw_tail, (int64_t)256 * 65536 * 4);
+  CTX_ALLOC(masked, 2048 * 4);
+  CTX_ALLOC(cnt_part, (Mp / 128 + 1) * 4);
+  if (!c->stats) CTX_MEM(alloc, stats, c->stats_cap * 8, DM_PEER);
+  CTX_ALLOC(stats_part, 1024 * 4);
   if (c->fp8) {
-    ALLOC(c->x8, Mp * c->d_p);
-    ALLOC(c->c8, Mp * c->n_p);
-    ALLOC(c->W8, c->nW);
-    ALLOC(c->W8t, c->nW);
-    ALLOC(c->scal8, S8_COUNT * 4);
-    ALLOC(c->x8_part, 2 * 1024 * 4);
-    if (c->fp8_bwd) ALLOC(c->dxh8, Mp * c->d_p);
+    CTX_ALLOC(x8, Mp * c->d_p);
+    CTX_ALLOC(c8, Mp * c->n_p);
+    CTX_ALLOC(W8, c->nW);
+    CTX_ALLOC(W8t, c->nW);
+    CTX_ALLOC(scal8, S8_COUNT * 4);
+    CTX_ALLOC(x8_part, 2 * 1024 * 4);
+    if (c->fp8_bwd) CTX_ALLOC(dxh8, Mp * c->d_p);
   }
-#undef ALLOC
-  {
-    int rc_init = [&]() -> int {
-      HIP_TRY(hipMemset(c->P, 0, c->nparams * 4));
-      HIP_TRY(hipMemset(c->Mom, 0, c->nparams * 4));
-      HIP_TRY(hipMemset(c->Var, 0, c->nparams * 4));
-      HIP_TRY(hipMemset(c->G, 0, (c->nparams + SAE_NUM_METRICS) * 4));
-      int rc_ev = create_events(c);
-      if (rc_ev) return rc_ev;
-      // > 64 KiB dynamic LDS is opted in to lazily at the first launch of every kernel instantiation (LDS_ATTR)
-      HIP_TRY(hipDeviceSynchronize());
-      return SAE_OK;
-    }();
-    if (rc_init) {
-      sae_destroy(c);
-      return rc_init;
-    }
-  }
-  *out = c;
   return SAE_OK;
 }
 
@@ -1004,7 +952,7 @@ extern "C" int sae_dist_set_payload(sae_ctx* c, int dtype) {
   if (!c) return fail(SAE_ERR_INVALID, "null argument");
   if (dtype != SAE_DTYPE_F32 && dtype != SAE_DTYPE_BF16) return fail(SAE_ERR_INVALID, "payload must be SAE_DTYPE_F32 or SAE_DTYPE_BF16");
   USE_DEVICE(c);
-  if (dtype == SAE_DTYPE_BF16 && !c->Gb) HIP_TRY(peer_visible_malloc(c, (void**)&c->Gb, (size_t)c->nparams * 2));
+  if (dtype == SAE_DTYPE_BF16) CTX_MEM(grow, Gb, c->nparams * 2, DM_PEER);
   c->payload = dtype;
   return SAE_OK;
 }
@@ -1025,21 +973,20 @@ extern "C" int sae_p2p_export(sae_ctx* c, void* out, int64_t capacity) {
   if (capacity < (int64_t)sizeof(P2PBlob)) return fail(SAE_ERR_INVALID, "need %d bytes", (int)sizeof(P2PBlob));
   if (c->dist) return fail(SAE_ERR_STATE, "the context already runs a data-parallel protocol");
   USE_DEVICE(c);
-  if (!c->Gb) HIP_TRY(peer_visible_malloc(c, (void**)&c->Gb, (size_t)c->nparams * 2));
+  CTX_MEM(grow, Gb, c->nparams * 2, DM_PEER);
   if (!c->sig) {
     // flags the PEERS write and this rank polls: uncached device memory, so that a poll always reaches memory
     // [barrier flags of the exchange kernels | inbox of the statistics push: 2 parities x 8 sources x 4 words]
-    HIP_TRY(hipExtMallocWithFlags((void**)&c->sig, (size_t)(P2P_SIG_WORDS + 64) * 8, hipDeviceMallocUncached));
+    CTX_MEM(grow, sig, (P2P_SIG_WORDS + 64) * 8, DM_UNCACHED);
     HIP_TRY(hipMemset(c->sig, 0, (size_t)(P2P_SIG_WORDS + 64) * 8));
-    HIP_TRY(hipMalloc((void**)&c->p2p_status, 64));
+    CTX_MEM(grow, p2p_status, 64, DM_DEVICE);
     HIP_TRY(hipMemset(c->p2p_status, 0, 64));
     // a mirror of the failure word the host can read without touching the stream (sae_dist_poll); best effort: without it
     // the failure still shows at the next sae_dist_check
-    if (hipHostMalloc((void**)&c->p2p_status_host, 64, hipHostMallocMapped) == hipSuccess) {
+    if (c->mem.grow(c->p2p_status_host, 64, DM_MAPPED, "c->p2p_status_host")) {
       memset(c->p2p_status_host, 0, 64);
       if (hipHostGetDevicePointer((void**)&c->p2p_status_hostdev, c->p2p_status_host, 0) != hipSuccess) c->p2p_status_hostdev = nullptr;
     } else {
-      c->p2p_status_host = nullptr;
       (void)hipGetLastError();
     }
     HIP_TRY(hipDeviceSynchronize());
@@ -1786,9 +1733,7 @@ static int dw_row_chunks(sae_ctx* c, const DwPlan& p, int64_t Mp, hipStream_t s)
 
 // the staging buffer of the column chunks, on first use by a staged form
 static int col_stage_ready(sae_ctx* c, const DwPlan& p) {
-  if (!p.staged || c->col_stage) return SAE_OK;
-  hipError_t e_ = hipMalloc((void**)&c->col_stage, (size_t)c->nW * 4);
-  if (e_ != hipSuccess) return fail(SAE_ERR_HIP, "staging buffer of the column chunks: %s", hipGetErrorString(e_));
+  if (p.staged) CTX_MEM(grow, col_stage, c->nW * 4, DM_DEVICE);
   return SAE_OK;
 }
 
@@ -2471,20 +2416,13 @@ static int dispatch_fwd_bwd_inner(sae_ctx* c, const void* x, int64_t M, int x_dt
 
 // ---- fp32 evaluation forward (eval_fp32.h): validate() of the reference on device='cpu' runs without autocast
 static int e32_ensure(sae_ctx* c, int64_t M) {
-  if (c->e32_rows >= M && c->e32_x) return SAE_OK;
-  for (void** p : {(void**)&c->e32_x, (void**)&c->e32_pre, (void**)&c->e32_sel, (void**)&c->e32_xhat, (void**)&c->e32_part}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  c->e32_rows = 0;
-  const int64_t rows = M;
-  HIP_TRY(hipMalloc((void**)&c->e32_x, (size_t)rows * c->d_p * 4));
-  HIP_TRY(hipMalloc((void**)&c->e32_pre, (size_t)rows * c->n_p * 4));
-  if (c->topk) HIP_TRY(hipMalloc((void**)&c->e32_sel, (size_t)rows * c->n_p * 4));
-  HIP_TRY(hipMalloc((void**)&c->e32_xhat, (size_t)rows * c->d_p * 4));
-  HIP_TRY(hipMalloc((void**)&c->e32_part, (size_t)(E32_FIXED_DOUBLES + e32_l1_parts(c->n_p, rows)) * 8));
-  if (!c->e32_colmax) HIP_TRY(hipMalloc((void**)&c->e32_colmax, (size_t)c->n_p * 4));
-  c->e32_rows = rows;
+  // every size grows with M, so each buffer's own recorded size stands for the rows it serves
+  CTX_MEM(grow, e32_x, M * c->d_p * 4, DM_DEVICE);
+  CTX_MEM(grow, e32_pre, M * c->n_p * 4, DM_DEVICE);
+  if (c->topk) CTX_MEM(grow, e32_sel, M * c->n_p * 4, DM_DEVICE);
+  CTX_MEM(grow, e32_xhat, M * c->d_p * 4, DM_DEVICE);
+  CTX_MEM(grow, e32_part, (E32_FIXED_DOUBLES + e32_l1_parts(c->n_p, M)) * 8, DM_DEVICE);
+  CTX_MEM(grow, e32_colmax, (int64_t)c->n_p * 4, DM_DEVICE);
   return SAE_OK;
 }
 

@@ -10,6 +10,7 @@
 
 #include "../../include/freud_sae.h"
 #include "common.h"
+#include "dev_mem.h"
 #include "gemm.h"
 #include "p2p_index.h"
 
@@ -169,6 +170,9 @@ static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kC
                                                   &kTimingPass, &kResamplePass, &kFrontierPass};
 
 struct sae_ctx {
+  // Every pointer field below that the context OWNS is allocated through `mem` (dev_mem.h; the last member, behind everything a step
+  // touches) -- at creation with alloc, lazily with grow -- and released by its free_all in sae_destroy; nothing else frees.  What
+  // is not owned says so: aliases and peer mappings.
   sae_config cfg;
   int d, n, d_p, n_p;
   int64_t max_rows_p;
@@ -297,11 +301,12 @@ struct sae_ctx {
   unsigned long long* sig = nullptr;             // this rank's flag block (uncached device memory)
   unsigned int* p2p_status = nullptr;            // device words: [0] sticky failure bits the exchange kernels set (P2P_ST_*), [1] self-test mismatches
   unsigned int* p2p_status_host = nullptr;       // host-mapped mirror of word 0 (hipHostMalloc): sae_dist_poll reads it without a sync
-  unsigned int* p2p_status_hostdev = nullptr;    // its device address
+  unsigned int* p2p_status_hostdev = nullptr;    // its device address: an alias of p2p_status_host, not owned (never freed)
   int p2p_fault_kind = 0, p2p_fault_rank = -1;   // FREUD_P2P_FAULT=skip_phase2:<rank>[:<after exchanges>] (tests: the guards must catch it)
   unsigned long long p2p_fault_after = 0;
   float* col_stage = nullptr;                    // in-engine RCCL, d >= 1024: contiguous staging of the dW column chunks ([d_p x n_p] floats)
-  float* audit_dst = nullptr;                    // sae_dist_audit: every gradient exchange first copies its segments here
+  float* audit_dst = nullptr;                    // sae_dist_audit: every gradient exchange first copies its segments here (the
+                                                 // caller's buffer: an alias, not owned)
   bool finegrained = false;                      // FREUD_P2P_FINEGRAINED=1: G / Gb / stats in fine-grained device memory
   unsigned long long p2p_epoch[P2P_CHANNELS] = {};
   unsigned long long p2p_epoch_push = 0;         // epoch of the statistics push inside finalize_losses_kernel
@@ -319,16 +324,10 @@ struct sae_ctx {
   bool no_stream = false;       // this context's K = d GEMMs stay on the tile form (FREUD_GEMM_STREAM=0 / debug_flags 86 at ITS creation)
   int eval_prec = 0;            // 0 = the training kernels' arithmetic (bf16 operands, fp32 accumulate), 1 = fp32 end to end
   LastCall last_call = LAST_FWD_BF16;   // what the last forward-like call left behind (no_forward_left, the getters)
-  void* fs_slab = nullptr;      // sae_stats_files scratch (stats.h): the slab [max_rows_p / 128][n] x 4 words, then the L0 bytes
-  int8_t* co_zt = nullptr;      // sae_coact_files scratch (coact.h): the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)]
-  int8_t* lb_lt = nullptr;      // sae_label_files scratch (labels.h): the int8 label pack Lt [lb_rows][round_up(max_rows_p, CO_BK)]
-  int lb_rows = 0;              // its rows: the largest C_p = round_up(n_classes + 1, CO_BM) asked for so far
-  uint32_t* hs_fmax = nullptr;  // sae_hist_files scratch of a TopK context (hist.h): the file maxima [hs_files][n] of one batch
-  int64_t hs_files = 0;         // its files: the largest n_files asked for so far
-  float* mn_w = nullptr;        // sae_manipulate_files scratch (manip.h): the operand rows [SM_MAX_EDITS][d_p]
-  float* rc_buf = nullptr;      // sae_recon_files scratch (recon.h): x_hat / r, the slabs, the row and dimension partials, TopK's p
-  char* fr_buf = nullptr;       // sae_frontier_files scratch (frontier.h): the slots, the row records and the partials
-  int64_t e32_rows = 0;
+  // The one scratch of the file passes (passes.hip: pass_scratch), grow-only: a pass runs start to finish inside its entry point and
+  // reads nothing of it afterwards, so each pass carves what it needs from the same bytes -- and finds another pass's leftovers there.
+  char* pass_scratch = nullptr;
+  // the fp32 evaluation's buffers: each grows to the largest evaluation batch seen; e32_colmax [n_p] is allocated once
   float *e32_x = nullptr, *e32_pre = nullptr, *e32_sel = nullptr, *e32_xhat = nullptr;
   double* e32_part = nullptr;
   int* e32_colmax = nullptr;
@@ -340,6 +339,7 @@ struct sae_ctx {
   int prof_period = 8;
   EvRing ev[KID_COUNT];
   bool ev_init = false;
+  DevMem mem;
 };
 
 #pragma GCC visibility push(hidden)
@@ -350,6 +350,13 @@ int use_device(const sae_ctx* c);
     int rc_ = use_device(c);   \
     if (rc_) return rc_;       \
   } while (0)
+
+// c->field through the context's owner (op: alloc at creation, grow for a lazy buffer); a failure returns the owner's message
+#define CTX_MEM(op, field, bytes, kind)                                                  \
+  do {                                                                                   \
+    if (!c->mem.op(c->field, (long long)(bytes), (kind), "c->" #field)) return fail(SAE_ERR_HIP, "%s", c->mem.err); \
+  } while (0)
+#define CTX_ALLOC(field, bytes) CTX_MEM(alloc, field, bytes, DM_DEVICE)
 
 // the getters of the last forward refuse after a file pass (after_search = false: after a statistics pass only)
 static int no_forward_left(const sae_ctx* c, bool after_search = true) {

@@ -73,6 +73,20 @@ static int file_pass_begin(const FilePassKind& kind, sae_ctx* c, const void* x, 
   return SAE_OK;
 }
 
+// The passes' one scratch (c->pass_scratch, grow-only): a pass names the bytes of each area it needs and gets their bases, each
+// aligned to 256 bytes.  The areas hold whatever the last pass left there -- a pass clears what its kernels assume clear.
+static int pass_scratch(sae_ctx* c, std::initializer_list<int64_t> bytes, char** base) {
+  int64_t total = 0;
+  for (const int64_t b : bytes) total += round_up(b, 256);
+  CTX_MEM(grow, pass_scratch, total, DM_DEVICE);     // (a grow frees first: hipFree waits for the work that still reads the old block)
+  char* p = c->pass_scratch;
+  for (const int64_t b : bytes) {
+    *base++ = p;
+    p += round_up(b, 256);
+  }
+  return SAE_OK;
+}
+
 // L1: the training forward's (l1_prepare) weights preparation and bf16 copy of x, then the GEMM arguments of its encoder -- for the epilogue the pass
 // brings (EpiSearch, EpiStats) where the GEMM streams, for file_pass_l1_encode and a reduction of the stored latent where it does not
 template <typename T>
@@ -202,21 +216,18 @@ extern "C" int sae_file_top_features(const uint64_t* file_keys, int64_t n_files,
 }
 
 // ---- feature statistics (stats.h): per-latent firing counts, sums, maxima and the L0 histogram of one batch of files
-// fs_slab: the slab [max_rows_p / STATS_RB][n] x 4 words of 4 bytes, then (L1) one L0 byte per row and 64 latents
+// its scratch area: the slab [max_rows_p / STATS_RB][n] x 4 words of 4 bytes, then (L1) one L0 byte per row and 64 latents.  Every
+// slab row and L0 byte a call reads it has written with plain stores first: nothing to clear.
 static int64_t stats_slab_words(const sae_ctx* c) { return (c->max_rows_p / STATS_RB) * (int64_t)c->n; }
-static uint8_t* stats_l0_bytes(const sae_ctx* c) { return (uint8_t*)c->fs_slab + stats_slab_words(c) * 16; }
-
-static int stats_ensure(sae_ctx* c) {
-  if (c->fs_slab) return SAE_OK;
-  const int64_t l0_bytes = c->topk ? 0 : c->max_rows_p * (int64_t)(c->n_p / 64);
-  HIP_TRY(hipMalloc(&c->fs_slab, (size_t)(stats_slab_words(c) * 16 + l0_bytes)));
-  return SAE_OK;
+static uint8_t* stats_l0_bytes(const sae_ctx* c, char* base) { return (uint8_t*)base + stats_slab_words(c) * 16; }
+static int64_t stats_scratch_bytes(const sae_ctx* c) {
+  return stats_slab_words(c) * 16 + (c->topk ? 0 : c->max_rows_p * (int64_t)(c->n_p / 64));
 }
 
-static StatsSlab stats_slab(sae_ctx* c) {
+static StatsSlab stats_slab(const sae_ctx* c, char* base) {
   const int64_t words = stats_slab_words(c);
   StatsSlab sl;
-  sl.cnt = (uint32_t*)c->fs_slab;
+  sl.cnt = (uint32_t*)base;
   sl.mx = sl.cnt + words;
   sl.sum = (float*)(sl.mx + words);
   sl.sq = sl.sum + words;
@@ -246,21 +257,21 @@ static void stats_launch_l0(Src src, int64_t M, int T, const int* lengths, int n
   hipLaunchKernelGGL(stats_l0_kernel<Src>, dim3(grid_for(M, 1024, 4)), dim3(256), 0, s, src, M, T, lengths, n + 1, o.hist, o.n_frames);
 }
 
-static void stats_launch_fold(sae_ctx* c, int nrb, const StatsOut& o, hipStream_t s) {
-  hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, stats_slab(c), nrb, c->n, o.fire, o.asum, o.asq,
-                     o.amax);
+static void stats_launch_fold(sae_ctx* c, const StatsSlab& sl, int nrb, const StatsOut& o, hipStream_t s) {
+  hipLaunchKernelGGL(stats_fold_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, sl, nrb, c->n, o.fire, o.asum, o.asq, o.amax);
 }
 
 // L1 statistics: where the streaming GEMM does not apply, or `unfused` is asked for, the ordinary encoder stores the latent and two
 // kernels reduce it (column statistics into the slab, row counts into the histogram).
 template <typename T>
-static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, const StatsOut& o, bool unfused, hipStream_t s) {
+static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, const StatsOut& o, bool unfused, char* scratch,
+                         hipStream_t s) {
   const int n_p = c->n_p;
   const GemmArgs g = file_pass_l1_front(c, x, M, s);
-  const StatsSlab sl = stats_slab(c);
+  const StatsSlab sl = stats_slab(c, scratch);
   const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
   if (!unfused && gemm_streams<OP_ROW, OP_ROW, EpiStats>(g)) {
-    uint8_t* l0b = stats_l0_bytes(c);
+    uint8_t* l0b = stats_l0_bytes(c, scratch);
     EpiStats e{};
     e.bias = c->P + c->nW; e.slab = sl; e.l0b = l0b; e.lengths = lengths; e.M = M; e.T = Trows; e.n = c->n; e.ncb = n_p / 64;
     e.inv_T = 1.0f / (float)Trows;
@@ -273,7 +284,7 @@ static int stats_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int
                        M, Trows, lengths, sl);
     stats_launch_l0(L0Latent{lat, n_p, c->n}, M, Trows, lengths, c->n, o, s);
   }
-  stats_launch_fold(c, nrb, o, s);
+  stats_launch_fold(c, sl, nrb, o, s);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }
@@ -283,7 +294,8 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
   int64_t M;
   if (int rc = file_pass_begin(kStatsPass, c, x, stats, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   if (misaligned(stats, 8)) return fail(SAE_ERR_INVALID, "the stats block must be 8-byte aligned");
-  if (int rc = stats_ensure(c)) return rc;
+  char* scratch;
+  if (int rc = pass_scratch(c, {stats_scratch_bytes(c)}, &scratch)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   const StatsOut o = stats_out(stats, c->n);
@@ -293,13 +305,13 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
     const int nrb = (int)((M + STATS_TK_RB - 1) / STATS_TK_RB);
     const unsigned short* vals = (const unsigned short*)c->top_vals;
     hipLaunchKernelGGL(stats_topk_cols_kernel, dim3((unsigned)nrb, (unsigned)((c->n + STATS_TK_SEG - 1) / STATS_TK_SEG)), dim3(64), 0, s,
-                       c->top_idx, vals, c->k, M, Trows, lengths, c->n, stats_slab(c));
+                       c->top_idx, vals, c->k, M, Trows, lengths, c->n, stats_slab(c, scratch));
     stats_launch_l0(L0Topk{vals, c->k}, M, Trows, lengths, c->n, o, s);
-    stats_launch_fold(c, nrb, o, s);
+    stats_launch_fold(c, stats_slab(c, scratch), nrb, o, s);
     HIP_TRY(hipGetLastError());
   } else {
     const bool unfused = (flags & SAE_STATS_UNFUSED) != 0;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return stats_l1_impl(c, xt, M, Trows, lengths, o, unfused, s); })) return rc;
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return stats_l1_impl(c, xt, M, Trows, lengths, o, unfused, scratch, s); })) return rc;
   }
   file_pass_end(kStatsPass, c);
   return SAE_OK;
@@ -308,11 +320,9 @@ extern "C" int sae_stats_files(sae_ctx* c, const void* x, int64_t n_files, int64
 // ---- feature co-activation (coact.h): C += Zt Zt^T of one batch of files on the i8 MFMA, and the neighbour keys of rows of C
 static_assert(SAE_COACT_JACCARD == CO_JACCARD && SAE_COACT_COND == CO_COND && SAE_COACT_COUNT == CO_COUNT, "freud_sae.h and coact.h disagree");
 
-static int coact_ensure(sae_ctx* c) {
-  if (c->co_zt) return SAE_OK;
-  HIP_TRY(hipMalloc((void**)&c->co_zt, (size_t)((int64_t)c->n_p * round_up(c->max_rows_p, CO_BK))));
-  return SAE_OK;
-}
+// its scratch area: the int8 mask Zt [n_p][round_up(max_rows_p, CO_BK)], every byte of a call's [n_p][Kp] written by its pack (L1)
+// or cleared before the scatter (TopK)
+static int64_t coact_zt_bytes(const sae_ctx* c) { return (int64_t)c->n_p * round_up(c->max_rows_p, CO_BK); }
 
 // the K split of coact.h's header: enough slices of the Kp / CO_BK steps that `tiles` output tiles fill CO_MIN_WGS workgroups, `per` steps each
 struct KSplit { int ksplit, per; };
@@ -337,20 +347,21 @@ static int coact_launch_update(sae_ctx* c, const int8_t* zt, int64_t Kp, int n_p
   return SAE_OK;
 }
 
-// the batch's activity mask into c->co_zt: the encoder as encode() runs it, then the mask pack (sae_coact_files, sae_label_files)
-static int coact_encode_pack(sae_ctx* c, const void* x, int64_t M, int Trows, int x_dtype, const int32_t* lengths, int64_t Kp, void* stream) {
+// the batch's activity mask into zt: the encoder as encode() runs it, then the mask pack (sae_coact_files, sae_label_files)
+static int coact_encode_pack(sae_ctx* c, const void* x, int64_t M, int Trows, int x_dtype, const int32_t* lengths, int8_t* zt, int64_t Kp,
+                             void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
   ev_begin(c, KID_COACT_PACK, s);
   hipError_t memset_zt = hipSuccess;
   if (c->topk) {                            // the selection scattered into the zeroed mask
-    memset_zt = hipMemsetAsync(c->co_zt, 0, (size_t)((int64_t)c->n_p * Kp), s);
+    memset_zt = hipMemsetAsync(zt, 0, (size_t)((int64_t)c->n_p * Kp), s);
     if (memset_zt == hipSuccess)
       hipLaunchKernelGGL(coact_pack_topk_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
-                         c->k, M, Trows, lengths, c->n, c->co_zt, Kp);
+                         c->k, M, Trows, lengths, c->n, zt, Kp);
   } else {
     hipLaunchKernelGGL(coact_pack_l1_kernel, dim3((unsigned)(Kp / 64), (unsigned)(c->n_p / 64)), dim3(256), 0, s, (const unsigned short*)c->c,
-                       (int64_t)c->n_p, c->n, M, Trows, lengths, c->co_zt, Kp);
+                       (int64_t)c->n_p, c->n, M, Trows, lengths, zt, Kp);
   }
   ev_end(c, KID_COACT_PACK, s);             // (the bracket closes whatever the memset answered)
   HIP_TRY(memset_zt);
@@ -363,10 +374,11 @@ extern "C" int sae_coact_files(sae_ctx* c, const void* x, int64_t n_files, int64
   int64_t M;
   if (int rc = file_pass_begin(kCoactPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   if (misaligned(counts, 4)) return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned");
-  if (int rc = coact_ensure(c)) return rc;
+  char* zt;
+  if (int rc = pass_scratch(c, {coact_zt_bytes(c)}, &zt)) return rc;
   const int64_t Kp = round_up(M, CO_BK);
-  if (int rc = coact_encode_pack(c, x, M, (int)rows_per_file, x_dtype, lengths, Kp, stream)) return rc;
-  if (int rc = coact_launch_update(c, c->co_zt, Kp, c->n_p, c->n, counts, (hipStream_t)stream)) return rc;
+  if (int rc = coact_encode_pack(c, x, M, (int)rows_per_file, x_dtype, lengths, (int8_t*)zt, Kp, stream)) return rc;
+  if (int rc = coact_launch_update(c, (int8_t*)zt, Kp, c->n_p, c->n, counts, (hipStream_t)stream)) return rc;
   file_pass_end(kCoactPass, c);
   return SAE_OK;
 }
@@ -388,16 +400,6 @@ extern "C" int sae_coact_neighbor_keys(const int32_t* counts, int64_t n, int64_t
 static_assert(SAE_LABEL_F1 == LB_F1 && SAE_LABEL_PRECISION == LB_PRECISION && SAE_LABEL_RECALL == LB_RECALL && SAE_LABEL_COUNT == LB_COUNT &&
               SAE_LABEL_MAX_CLASSES == LB_MAX_CLASSES && SAE_LABEL_MAX_SLOTS == LB_MAX_SLOTS, "freud_sae.h and labels.h disagree");
 
-static int label_ensure(sae_ctx* c, int C_p) {
-  if (C_p <= c->lb_rows) return SAE_OK;
-  if (c->lb_lt) HIP_TRY(hipFree(c->lb_lt));          // (hipFree waits for the work that still reads it)
-  c->lb_lt = nullptr;
-  c->lb_rows = 0;
-  HIP_TRY(hipMalloc((void**)&c->lb_lt, (size_t)((int64_t)C_p * round_up(c->max_rows_p, CO_BK))));
-  c->lb_rows = C_p;
-  return SAE_OK;
-}
-
 extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
                                const int32_t* labels, int n_slots, int n_classes, int flags, int32_t* counts, int64_t* label_count,
                                void* stream) {
@@ -409,19 +411,21 @@ extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64
     return fail(SAE_ERR_INVALID, "the count table must be 4-byte aligned and label_count 8-byte aligned");
   if (int rc = file_pass_begin(kLabelPass, c, x, counts, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   const int C_p = (int)round_up(n_classes + 1, CO_BM);
-  if (int rc = coact_ensure(c)) return rc;
-  if (int rc = label_ensure(c, C_p)) return rc;
+  // two scratch areas: co-activation's mask and the int8 label pack Lt [C_p][round_up(max_rows_p, CO_BK)] (its [C_p][Kp] cleared below)
+  char* area[2];
+  if (int rc = pass_scratch(c, {coact_zt_bytes(c), (int64_t)C_p * round_up(c->max_rows_p, CO_BK)}, area)) return rc;
+  int8_t *zt = (int8_t*)area[0], *lt = (int8_t*)area[1];
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   const int64_t Kp = round_up(M, CO_BK);
-  if (int rc = coact_encode_pack(c, x, M, Trows, x_dtype, lengths, Kp, stream)) return rc;
+  if (int rc = coact_encode_pack(c, x, M, Trows, x_dtype, lengths, zt, Kp, stream)) return rc;
 
   ev_begin(c, KID_LABEL_PACK, s);
-  const hipError_t memset_lt = hipMemsetAsync(c->lb_lt, 0, (size_t)((int64_t)C_p * Kp), s);
+  const hipError_t memset_lt = hipMemsetAsync(lt, 0, (size_t)((int64_t)C_p * Kp), s);
   if (memset_lt == hipSuccess) {
     hipLaunchKernelGGL(label_pack_kernel, dim3(grid_for(M * n_slots, 4096)), dim3(256), 0, s, labels, n_slots, n_classes, M, Trows, lengths,
-                       c->lb_lt, Kp);
-    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)(n_classes + 1)), dim3(256), 0, s, c->lb_lt, Kp, (unsigned long long*)label_count);
+                       lt, Kp);
+    hipLaunchKernelGGL(label_count_kernel, dim3((unsigned)(n_classes + 1)), dim3(256), 0, s, lt, Kp, (unsigned long long*)label_count);
   }
   ev_end(c, KID_LABEL_PACK, s);             // (the bracket closes whatever the memset answered)
   HIP_TRY(memset_lt);
@@ -432,8 +436,8 @@ extern "C" int sae_label_files(sae_ctx* c, const void* x, int64_t n_files, int64
   const KSplit ks = coact_ksplit(ntr * ntc, Kp);
   const dim3 grid((unsigned)ntc, (unsigned)ntr, (unsigned)ks.ksplit);
   ev_begin(c, KID_LABEL_UPDATE, s);
-  if (ks.ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, ks.per, counts);
-  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, c->lb_lt, c->co_zt, Kp, n_classes + 1, c->n, ks.per, counts);
+  if (ks.ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, lt, zt, Kp, n_classes + 1, c->n, ks.per, counts);
+  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, lt, zt, Kp, n_classes + 1, c->n, ks.per, counts);
   ev_end(c, KID_LABEL_UPDATE, s);
   HIP_TRY(hipGetLastError());
   file_pass_end(kLabelPass, c);
@@ -460,16 +464,6 @@ extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count,
 // ---- activation histograms (hist.h): per latent the histogram of its value on every counted frame and of every file's maximum,
 // and the frame histogram of a few chosen latents split by label
 static_assert(SAE_HIST_MAX_BINS == HB_MAX_BINS && SAE_HIST_MAX_SEL == HIST_MAX_SEL, "freud_sae.h, hist_bins.h and hist.h disagree");
-
-static int hist_ensure(sae_ctx* c, int64_t n_files) {
-  if (!c->topk || n_files <= c->hs_files) return SAE_OK;
-  if (c->hs_fmax) HIP_TRY(hipFree(c->hs_fmax));        // (hipFree waits for the work that still reads it)
-  c->hs_fmax = nullptr;
-  c->hs_files = 0;
-  HIP_TRY(hipMalloc((void**)&c->hs_fmax, (size_t)(n_files * c->n) * 4));
-  c->hs_files = n_files;
-  return SAE_OK;
-}
 
 // the stored latent of file_pass_encode binned by hist_l1_kernel.  Chunks of whole files: the fewest files per chunk that still give
 // HIST_MIN_WGS workgroups (every chunk flushes its non-empty bins with global adds, so fewer chunks are cheaper).  Columns per
@@ -506,7 +500,11 @@ extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_
   for (const void* p : {(const void*)frame_hist, (const void*)file_max_hist, (const void*)n_frames, (const void*)label_hist, (const void*)label_count})
     if (misaligned(p, 8)) return fail(SAE_ERR_INVALID, "the histogram arrays must be 8-byte aligned");
   if (int rc = file_pass_begin(kHistPass, c, x, frame_hist, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
-  if (int rc = hist_ensure(c, n_files)) return rc;
+  // TopK scratch: the file maxima [n_files][n] of this batch (cleared below: the scatter takes maxima into it)
+  char* scratch = nullptr;
+  if (c->topk)
+    if (int rc = pass_scratch(c, {n_files * c->n * 4}, &scratch)) return rc;
+  uint32_t* fmax = (uint32_t*)scratch;
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
@@ -515,11 +513,11 @@ extern "C" int sae_hist_files(sae_ctx* c, const void* x, int64_t n_files, int64_
   hipError_t memset_fmax = hipSuccess;
   hipLaunchKernelGGL(hist_frames_kernel, dim3(1), dim3(256), 0, s, n_files, Trows, lengths, n_frames, n_sel > 0 ? label_count + n_classes : nullptr);
   if (c->topk) {
-    memset_fmax = hipMemsetAsync(c->hs_fmax, 0, (size_t)(n_files * c->n) * 4, s);
+    memset_fmax = hipMemsetAsync(fmax, 0, (size_t)(n_files * c->n) * 4, s);
     if (memset_fmax == hipSuccess) {
       hipLaunchKernelGGL(hist_topk_scatter_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
-                         c->k, M, Trows, lengths, c->n, sp, frame_hist, c->hs_fmax);
-      hipLaunchKernelGGL(hist_topk_finish_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, c->hs_fmax, n_files, c->n, sp, n_frames,
+                         c->k, M, Trows, lengths, c->n, sp, frame_hist, fmax);
+      hipLaunchKernelGGL(hist_topk_finish_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, fmax, n_files, c->n, sp, n_frames,
                          frame_hist, file_max_hist);
     }
   } else {
@@ -699,7 +697,10 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
   int64_t M;
   if (int rc = file_pass_begin(kManipPass, c, x, standard, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_manipulate_files: the TopK decode serves d_model <= 1536");
-  if (!c->mn_w) HIP_TRY(hipMalloc((void**)&c->mn_w, (size_t)SM_MAX_EDITS * c->d_p * 4));
+  // scratch: the operand rows [SM_MAX_EDITS][d_p] (manip_rows_kernel writes every element the apply reads)
+  char* scratch;
+  if (int rc = pass_scratch(c, {(int64_t)SM_MAX_EDITS * c->d_p * 4}, &scratch)) return rc;
+  float* wrows = (float*)scratch;
   hipStream_t s = (hipStream_t)stream;
   const int d = c->d;
   // the bf16 eval forward: encode() -- and the state sae_eval leaves (latent rows, indices, metrics)
@@ -716,11 +717,11 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
   if (c->topk) {
     hipLaunchKernelGGL(manip_series_topk_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, c->top_idx, c->top_vals, c->k, M, ed, series);
     hipLaunchKernelGGL(manip_rows_kernel, dim3((d + 255) / 256, n_edits), dim3(256), 0, s, c->Wd_b, (int64_t)c->d_p, (int64_t)1, d, ed,
-                       c->mn_w, c->d_p);
+                       wrows, c->d_p);
   } else {
     hipLaunchKernelGGL(manip_series_kernel, dim3(grid_for(M * n_edits, 4096)), dim3(256), 0, s, c->c, (int64_t)c->n_p, M, ed, series);
     hipLaunchKernelGGL(manip_rows_kernel, dim3((d + 255) / 256, n_edits), dim3(256), 0, s, c->Wb, (int64_t)1, (int64_t)c->n_p, d, ed,
-                       c->mn_w, c->d_p);
+                       wrows, c->d_p);
   }
   ev_end(c, KID_MANIP_SERIES, s);
 
@@ -732,8 +733,8 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
     // groups of 8 half waves, a multiple of the slabs: every frame x slab once, at most ~4096 groups striding over the frames
     const int64_t per_slab = std::min<int64_t>((M + 7) / 8, std::max<int64_t>(4096 / nslab, 1));
     const dim3 grid((unsigned)(per_slab * nslab));
-    if (vec) hipLaunchKernelGGL(manip_apply_kernel<4>, grid, dim3(256), 0, s, standard, series, c->mn_w, c->d_p, M, d, nslab, ed, manipulated);
-    else hipLaunchKernelGGL(manip_apply_kernel<1>, grid, dim3(256), 0, s, standard, series, c->mn_w, c->d_p, M, d, nslab, ed, manipulated);
+    if (vec) hipLaunchKernelGGL(manip_apply_kernel<4>, grid, dim3(256), 0, s, standard, series, wrows, c->d_p, M, d, nslab, ed, manipulated);
+    else hipLaunchKernelGGL(manip_apply_kernel<1>, grid, dim3(256), 0, s, standard, series, wrows, c->d_p, M, d, nslab, ed, manipulated);
   }
   ev_end(c, KID_MANIP_APPLY, s);
   HIP_TRY(hipGetLastError());
@@ -744,14 +745,14 @@ extern "C" int sae_manipulate_files(sae_ctx* c, const void* x, int64_t n_files, 
 // and per latent the attribution sums P_j = sum a_j (r . w_j), sum a_j^2 and |w_j|^2
 static_assert(SAE_RECON_UNFUSED == 1, "freud_sae.h and passes.hip disagree");
 
-struct ReconScratch {           // c->rc_buf carved up (floats)
-  float *xr, *slab_p, *slab_q, *rowpart, *dimpart, *p;
+struct ReconScratch {           // its scratch area carved up (floats): x_hat / r, the slabs, the row and dimension partials, TopK's p.
+  float *xr, *slab_p, *slab_q, *rowpart, *dimpart, *p;      // All written with plain stores before the call reads them: nothing to clear.
 };
 
-static ReconScratch recon_scratch(const sae_ctx* c) {
+static ReconScratch recon_scratch(const sae_ctx* c, char* base) {
   const int64_t rows = c->cfg.max_rows, nrb = c->max_rows_p / STATS_RB, nch = c->d_p / RC_CW;
   ReconScratch r;
-  r.xr = c->rc_buf;
+  r.xr = (float*)base;
   r.slab_p = r.xr + round_up(rows * c->d, 4);
   r.slab_q = r.slab_p + nrb * c->n_p;
   r.rowpart = r.slab_q + nrb * c->n_p;
@@ -760,12 +761,9 @@ static ReconScratch recon_scratch(const sae_ctx* c) {
   return r;
 }
 
-static int recon_ensure(sae_ctx* c) {
-  if (c->rc_buf) return SAE_OK;
-  const ReconScratch r = recon_scratch(c);        // (offsets from a null base: only their differences are used)
-  const int64_t floats = (r.p - r.xr) + (c->topk ? c->cfg.max_rows * (int64_t)c->k : 0);
-  HIP_TRY(hipMalloc((void**)&c->rc_buf, (size_t)floats * 4));
-  return SAE_OK;
+static int64_t recon_scratch_bytes(const sae_ctx* c) {
+  const ReconScratch r = recon_scratch(c, nullptr);        // (offsets from a null base: only their differences are used)
+  return ((r.p - r.xr) + (c->topk ? c->cfg.max_rows * (int64_t)c->k : 0)) * 4;
 }
 
 static ReconOut recon_out(void* block, int n, int d) {
@@ -803,11 +801,10 @@ static void recon_launch_fold(sae_ctx* c, const ReconScratch& sc, int nrb_lat, i
 // launch_gemm would take it (gemm_streams), in the tile forms elsewhere and with `unfused` (SAE_RECON_UNFUSED).
 template <typename T>
 static int recon_l1_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
-                         double* file_out, float* resid, bool unfused, hipStream_t s) {
+                         double* file_out, float* resid, bool unfused, const ReconScratch& sc, hipStream_t s) {
   const int n_p = c->n_p;
   int64_t Mp;
   if (int rc = file_pass_l1_encode(c, x, M, s, nullptr, &Mp)) return rc;
-  const ReconScratch sc = recon_scratch(c);
 
   ev_begin(c, KID_RECON_DECODE, s);
   int rc = decode_l1_latent(c, c->c, round_up(M, c->row_pad) / 128, M, sc.xr, s);      // (sae_decode's M_p)
@@ -838,8 +835,7 @@ static int recon_l1_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int
 
 template <typename T>
 static int recon_topk_impl(sae_ctx* c, const T* x, int64_t M, int64_t n_files, int Trows, const int* lengths, const ReconOut& o,
-                           double* file_out, float* resid, hipStream_t s) {
-  const ReconScratch sc = recon_scratch(c);
+                           double* file_out, float* resid, const ReconScratch& sc, hipStream_t s) {
   const int64_t rows_cover = round_up(M, STATS_RB);
   ev_begin(c, KID_RECON_DECODE, s);
   manip_decode_topk(c, M, sc.xr, s);
@@ -879,18 +875,20 @@ extern "C" int sae_recon_files(sae_ctx* c, const void* x, int64_t n_files, int64
   if (c->topk && c->d_p > 1536) return fail(SAE_ERR_INVALID, "sae_recon_files: the TopK decode serves d_model <= 1536");
   if ((c->max_rows_p / STATS_RB) * (int64_t)c->n_p >= ((int64_t)1 << 31))
     return fail(SAE_ERR_INVALID, "sae_recon_files: max_rows / 128 x n_dict = %lld slab entries >= 2^31", (long long)((c->max_rows_p / STATS_RB) * (int64_t)c->n_p));
-  if (int rc = recon_ensure(c)) return rc;
+  char* scratch;
+  if (int rc = pass_scratch(c, {recon_scratch_bytes(c)}, &scratch)) return rc;
+  const ReconScratch sc = recon_scratch(c, scratch);
   hipStream_t s = (hipStream_t)stream;
   const int Trows = (int)rows_per_file;
   const ReconOut o = recon_out(block, c->n, c->d);
   if (c->topk) {
     // the sparse decode and the attribution of encode()'s selection
     if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_topk_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, s); }))
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_topk_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, sc, s); }))
       return rc;
   } else {
     const bool unfused = (flags & SAE_RECON_UNFUSED) != 0;
-    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_l1_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, unfused, s); }))
+    if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return recon_l1_impl(c, xt, M, n_files, Trows, lengths, o, file_out, resid, unfused, sc, s); }))
       return rc;
   }
   file_pass_end(kReconPass, c);
@@ -943,7 +941,7 @@ extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int
 static_assert(SAE_FRONTIER_MAX_K == FR_MAX_K && SAE_FRONTIER_MAX_TAU == FR_MAX_TAU && FR_MAX_K <= CL_MAX_K && FR_UNIT % 4 == 0,
               "freud_sae.h, frontier.h and collect.h disagree");
 
-struct FrontierScratch {        // c->fr_buf carved up
+struct FrontierScratch {        // its scratch area carved up
   float* vals;                  // [max_rows][kcap] the slots, kcap = min(FR_MAX_K, k or n)
   int* idx;
   int64_t* cstats;              // [8] the collect kernels' totals (not reported)
@@ -953,10 +951,10 @@ struct FrontierScratch {        // c->fr_buf carved up
   int64_t bytes;
 };
 
-static FrontierScratch frontier_scratch(const sae_ctx* c) {
+static FrontierScratch frontier_scratch(const sae_ctx* c, char* base) {
   const int64_t rows = c->cfg.max_rows, kcap = std::min<int64_t>(FR_MAX_K, c->topk ? c->k : c->n);
   const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
-  char* p = c->fr_buf;
+  char* p = base;
   auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
   FrontierScratch f;
   f.vals = (float*)take(rows * kcap * 4);
@@ -967,16 +965,8 @@ static FrontierScratch frontier_scratch(const sae_ctx* c) {
   f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
   f.part = (float*)take(units * FR_PART_LD * 4);
   f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
-  f.bytes = p - c->fr_buf;
+  f.bytes = p - base;
   return f;
-}
-
-static int frontier_ensure(sae_ctx* c) {
-  if (c->fr_buf) return SAE_OK;
-  const int64_t bytes = frontier_scratch(c).bytes;        // (offsets from a null base: only their differences are used)
-  HIP_TRY(hipMalloc((void**)&c->fr_buf, (size_t)bytes));
-  HIP_TRY(hipMemset(frontier_scratch(c).cstats, 0, 64));       // (the collect kernels add to it on every call; it is never read)
-  return SAE_OK;
 }
 
 static FrOut frontier_out(void* block, int n_tau, int K, int d) {
@@ -994,8 +984,10 @@ static FrOut frontier_out(void* block, int n_tau, int K, int d) {
 
 template <typename T>
 static int frontier_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const FrOut& o,
-                         hipStream_t s) {
-  const FrontierScratch f = frontier_scratch(c);
+                         const FrontierScratch& f, hipStream_t s) {
+  // the collect kernels ADD their totals to cstats (never reported): cleared, since the area holds another pass's leftovers; every
+  // other part of the scratch is written with plain stores before it is read
+  HIP_TRY(hipMemsetAsync(f.cstats, 0, 64, s));
   ev_begin(c, KID_FRONTIER_SORT, s);
   collect_launch(c, M, K, f.vals, f.idx, f.cstats, s, f.row_nnz);
   ev_end(c, KID_FRONTIER_SORT, s);
@@ -1044,11 +1036,13 @@ extern "C" int sae_frontier_files(sae_ctx* c, const void* x, int64_t n_files, in
   }
   if (c->d_p > FR_MAX_D) return fail(SAE_ERR_INVALID, "sae_frontier_files: the walk serves d_model <= %d", FR_MAX_D);
   if (c->topk && c->k > CL_MAX_K) return fail(SAE_ERR_INVALID, "sae_frontier_files: k=%d > %d", c->k, CL_MAX_K);
-  if (int rc = frontier_ensure(c)) return rc;
+  char* scratch;
+  if (int rc = pass_scratch(c, {frontier_scratch(c, nullptr).bytes}, &scratch)) return rc;        // (from a null base: the size alone)
+  const FrontierScratch f = frontier_scratch(c, scratch);
   hipStream_t s = (hipStream_t)stream;
   if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
   const FrOut o = frontier_out(block, n_tau, K, c->d);
-  if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return frontier_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, s); })) return rc;
+  if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return frontier_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, f, s); })) return rc;
   file_pass_end(kFrontierPass, c);
   return SAE_OK;
 }
@@ -1164,16 +1158,14 @@ static int resample_refuse(const sae_ctx* c, const char* fn) {
 
 template <typename T>
 static int resample_l1_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, float* row_loss, unsigned long long* fire,
-                            hipStream_t s) {
+                            const StatsSlab& sl, const ReconScratch& sc, hipStream_t s) {
   if (int rc = file_pass_l1_encode(c, x, M, s)) return rc;
   // the firing counts of the stored latent: the unfused statistics path's column reduction, folded for the counts alone
   const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
-  const StatsSlab sl = stats_slab(c);
   hipLaunchKernelGGL(stats_colreduce_kernel, dim3((unsigned)((c->n + 255) / 256), (unsigned)nrb), dim3(256), 0, s, (const unsigned short*)c->c,
                      (int64_t)c->n_p, c->n, M, Trows, lengths, sl);
   hipLaunchKernelGGL(rs_fire_fold_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, s, sl.cnt, nrb, c->n, fire);
   // x_hat of exactly that latent and the residual sweep, as sae_recon_files runs them -- and no attribution GEMM
-  const ReconScratch sc = recon_scratch(c);
   ev_begin(c, KID_RECON_DECODE, s);
   const int rc = decode_l1_latent(c, c->c, round_up(M, c->row_pad) / 128, M, sc.xr, s);
   ev_end(c, KID_RECON_DECODE, s);
@@ -1196,11 +1188,13 @@ extern "C" int sae_resample_files(sae_ctx* c, const void* x, int64_t n_files, in
   if (misaligned(row_loss, 4) || misaligned(fire_count, 8)) return fail(SAE_ERR_INVALID, "row_loss must be 4-byte aligned, fire_count 8-byte aligned");
   if ((c->max_rows_p / STATS_RB) * (int64_t)c->n_p >= ((int64_t)1 << 31))
     return fail(SAE_ERR_INVALID, "sae_resample_files: max_rows / 128 x n_dict = %lld slab entries >= 2^31", (long long)((c->max_rows_p / STATS_RB) * (int64_t)c->n_p));
-  if (int rc = stats_ensure(c)) return rc;
-  if (int rc = recon_ensure(c)) return rc;
+  char* area[2];                // the statistics pass's slab and the reconstruction report's scratch, side by side
+  if (int rc = pass_scratch(c, {stats_scratch_bytes(c), recon_scratch_bytes(c)}, area)) return rc;
+  const StatsSlab sl = stats_slab(c, area[0]);
+  const ReconScratch sc = recon_scratch(c, area[1]);
   hipStream_t s = (hipStream_t)stream;
   if (int rc = with_x_type(x_dtype, x, [&](auto* xt) {
-        return resample_l1_impl(c, xt, M, (int)rows_per_file, lengths, row_loss, reinterpret_cast<unsigned long long*>(fire_count), s);
+        return resample_l1_impl(c, xt, M, (int)rows_per_file, lengths, row_loss, reinterpret_cast<unsigned long long*>(fire_count), sl, sc, s);
       }))
     return rc;
   file_pass_end(kResamplePass, c);
