@@ -76,7 +76,8 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "fwd_bwd_total", "coact_pack", "coact_update", "manip_series", "manip_decode",
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
                                               "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing",
-                                              "frontier_sort", "frontier_walk", "frontier_fold"};
+                                              "frontier_sort", "frontier_walk", "frontier_fold", "pursuit_gemm", "pursuit_step",
+                                              "pursuit_fold"};
 
 // fused d = 384 L1 path with the peer exchange: the batch statistics are exchanged inside finalize_losses_kernel (StatsPush)
 // (FREUD_DP_STATS=stream: the statistics leave the critical path instead -- a pass over x and their exchange on the communication stream

@@ -134,6 +134,9 @@ enum KernelId {
   KID_FRONTIER_SORT,   // sparsity frontier (frontier.h): the collect kernels into scratch, the walk alone, the dimension sums + the fold
   KID_FRONTIER_WALK,
   KID_FRONTIER_FOLD,
+  KID_PURSUIT_GEMM,    // pursuit frontier (pursuit.h): the K selection GEMMs with EpiPursuit, the K step kernels, the finish + dimension sums + fold
+  KID_PURSUIT_STEP,
+  KID_PURSUIT_FOLD,
   KID_COUNT
 };
 constexpr int EV_RING = 64;
@@ -145,7 +148,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER, LAST_PURSUIT };
 
 // A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
 // of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
@@ -166,8 +169,9 @@ static const FilePassKind kCollectPass = {"sae_collect_files", "collect the feat
 static const FilePassKind kTimingPass = {"sae_timing_files", "time the features in a bf16 context", "timing", SAE_TIMING_ONE_CHUNK, LAST_TIMING, "a feature timing pass"};
 static const FilePassKind kResamplePass = {"sae_resample_files", "resample in a bf16 context", "resample", 0, LAST_RESAMPLE, "a resampling pass"};
 static const FilePassKind kFrontierPass = {"sae_frontier_files", "build the sparsity frontier in a bf16 context", "frontier", 0, LAST_FRONTIER, "a sparsity frontier pass"};
+static const FilePassKind kPursuitPass = {"sae_pursuit_files", "run the pursuit in a bf16 context", "pursuit", 0, LAST_PURSUIT, "a pursuit frontier pass"};
 static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
-                                                  &kTimingPass, &kResamplePass, &kFrontierPass};
+                                                  &kTimingPass, &kResamplePass, &kFrontierPass, &kPursuitPass};
 
 struct sae_ctx {
   // Every pointer field below that the context OWNS is allocated through `mem` (dev_mem.h; the last member, behind everything a step

@@ -23,6 +23,7 @@
 #include "dict_match.h"
 #include "recon.h"
 #include "frontier.h"
+#include "pursuit.h"
 #include "resample.h"
 #include "input_stats.h"
 #include "input_cov_plan.h"
@@ -1044,6 +1045,151 @@ extern "C" int sae_frontier_files(sae_ctx* c, const void* x, int64_t n_files, in
   const FrOut o = frontier_out(block, n_tau, K, c->d);
   if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return frontier_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, f, s); })) return rc;
   file_pass_end(kFrontierPass, c);
+  return SAE_OK;
+}
+
+// ---- pursuit frontier (pursuit.h): every counted frame coded greedily against the decoder directions -- K (selection GEMM, step)
+// launch pairs on the caller's stream, then the frontier's own fold
+static_assert(SAE_PURSUIT_MAX_K == PU_MAX_K && SAE_PURSUIT_MAX_TAU == PU_MAX_TAU, "freud_sae.h and pursuit.h disagree");
+
+struct PursuitScratch {         // its scratch area carved up
+  float* r32;                   // [max_rows_p][d_p] the fp32 residual
+  unsigned short* rho;          // [max_rows_p][d_p] its bf16 image: the A operand of the selection GEMM
+  unsigned long long* rowkey;   // [max_rows_p] the row's best key of the current step
+  float *q, *z;                 // [n_p] the per-direction constants
+  uint32_t *rowstate, *rowinfo; // [max_rows]
+  float* err;                   // [max_rows][K + 1] the rows' e_s (the caller's trace_err instead when a trace is asked for)
+  unsigned short* bud;          // [max_rows][FR_MAX_TAU]
+  float *part, *dimpart;        // [units][FR_PART_LD], [128-row blocks][2][d_p]
+  unsigned long long* unused;   // [2] where the shared fold adds the frontier's cut counts (not reported)
+  int64_t bytes;
+};
+
+static PursuitScratch pursuit_scratch(const sae_ctx* c, int K, char* base) {
+  const int64_t rows = c->cfg.max_rows, rows_p = c->max_rows_p;
+  const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
+  char* p = base;
+  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
+  PursuitScratch f;
+  f.r32 = (float*)take(rows_p * c->d_p * 4);
+  f.rho = (unsigned short*)take(rows_p * c->d_p * 2);
+  f.rowkey = (unsigned long long*)take(rows_p * 8);
+  f.q = (float*)take((int64_t)c->n_p * 4);
+  f.z = (float*)take((int64_t)c->n_p * 4);
+  f.rowstate = (uint32_t*)take(rows * 4);
+  f.rowinfo = (uint32_t*)take(rows * 4);
+  f.err = (float*)take(rows * (K + 1) * 4);
+  f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
+  f.part = (float*)take(units * FR_PART_LD * 4);
+  f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
+  f.unused = (unsigned long long*)take(16);
+  f.bytes = p - base;
+  return f;
+}
+
+struct PursuitOut {             // the caller's block (include/freud_sae.h, SAE_PURSUIT_*)
+  FrOut fold;                   // what the frontier's fold adds: n_frames, sse, sum_x, sum_x_sq, budget
+  unsigned long long *steps, *picks, *in_support;
+};
+
+static PursuitOut pursuit_out(void* block, int n_tau, int K, int d, int n, const PursuitScratch& f) {
+  char* b = (char*)block;
+  PursuitOut o;
+  o.fold.n_frames = (unsigned long long*)(b + SAE_PURSUIT_N_FRAMES(n_tau, K, d, n));
+  o.fold.rows_cut = f.unused;
+  o.fold.active_cut = f.unused + 1;
+  o.fold.sse = (double*)(b + SAE_PURSUIT_SSE(n_tau, K, d, n));
+  o.fold.sx = (double*)(b + SAE_PURSUIT_SUM_X(n_tau, K, d, n));
+  o.fold.sxx = (double*)(b + SAE_PURSUIT_SUM_X_SQ(n_tau, K, d, n));
+  o.fold.budget = (unsigned long long*)(b + SAE_PURSUIT_BUDGET(n_tau, K, d, n));
+  o.steps = (unsigned long long*)(b + SAE_PURSUIT_STEPS(n_tau, K, d, n));
+  o.picks = (unsigned long long*)(b + SAE_PURSUIT_PICKS(n_tau, K, d, n));
+  o.in_support = (unsigned long long*)(b + SAE_PURSUIT_IN_SUPPORT(n_tau, K, d, n));
+  return o;
+}
+
+template <typename T>
+static int pursuit_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const PursuitOut& o,
+                        const PursuitScratch& f, float* err, const PuTrace& tr, hipStream_t s) {
+  // the operand rows [n_p][d_p] and the bias, as the frontier takes them
+  const bf16_t* W = c->topk ? c->Wd_b : c->Wt;
+  const float* b = c->topk ? c->P + 2 * c->nW + c->n_p : nullptr;
+  const float inv_T = 1.0f / (float)Trows;
+  int64_t Mp = round_up(M, 128);
+  if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);        // (an even number of row blocks: the 256-edge tile grid)
+  PuSupport sup{};
+  if (c->topk) { sup.top_idx = c->top_idx; sup.top_vals = (const unsigned short*)c->top_vals; sup.k_sel = c->k; }
+  else { sup.lat = (const unsigned short*)c->c; sup.lat_ld = c->n_p; }
+
+  // (the constants and the initialiser run once per call: outside the per-step brackets, which then hold K records each)
+  hipLaunchKernelGGL(pursuit_const_kernel, dim3((unsigned)((c->n_p + 3) / 4)), dim3(256), 0, s, W, c->n, c->n_p, c->d_p, f.q, f.z);
+  hipLaunchKernelGGL(pursuit_init_kernel<T>, dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, s, x, b, M, Mp, Trows, inv_T, lengths, c->d, c->d_p, K,
+                     f.r32, f.rho, err, f.rowstate, f.rowkey, tr);
+  HIP_TRY(hipGetLastError());
+
+  GemmArgs g{};
+  g.A0 = (const bf16_t*)f.rho; g.B0 = W; g.lda = c->d_p; g.ldb = c->d_p;
+  g.nbm = (int)(Mp / 128); g.nbn = c->n_p / 128; g.ktiles0 = g.ktiles = c->d_p / 64; g.splits = 1;
+  EpiPursuit e{};
+  e.z = f.z; e.rowkey = f.rowkey; e.M = M; e.n = c->n;
+  for (int step = 0; step < K; ++step) {
+    ev_begin(c, KID_PURSUIT_GEMM, s);
+    const int rc = launch_gemm<OP_ROW, OP_ROW>(g, e, s);
+    ev_end(c, KID_PURSUIT_GEMM, s);
+    if (rc) return rc;
+    ev_begin(c, KID_PURSUIT_STEP, s);
+    with_np(c->d_p, [&](auto np_tag) {
+      constexpr int NP = decltype(np_tag)::value;
+      hipLaunchKernelGGL(pursuit_step_kernel<NP>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, step, K, M, c->n, c->d_p, W, f.q, f.r32, f.rho, err,
+                         f.rowstate, f.rowkey, tr, sup, o.picks, o.in_support);
+    });
+    ev_end(c, KID_PURSUIT_STEP, s);
+  }
+
+  ev_begin(c, KID_PURSUIT_FOLD, s);
+  const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT);
+  hipLaunchKernelGGL(pursuit_finish_kernel, dim3((unsigned)n_units), dim3(256), 0, s, err, f.rowstate, M, K, tau, f.part, f.rowinfo, f.bud, o.steps);
+  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
+  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, inv_T, lengths, c->d,
+                     c->d_p, f.dimpart);
+  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
+  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
+  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (tau.n + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
+                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, tau.n, o.fold, nb_s, nb_dim, n_chunks);
+  ev_end(c, KID_PURSUIT_FOLD, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_pursuit_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                                 int K, const float* thresholds, int n_tau, int flags, void* block, int32_t* trace_idx, float* trace_val,
+                                 float* trace_err, void* stream) {
+  int64_t M;
+  if (int rc = file_pass_begin(kPursuitPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (misaligned(block, 8)) return fail(SAE_ERR_INVALID, "the pursuit block must be 8-byte aligned");
+  if (K < 1 || K > SAE_PURSUIT_MAX_K) return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (SAE_PURSUIT_MAX_K)", K, SAE_PURSUIT_MAX_K);
+  if (n_tau < 0 || n_tau > SAE_PURSUIT_MAX_TAU) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, SAE_PURSUIT_MAX_TAU);
+  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
+  FrTau tau{};
+  tau.n = n_tau;
+  for (int t = 0; t < n_tau; ++t) {
+    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
+    tau.t[t] = thresholds[t];
+  }
+  const int n_trace = (trace_idx != nullptr) + (trace_val != nullptr) + (trace_err != nullptr);
+  if (n_trace != 0 && n_trace != 3) return fail(SAE_ERR_INVALID, "the trace is three pointers, all or none");
+  if (misaligned(trace_idx, 4) || misaligned(trace_val, 4) || misaligned(trace_err, 4)) return fail(SAE_ERR_INVALID, "the trace arrays must be 4-byte aligned");
+  if (c->d_p > FR_MAX_D) return fail(SAE_ERR_INVALID, "sae_pursuit_files: the step serves d_model <= %d", FR_MAX_D);
+  char* scratch;
+  if (int rc = pass_scratch(c, {pursuit_scratch(c, K, nullptr).bytes}, &scratch)) return rc;      // (from a null base: the size alone)
+  const PursuitScratch f = pursuit_scratch(c, K, scratch);
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;          // (the encoder's own active set, for IN_SUPPORT)
+  const PursuitOut o = pursuit_out(block, n_tau, K, c->d, c->n, f);
+  PuTrace tr{trace_idx, trace_val};
+  float* err = n_trace ? trace_err : f.err;
+  if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return pursuit_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, f, err, tr, s); })) return rc;
+  file_pass_end(kPursuitPass, c);
   return SAE_OK;
 }
 

@@ -134,6 +134,7 @@ _SIGNATURES = {
     "sae_recon_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_collect_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_frontier_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _fptr, C.c_int, C.c_int, _vp, _vp]),
+    "sae_pursuit_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _fptr, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "sae_resample_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_resample_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_resample_select": (C.c_int, [_vp, _i64, _vp, _i64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -207,6 +208,7 @@ TIMING_MAX_BINS, TIMING_MAX_BRIDGE, TIMING_MAX_ROWS = 111, 15, 65535  # include/
 COLLECT_IDX32 = 1                                                   # include/freud_sae.h: SAE_COLLECT_IDX32
 COLLECT_MAX_K = 1024                                                # include/freud_sae.h: SAE_COLLECT_MAX_K
 FRONTIER_MAX_K, FRONTIER_MAX_TAU = 256, 8                           # include/freud_sae.h: SAE_FRONTIER_MAX_K / SAE_FRONTIER_MAX_TAU
+PURSUIT_MAX_K, PURSUIT_MAX_TAU = 256, 8                             # include/freud_sae.h: SAE_PURSUIT_MAX_K / SAE_PURSUIT_MAX_TAU
 FINDEX_IDX32 = 1                                                    # include/freud_sae.h: SAE_FINDEX_IDX32
 FINDEX_NSTATS = 8                                                   # include/freud_sae.h: SAE_FINDEX_NSTATS
 FINDEX_STAT_NAMES = ("slots", "zero_slots", "out_of_range", "posted")
@@ -246,6 +248,19 @@ def frontier_layout(n_tau: int, K: int, d: int) -> dict:
     return {"n_frames": (0, "int64", 1), "rows_cut": (8, "int64", 1), "active_cut": (16, "int64", 1), "sse": (24, "float64", K + 1),
             "sum_x": (32 + 8 * K, "float64", d), "sum_x_sq": (32 + 8 * K + 8 * d, "float64", d),
             "budget": (32 + 8 * K + 16 * d, "int64", n_tau * (K + 2)), "bytes": 32 + 8 * K + 16 * d + 8 * n_tau * (K + 2)}
+
+
+def pursuit_layout(n_tau: int, K: int, d: int, n: int) -> dict:
+    """Byte offsets of the sae_pursuit_files block for n_tau thresholds, K steps, d model dimensions and n latents (include/freud_sae.h:
+    SAE_PURSUIT_*): name -> (offset, dtype, count), plus "bytes": the block's size."""
+    sx = 16 + 8 * K
+    bud = sx + 16 * d
+    steps = bud + 8 * n_tau * (K + 2)
+    picks = steps + 8 * (K + 1)
+    sup = picks + 8 * n
+    return {"n_frames": (0, "int64", 1), "sse": (8, "float64", K + 1), "sum_x": (sx, "float64", d), "sum_x_sq": (sx + 8 * d, "float64", d),
+            "budget": (bud, "int64", n_tau * (K + 2)), "steps": (steps, "int64", K + 1), "picks": (picks, "int64", n),
+            "in_support": (sup, "int64", K), "bytes": sup + 8 * K}
 
 
 def unpack_block(block, layout: dict) -> Dict[str, np.ndarray]:
@@ -829,6 +844,30 @@ class SaeEngine:
         blk = _dev("block", block, "uint8", frontier_layout(tau.size, max(K, 0), self.d)["bytes"], at_least=True)
         _check(self._lib.sae_frontier_files(self._ctx, xp, B, T, dt, lp, K, tau.ctypes.data_as(_fptr), int(tau.size), 0, blk,
                                             _stream_ptr(stream)))
+
+    # -- pursuit frontier (include/freud_sae.h: sae_pursuit_files; freud_amd/pursuit.py) ------------------------------------------
+    def pursuit_files(self, x, K: int, thresholds, block, lengths=None, trace=None, stream=None) -> None:
+        """Add the pursuit frontier of x [n_files, T, d] (CUDA) -- every counted frame coded by K steps of non-negative matching pursuit
+        on the decoder directions -- to block (a zero-initialised uint8 CUDA tensor of pursuit_layout(len(thresholds), K, d, n)["bytes"]
+        bytes); thresholds: up to PURSUIT_MAX_TAU floats inside (0, 1); lengths: int32 CUDA tensor [n_files] or None; trace: None or
+        three contiguous CUDA tensors (idx int32 [n_files * T * K], val float32 of the same size, err float32 [n_files * T * (K + 1)])
+        that receive this batch's pursuit code in pick order.  Asynchronous.  Afterwards the last-forward getters fail until the next
+        eval() / step()."""
+        x, xp, B, T, _d, dt, lp = _files_args(x, "pursuit_files", lengths)
+        tau = _np_f32(thresholds).reshape(-1)
+        if tau.size > PURSUIT_MAX_TAU:
+            raise EngineError(f"pursuit_files: {tau.size} thresholds > {PURSUIT_MAX_TAU}")
+        K = int(K)
+        blk = _dev("block", block, "uint8", pursuit_layout(tau.size, max(K, 0), self.d, self.n)["bytes"], at_least=True)
+        ti = tv = te = None
+        if trace is not None:
+            idx, val, err = trace
+            rows = B * T
+            ti = _dev("trace idx", idx, "int32", rows * max(K, 0))
+            tv = _dev("trace val", val, "float32", rows * max(K, 0))
+            te = _dev("trace err", err, "float32", rows * (max(K, 0) + 1))
+        _check(self._lib.sae_pursuit_files(self._ctx, xp, B, T, dt, lp, K, tau.ctypes.data_as(_fptr), int(tau.size), 0, blk, ti, tv, te,
+                                           _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:

@@ -841,6 +841,79 @@ int sae_collect_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t 
 int sae_frontier_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
                        int K, const float* thresholds /* host, [n_tau] */, int n_tau, int flags, void* block_dev, void* stream);
 
+/* ---- Pursuit frontier: the DECODER's best-case squared error at every per-frame latent budget s = 0 .. K -- every counted frame
+ * coded greedily against the decoder directions, without the trained encoder (non-negative matching pursuit, "inference-time
+ * optimisation").  The curve between sae_input_cov's PCA curve and sae_frontier_files' encoder curve: their difference at a budget
+ * is the amortisation gap (freud_amd/pursuit.py; kernels: freud_amd/csrc/pursuit.h).
+ *
+ * Semantics.  Counted frames as in sae_frontier_files (lengths_dev, trimmed to min(length, rows_per_file)).  w_j, j < n_dict, is the
+ * bf16 operand row the frontier uses: L1 -- row j of the transposed normalised copy, b = 0; TopK -- row j of the bf16 W_dec,
+ * b = b_dec.  The per-direction constants are fp32, computed once per call in one fixed order (pursuit.h):
+ *   q_j = sum_e w_j[e]^2,   z_j = 1 / sqrt(q_j);   a direction with q_j == 0 has z_j = 0 and is never chosen.
+ * Per counted frame:
+ *   r_0 = float(x) - b                          one fp32 subtraction on the delivered x
+ *   step s = 0 .. K - 1, unless the row has stopped:
+ *     rho   = bf16(r_s)                         round to nearest even, per element
+ *     sc_j  = fp32_acc(rho . w_j) * z_j         the bf16 MFMA product; SELECTION ONLY
+ *     j*    = argmax_j sc_j over j < n_dict     ties to the LOWER j; padding rows / columns are never eligible
+ *     stop if sc_j* <= 0
+ *     a     = fp32 dot(r_s, w_j*) / q_j*        from the fp32 residual, fixed order, IEEE division
+ *     stop if not (a > 0)
+ *     r_{s+1} = fmaf(-a, w_j*, r_s)
+ *   e_s = |r_s|^2 (fp32, fixed order), s = 0 .. K; a stopped row keeps its e for the remaining s.
+ * Non-negative matching pursuit, because SAE codes are non-negative.  A latent may be chosen again later -- the code then
+ * accumulates -- so e_s is the error with AT MOST s distinct latents.  The bf16 product only chooses: every reported number comes
+ * from the fp32 residual and the fp32 coefficient.  The frame's budget at a threshold is the frontier's (smallest s with
+ * e_s <= tau e_0, K + 1 if none, e_0 == 0: budget 0).
+ *
+ * Output block: caller-owned device memory, 8-byte aligned, SAE_PURSUIT_BYTES(n_tau, K, d, n) bytes of running totals; zero it
+ * before the first batch, every call adds one batch (the same K and thresholds).  Byte offsets:
+ *   SAE_PURSUIT_N_FRAMES     int64                  frames counted
+ *   SAE_PURSUIT_SSE          float64 [K + 1]        summed e_s
+ *   SAE_PURSUIT_SUM_X        float64 [d]            the frontier's denominators
+ *   SAE_PURSUIT_SUM_X_SQ     float64 [d]
+ *   SAE_PURSUIT_BUDGET       int64 [n_tau][K + 2]   the frontier's budget histogram
+ *   SAE_PURSUIT_STEPS        int64 [K + 1]          histogram of the number of picks a frame made before it stopped
+ *   SAE_PURSUIT_PICKS        int64 [n]              how often latent j was chosen
+ *   SAE_PURSUIT_IN_SUPPORT   int64 [K]              picks of step s that lie in the encoder's own active set for that frame (L1: the
+ *                                                   stored bf16 latent of the eval encoder is > 0; TopK: the latent is among the
+ *                                                   selected indices with a positive value)
+ *
+ * Optional trace, three device pointers, all or none (4-byte aligned), per row of THIS batch: trace_idx int32 [M][K] -- the pick, -1
+ * after the stop and on uncounted frames; trace_val float32 [M][K] -- a, or +0.0; trace_err float32 [M][K + 1] -- e_s, 0 on
+ * uncounted frames.  The trace is the pursuit code in pick order, not a feature store: indices may repeat.
+ *
+ * Limits: 1 <= K <= SAE_PURSUIT_MAX_K (whatever the context's k); n_tau <= SAE_PURSUIT_MAX_TAU, thresholds inside (0, 1);
+ * d_model <= 1536 (padded); n_files * rows_per_file <= max_rows; bf16 contexts only; no flag bits are defined.  Every check fails
+ * before anything is enqueued.
+ *
+ * Determinism: two runs give the same bytes.  The trace, STEPS, PICKS, IN_SUPPORT, BUDGET and N_FRAMES do not depend on the split
+ * of the files into batches: a score's sum over K does not depend on the tile it is computed in, and everything after the pick is
+ * per row.  Float sums are fixed-order fp32 partials folded in ascending order into fp64, as for sae_frontier_files; no float
+ * atomics (integer adds and an unsigned 64-bit max only).
+ *
+ * The call is the bf16 eval encoder (for IN_SUPPORT), then K (GEMM, step) launch pairs on `stream` with no host synchronisation
+ * between them, then the fold.  Context scratch: 6 d_p + 4 K + 48 bytes per row of max_rows, allocated by the first call.
+ * Training state is untouched; the last-forward getters return SAE_ERR_STATE until the next sae_eval / step, as after
+ * sae_frontier_files.
+ *
+ * Out of scope: orthogonal or gradient pursuit; signed codes; the pursuit code as a feature store (repeated picks would need
+ * merging); an early exit of the GEMM for row blocks that have stopped; fp8 contexts. */
+#define SAE_PURSUIT_MAX_K 256
+#define SAE_PURSUIT_MAX_TAU 8
+#define SAE_PURSUIT_N_FRAMES(n_tau, K, d, n) ((int64_t)0)
+#define SAE_PURSUIT_SSE(n_tau, K, d, n) ((int64_t)8)
+#define SAE_PURSUIT_SUM_X(n_tau, K, d, n) ((int64_t)16 + 8 * (int64_t)(K))
+#define SAE_PURSUIT_SUM_X_SQ(n_tau, K, d, n) (SAE_PURSUIT_SUM_X(n_tau, K, d, n) + 8 * (int64_t)(d))
+#define SAE_PURSUIT_BUDGET(n_tau, K, d, n) (SAE_PURSUIT_SUM_X(n_tau, K, d, n) + 16 * (int64_t)(d))
+#define SAE_PURSUIT_STEPS(n_tau, K, d, n) (SAE_PURSUIT_BUDGET(n_tau, K, d, n) + 8 * (int64_t)(n_tau) * ((int64_t)(K) + 2))
+#define SAE_PURSUIT_PICKS(n_tau, K, d, n) (SAE_PURSUIT_STEPS(n_tau, K, d, n) + 8 * ((int64_t)(K) + 1))
+#define SAE_PURSUIT_IN_SUPPORT(n_tau, K, d, n) (SAE_PURSUIT_PICKS(n_tau, K, d, n) + 8 * (int64_t)(n))
+#define SAE_PURSUIT_BYTES(n_tau, K, d, n) (SAE_PURSUIT_IN_SUPPORT(n_tau, K, d, n) + 8 * (int64_t)(K))
+int sae_pursuit_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                      int K, const float* thresholds /* host, [n_tau] */, int n_tau, int flags, void* block_dev, int32_t* trace_idx_dev,
+                      float* trace_val_dev, float* trace_err_dev, void* stream);
+
 /* ---- Feature index: the latent-major postings of an indexed feature store -- for every latent the (position, value) of the slots
  * that fire it, positions ascending (freud_amd/feature_index.py; kernels: freud_amd/csrc/findex.h).  The reference has no index:
  * it rebuilds one latent's series from the row-major store by scanning every slot of every file, per query
