@@ -77,7 +77,7 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
                                               "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing",
                                               "frontier_sort", "frontier_walk", "frontier_fold", "pursuit_gemm", "pursuit_step",
-                                              "pursuit_fold"};
+                                              "pursuit_fold", "refit_sort", "refit_chol", "refit_fold"};
 
 // fused d = 384 L1 path with the peer exchange: the batch statistics are exchanged inside finalize_losses_kernel (StatsPush)
 // (FREUD_DP_STATS=stream: the statistics leave the critical path instead -- a pass over x and their exchange on the communication stream
@@ -2972,4 +2972,13 @@ extern "C" int sae_kernel_times(sae_ctx* c, float* ms_sum, int32_t* launches, in
     r.n = 0;
   }
   return SAE_OK;
+}
+
+// The bf16 decoder operand rows of the CURRENT weights for a pass that runs no encoder (sae_refit_files on a given support): L1 -- the
+// in-place normalisation every forward starts with, which writes Wt; TopK -- the cast of W_dec unless the last step already left it.
+void refresh_decoder_operand(sae_ctx* c, hipStream_t s) {
+  if (!c->topk) return prep_weights_l1(c, s);
+  if (c->wb_valid) return;
+  const int64_t n8 = c->nW / 8;
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(grid_for(n8, 2048)), dim3(256), 0, s, c->P + c->nW + c->n_p, c->Wd_b, n8);
 }

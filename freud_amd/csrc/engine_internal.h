@@ -137,6 +137,9 @@ enum KernelId {
   KID_PURSUIT_GEMM,    // pursuit frontier (pursuit.h): the K selection GEMMs with EpiPursuit, the K step kernels, the finish + dimension sums + fold
   KID_PURSUIT_STEP,
   KID_PURSUIT_FOLD,
+  KID_REFIT_SORT,      // refit frontier (refit.h): the collect kernels into scratch, the refit kernel alone, the finish + dimension sums + fold
+  KID_REFIT_CHOL,
+  KID_REFIT_FOLD,
   KID_COUNT
 };
 constexpr int EV_RING = 64;
@@ -148,7 +151,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER, LAST_PURSUIT };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER, LAST_PURSUIT, LAST_REFIT };
 
 // A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
 // of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
@@ -170,8 +173,9 @@ static const FilePassKind kTimingPass = {"sae_timing_files", "time the features 
 static const FilePassKind kResamplePass = {"sae_resample_files", "resample in a bf16 context", "resample", 0, LAST_RESAMPLE, "a resampling pass"};
 static const FilePassKind kFrontierPass = {"sae_frontier_files", "build the sparsity frontier in a bf16 context", "frontier", 0, LAST_FRONTIER, "a sparsity frontier pass"};
 static const FilePassKind kPursuitPass = {"sae_pursuit_files", "run the pursuit in a bf16 context", "pursuit", 0, LAST_PURSUIT, "a pursuit frontier pass"};
+static const FilePassKind kRefitPass = {"sae_refit_files", "run the refit in a bf16 context", "refit", 0, LAST_REFIT, "a refit frontier pass"};
 static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
-                                                  &kTimingPass, &kResamplePass, &kFrontierPass, &kPursuitPass};
+                                                  &kTimingPass, &kResamplePass, &kFrontierPass, &kPursuitPass, &kRefitPass};
 
 struct sae_ctx {
   // Every pointer field below that the context OWNS is allocated through `mem` (dev_mem.h; the last member, behind everything a step
@@ -409,6 +413,7 @@ static void ev_end(sae_ctx* c, int kid, hipStream_t s) {
 #pragma GCC visibility push(hidden)
 void prep_weights_l1(sae_ctx* c, hipStream_t s);
 void settle_weights(sae_ctx* c, hipStream_t s);
+void refresh_decoder_operand(sae_ctx* c, hipStream_t s);
 GemmArgs enc_gemm_args(const sae_ctx* c, const bf16_t* xb, int64_t Mp);
 int dispatch_fwd_bwd(sae_ctx* c, const void* x, int64_t M, int x_dtype, void* stream, bool backward);
 int decode_l1_latent(sae_ctx* c, const bf16_t* lat, int64_t nbm, int64_t M, float* x_hat, hipStream_t s);

@@ -24,6 +24,7 @@
 #include "recon.h"
 #include "frontier.h"
 #include "pursuit.h"
+#include "refit.h"
 #include "resample.h"
 #include "input_stats.h"
 #include "input_cov_plan.h"
@@ -1190,6 +1191,168 @@ extern "C" int sae_pursuit_files(sae_ctx* c, const void* x, int64_t n_files, int
   float* err = n_trace ? trace_err : f.err;
   if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return pursuit_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, f, err, tr, s); })) return rc;
   file_pass_end(kPursuitPass, c);
+  return SAE_OK;
+}
+
+// ---- refit frontier (refit.h): the least-squares code of every counted frame on its encoder's support (the slots of the collect
+// kernels, in context scratch) or on a support the caller gives, one wave per frame, then the frontier's own fold
+static_assert(SAE_REFIT_MAX_K == RF_MAX_K && SAE_REFIT_MAX_TAU == RF_MAX_TAU && SAE_REFIT_RATIO_BINS == RF_RATIO_BINS && RF_MAX_K <= FR_MAX_K &&
+                  RF_MAX_K % 32 == 0,
+              "freud_sae.h, refit_chol.h and frontier.h disagree");
+
+struct RefitScratch {           // its scratch area carved up
+  float* vals;                  // [max_rows][kcap] the slots, kcap = min(RF_MAX_K, k or n)
+  int* idx;
+  int64_t* cstats;              // [8] the collect kernels' totals (not reported)
+  uint32_t *row_nnz, *rowinfo;  // [max_rows]
+  unsigned short* bud;          // [max_rows][FR_MAX_TAU]
+  float *part, *dimpart;        // [units][FR_PART_LD], [128-row blocks][2][d_p]
+  float* err;                   // [max_rows][K + 1] the rows' e_s (the caller's trace_err instead when it is given)
+  float* efin;                  // [max_rows]
+  int* keptn;                   // [max_rows] the row's kept slots, -1 on a row that does not count
+  float* finpart;               // [units] sums of e_final
+  unsigned long long* unused;   // [2] where the shared fold adds the frontier's cut counts (not reported)
+  int64_t bytes;
+};
+
+static RefitScratch refit_scratch(const sae_ctx* c, int K, char* base) {
+  const int64_t rows = c->cfg.max_rows, kcap = std::min<int64_t>(RF_MAX_K, c->topk ? c->k : c->n);
+  const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
+  char* p = base;
+  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
+  RefitScratch f;
+  f.vals = (float*)take(rows * kcap * 4);
+  f.idx = (int*)take(rows * kcap * 4);
+  f.cstats = (int64_t*)take(64);
+  f.row_nnz = (uint32_t*)take(rows * 4);
+  f.rowinfo = (uint32_t*)take(rows * 4);
+  f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
+  f.part = (float*)take(units * FR_PART_LD * 4);
+  f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
+  f.err = (float*)take(rows * (K + 1) * 4);
+  f.efin = (float*)take(rows * 4);
+  f.keptn = (int*)take(rows * 4);
+  f.finpart = (float*)take(units * 4);
+  f.unused = (unsigned long long*)take(16);
+  f.bytes = p - base;
+  return f;
+}
+
+struct RefitOut {               // the caller's block (include/freud_sae.h, SAE_REFIT_*)
+  FrOut fold;                   // what the frontier's fold adds: n_frames, sse, sum_x, sum_x_sq, budget
+  double* sse_final;
+  unsigned long long* kept;
+  RfCount cnt;
+};
+
+static RefitOut refit_out(void* block, int n_tau, int K, int d, int n, const RefitScratch& f) {
+  char* b = (char*)block;
+  RefitOut o;
+  o.fold.n_frames = (unsigned long long*)(b + SAE_REFIT_N_FRAMES(n_tau, K, d, n));
+  o.fold.rows_cut = f.unused;
+  o.fold.active_cut = f.unused + 1;
+  o.fold.sse = (double*)(b + SAE_REFIT_SSE(n_tau, K, d, n));
+  o.fold.sx = (double*)(b + SAE_REFIT_SUM_X(n_tau, K, d, n));
+  o.fold.sxx = (double*)(b + SAE_REFIT_SUM_X_SQ(n_tau, K, d, n));
+  o.fold.budget = (unsigned long long*)(b + SAE_REFIT_BUDGET(n_tau, K, d, n));
+  o.sse_final = (double*)(b + SAE_REFIT_SSE_FINAL(n_tau, K, d, n));
+  o.kept = (unsigned long long*)(b + SAE_REFIT_KEPT(n_tau, K, d, n));
+  o.cnt.slots = (unsigned long long*)(b + SAE_REFIT_SLOTS(n_tau, K, d, n));
+  o.cnt.neg = (unsigned long long*)(b + SAE_REFIT_NEG(n_tau, K, d, n));
+  o.cnt.dep = (unsigned long long*)(b + SAE_REFIT_DEP(n_tau, K, d, n));
+  o.cnt.ratio = (unsigned long long*)(b + SAE_REFIT_RATIO(n_tau, K, d, n));
+  o.cnt.bad_index = (unsigned long long*)(b + SAE_REFIT_BAD_INDEX(n_tau, K, d, n));
+  return o;
+}
+
+template <typename T, int NT>
+static int refit_launch(sae_ctx* c, const T* x, const float* b, const RfSupport& sup, int K, const bf16_t* W, int64_t M, int Trows,
+                        const int* lengths, float* err, const RefitScratch& f, const RfTrace& tr, const RfCount& cnt, hipStream_t s) {
+  constexpr int Kp = 32 * NT, NW = rf_waves(Kp), lds = NW * rf_region_floats(Kp) * 4;
+  auto kern = refit_kernel<T, NT>;
+  LDS_ATTR(kern, lds, g_device);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((M + NW - 1) / NW)), dim3(64 * NW), lds, s, x, b, sup, K, W, M, Trows, 1.0f / (float)Trows, lengths,
+                     c->d, c->d_p, c->n, err, f.efin, f.keptn, tr, cnt);
+  return SAE_OK;
+}
+
+template <typename T>
+static int refit_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const int* given,
+                      const RefitOut& o, const RefitScratch& f, float* err, const RfTrace& tr, hipStream_t s) {
+  RfSupport sup{f.vals, f.idx, given};
+  if (!given) {
+    // the collect kernels ADD their totals to cstats (never reported): cleared, since the area holds another pass's leftovers
+    HIP_TRY(hipMemsetAsync(f.cstats, 0, 64, s));
+    ev_begin(c, KID_REFIT_SORT, s);
+    collect_launch(c, M, K, f.vals, f.idx, f.cstats, s, f.row_nnz);
+    ev_end(c, KID_REFIT_SORT, s);
+  }
+  // the operand rows [n_p][d_p] and the bias, as the frontier takes them
+  const bf16_t* W = c->topk ? c->Wd_b : c->Wt;
+  const float* b = c->topk ? c->P + 2 * c->nW + c->n_p : nullptr;
+  ev_begin(c, KID_REFIT_CHOL, s);
+  int rc;
+  switch ((K + 31) / 32) {
+    case 1: rc = refit_launch<T, 1>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    case 2: rc = refit_launch<T, 2>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    case 3: rc = refit_launch<T, 3>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    default: rc = refit_launch<T, 4>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+  }
+  ev_end(c, KID_REFIT_CHOL, s);
+  if (rc) return rc;
+
+  ev_begin(c, KID_REFIT_FOLD, s);
+  const float inv_T = 1.0f / (float)Trows;
+  const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT);
+  hipLaunchKernelGGL(refit_finish_kernel, dim3((unsigned)n_units), dim3(256), 0, s, err, f.efin, f.keptn, M, K, tau, f.part, f.rowinfo, f.bud,
+                     f.finpart, o.kept);
+  hipLaunchKernelGGL(refit_final_kernel, dim3(1), dim3(64), 0, s, f.finpart, n_units, o.sse_final);
+  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
+  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, inv_T, lengths, c->d,
+                     c->d_p, f.dimpart);
+  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
+  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
+  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (tau.n + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
+                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, tau.n, o.fold, nb_s, nb_dim, n_chunks);
+  ev_end(c, KID_REFIT_FOLD, s);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_refit_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                               int K, const float* thresholds, int n_tau, int flags, const int32_t* support_idx, void* block,
+                               float* trace_coef, float* trace_err, unsigned char* trace_dep, float* trace_gram, void* stream) {
+  int64_t M;
+  if (int rc = file_pass_begin(kRefitPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
+  if (misaligned(block, 8)) return fail(SAE_ERR_INVALID, "the refit block must be 8-byte aligned");
+  const int k_max = support_idx ? (int)SAE_REFIT_MAX_K : std::min(c->topk ? c->k : c->n, (int)SAE_REFIT_MAX_K);
+  if (K < 1 || K > k_max)
+    return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max,
+                support_idx ? "SAE_REFIT_MAX_K" : c->topk ? "min(the context's k, SAE_REFIT_MAX_K)" : "min(n_dict, SAE_REFIT_MAX_K)");
+  if (n_tau < 0 || n_tau > SAE_REFIT_MAX_TAU) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, SAE_REFIT_MAX_TAU);
+  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
+  FrTau tau{};
+  tau.n = n_tau;
+  for (int t = 0; t < n_tau; ++t) {
+    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
+    tau.t[t] = thresholds[t];
+  }
+  if (misaligned(support_idx, 4) || misaligned(trace_coef, 4) || misaligned(trace_err, 4) || misaligned(trace_gram, 4))
+    return fail(SAE_ERR_INVALID, "the support and the trace arrays must be 4-byte aligned");
+  if (c->d_p > FR_MAX_D) return fail(SAE_ERR_INVALID, "sae_refit_files: the refit serves d_model <= %d", FR_MAX_D);
+  if (!support_idx && c->topk && c->k > CL_MAX_K) return fail(SAE_ERR_INVALID, "sae_refit_files: k=%d > %d", c->k, CL_MAX_K);
+  char* scratch;
+  if (int rc = pass_scratch(c, {refit_scratch(c, K, nullptr).bytes}, &scratch)) return rc;        // (from a null base: the size alone)
+  const RefitScratch f = refit_scratch(c, K, scratch);
+  hipStream_t s = (hipStream_t)stream;
+  if (support_idx) refresh_decoder_operand(c, s);       // (no encoder runs: the operand rows of the current weights all the same)
+  else if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
+  const RefitOut o = refit_out(block, n_tau, K, c->d, c->n, f);
+  const RfTrace tr{trace_coef, trace_dep, trace_gram};
+  float* err = trace_err ? trace_err : f.err;
+  if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return refit_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, support_idx, o, f, err, tr, s); }))
+    return rc;
+  file_pass_end(kRefitPass, c);
   return SAE_OK;
 }
 

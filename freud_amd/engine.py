@@ -135,6 +135,7 @@ _SIGNATURES = {
     "sae_collect_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_frontier_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _fptr, C.c_int, C.c_int, _vp, _vp]),
     "sae_pursuit_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _fptr, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "sae_refit_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _fptr, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sae_resample_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, _vp, _vp]),
     "sae_resample_workspace_bytes": (_i64, [_i64, _i64]),
     "sae_resample_select": (C.c_int, [_vp, _i64, _vp, _i64, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _i64, _vp]),
@@ -209,6 +210,7 @@ COLLECT_IDX32 = 1                                                   # include/fr
 COLLECT_MAX_K = 1024                                                # include/freud_sae.h: SAE_COLLECT_MAX_K
 FRONTIER_MAX_K, FRONTIER_MAX_TAU = 256, 8                           # include/freud_sae.h: SAE_FRONTIER_MAX_K / SAE_FRONTIER_MAX_TAU
 PURSUIT_MAX_K, PURSUIT_MAX_TAU = 256, 8                             # include/freud_sae.h: SAE_PURSUIT_MAX_K / SAE_PURSUIT_MAX_TAU
+REFIT_MAX_K, REFIT_MAX_TAU, REFIT_RATIO_BINS = 128, 8, 36           # include/freud_sae.h: SAE_REFIT_MAX_K / _MAX_TAU / _RATIO_BINS
 FINDEX_IDX32 = 1                                                    # include/freud_sae.h: SAE_FINDEX_IDX32
 FINDEX_NSTATS = 8                                                   # include/freud_sae.h: SAE_FINDEX_NSTATS
 FINDEX_STAT_NAMES = ("slots", "zero_slots", "out_of_range", "posted")
@@ -261,6 +263,22 @@ def pursuit_layout(n_tau: int, K: int, d: int, n: int) -> dict:
     return {"n_frames": (0, "int64", 1), "sse": (8, "float64", K + 1), "sum_x": (sx, "float64", d), "sum_x_sq": (sx + 8 * d, "float64", d),
             "budget": (bud, "int64", n_tau * (K + 2)), "steps": (steps, "int64", K + 1), "picks": (picks, "int64", n),
             "in_support": (sup, "int64", K), "bytes": sup + 8 * K}
+
+
+def refit_layout(n_tau: int, K: int, d: int, n: int) -> dict:
+    """Byte offsets of the sae_refit_files block for n_tau thresholds, K slots, d model dimensions and n latents (include/freud_sae.h:
+    SAE_REFIT_*): name -> (offset, dtype, count), plus "bytes": the block's size."""
+    fin = 16 + 8 * K
+    sx = fin + 8
+    bud = sx + 16 * d
+    kept = bud + 8 * n_tau * (K + 2)
+    slots = kept + 8 * (K + 1)
+    ratio = slots + 24 * n
+    bad = ratio + 8 * REFIT_RATIO_BINS
+    return {"n_frames": (0, "int64", 1), "sse": (8, "float64", K + 1), "sse_final": (fin, "float64", 1), "sum_x": (sx, "float64", d),
+            "sum_x_sq": (sx + 8 * d, "float64", d), "budget": (bud, "int64", n_tau * (K + 2)), "kept": (kept, "int64", K + 1),
+            "slots": (slots, "int64", n), "neg": (slots + 8 * n, "int64", n), "dep": (slots + 16 * n, "int64", n),
+            "ratio": (ratio, "int64", REFIT_RATIO_BINS), "bad_index": (bad, "int64", 1), "bytes": bad + 8}
 
 
 def unpack_block(block, layout: dict) -> Dict[str, np.ndarray]:
@@ -868,6 +886,34 @@ class SaeEngine:
             te = _dev("trace err", err, "float32", rows * (max(K, 0) + 1))
         _check(self._lib.sae_pursuit_files(self._ctx, xp, B, T, dt, lp, K, tau.ctypes.data_as(_fptr), int(tau.size), 0, blk, ti, tv, te,
                                            _stream_ptr(stream)))
+
+    # -- refit frontier (include/freud_sae.h: sae_refit_files; freud_amd/refit.py) ------------------------------------------------
+    def refit_files(self, x, K: int, thresholds, block, lengths=None, support=None, trace=None, stream=None) -> None:
+        """Add the refit frontier of x [n_files, T, d] (CUDA) -- every counted frame's least-squares error on every prefix of its
+        support's K slots -- to block (a zero-initialised uint8 CUDA tensor of refit_layout(len(thresholds), K, d, n)["bytes"] bytes);
+        thresholds: up to REFIT_MAX_TAU floats inside (0, 1); lengths: int32 CUDA tensor [n_files] or None; support: None (the slots of
+        collect_files) or a contiguous int32 CUDA tensor of n_files * T * K indices (-1: an empty slot); trace: None or a dict with any
+        of "coef" (float32, n_files * T * K), "err" (float32, n_files * T * (K + 1)), "dep" (uint8, n_files * T * K) and "gram"
+        (float32, n_files * T * (K + 1) * K), contiguous CUDA tensors that receive this batch's rows.  Asynchronous.  Afterwards the
+        last-forward getters fail until the next eval() / step()."""
+        x, xp, B, T, _d, dt, lp = _files_args(x, "refit_files", lengths)
+        tau = _np_f32(thresholds).reshape(-1)
+        if tau.size > REFIT_MAX_TAU:
+            raise EngineError(f"refit_files: {tau.size} thresholds > {REFIT_MAX_TAU}")
+        K = int(K)
+        Kc, rows = max(K, 0), B * T
+        blk = _dev("block", block, "uint8", refit_layout(tau.size, Kc, self.d, self.n)["bytes"], at_least=True)
+        sup = None if support is None else _dev("support", support, "int32", rows * Kc)
+        trace = dict(trace or {})
+        unknown = set(trace) - {"coef", "err", "dep", "gram"}
+        if unknown:
+            raise EngineError(f"refit_files: unknown trace arrays {sorted(unknown)}")
+        tc = _dev("trace coef", trace["coef"], "float32", rows * Kc) if trace.get("coef") is not None else None
+        te = _dev("trace err", trace["err"], "float32", rows * (Kc + 1)) if trace.get("err") is not None else None
+        td = _dev("trace dep", trace["dep"], "uint8", rows * Kc) if trace.get("dep") is not None else None
+        tg = _dev("trace gram", trace["gram"], "float32", rows * (Kc + 1) * Kc) if trace.get("gram") is not None else None
+        _check(self._lib.sae_refit_files(self._ctx, xp, B, T, dt, lp, K, tau.ctypes.data_as(_fptr), int(tau.size), 0, sup, blk, tc, te, td, tg,
+                                         _stream_ptr(stream)))
 
     # -- inspection -----------------------------------------------------------------------------
     def debug_read(self, which: int, count: int) -> np.ndarray:

@@ -914,6 +914,95 @@ int sae_pursuit_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t 
                       int K, const float* thresholds /* host, [n_tau] */, int n_tau, int flags, void* block_dev, int32_t* trace_idx_dev,
                       float* trace_val_dev, float* trace_err_dev, void* stream);
 
+/* ---- Refit frontier: the squared error at every per-frame latent budget s = 0 .. K when the SUPPORT is the encoder's own (or one
+ * the caller gives) and the COEFFICIENTS are the least-squares ones on every prefix of its slots.  It splits the amortisation gap of
+ * the pursuit frontier: encoder - refit is the coefficient error (shrinkage, cross-talk), refit - pursuit the support error; on the
+ * pursuit's own trace it is pursuit with a final orthogonal projection (freud_amd/refit.py; kernels: freud_amd/csrc/refit.h, the
+ * rule in freud_amd/csrc/refit_chol.h).
+ *
+ * Semantics.  Counted frames, w_j, b and r_0 = float(x) - b are exactly those of sae_frontier_files.  The support of a frame:
+ *   support_idx_dev == NULL   the K slots (v_s, i_s) of sae_collect_files (the same entry word, tie rule and padding); a slot is
+ *                             ACTIVE iff v_s != 0;
+ *   support_idx_dev != NULL   int32 [M][K], those indices; no encoder and no collect run.  -1 marks an empty slot; an index outside
+ *                             [0, n_dict) is counted in BAD_INDEX, is never used as an address and leaves its slot empty; a repeated
+ *                             index is legal (the rank rule below drops it).
+ * Per frame, with the active slots in slot order:
+ *   G[s][t] = sum_e w_{i_s}[e] w_{i_t}[e]   the products are exact, accumulated in fp32 by the bf16 MFMA in an order that depends on
+ *             d_p alone (not on K, the row's neighbours or the batch).  G is specified by a bound, not by an order:
+ *             |G - G64| <= gamma(d_p) sum |w w|, gamma(n) = n 2^-24 / (1 - n 2^-24).  A slot that is not active has G = 0.
+ *   c[s]    = fp32 dot(r_0, w_{i_s}) in the lane and column order of the frontier (frontier.h: a lane's d_p / 64 columns in order
+ *             from 0, the shares by fr_wave_sum); 0 on a slot that is not active
+ *   e_0     = |r_0|^2 by the frontier's functions: bit-equal to the frontier's e_0.
+ * From here every number has ONE defined order; the chains run over the KEPT slots u in ascending order:
+ *   piv_s   = G[s][s], then fmaf(-L[s][u], L[s][u], .) over kept u < s
+ *   the slot is DEPENDENT iff piv_s <= 2^-10 * G[s][s] (one fp32 product, one compare; G[s][s] == 0 is dependent);
+ *   otherwise d_s = sqrt(piv_s) and the slot is kept
+ *   L[s][t] = (G[s][t], then fmaf(-L[s][u], L[t][u], .) over kept u < t) / d_t, for kept t < s
+ *   y_s     = (c[s], then fmaf(-L[s][u], y_u, .) over kept u < s) / d_s
+ *   e_{s+1} = fmaxf(fmaf(-y_s, y_s, e_s), 0);   an empty, inactive or dependent slot has e_{s+1} = e_s
+ * with correctly rounded square root and division.  e_s is the squared error of the least-squares fit on the first s slots; row s
+ * of L depends on the slots <= s only, so the first K' + 1 entries equal those of a run at K'.  (2^-10: on unit bf16 directions,
+ * random or strongly correlated, every kept slot has a pivot ratio >= 0.05 and every exact duplicate one <= 1e-6.)
+ * Coefficients at the full budget: a_s = (y_s, then fmaf(-L[u][s], a_u, .) over kept u > s, DESCENDING) / d_s, a_s = +0.0 on every
+ * other slot; r = r_0, then r = fmaf(-a_s, w_{i_s}, r) over the kept slots in slot order; e_final = |r|^2 by the frontier's norm --
+ * the directly computed error at budget K, reported beside the curve, whose end comes from e_0 - sum y^2.  The coefficients are
+ * signed; negative ones are counted.
+ *
+ * Output block: caller-owned device memory, 8-byte aligned, SAE_REFIT_BYTES(n_tau, K, d, n) bytes of running totals; zero it before
+ * the first batch, every call adds one batch (the same K, thresholds and kind of support).  Byte offsets:
+ *   SAE_REFIT_N_FRAMES    int64                  frames counted
+ *   SAE_REFIT_SSE         float64 [K + 1]        summed e_s: the curve
+ *   SAE_REFIT_SSE_FINAL   float64                summed e_final
+ *   SAE_REFIT_SUM_X       float64 [d]            the frontier's denominators
+ *   SAE_REFIT_SUM_X_SQ    float64 [d]
+ *   SAE_REFIT_BUDGET      int64 [n_tau][K + 2]   the frontier's budget predicate on the refit curve
+ *   SAE_REFIT_KEPT        int64 [K + 1]          histogram of the number of kept slots per frame
+ *   SAE_REFIT_SLOTS       int64 [n]              frames that hold latent j in an active slot
+ *   SAE_REFIT_NEG         int64 [n]              kept slots of latent j whose refit coefficient is below zero
+ *   SAE_REFIT_DEP         int64 [n]              active slots of latent j that were dependent
+ *   SAE_REFIT_RATIO       int64 [36]             histogram of a_s / v_s over the kept slots (ONE IEEE division, binned on the fp32
+ *                                                bit pattern: negative | zero | below 2^-4 | the eight octaves [2^-4, 2^4) in four
+ *                                                sub-bins each | at or above 2^4); the default support only
+ *   SAE_REFIT_BAD_INDEX   int64                  out-of-range indices of a given support
+ *
+ * Optional trace, device pointers, each nullable and 4-byte aligned (trace_dep: bytes), for the rows of THIS batch:
+ *   trace_coef float32 [M][K]          a_s
+ *   trace_err  float32 [M][K + 1]      e_s, 0 on uncounted frames
+ *   trace_dep  uint8   [M][K]          1 = the slot is active and dependent
+ *   trace_gram float32 [M][K + 1][K]   rows 0 .. K - 1: G with both triangles filled; row K: c
+ * The Gram trace lets a host replay everything after the MFMA to the bit (refit_chol.h: rf_row_serial).
+ *
+ * Limits: 1 <= K <= SAE_REFIT_MAX_K; for the default support K <= k (TopK) and K <= n_dict (L1); d_model <= 1536 (padded); bf16
+ * contexts only; no flag bits are defined; n_tau and the thresholds as for sae_frontier_files.  Every check fails before anything
+ * is enqueued.
+ *
+ * State and determinism: training state is untouched (an L1 context normalises its weights in place, as every forward does); the
+ * last-forward getters return SAE_ERR_STATE until the next sae_eval / step.  No float atomics: two runs give the same bytes; the
+ * integer fields and the trace do not depend on the split of the files into batches.
+ *
+ * Out of scope: non-negative or sparsity-regularised refits; orthogonal pursuit with a refit inside every step; per-latent float
+ * sums; K above 128; fp8 contexts; writing refit codes as a feature store. */
+#define SAE_REFIT_MAX_K 128
+#define SAE_REFIT_MAX_TAU 8
+#define SAE_REFIT_RATIO_BINS 36
+#define SAE_REFIT_N_FRAMES(n_tau, K, d, n) ((int64_t)0)
+#define SAE_REFIT_SSE(n_tau, K, d, n) ((int64_t)8)
+#define SAE_REFIT_SSE_FINAL(n_tau, K, d, n) ((int64_t)16 + 8 * (int64_t)(K))
+#define SAE_REFIT_SUM_X(n_tau, K, d, n) ((int64_t)24 + 8 * (int64_t)(K))
+#define SAE_REFIT_SUM_X_SQ(n_tau, K, d, n) (SAE_REFIT_SUM_X(n_tau, K, d, n) + 8 * (int64_t)(d))
+#define SAE_REFIT_BUDGET(n_tau, K, d, n) (SAE_REFIT_SUM_X(n_tau, K, d, n) + 16 * (int64_t)(d))
+#define SAE_REFIT_KEPT(n_tau, K, d, n) (SAE_REFIT_BUDGET(n_tau, K, d, n) + 8 * (int64_t)(n_tau) * ((int64_t)(K) + 2))
+#define SAE_REFIT_SLOTS(n_tau, K, d, n) (SAE_REFIT_KEPT(n_tau, K, d, n) + 8 * ((int64_t)(K) + 1))
+#define SAE_REFIT_NEG(n_tau, K, d, n) (SAE_REFIT_SLOTS(n_tau, K, d, n) + 8 * (int64_t)(n))
+#define SAE_REFIT_DEP(n_tau, K, d, n) (SAE_REFIT_SLOTS(n_tau, K, d, n) + 16 * (int64_t)(n))
+#define SAE_REFIT_RATIO(n_tau, K, d, n) (SAE_REFIT_SLOTS(n_tau, K, d, n) + 24 * (int64_t)(n))
+#define SAE_REFIT_BAD_INDEX(n_tau, K, d, n) (SAE_REFIT_RATIO(n_tau, K, d, n) + 8 * (int64_t)SAE_REFIT_RATIO_BINS)
+#define SAE_REFIT_BYTES(n_tau, K, d, n) (SAE_REFIT_BAD_INDEX(n_tau, K, d, n) + 8)
+int sae_refit_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                    int K, const float* thresholds /* host, [n_tau] */, int n_tau, int flags, const int32_t* support_idx_dev,
+                    void* block_dev, float* trace_coef_dev, float* trace_err_dev, unsigned char* trace_dep_dev, float* trace_gram_dev,
+                    void* stream);
+
 /* ---- Feature index: the latent-major postings of an indexed feature store -- for every latent the (position, value) of the slots
  * that fire it, positions ascending (freud_amd/feature_index.py; kernels: freud_amd/csrc/findex.h).  The reference has no index:
  * it rebuilds one latent's series from the row-major store by scanning every slot of every file, per query
