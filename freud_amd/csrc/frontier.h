@@ -150,6 +150,16 @@ struct FrTau {
   int n;
 };
 
+// The per-row tail of a pass that keeps its rows' norms in memory (pursuit.h, refit.h; the walk takes them from LDS): rowinfo, and
+// on a counted row the budgets of its e[K + 1] by the serial rule.  -> counted
+__device__ __forceinline__ bool fr_row_finish(bool counted, int64_t row, const float* __restrict__ e, int K, const FrTau& tau,
+                                              uint32_t* __restrict__ rowinfo, unsigned short* __restrict__ bud) {
+  rowinfo[row] = counted ? FR_COUNTED : 0u;
+  if (counted)
+    for (int t = 0; t < tau.n; ++t) bud[row * FR_MAX_TAU + t] = (unsigned short)fr_budget(e, K, tau.t[t]);
+  return counted;
+}
+
 // ---- the walk.  Grid: one workgroup per FR_UNIT rows.  vals / idx [M][K]: the slots collect.h wrote; row_nnz[M]: the row's active
 // latents; W [n_p][d_p]: the bf16 operand rows; b: fp32 [d] or null.  NPAIR > 0: d_p == 128 NPAIR at compile time.
 //   part    [units][FR_PART_LD]: sum of e_m over the unit's counted rows
@@ -369,8 +379,8 @@ __global__ __launch_bounds__(256) void frontier_dim_kernel(const T* __restrict__
 //   the next n_tau x chunks per threshold and chunk of FR_FOLD_ROWS rows: the histogram of the counted rows' budgets in LDS, its
 //                           non-empty bins added to budget[t] (integer atomics: order-free)
 //   the last chunks         n_frames, rows_cut, active_cut of a chunk (integer atomics)
-struct FrOut {                  // the caller's block (include/freud_sae.h, SAE_FRONTIER_*)
-  unsigned long long *n_frames, *rows_cut, *active_cut;
+struct FrOut {                  // the caller's block (include/freud_sae.h, SAE_FRONTIER_*, and the same fields of SAE_PURSUIT_* / SAE_REFIT_*)
+  unsigned long long *n_frames, *rows_cut, *active_cut;        // rows_cut / active_cut: null in a block without them
   double *sse, *sx, *sxx;
   unsigned long long* budget;
 };
@@ -432,8 +442,8 @@ __global__ __launch_bounds__(256) void frontier_fold_kernel(const float* __restr
       __syncthreads();
       if (tid == 0) {
         atomicAdd(o.n_frames, tot[0]);
-        atomicAdd(o.rows_cut, tot[1]);
-        atomicAdd(o.active_cut, tot[2]);
+        if (o.rows_cut) atomicAdd(o.rows_cut, tot[1]);
+        if (o.active_cut) atomicAdd(o.active_cut, tot[2]);
       }
     }
   }

@@ -938,83 +938,142 @@ extern "C" int sae_collect_files(sae_ctx* c, const void* x, int64_t n_files, int
   return SAE_OK;
 }
 
-// ---- sparsity frontier (frontier.h): the squared error of every counted frame at every latent budget 0 .. K -- the slots of
-// sae_collect_files into context scratch, one walk of them per row, the fold into the caller's block
+// ---- the frontier family: sae_frontier_files (frontier.h), sae_pursuit_files (pursuit.h), sae_refit_files (refit.h).  Each gets the
+// squared error of every counted frame at every latent budget 0 .. K its own way, leaves part / rowinfo / bud in context scratch and
+// ends in the frontier's fold into the caller's block.  First what the three share on the host.
 static_assert(SAE_FRONTIER_MAX_K == FR_MAX_K && SAE_FRONTIER_MAX_TAU == FR_MAX_TAU && FR_MAX_K <= CL_MAX_K && FR_UNIT % 4 == 0,
               "freud_sae.h, frontier.h and collect.h disagree");
+static_assert(SAE_PURSUIT_MAX_K == PU_MAX_K && SAE_PURSUIT_MAX_TAU == PU_MAX_TAU, "freud_sae.h and pursuit.h disagree");
+static_assert(SAE_REFIT_MAX_K == RF_MAX_K && SAE_REFIT_MAX_TAU == RF_MAX_TAU && SAE_REFIT_RATIO_BINS == RF_RATIO_BINS && RF_MAX_K <= FR_MAX_K &&
+                  RF_MAX_K % 32 == 0,
+              "freud_sae.h, refit_chol.h and frontier.h disagree");
 
-struct FrontierScratch {        // its scratch area carved up
-  float* vals;                  // [max_rows][kcap] the slots, kcap = min(FR_MAX_K, k or n)
-  int* idx;
-  int64_t* cstats;              // [8] the collect kernels' totals (not reported)
-  uint32_t *row_nnz, *rowinfo;  // [max_rows]
+// the caller's thresholds (a host array) as the kernels' argument
+static int frontier_tau(const float* thresholds, int n_tau, int max_tau, FrTau* tau) {
+  if (n_tau < 0 || n_tau > max_tau) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, max_tau);
+  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
+  *tau = FrTau{};
+  tau->n = n_tau;
+  for (int t = 0; t < n_tau; ++t) {
+    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
+    tau->t[t] = thresholds[t];
+  }
+  return SAE_OK;
+}
+
+// the operand rows [n_p][d_p] and the bias: L1 -- the transposed copy of the normalised bf16 W, no bias; TopK -- W_dec and b_dec
+struct FrOperand {
+  const bf16_t* W;
+  const float* b;
+};
+static FrOperand frontier_operand(const sae_ctx* c) {
+  if (c->topk) return {c->Wd_b, c->P + 2 * c->nW + c->n_p};
+  return {c->Wt, nullptr};
+}
+
+// The scratch areas are carved piece by piece from a running pointer (from a null base: the size alone).  Apart from cstats every
+// piece is written with plain stores before it is read, so the leftovers of another pass do not matter.
+static char* take(char*& p, int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; }
+static int64_t frontier_units(const sae_ctx* c) { return (c->cfg.max_rows + FR_UNIT - 1) / FR_UNIT; }
+
+struct FoldScratch {            // what the fold reads
+  uint32_t* rowinfo;            // [max_rows]
   unsigned short* bud;          // [max_rows][FR_MAX_TAU]
   float *part, *dimpart;        // [units][FR_PART_LD], [128-row blocks][2][d_p]
+};
+static FoldScratch fold_scratch(const sae_ctx* c, char*& p) {
+  const int64_t rows = c->cfg.max_rows, nrb = (rows + STATS_RB - 1) / STATS_RB;
+  FoldScratch f;
+  f.rowinfo = (uint32_t*)take(p, rows * 4);
+  f.bud = (unsigned short*)take(p, rows * FR_MAX_TAU * 2);
+  f.part = (float*)take(p, frontier_units(c) * FR_PART_LD * 4);
+  f.dimpart = (float*)take(p, nrb * 2 * c->d_p * 4);
+  return f;
+}
+
+struct SlotScratch {            // the slots of the collect kernels
+  float* vals;                  // [max_rows][kcap], kcap = min(the pass's MAX_K, k or n)
+  int* idx;
+  int64_t* cstats;              // [8] the collect kernels' totals (not reported)
+  uint32_t* row_nnz;            // [max_rows]
+};
+static SlotScratch slot_scratch(const sae_ctx* c, int64_t max_k, char*& p) {
+  const int64_t rows = c->cfg.max_rows, kcap = std::min<int64_t>(max_k, c->topk ? c->k : c->n);
+  SlotScratch sl;
+  sl.vals = (float*)take(p, rows * kcap * 4);
+  sl.idx = (int*)take(p, rows * kcap * 4);
+  sl.cstats = (int64_t*)take(p, 64);
+  sl.row_nnz = (uint32_t*)take(p, rows * 4);
+  return sl;
+}
+
+// every row's K slots and its number of active latents into sl, inside the bracket kid
+static int collect_slots(sae_ctx* c, int64_t M, int K, const SlotScratch& sl, int kid, hipStream_t s) {
+  // the collect kernels ADD their totals to cstats (never reported): cleared, since the area holds another pass's leftovers
+  HIP_TRY(hipMemsetAsync(sl.cstats, 0, 64, s));
+  ev_begin(c, kid, s);
+  collect_launch(c, M, K, sl.vals, sl.idx, sl.cstats, s, sl.row_nnz);
+  ev_end(c, kid, s);
+  return SAE_OK;
+}
+
+// the fields every block of the family has, at their offsets in block; rows_cut / active_cut stay null (the fold skips them)
+static FrOut fold_out(void* block, int64_t n_frames, int64_t sse, int64_t sum_x, int64_t sum_x_sq, int64_t budget) {
+  char* b = (char*)block;
+  FrOut o{};
+  o.n_frames = (unsigned long long*)(b + n_frames);
+  o.sse = (double*)(b + sse);
+  o.sx = (double*)(b + sum_x);
+  o.sxx = (double*)(b + sum_x_sq);
+  o.budget = (unsigned long long*)(b + budget);
+  return o;
+}
+
+// the dimension sums of the batch, then the fold of part / rowinfo / bud / dimpart into the block (the caller's KID_*_FOLD bracket)
+template <typename T>
+static void frontier_fold_launch(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, int n_tau, const FoldScratch& f,
+                                 const FrOut& o, hipStream_t s) {
+  const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT), nrb = (int)((M + STATS_RB - 1) / STATS_RB);
+  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, 1.0f / (float)Trows,
+                     lengths, c->d, c->d_p, f.dimpart);
+  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
+  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
+  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (n_tau + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
+                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, n_tau, o, nb_s, nb_dim, n_chunks);
+}
+
+// ---- sparsity frontier (frontier.h): the slots of sae_collect_files into context scratch, one walk of them per row, the fold
+struct FrontierScratch {
+  SlotScratch slots;
+  FoldScratch fold;
   int64_t bytes;
 };
 
 static FrontierScratch frontier_scratch(const sae_ctx* c, char* base) {
-  const int64_t rows = c->cfg.max_rows, kcap = std::min<int64_t>(FR_MAX_K, c->topk ? c->k : c->n);
-  const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
   char* p = base;
-  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
   FrontierScratch f;
-  f.vals = (float*)take(rows * kcap * 4);
-  f.idx = (int*)take(rows * kcap * 4);
-  f.cstats = (int64_t*)take(64);
-  f.row_nnz = (uint32_t*)take(rows * 4);
-  f.rowinfo = (uint32_t*)take(rows * 4);
-  f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
-  f.part = (float*)take(units * FR_PART_LD * 4);
-  f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
+  f.slots = slot_scratch(c, FR_MAX_K, p);
+  f.fold = fold_scratch(c, p);
   f.bytes = p - base;
   return f;
-}
-
-static FrOut frontier_out(void* block, int n_tau, int K, int d) {
-  char* b = (char*)block;
-  FrOut o;
-  o.n_frames = (unsigned long long*)(b + SAE_FRONTIER_N_FRAMES(n_tau, K, d));
-  o.rows_cut = (unsigned long long*)(b + SAE_FRONTIER_ROWS_CUT(n_tau, K, d));
-  o.active_cut = (unsigned long long*)(b + SAE_FRONTIER_ACTIVE_CUT(n_tau, K, d));
-  o.sse = (double*)(b + SAE_FRONTIER_SSE(n_tau, K, d));
-  o.sx = (double*)(b + SAE_FRONTIER_SUM_X(n_tau, K, d));
-  o.sxx = (double*)(b + SAE_FRONTIER_SUM_X_SQ(n_tau, K, d));
-  o.budget = (unsigned long long*)(b + SAE_FRONTIER_BUDGET(n_tau, K, d));
-  return o;
 }
 
 template <typename T>
 static int frontier_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const FrOut& o,
                          const FrontierScratch& f, hipStream_t s) {
-  // the collect kernels ADD their totals to cstats (never reported): cleared, since the area holds another pass's leftovers; every
-  // other part of the scratch is written with plain stores before it is read
-  HIP_TRY(hipMemsetAsync(f.cstats, 0, 64, s));
-  ev_begin(c, KID_FRONTIER_SORT, s);
-  collect_launch(c, M, K, f.vals, f.idx, f.cstats, s, f.row_nnz);
-  ev_end(c, KID_FRONTIER_SORT, s);
-
-  // the operand rows [n_p][d_p] and the bias: L1 -- the transposed copy of the normalised bf16 W, no bias; TopK -- W_dec and b_dec
-  const bf16_t* W = c->topk ? c->Wd_b : c->Wt;
-  const float* b = c->topk ? c->P + 2 * c->nW + c->n_p : nullptr;
-  const float inv_T = 1.0f / (float)Trows;
-  const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT);
+  if (int rc = collect_slots(c, M, K, f.slots, KID_FRONTIER_SORT, s)) return rc;
+  const FrOperand op = frontier_operand(c);
   ev_begin(c, KID_FRONTIER_WALK, s);
   with_np(c->d_p, [&](auto np_tag) {
     constexpr int NP = decltype(np_tag)::value;
-    hipLaunchKernelGGL((frontier_walk_kernel<T, NP>), dim3((unsigned)n_units), dim3(256), 0, s, x, b, f.vals, f.idx, f.row_nnz, K, W, M, Trows,
-                       inv_T, lengths, c->d, c->d_p, c->n_p, tau, f.part, f.rowinfo, f.bud);
+    hipLaunchKernelGGL((frontier_walk_kernel<T, NP>), dim3((unsigned)((M + FR_UNIT - 1) / FR_UNIT)), dim3(256), 0, s, x, op.b, f.slots.vals,
+                       f.slots.idx, f.slots.row_nnz, K, op.W, M, Trows, 1.0f / (float)Trows, lengths, c->d, c->d_p, c->n_p, tau, f.fold.part,
+                       f.fold.rowinfo, f.fold.bud);
   });
   ev_end(c, KID_FRONTIER_WALK, s);
 
   ev_begin(c, KID_FRONTIER_FOLD, s);
-  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
-  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, inv_T, lengths, c->d,
-                     c->d_p, f.dimpart);
-  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
-  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
-  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (tau.n + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
-                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, tau.n, o, nb_s, nb_dim, n_chunks);
+  frontier_fold_launch(c, x, M, Trows, lengths, K, tau.n, f.fold, o, s);
   ev_end(c, KID_FRONTIER_FOLD, s);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
@@ -1028,14 +1087,8 @@ extern "C" int sae_frontier_files(sae_ctx* c, const void* x, int64_t n_files, in
   const int k_max = std::min(c->topk ? c->k : c->n, (int)SAE_FRONTIER_MAX_K);
   if (K < 1 || K > k_max)
     return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max, c->topk ? "min(the context's k, SAE_FRONTIER_MAX_K)" : "min(n_dict, SAE_FRONTIER_MAX_K)");
-  if (n_tau < 0 || n_tau > SAE_FRONTIER_MAX_TAU) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, SAE_FRONTIER_MAX_TAU);
-  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
-  FrTau tau{};
-  tau.n = n_tau;
-  for (int t = 0; t < n_tau; ++t) {
-    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
-    tau.t[t] = thresholds[t];
-  }
+  FrTau tau;
+  if (int rc = frontier_tau(thresholds, n_tau, SAE_FRONTIER_MAX_TAU, &tau)) return rc;
   if (c->d_p > FR_MAX_D) return fail(SAE_ERR_INVALID, "sae_frontier_files: the walk serves d_model <= %d", FR_MAX_D);
   if (c->topk && c->k > CL_MAX_K) return fail(SAE_ERR_INVALID, "sae_frontier_files: k=%d > %d", c->k, CL_MAX_K);
   char* scratch;
@@ -1043,7 +1096,11 @@ extern "C" int sae_frontier_files(sae_ctx* c, const void* x, int64_t n_files, in
   const FrontierScratch f = frontier_scratch(c, scratch);
   hipStream_t s = (hipStream_t)stream;
   if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-  const FrOut o = frontier_out(block, n_tau, K, c->d);
+  const int d = c->d;
+  FrOut o = fold_out(block, SAE_FRONTIER_N_FRAMES(n_tau, K, d), SAE_FRONTIER_SSE(n_tau, K, d), SAE_FRONTIER_SUM_X(n_tau, K, d),
+                     SAE_FRONTIER_SUM_X_SQ(n_tau, K, d), SAE_FRONTIER_BUDGET(n_tau, K, d));
+  o.rows_cut = (unsigned long long*)((char*)block + SAE_FRONTIER_ROWS_CUT(n_tau, K, d));
+  o.active_cut = (unsigned long long*)((char*)block + SAE_FRONTIER_ACTIVE_CUT(n_tau, K, d));
   if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return frontier_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, f, s); })) return rc;
   file_pass_end(kFrontierPass, c);
   return SAE_OK;
@@ -1051,39 +1108,29 @@ extern "C" int sae_frontier_files(sae_ctx* c, const void* x, int64_t n_files, in
 
 // ---- pursuit frontier (pursuit.h): every counted frame coded greedily against the decoder directions -- K (selection GEMM, step)
 // launch pairs on the caller's stream, then the frontier's own fold
-static_assert(SAE_PURSUIT_MAX_K == PU_MAX_K && SAE_PURSUIT_MAX_TAU == PU_MAX_TAU, "freud_sae.h and pursuit.h disagree");
-
-struct PursuitScratch {         // its scratch area carved up
+struct PursuitScratch {
   float* r32;                   // [max_rows_p][d_p] the fp32 residual
   unsigned short* rho;          // [max_rows_p][d_p] its bf16 image: the A operand of the selection GEMM
   unsigned long long* rowkey;   // [max_rows_p] the row's best key of the current step
   float *q, *z;                 // [n_p] the per-direction constants
-  uint32_t *rowstate, *rowinfo; // [max_rows]
+  uint32_t* rowstate;           // [max_rows]
   float* err;                   // [max_rows][K + 1] the rows' e_s (the caller's trace_err instead when a trace is asked for)
-  unsigned short* bud;          // [max_rows][FR_MAX_TAU]
-  float *part, *dimpart;        // [units][FR_PART_LD], [128-row blocks][2][d_p]
-  unsigned long long* unused;   // [2] where the shared fold adds the frontier's cut counts (not reported)
+  FoldScratch fold;
   int64_t bytes;
 };
 
 static PursuitScratch pursuit_scratch(const sae_ctx* c, int K, char* base) {
   const int64_t rows = c->cfg.max_rows, rows_p = c->max_rows_p;
-  const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
   char* p = base;
-  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
   PursuitScratch f;
-  f.r32 = (float*)take(rows_p * c->d_p * 4);
-  f.rho = (unsigned short*)take(rows_p * c->d_p * 2);
-  f.rowkey = (unsigned long long*)take(rows_p * 8);
-  f.q = (float*)take((int64_t)c->n_p * 4);
-  f.z = (float*)take((int64_t)c->n_p * 4);
-  f.rowstate = (uint32_t*)take(rows * 4);
-  f.rowinfo = (uint32_t*)take(rows * 4);
-  f.err = (float*)take(rows * (K + 1) * 4);
-  f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
-  f.part = (float*)take(units * FR_PART_LD * 4);
-  f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
-  f.unused = (unsigned long long*)take(16);
+  f.r32 = (float*)take(p, rows_p * c->d_p * 4);
+  f.rho = (unsigned short*)take(p, rows_p * c->d_p * 2);
+  f.rowkey = (unsigned long long*)take(p, rows_p * 8);
+  f.q = (float*)take(p, (int64_t)c->n_p * 4);
+  f.z = (float*)take(p, (int64_t)c->n_p * 4);
+  f.rowstate = (uint32_t*)take(p, rows * 4);
+  f.err = (float*)take(p, rows * (K + 1) * 4);
+  f.fold = fold_scratch(c, p);
   f.bytes = p - base;
   return f;
 }
@@ -1093,16 +1140,11 @@ struct PursuitOut {             // the caller's block (include/freud_sae.h, SAE_
   unsigned long long *steps, *picks, *in_support;
 };
 
-static PursuitOut pursuit_out(void* block, int n_tau, int K, int d, int n, const PursuitScratch& f) {
+static PursuitOut pursuit_out(void* block, int n_tau, int K, int d, int n) {
   char* b = (char*)block;
   PursuitOut o;
-  o.fold.n_frames = (unsigned long long*)(b + SAE_PURSUIT_N_FRAMES(n_tau, K, d, n));
-  o.fold.rows_cut = f.unused;
-  o.fold.active_cut = f.unused + 1;
-  o.fold.sse = (double*)(b + SAE_PURSUIT_SSE(n_tau, K, d, n));
-  o.fold.sx = (double*)(b + SAE_PURSUIT_SUM_X(n_tau, K, d, n));
-  o.fold.sxx = (double*)(b + SAE_PURSUIT_SUM_X_SQ(n_tau, K, d, n));
-  o.fold.budget = (unsigned long long*)(b + SAE_PURSUIT_BUDGET(n_tau, K, d, n));
+  o.fold = fold_out(block, SAE_PURSUIT_N_FRAMES(n_tau, K, d, n), SAE_PURSUIT_SSE(n_tau, K, d, n), SAE_PURSUIT_SUM_X(n_tau, K, d, n),
+                    SAE_PURSUIT_SUM_X_SQ(n_tau, K, d, n), SAE_PURSUIT_BUDGET(n_tau, K, d, n));
   o.steps = (unsigned long long*)(b + SAE_PURSUIT_STEPS(n_tau, K, d, n));
   o.picks = (unsigned long long*)(b + SAE_PURSUIT_PICKS(n_tau, K, d, n));
   o.in_support = (unsigned long long*)(b + SAE_PURSUIT_IN_SUPPORT(n_tau, K, d, n));
@@ -1112,9 +1154,8 @@ static PursuitOut pursuit_out(void* block, int n_tau, int K, int d, int n, const
 template <typename T>
 static int pursuit_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const PursuitOut& o,
                         const PursuitScratch& f, float* err, const PuTrace& tr, hipStream_t s) {
-  // the operand rows [n_p][d_p] and the bias, as the frontier takes them
-  const bf16_t* W = c->topk ? c->Wd_b : c->Wt;
-  const float* b = c->topk ? c->P + 2 * c->nW + c->n_p : nullptr;
+  const FrOperand op = frontier_operand(c);
+  const bf16_t* W = op.W;
   const float inv_T = 1.0f / (float)Trows;
   int64_t Mp = round_up(M, 128);
   if (round_up(M, 256) <= c->max_rows_p) Mp = round_up(M, 256);        // (an even number of row blocks: the 256-edge tile grid)
@@ -1124,7 +1165,7 @@ static int pursuit_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int*
 
   // (the constants and the initialiser run once per call: outside the per-step brackets, which then hold K records each)
   hipLaunchKernelGGL(pursuit_const_kernel, dim3((unsigned)((c->n_p + 3) / 4)), dim3(256), 0, s, W, c->n, c->n_p, c->d_p, f.q, f.z);
-  hipLaunchKernelGGL(pursuit_init_kernel<T>, dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, s, x, b, M, Mp, Trows, inv_T, lengths, c->d, c->d_p, K,
+  hipLaunchKernelGGL(pursuit_init_kernel<T>, dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, s, x, op.b, M, Mp, Trows, inv_T, lengths, c->d, c->d_p, K,
                      f.r32, f.rho, err, f.rowstate, f.rowkey, tr);
   HIP_TRY(hipGetLastError());
 
@@ -1148,15 +1189,9 @@ static int pursuit_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int*
   }
 
   ev_begin(c, KID_PURSUIT_FOLD, s);
-  const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT);
-  hipLaunchKernelGGL(pursuit_finish_kernel, dim3((unsigned)n_units), dim3(256), 0, s, err, f.rowstate, M, K, tau, f.part, f.rowinfo, f.bud, o.steps);
-  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
-  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, inv_T, lengths, c->d,
-                     c->d_p, f.dimpart);
-  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
-  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
-  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (tau.n + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
-                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, tau.n, o.fold, nb_s, nb_dim, n_chunks);
+  hipLaunchKernelGGL(pursuit_finish_kernel, dim3((unsigned)((M + FR_UNIT - 1) / FR_UNIT)), dim3(256), 0, s, err, f.rowstate, M, K, tau, f.fold.part,
+                     f.fold.rowinfo, f.fold.bud, o.steps);
+  frontier_fold_launch(c, x, M, Trows, lengths, K, tau.n, f.fold, o.fold, s);
   ev_end(c, KID_PURSUIT_FOLD, s);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
@@ -1169,14 +1204,8 @@ extern "C" int sae_pursuit_files(sae_ctx* c, const void* x, int64_t n_files, int
   if (int rc = file_pass_begin(kPursuitPass, c, x, block, n_files, rows_per_file, x_dtype, flags, &M)) return rc;
   if (misaligned(block, 8)) return fail(SAE_ERR_INVALID, "the pursuit block must be 8-byte aligned");
   if (K < 1 || K > SAE_PURSUIT_MAX_K) return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (SAE_PURSUIT_MAX_K)", K, SAE_PURSUIT_MAX_K);
-  if (n_tau < 0 || n_tau > SAE_PURSUIT_MAX_TAU) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, SAE_PURSUIT_MAX_TAU);
-  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
-  FrTau tau{};
-  tau.n = n_tau;
-  for (int t = 0; t < n_tau; ++t) {
-    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
-    tau.t[t] = thresholds[t];
-  }
+  FrTau tau;
+  if (int rc = frontier_tau(thresholds, n_tau, SAE_PURSUIT_MAX_TAU, &tau)) return rc;
   const int n_trace = (trace_idx != nullptr) + (trace_val != nullptr) + (trace_err != nullptr);
   if (n_trace != 0 && n_trace != 3) return fail(SAE_ERR_INVALID, "the trace is three pointers, all or none");
   if (misaligned(trace_idx, 4) || misaligned(trace_val, 4) || misaligned(trace_err, 4)) return fail(SAE_ERR_INVALID, "the trace arrays must be 4-byte aligned");
@@ -1186,7 +1215,7 @@ extern "C" int sae_pursuit_files(sae_ctx* c, const void* x, int64_t n_files, int
   const PursuitScratch f = pursuit_scratch(c, K, scratch);
   hipStream_t s = (hipStream_t)stream;
   if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;          // (the encoder's own active set, for IN_SUPPORT)
-  const PursuitOut o = pursuit_out(block, n_tau, K, c->d, c->n, f);
+  const PursuitOut o = pursuit_out(block, n_tau, K, c->d, c->n);
   PuTrace tr{trace_idx, trace_val};
   float* err = n_trace ? trace_err : f.err;
   if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return pursuit_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, o, f, err, tr, s); })) return rc;
@@ -1196,44 +1225,26 @@ extern "C" int sae_pursuit_files(sae_ctx* c, const void* x, int64_t n_files, int
 
 // ---- refit frontier (refit.h): the least-squares code of every counted frame on its encoder's support (the slots of the collect
 // kernels, in context scratch) or on a support the caller gives, one wave per frame, then the frontier's own fold
-static_assert(SAE_REFIT_MAX_K == RF_MAX_K && SAE_REFIT_MAX_TAU == RF_MAX_TAU && SAE_REFIT_RATIO_BINS == RF_RATIO_BINS && RF_MAX_K <= FR_MAX_K &&
-                  RF_MAX_K % 32 == 0,
-              "freud_sae.h, refit_chol.h and frontier.h disagree");
-
-struct RefitScratch {           // its scratch area carved up
-  float* vals;                  // [max_rows][kcap] the slots, kcap = min(RF_MAX_K, k or n)
-  int* idx;
-  int64_t* cstats;              // [8] the collect kernels' totals (not reported)
-  uint32_t *row_nnz, *rowinfo;  // [max_rows]
-  unsigned short* bud;          // [max_rows][FR_MAX_TAU]
-  float *part, *dimpart;        // [units][FR_PART_LD], [128-row blocks][2][d_p]
+struct RefitScratch {
+  SlotScratch slots;
+  FoldScratch fold;
   float* err;                   // [max_rows][K + 1] the rows' e_s (the caller's trace_err instead when it is given)
   float* efin;                  // [max_rows]
   int* keptn;                   // [max_rows] the row's kept slots, -1 on a row that does not count
   float* finpart;               // [units] sums of e_final
-  unsigned long long* unused;   // [2] where the shared fold adds the frontier's cut counts (not reported)
   int64_t bytes;
 };
 
 static RefitScratch refit_scratch(const sae_ctx* c, int K, char* base) {
-  const int64_t rows = c->cfg.max_rows, kcap = std::min<int64_t>(RF_MAX_K, c->topk ? c->k : c->n);
-  const int64_t units = (rows + FR_UNIT - 1) / FR_UNIT, nrb = (rows + STATS_RB - 1) / STATS_RB;
+  const int64_t rows = c->cfg.max_rows;
   char* p = base;
-  auto take = [&](int64_t bytes) { char* q = p; p += round_up(bytes, 16); return q; };
   RefitScratch f;
-  f.vals = (float*)take(rows * kcap * 4);
-  f.idx = (int*)take(rows * kcap * 4);
-  f.cstats = (int64_t*)take(64);
-  f.row_nnz = (uint32_t*)take(rows * 4);
-  f.rowinfo = (uint32_t*)take(rows * 4);
-  f.bud = (unsigned short*)take(rows * FR_MAX_TAU * 2);
-  f.part = (float*)take(units * FR_PART_LD * 4);
-  f.dimpart = (float*)take(nrb * 2 * c->d_p * 4);
-  f.err = (float*)take(rows * (K + 1) * 4);
-  f.efin = (float*)take(rows * 4);
-  f.keptn = (int*)take(rows * 4);
-  f.finpart = (float*)take(units * 4);
-  f.unused = (unsigned long long*)take(16);
+  f.slots = slot_scratch(c, RF_MAX_K, p);
+  f.fold = fold_scratch(c, p);
+  f.err = (float*)take(p, rows * (K + 1) * 4);
+  f.efin = (float*)take(p, rows * 4);
+  f.keptn = (int*)take(p, rows * 4);
+  f.finpart = (float*)take(p, frontier_units(c) * 4);
   f.bytes = p - base;
   return f;
 }
@@ -1245,16 +1256,11 @@ struct RefitOut {               // the caller's block (include/freud_sae.h, SAE_
   RfCount cnt;
 };
 
-static RefitOut refit_out(void* block, int n_tau, int K, int d, int n, const RefitScratch& f) {
+static RefitOut refit_out(void* block, int n_tau, int K, int d, int n) {
   char* b = (char*)block;
   RefitOut o;
-  o.fold.n_frames = (unsigned long long*)(b + SAE_REFIT_N_FRAMES(n_tau, K, d, n));
-  o.fold.rows_cut = f.unused;
-  o.fold.active_cut = f.unused + 1;
-  o.fold.sse = (double*)(b + SAE_REFIT_SSE(n_tau, K, d, n));
-  o.fold.sx = (double*)(b + SAE_REFIT_SUM_X(n_tau, K, d, n));
-  o.fold.sxx = (double*)(b + SAE_REFIT_SUM_X_SQ(n_tau, K, d, n));
-  o.fold.budget = (unsigned long long*)(b + SAE_REFIT_BUDGET(n_tau, K, d, n));
+  o.fold = fold_out(block, SAE_REFIT_N_FRAMES(n_tau, K, d, n), SAE_REFIT_SSE(n_tau, K, d, n), SAE_REFIT_SUM_X(n_tau, K, d, n),
+                    SAE_REFIT_SUM_X_SQ(n_tau, K, d, n), SAE_REFIT_BUDGET(n_tau, K, d, n));
   o.sse_final = (double*)(b + SAE_REFIT_SSE_FINAL(n_tau, K, d, n));
   o.kept = (unsigned long long*)(b + SAE_REFIT_KEPT(n_tau, K, d, n));
   o.cnt.slots = (unsigned long long*)(b + SAE_REFIT_SLOTS(n_tau, K, d, n));
@@ -1279,41 +1285,27 @@ static int refit_launch(sae_ctx* c, const T* x, const float* b, const RfSupport&
 template <typename T>
 static int refit_impl(sae_ctx* c, const T* x, int64_t M, int Trows, const int* lengths, int K, const FrTau& tau, const int* given,
                       const RefitOut& o, const RefitScratch& f, float* err, const RfTrace& tr, hipStream_t s) {
-  RfSupport sup{f.vals, f.idx, given};
-  if (!given) {
-    // the collect kernels ADD their totals to cstats (never reported): cleared, since the area holds another pass's leftovers
-    HIP_TRY(hipMemsetAsync(f.cstats, 0, 64, s));
-    ev_begin(c, KID_REFIT_SORT, s);
-    collect_launch(c, M, K, f.vals, f.idx, f.cstats, s, f.row_nnz);
-    ev_end(c, KID_REFIT_SORT, s);
-  }
-  // the operand rows [n_p][d_p] and the bias, as the frontier takes them
-  const bf16_t* W = c->topk ? c->Wd_b : c->Wt;
-  const float* b = c->topk ? c->P + 2 * c->nW + c->n_p : nullptr;
+  RfSupport sup{f.slots.vals, f.slots.idx, given};
+  if (!given)
+    if (int rc = collect_slots(c, M, K, f.slots, KID_REFIT_SORT, s)) return rc;
+  const FrOperand op = frontier_operand(c);
   ev_begin(c, KID_REFIT_CHOL, s);
   int rc;
   switch ((K + 31) / 32) {
-    case 1: rc = refit_launch<T, 1>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
-    case 2: rc = refit_launch<T, 2>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
-    case 3: rc = refit_launch<T, 3>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
-    default: rc = refit_launch<T, 4>(c, x, b, sup, K, W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    case 1: rc = refit_launch<T, 1>(c, x, op.b, sup, K, op.W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    case 2: rc = refit_launch<T, 2>(c, x, op.b, sup, K, op.W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    case 3: rc = refit_launch<T, 3>(c, x, op.b, sup, K, op.W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
+    default: rc = refit_launch<T, 4>(c, x, op.b, sup, K, op.W, M, Trows, lengths, err, f, tr, o.cnt, s); break;
   }
   ev_end(c, KID_REFIT_CHOL, s);
   if (rc) return rc;
 
   ev_begin(c, KID_REFIT_FOLD, s);
-  const float inv_T = 1.0f / (float)Trows;
   const int n_units = (int)((M + FR_UNIT - 1) / FR_UNIT);
-  hipLaunchKernelGGL(refit_finish_kernel, dim3((unsigned)n_units), dim3(256), 0, s, err, f.efin, f.keptn, M, K, tau, f.part, f.rowinfo, f.bud,
-                     f.finpart, o.kept);
+  hipLaunchKernelGGL(refit_finish_kernel, dim3((unsigned)n_units), dim3(256), 0, s, err, f.efin, f.keptn, M, K, tau, f.fold.part, f.fold.rowinfo,
+                     f.fold.bud, f.finpart, o.kept);
   hipLaunchKernelGGL(refit_final_kernel, dim3(1), dim3(64), 0, s, f.finpart, n_units, o.sse_final);
-  const int nrb = (int)((M + STATS_RB - 1) / STATS_RB);
-  hipLaunchKernelGGL(frontier_dim_kernel<T>, dim3((unsigned)nrb, (unsigned)(c->d_p / 64)), dim3(256), 0, s, x, M, Trows, inv_T, lengths, c->d,
-                     c->d_p, f.dimpart);
-  const int nb_s = (K + 1 + 255) / 256, nb_dim = (c->d + 255) / 256;
-  const int n_chunks = (int)((M + FR_FOLD_ROWS - 1) / FR_FOLD_ROWS);
-  hipLaunchKernelGGL(frontier_fold_kernel, dim3((unsigned)(nb_s + nb_dim + (tau.n + 1) * n_chunks)), dim3(256), 0, s, f.part, n_units, K,
-                     f.dimpart, nrb, c->d, c->d_p, f.rowinfo, f.bud, M, tau.n, o.fold, nb_s, nb_dim, n_chunks);
+  frontier_fold_launch(c, x, M, Trows, lengths, K, tau.n, f.fold, o.fold, s);
   ev_end(c, KID_REFIT_FOLD, s);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
@@ -1329,14 +1321,8 @@ extern "C" int sae_refit_files(sae_ctx* c, const void* x, int64_t n_files, int64
   if (K < 1 || K > k_max)
     return fail(SAE_ERR_INVALID, "K=%d outside [1, %d] (%s)", K, k_max,
                 support_idx ? "SAE_REFIT_MAX_K" : c->topk ? "min(the context's k, SAE_REFIT_MAX_K)" : "min(n_dict, SAE_REFIT_MAX_K)");
-  if (n_tau < 0 || n_tau > SAE_REFIT_MAX_TAU) return fail(SAE_ERR_INVALID, "n_tau=%d outside [0, %d]", n_tau, SAE_REFIT_MAX_TAU);
-  if (n_tau > 0 && !thresholds) return fail(SAE_ERR_INVALID, "null argument");
-  FrTau tau{};
-  tau.n = n_tau;
-  for (int t = 0; t < n_tau; ++t) {
-    if (!(thresholds[t] > 0.f && thresholds[t] < 1.f)) return fail(SAE_ERR_INVALID, "threshold %d = %g is not inside (0, 1)", t, (double)thresholds[t]);
-    tau.t[t] = thresholds[t];
-  }
+  FrTau tau;
+  if (int rc = frontier_tau(thresholds, n_tau, SAE_REFIT_MAX_TAU, &tau)) return rc;
   if (misaligned(support_idx, 4) || misaligned(trace_coef, 4) || misaligned(trace_err, 4) || misaligned(trace_gram, 4))
     return fail(SAE_ERR_INVALID, "the support and the trace arrays must be 4-byte aligned");
   if (c->d_p > FR_MAX_D) return fail(SAE_ERR_INVALID, "sae_refit_files: the refit serves d_model <= %d", FR_MAX_D);
@@ -1347,7 +1333,7 @@ extern "C" int sae_refit_files(sae_ctx* c, const void* x, int64_t n_files, int64
   hipStream_t s = (hipStream_t)stream;
   if (support_idx) refresh_decoder_operand(c, s);       // (no encoder runs: the operand rows of the current weights all the same)
   else if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
-  const RefitOut o = refit_out(block, n_tau, K, c->d, c->n, f);
+  const RefitOut o = refit_out(block, n_tau, K, c->d, c->n);
   const RfTrace tr{trace_coef, trace_dep, trace_gram};
   float* err = trace_err ? trace_err : f.err;
   if (int rc = with_x_type(x_dtype, x, [&](auto* xt) { return refit_impl(c, xt, M, (int)rows_per_file, lengths, K, tau, support_idx, o, f, err, tr, s); }))

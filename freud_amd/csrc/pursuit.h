@@ -398,13 +398,7 @@ __global__ __launch_bounds__(256) void pursuit_finish_kernel(const float* __rest
   const int64_t row = row0 + tid;
   if (tid < FR_UNIT && row < M) {
     const uint32_t st = rowstate[row];
-    if (!(st & PU_COUNTED)) {
-      rowinfo[row] = 0u;
-      return;
-    }
-    rowinfo[row] = FR_COUNTED;
-    const float* e = err + row * (K + 1);
-    for (int t = 0; t < tau.n; ++t) bud[row * FR_MAX_TAU + t] = (unsigned short)fr_budget(e, K, tau.t[t]);
+    if (!fr_row_finish((st & PU_COUNTED) != 0, row, err + row * (K + 1), K, tau, rowinfo, bud)) return;
     const uint32_t ns = st & PU_STEPS_MASK;
     atomicAdd(steps + (ns <= (uint32_t)K ? ns : (uint32_t)K), 1ull);
   }

@@ -423,13 +423,7 @@ __global__ __launch_bounds__(256) void refit_finish_kernel(const float* __restri
   const int64_t row = row0 + tid;
   if (tid < FR_UNIT && row < M) {
     const int nk = keptn[row];
-    if (nk < 0) {
-      rowinfo[row] = 0u;
-      return;
-    }
-    rowinfo[row] = FR_COUNTED;
-    const float* e = err + row * (K + 1);
-    for (int t = 0; t < tau.n; ++t) bud[row * FR_MAX_TAU + t] = (unsigned short)fr_budget(e, K, tau.t[t]);
+    if (!fr_row_finish(nk >= 0, row, err + row * (K + 1), K, tau, rowinfo, bud)) return;
     atomicAdd(kept_hist + (nk <= K ? nk : K), 1ull);
   }
 }

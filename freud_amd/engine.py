@@ -227,58 +227,56 @@ RESAMPLE_NCOUNTS = 8                                                # include/fr
 INPUT_MAX_D, INPUT_MAX_ITERATIONS = 2048, 1024                      # include/freud_sae.h: SAE_INPUT_MAX_*
 
 
+_DTYPE_BYTES = {"int64": 8, "float64": 8, "float32": 4}
+
+
+def _layout(fields, align: int = 1) -> dict:
+    """An output block as include/freud_sae.h lays it out -- the fields (name, dtype, count) one after another from offset 0:
+    name -> (offset, dtype, count), plus "bytes": the block's size, rounded up to `align`."""
+    out, at = {}, 0
+    for name, dtype, count in fields:
+        out[name] = (at, dtype, count)
+        at += _DTYPE_BYTES[dtype] * count
+    out["bytes"] = -(-at // align) * align
+    return out
+
+
 def stats_layout(n: int) -> dict:
-    """Byte offsets of the sae_stats_files block for n latents (include/freud_sae.h: SAE_STATS_*): name -> (offset, dtype, count),
-    plus "bytes": the block's size."""
-    return {"n_frames": (0, "int64", 1), "fire_count": (8, "int64", n), "act_sum": (8 + 8 * n, "float64", n),
-            "act_sq_sum": (8 + 16 * n, "float64", n), "l0_hist": (8 + 24 * n, "int64", n + 1),
-            "act_max": (16 + 32 * n, "float32", n), "bytes": 16 + 36 * n}
+    """The sae_stats_files block for n latents (include/freud_sae.h: SAE_STATS_*): see _layout."""
+    return _layout([("n_frames", "int64", 1), ("fire_count", "int64", n), ("act_sum", "float64", n), ("act_sq_sum", "float64", n),
+                    ("l0_hist", "int64", n + 1), ("act_max", "float32", n)])
 
 
 def recon_layout(n: int, d: int) -> dict:
-    """Byte offsets of the sae_recon_files block for n latents and d model dimensions (include/freud_sae.h: SAE_RECON_*):
-    name -> (offset, dtype, count), plus "bytes": the block's size."""
-    return {"n_frames": (0, "int64", 1), "attr_sum": (8, "float64", n), "act_sq_sum": (8 + 8 * n, "float64", n),
-            "sum_x": (8 + 16 * n, "float64", d), "sum_x_sq": (8 + 16 * n + 8 * d, "float64", d),
-            "sum_r_sq": (8 + 16 * n + 16 * d, "float64", d), "dec_norm_sq": (8 + 16 * n + 24 * d, "float32", n),
-            "bytes": (8 + 20 * n + 24 * d + 7) // 8 * 8}
+    """The sae_recon_files block for n latents and d model dimensions (include/freud_sae.h: SAE_RECON_*): see _layout."""
+    return _layout([("n_frames", "int64", 1), ("attr_sum", "float64", n), ("act_sq_sum", "float64", n), ("sum_x", "float64", d),
+                    ("sum_x_sq", "float64", d), ("sum_r_sq", "float64", d), ("dec_norm_sq", "float32", n)], align=8)
+
+
+def _curve_fields(n_tau: int, K: int, d: int, after_sse=()) -> list:
+    """What every block of the frontier family holds after its leading counts: the curve, the denominators, the budget histograms."""
+    return [("sse", "float64", K + 1), *after_sse, ("sum_x", "float64", d), ("sum_x_sq", "float64", d), ("budget", "int64", n_tau * (K + 2))]
 
 
 def frontier_layout(n_tau: int, K: int, d: int) -> dict:
-    """Byte offsets of the sae_frontier_files block for n_tau thresholds, K slots and d model dimensions (include/freud_sae.h:
-    SAE_FRONTIER_*): name -> (offset, dtype, count), plus "bytes": the block's size."""
-    return {"n_frames": (0, "int64", 1), "rows_cut": (8, "int64", 1), "active_cut": (16, "int64", 1), "sse": (24, "float64", K + 1),
-            "sum_x": (32 + 8 * K, "float64", d), "sum_x_sq": (32 + 8 * K + 8 * d, "float64", d),
-            "budget": (32 + 8 * K + 16 * d, "int64", n_tau * (K + 2)), "bytes": 32 + 8 * K + 16 * d + 8 * n_tau * (K + 2)}
+    """The sae_frontier_files block for n_tau thresholds, K slots and d model dimensions (include/freud_sae.h: SAE_FRONTIER_*): see
+    _layout."""
+    return _layout([("n_frames", "int64", 1), ("rows_cut", "int64", 1), ("active_cut", "int64", 1), *_curve_fields(n_tau, K, d)])
 
 
 def pursuit_layout(n_tau: int, K: int, d: int, n: int) -> dict:
-    """Byte offsets of the sae_pursuit_files block for n_tau thresholds, K steps, d model dimensions and n latents (include/freud_sae.h:
-    SAE_PURSUIT_*): name -> (offset, dtype, count), plus "bytes": the block's size."""
-    sx = 16 + 8 * K
-    bud = sx + 16 * d
-    steps = bud + 8 * n_tau * (K + 2)
-    picks = steps + 8 * (K + 1)
-    sup = picks + 8 * n
-    return {"n_frames": (0, "int64", 1), "sse": (8, "float64", K + 1), "sum_x": (sx, "float64", d), "sum_x_sq": (sx + 8 * d, "float64", d),
-            "budget": (bud, "int64", n_tau * (K + 2)), "steps": (steps, "int64", K + 1), "picks": (picks, "int64", n),
-            "in_support": (sup, "int64", K), "bytes": sup + 8 * K}
+    """The sae_pursuit_files block for n_tau thresholds, K steps, d model dimensions and n latents (include/freud_sae.h:
+    SAE_PURSUIT_*): see _layout."""
+    return _layout([("n_frames", "int64", 1), *_curve_fields(n_tau, K, d), ("steps", "int64", K + 1), ("picks", "int64", n),
+                    ("in_support", "int64", K)])
 
 
 def refit_layout(n_tau: int, K: int, d: int, n: int) -> dict:
-    """Byte offsets of the sae_refit_files block for n_tau thresholds, K slots, d model dimensions and n latents (include/freud_sae.h:
-    SAE_REFIT_*): name -> (offset, dtype, count), plus "bytes": the block's size."""
-    fin = 16 + 8 * K
-    sx = fin + 8
-    bud = sx + 16 * d
-    kept = bud + 8 * n_tau * (K + 2)
-    slots = kept + 8 * (K + 1)
-    ratio = slots + 24 * n
-    bad = ratio + 8 * REFIT_RATIO_BINS
-    return {"n_frames": (0, "int64", 1), "sse": (8, "float64", K + 1), "sse_final": (fin, "float64", 1), "sum_x": (sx, "float64", d),
-            "sum_x_sq": (sx + 8 * d, "float64", d), "budget": (bud, "int64", n_tau * (K + 2)), "kept": (kept, "int64", K + 1),
-            "slots": (slots, "int64", n), "neg": (slots + 8 * n, "int64", n), "dep": (slots + 16 * n, "int64", n),
-            "ratio": (ratio, "int64", REFIT_RATIO_BINS), "bad_index": (bad, "int64", 1), "bytes": bad + 8}
+    """The sae_refit_files block for n_tau thresholds, K slots, d model dimensions and n latents (include/freud_sae.h: SAE_REFIT_*):
+    see _layout."""
+    return _layout([("n_frames", "int64", 1), *_curve_fields(n_tau, K, d, after_sse=[("sse_final", "float64", 1)]),
+                    ("kept", "int64", K + 1), ("slots", "int64", n), ("neg", "int64", n), ("dep", "int64", n),
+                    ("ratio", "int64", REFIT_RATIO_BINS), ("bad_index", "int64", 1)])
 
 
 def unpack_block(block, layout: dict) -> Dict[str, np.ndarray]:
@@ -330,6 +328,14 @@ def _check(rc: int) -> None:
 
 def _np_f32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+
+
+def _tau_arg(fn_name: str, thresholds, max_tau: int) -> np.ndarray:
+    """The thresholds of a frontier-family pass as a flat float32 host array of at most max_tau values."""
+    tau = _np_f32(thresholds).reshape(-1)
+    if tau.size > max_tau:
+        raise EngineError(f"{fn_name}: {tau.size} thresholds > {max_tau}")
+    return tau
 
 
 def _shaped(name: str, a, shape) -> np.ndarray:
@@ -855,9 +861,7 @@ class SaeEngine:
         frontier_layout(len(thresholds), K, d)["bytes"] bytes); thresholds: up to FRONTIER_MAX_TAU floats inside (0, 1); lengths:
         int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the last-forward getters fail until the next eval() / step()."""
         x, xp, B, T, _d, dt, lp = _files_args(x, "frontier_files", lengths)
-        tau = _np_f32(thresholds).reshape(-1)
-        if tau.size > FRONTIER_MAX_TAU:
-            raise EngineError(f"frontier_files: {tau.size} thresholds > {FRONTIER_MAX_TAU}")
+        tau = _tau_arg("frontier_files", thresholds, FRONTIER_MAX_TAU)
         K = int(K)
         blk = _dev("block", block, "uint8", frontier_layout(tau.size, max(K, 0), self.d)["bytes"], at_least=True)
         _check(self._lib.sae_frontier_files(self._ctx, xp, B, T, dt, lp, K, tau.ctypes.data_as(_fptr), int(tau.size), 0, blk,
@@ -872,9 +876,7 @@ class SaeEngine:
         that receive this batch's pursuit code in pick order.  Asynchronous.  Afterwards the last-forward getters fail until the next
         eval() / step()."""
         x, xp, B, T, _d, dt, lp = _files_args(x, "pursuit_files", lengths)
-        tau = _np_f32(thresholds).reshape(-1)
-        if tau.size > PURSUIT_MAX_TAU:
-            raise EngineError(f"pursuit_files: {tau.size} thresholds > {PURSUIT_MAX_TAU}")
+        tau = _tau_arg("pursuit_files", thresholds, PURSUIT_MAX_TAU)
         K = int(K)
         blk = _dev("block", block, "uint8", pursuit_layout(tau.size, max(K, 0), self.d, self.n)["bytes"], at_least=True)
         ti = tv = te = None
@@ -897,9 +899,7 @@ class SaeEngine:
         (float32, n_files * T * (K + 1) * K), contiguous CUDA tensors that receive this batch's rows.  Asynchronous.  Afterwards the
         last-forward getters fail until the next eval() / step()."""
         x, xp, B, T, _d, dt, lp = _files_args(x, "refit_files", lengths)
-        tau = _np_f32(thresholds).reshape(-1)
-        if tau.size > REFIT_MAX_TAU:
-            raise EngineError(f"refit_files: {tau.size} thresholds > {REFIT_MAX_TAU}")
+        tau = _tau_arg("refit_files", thresholds, REFIT_MAX_TAU)
         K = int(K)
         Kc, rows = max(K, 0), B * T
         blk = _dev("block", block, "uint8", refit_layout(tau.size, Kc, self.d, self.n)["bytes"], at_least=True)

@@ -25,20 +25,16 @@ bitwise identical arrays; the integer fields and the trace do not depend on batc
 """
 from __future__ import annotations
 
-import argparse
 import dataclasses
 import json
 from typing import Optional, Sequence
 
 import numpy as np
 
-from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng
-from .sparsity_frontier import DEFAULT_THRESHOLDS, SparsityFrontier, check_thresholds
+from .engine import PURSUIT_MAX_K as MAX_K, PURSUIT_MAX_TAU as MAX_TAU
+from .file_pass import keep_rng
+from .sparsity_frontier import DEFAULT_THRESHOLDS, FrontierCurve, SparsityFrontier, _run_frontier_pass, curve_marks, encode_rows, parse_curve_cli
 from .sparsity_frontier import check_K as _frontier_check_K
-
-MAX_K, MAX_TAU = 256, 8                     # include/freud_sae.h: SAE_PURSUIT_MAX_K, SAE_PURSUIT_MAX_TAU
-_ARRAYS = ("thresholds", "sse", "sum_x", "sum_x_sq", "budget", "steps", "picks", "in_support")
-_SCALARS = ("K", "n_frames")
 
 
 def check_K(K, variant: str, n: int, k: int) -> int:
@@ -53,7 +49,7 @@ def check_K(K, variant: str, n: int, k: int) -> int:
 
 
 @dataclasses.dataclass
-class PursuitFrontier:
+class PursuitFrontier(FrontierCurve):
     """The pursuit frontier of an SAE's decoder over a dataset (see the module docstring)."""
     K: int
     thresholds: np.ndarray      # float32 [n_tau]
@@ -66,25 +62,11 @@ class PursuitFrontier:
     picks: np.ndarray           # int64 [n]: how often latent j was picked
     in_support: np.ndarray      # int64 [K]: picks of step s inside the encoder's own active set of the frame
 
-    @property
-    def d(self) -> int:
-        return int(self.sum_x.shape[0])
+    _PASS = _NAME = "pursuit"
 
     @property
     def n(self) -> int:
         return int(self.picks.shape[0])
-
-    # -- the curve: SparsityFrontier's arithmetic on the same fields
-    sse_curve = SparsityFrontier.sse_curve
-    total_variance = SparsityFrontier.total_variance
-    fvu_curve = SparsityFrontier.fvu_curve
-    fvu = SparsityFrontier.fvu
-    marginal = SparsityFrontier.marginal
-    budget_for_fvu = SparsityFrontier.budget_for_fvu
-    _tau_index = SparsityFrontier._tau_index
-    frame_budget_hist = SparsityFrontier.frame_budget_hist
-    frame_budget_quantile = SparsityFrontier.frame_budget_quantile
-    compare_pca = SparsityFrontier.compare_pca
 
     @property
     def steps_hist(self) -> np.ndarray:
@@ -110,56 +92,24 @@ class PursuitFrontier:
         """The latents no frame ever picked, ascending."""
         return np.nonzero(self.picks == 0)[0]
 
-    def compare(self, frontier: SparsityFrontier) -> np.ndarray:
-        """float64 [min(K, frontier.K) + 1, 2]: (encoder FVU, pursuit FVU) at every budget, both over THIS object's denominator.  The
-        frontier must cover the same frames of the same d."""
-        if int(frontier.n_frames) != int(self.n_frames):
-            raise ValueError(f"the frontier counted {frontier.n_frames} frames, the pursuit {self.n_frames}")
-        if int(frontier.d) != self.d:
-            raise ValueError(f"the frontier has d={frontier.d}, the pursuit d={self.d}")
-        m = min(self.K, int(frontier.K)) + 1
-        tv = self.total_variance()
-        if not tv > 0:
-            return np.full((m, 2), np.nan)
-        return np.stack([np.asarray(frontier.sse, np.float64)[:m] / tv, self.sse[:m] / tv], axis=1)
-
     def amortisation_gap(self, frontier: SparsityFrontier) -> np.ndarray:
-        """float64 [min(K, frontier.K) + 1]: encoder FVU - pursuit FVU at every budget."""
+        """float64 [min(K, frontier.K) + 1]: encoder FVU - pursuit FVU at every budget (compare(): the two side by side)."""
         c = self.compare(frontier)
         return c[:, 0] - c[:, 1]
 
     def summary(self) -> dict:
-        fvu = self.fvu_curve()
-        marks = sorted({0, 1, 2, 4, 8, 16, 32, 64, 128, 256, self.K} & set(range(self.K + 1)))
         agree = self.support_agreement()
         made = int(self.picks.sum())
-        return {"n_frames": int(self.n_frames), "K": int(self.K), "d": self.d, "n": self.n,
-                "fvu": {str(k): float(fvu[k]) for k in marks},
-                "median_budget": {format(float(t), ".6g"): self.frame_budget_quantile(float(t), 0.5) for t in self.thresholds},
+        return {"n_frames": int(self.n_frames), "K": int(self.K), "d": self.d, "n": self.n, "fvu": self._fvu_marks(),
+                "median_budget": self._median_budgets(),
                 "mean_picks": made / max(self.n_frames, 1), "never_picked": int(self.never_picked().size),
                 "support_agreement": float(self.in_support.sum() / made) if made else None,
                 "support_agreement_step0": None if np.isnan(agree[0]) else float(agree[0])}
 
-    def save(self, path: str) -> None:
-        np.savez(path, **{k: np.int64(getattr(self, k)) for k in _SCALARS}, **{k: getattr(self, k) for k in _ARRAYS})
-
-    @classmethod
-    def load(cls, path: str) -> "PursuitFrontier":
-        z = np.load(path)
-        return cls(**{k: int(z[k]) for k in _SCALARS}, **{k: z[k] for k in _ARRAYS})
-
-    to_npz = save
-    from_npz = load
-
     @classmethod
     def from_block(cls, block: np.ndarray, K: int, thresholds: np.ndarray, d: int, n: int) -> "PursuitFrontier":
         """The arrays of an sae_pursuit_files block (uint8 bytes, engine.pursuit_layout)."""
-        from .engine import pursuit_layout, unpack_block
-        n_tau = int(len(thresholds))
-        a = unpack_block(block, pursuit_layout(n_tau, K, d, n))
-        return cls(K=int(K), thresholds=np.asarray(thresholds, np.float32).copy(), n_frames=int(a["n_frames"][0]), sse=a["sse"],
-                   sum_x=a["sum_x"], sum_x_sq=a["sum_x_sq"], budget=a["budget"].reshape(n_tau, K + 2), steps=a["steps"],
-                   picks=a["picks"], in_support=a["in_support"])
+        return cls._from_layout(block, cls._layout(len(thresholds), K, d, n), K, thresholds)
 
 
 @keep_rng
@@ -169,25 +119,9 @@ def pursuit_frontier(sae, data_path: str, layer_name: str, *, K: Optional[int] =
     """The pursuit frontier of `sae` (a checkpoint path, a freud_amd.models SAE or a SaeEngine; bf16 contexts) over the files of a
     shard directory, in one pass.  K: pursuit steps per frame (default: a TopK SAE's k, min(n, 64) for L1; at most 256); thresholds:
     up to 8 shares of a frame's energy, each inside (0, 1); files: the first `files` files only; batch_files: files per engine call."""
-    import torch
-    from . import engine as E
-
-    if is_raw(sae):
-        raise ValueError("a pursuit frontier needs an SAE (raw activations have no dictionary to pursue)")
-    tau = check_thresholds(thresholds)
-    if K is not None:
-        check_K(K, "topk", 0, 0)
-    fp = FilePass(sae, data_path, layer_name, what="pursuit frontier", lengths=lengths, subset_size=files, batch_files=batch_files)
-    K = check_K(K, fp.eng.variant, fp.eng.n, fp.eng.k)
-    d, n = fp.eng.d, fp.eng.n
-    with torch.cuda.device(fp.device):
-        block = torch.zeros(E.pursuit_layout(tau.size, K, d, n)["bytes"], dtype=torch.uint8, device=fp.device)
-        for x, _file0, _nb, lb in fp:
-            fp.eng.pursuit_files(x, K, tau, block, lb)
-        host = block.cpu().numpy()                                      # the one read-back
-    out = PursuitFrontier.from_block(host, K, tau, d, n)
-    fp.check_counted(out.n_frames)
-    return out
+    return _run_frontier_pass(PursuitFrontier, check_K, MAX_K, sae, data_path, layer_name, what="pursuit frontier",
+                              lacks="dictionary to pursue", K=K, thresholds=thresholds, lengths=lengths, subset_size=files,
+                              batch_files=batch_files)
 
 
 @keep_rng
@@ -197,23 +131,10 @@ def pursuit_encode(sae, x, K: int):
     Indices may repeat: the code of a latent is the sum of its values.  sae: a freud_amd.models SAE or a SaeEngine."""
     import torch
     from . import engine as E
-    from .file_pass import resolve_sae
 
     K = check_K(int(K), "topk", 0, 0)
-    model, eng = resolve_sae(sae)
-    if model is None and eng is None:
-        raise ValueError("pursuit_encode needs an SAE")
-    if not (hasattr(x, "is_cuda") and x.is_cuda and x.dim() >= 1):
-        raise ValueError("x must be a CUDA tensor [..., d]")
-    lead, d = tuple(x.shape[:-1]), int(x.shape[-1])
-    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
-    if rows < 1:
-        raise ValueError("x holds no rows")
-    if eng is None:
-        eng = model._ensure(-(-rows // 256) * 256)
-    if eng.d != d:
-        raise ValueError(f"the SAE expects d_model={eng.d}, x has d={d}")
-    xr = x.reshape(rows, d).contiguous()
+    eng, xr, lead = encode_rows(sae, x, "pursuit_encode")
+    rows, d = xr.shape
     with torch.cuda.device(x.device):
         idx = torch.empty(rows, K, dtype=torch.int32, device=x.device)
         val = torch.empty(rows, K, dtype=torch.float32, device=x.device)
@@ -227,24 +148,17 @@ def pursuit_encode(sae, x, K: int):
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="FVU of an SAE's decoder under greedy (matching pursuit) coding at every per-frame latent "
-                                             "budget, over a shard directory.")
-    add_pass_arguments(ap)
-    ap.add_argument("--K", type=int, default=None, help="pursuit steps per frame (default: a TopK SAE's k, min(n, 64) for L1)")
-    ap.add_argument("--thresholds", default=",".join(str(t) for t in DEFAULT_THRESHOLDS), help="comma-separated shares of a frame's energy")
-    ap.add_argument("--frontier", default=None, help="a sparsity frontier (.npz of freud_amd.sparsity_frontier) over the same files: adds "
-                                                     "the amortisation gap to the summary")
-    a = ap.parse_args(argv)
-    tau = [float(t) for t in a.thresholds.split(",") if t.strip()]
+    a, tau = parse_curve_cli(argv, "FVU of an SAE's decoder under greedy (matching pursuit) coding at every per-frame latent budget, over a "
+                                   "shard directory.", "pursuit steps per frame (default: a TopK SAE's k, min(n, 64) for L1)",
+                             [("--frontier", "a sparsity frontier (.npz of freud_amd.sparsity_frontier) over the same files: adds the "
+                                             "amortisation gap to the summary")])
     out = pursuit_frontier(a.sae, a.data_path, a.layer_name, K=a.K, thresholds=tau, lengths=np.load(a.lengths) if a.lengths else None,
                            batch_files=a.batch_files)
     if a.out:
         out.save(a.out)
     summary = {"out": a.out, **out.summary()}
     if a.frontier:
-        cmp_ = out.compare(SparsityFrontier.from_npz(a.frontier))
-        marks = [k for k in (1, 2, 4, 8, 16, 32, 64, 128, 256, cmp_.shape[0] - 1) if k < cmp_.shape[0]]
-        summary["amortisation_gap"] = {str(k): float(cmp_[k, 0] - cmp_[k, 1]) for k in sorted(set(marks))}
+        summary["amortisation_gap"] = curve_marks(out.amortisation_gap(SparsityFrontier.from_npz(a.frontier)))
     print(json.dumps(summary))
 
 

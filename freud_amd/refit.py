@@ -23,21 +23,16 @@ K computed directly from the residual.  Two runs give bitwise identical arrays; 
 """
 from __future__ import annotations
 
-import argparse
 import dataclasses
 import json
 from typing import Optional, Sequence
 
 import numpy as np
 
-from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng
-from .sparsity_frontier import DEFAULT_THRESHOLDS, SparsityFrontier, check_thresholds
+from .engine import REFIT_MAX_K as MAX_K, REFIT_MAX_TAU as MAX_TAU, REFIT_RATIO_BINS as RATIO_BINS
+from .file_pass import keep_rng
+from .sparsity_frontier import DEFAULT_THRESHOLDS, FrontierCurve, SparsityFrontier, _run_frontier_pass, curve_marks, encode_rows, parse_curve_cli
 from .sparsity_frontier import check_K as _frontier_check_K
-
-MAX_K, MAX_TAU, RATIO_BINS = 128, 8, 36     # include/freud_sae.h: SAE_REFIT_MAX_K, SAE_REFIT_MAX_TAU, SAE_REFIT_RATIO_BINS
-_ARRAYS = ("thresholds", "sse", "sum_x", "sum_x_sq", "budget", "kept", "slots", "neg", "dep", "ratio")
-_SCALARS = ("K", "n_frames", "bad_index")
-_FLOATS = ("sse_final",)
 
 
 def check_K(K, variant: str, n: int, k: int, given: bool = False) -> int:
@@ -60,7 +55,7 @@ def ratio_edges() -> np.ndarray:
 
 
 @dataclasses.dataclass
-class RefitFrontier:
+class RefitFrontier(FrontierCurve):
     """The refit frontier of an SAE over a dataset (see the module docstring)."""
     K: int
     thresholds: np.ndarray      # float32 [n_tau]
@@ -77,25 +72,11 @@ class RefitFrontier:
     ratio: np.ndarray           # int64 [36]: histogram of a_s / v_s over the kept slots (the encoder's support only)
     bad_index: int = 0          # out-of-range indices of a given support
 
-    @property
-    def d(self) -> int:
-        return int(self.sum_x.shape[0])
+    _PASS = _NAME = "refit"
 
     @property
     def n(self) -> int:
         return int(self.slots.shape[0])
-
-    # -- the curve: SparsityFrontier's arithmetic on the same fields
-    sse_curve = SparsityFrontier.sse_curve
-    total_variance = SparsityFrontier.total_variance
-    fvu_curve = SparsityFrontier.fvu_curve
-    fvu = SparsityFrontier.fvu
-    marginal = SparsityFrontier.marginal
-    budget_for_fvu = SparsityFrontier.budget_for_fvu
-    _tau_index = SparsityFrontier._tau_index
-    frame_budget_hist = SparsityFrontier.frame_budget_hist
-    frame_budget_quantile = SparsityFrontier.frame_budget_quantile
-    compare_pca = SparsityFrontier.compare_pca
 
     def final_fvu(self) -> float:
         """The FVU at budget K from the directly computed residuals (beside fvu(K), which comes from e_0 - sum y^2)."""
@@ -141,22 +122,6 @@ class RefitFrontier:
             return 0.0
         return float(ratio_edges()[b - 3])
 
-    def _same_frames(self, other, what: str) -> None:
-        if int(other.n_frames) != int(self.n_frames):
-            raise ValueError(f"the {what} counted {other.n_frames} frames, the refit {self.n_frames}")
-        if int(other.d) != self.d:
-            raise ValueError(f"the {what} has d={other.d}, the refit d={self.d}")
-
-    def compare(self, frontier: SparsityFrontier) -> np.ndarray:
-        """float64 [min(K, frontier.K) + 1, 2]: (encoder FVU, refit FVU) at every budget, both over THIS object's denominator.  The
-        frontier must cover the same frames of the same d."""
-        self._same_frames(frontier, "frontier")
-        m = min(self.K, int(frontier.K)) + 1
-        tv = self.total_variance()
-        if not tv > 0:
-            return np.full((m, 2), np.nan)
-        return np.stack([np.asarray(frontier.sse, np.float64)[:m] / tv, self.sse[:m] / tv], axis=1)
-
     def decompose(self, frontier: SparsityFrontier, pursuit) -> dict:
         """The amortisation gap split at every budget s <= min of the three K: {"encoder", "refit", "pursuit": the three FVU curves
         over this object's denominator, "coefficient_gap": encoder - refit, "support_gap": refit - pursuit}."""
@@ -173,37 +138,17 @@ class RefitFrontier:
         return {"encoder": enc, "refit": ref, "pursuit": pur, "coefficient_gap": enc - ref, "support_gap": ref - pur}
 
     def summary(self) -> dict:
-        fvu = self.fvu_curve()
-        marks = sorted({0, 1, 2, 4, 8, 16, 32, 64, 128, self.K} & set(range(self.K + 1)))
         kept_total = int((self.kept * np.arange(self.K + 1)).sum())
-        return {"n_frames": int(self.n_frames), "K": int(self.K), "d": self.d, "n": self.n,
-                "fvu": {str(k): float(fvu[k]) for k in marks}, "final_fvu": self.final_fvu(),
-                "median_budget": {format(float(t), ".6g"): self.frame_budget_quantile(float(t), 0.5) for t in self.thresholds},
+        return {"n_frames": int(self.n_frames), "K": int(self.K), "d": self.d, "n": self.n, "fvu": self._fvu_marks(),
+                "final_fvu": self.final_fvu(), "median_budget": self._median_budgets(),
                 "mean_kept": kept_total / max(self.n_frames, 1), "dependent_fraction": self.dependent_fraction()[1],
                 "negative_fraction": self.negative_fraction()[1], "median_shrinkage": self.shrinkage_quantile(0.5),
                 "bad_index": int(self.bad_index)}
 
-    def save(self, path: str) -> None:
-        np.savez(path, **{k: np.int64(getattr(self, k)) for k in _SCALARS}, **{k: np.float64(getattr(self, k)) for k in _FLOATS},
-                 **{k: getattr(self, k) for k in _ARRAYS})
-
-    @classmethod
-    def load(cls, path: str) -> "RefitFrontier":
-        z = np.load(path)
-        return cls(**{k: int(z[k]) for k in _SCALARS}, **{k: float(z[k]) for k in _FLOATS}, **{k: z[k] for k in _ARRAYS})
-
-    to_npz = save
-    from_npz = load
-
     @classmethod
     def from_block(cls, block: np.ndarray, K: int, thresholds: np.ndarray, d: int, n: int) -> "RefitFrontier":
         """The arrays of an sae_refit_files block (uint8 bytes, engine.refit_layout)."""
-        from .engine import refit_layout, unpack_block
-        n_tau = int(len(thresholds))
-        a = unpack_block(block, refit_layout(n_tau, K, d, n))
-        return cls(K=int(K), thresholds=np.asarray(thresholds, np.float32).copy(), n_frames=int(a["n_frames"][0]), sse=a["sse"],
-                   sse_final=float(a["sse_final"][0]), sum_x=a["sum_x"], sum_x_sq=a["sum_x_sq"], budget=a["budget"].reshape(n_tau, K + 2),
-                   kept=a["kept"], slots=a["slots"], neg=a["neg"], dep=a["dep"], ratio=a["ratio"], bad_index=int(a["bad_index"][0]))
+        return cls._from_layout(block, cls._layout(len(thresholds), K, d, n), K, thresholds)
 
 
 @keep_rng
@@ -213,25 +158,9 @@ def refit_frontier(sae, data_path: str, layer_name: str, *, K: Optional[int] = N
     """The refit frontier of `sae` (a checkpoint path, a freud_amd.models SAE or a SaeEngine; bf16 contexts) over the files of a
     shard directory, in one pass.  K: slots per frame (default: a TopK SAE's k, min(n, 64) for L1; at most 128); thresholds: up to 8
     shares of a frame's energy, each inside (0, 1); files: the first `files` files only; batch_files: files per engine call."""
-    import torch
-    from . import engine as E
-
-    if is_raw(sae):
-        raise ValueError("a refit frontier needs an SAE (raw activations have no support to refit)")
-    tau = check_thresholds(thresholds)
-    if K is not None and not 1 <= int(K) <= MAX_K:
-        raise ValueError(f"K={K} outside [1, {MAX_K}]")
-    fp = FilePass(sae, data_path, layer_name, what="refit frontier", lengths=lengths, subset_size=files, batch_files=batch_files)
-    K = check_K(K, fp.eng.variant, fp.eng.n, fp.eng.k)
-    d, n = fp.eng.d, fp.eng.n
-    with torch.cuda.device(fp.device):
-        block = torch.zeros(E.refit_layout(tau.size, K, d, n)["bytes"], dtype=torch.uint8, device=fp.device)
-        for x, _file0, _nb, lb in fp:
-            fp.eng.refit_files(x, K, tau, block, lb)
-        host = block.cpu().numpy()                                      # the one read-back
-    out = RefitFrontier.from_block(host, K, tau, d, n)
-    fp.check_counted(out.n_frames)
-    return out
+    return _run_frontier_pass(RefitFrontier, check_K, MAX_K, sae, data_path, layer_name, what="refit frontier",
+                              lacks="support to refit", K=K, thresholds=thresholds, lengths=lengths, subset_size=files,
+                              batch_files=batch_files)
 
 
 @keep_rng
@@ -243,21 +172,9 @@ def refit_encode(sae, x, K: Optional[int] = None, support=None):
     freud_amd.pursuit.pursuit_encode: pursuit with a final orthogonal projection.  sae: a freud_amd.models SAE or a SaeEngine."""
     import torch
     from . import engine as E
-    from .file_pass import resolve_sae
 
-    model, eng = resolve_sae(sae)
-    if model is None and eng is None:
-        raise ValueError("refit_encode needs an SAE")
-    if not (hasattr(x, "is_cuda") and x.is_cuda and x.dim() >= 1):
-        raise ValueError("x must be a CUDA tensor [..., d]")
-    lead, d = tuple(x.shape[:-1]), int(x.shape[-1])
-    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
-    if rows < 1:
-        raise ValueError("x holds no rows")
-    if eng is None:
-        eng = model._ensure(-(-rows // 256) * 256)
-    if eng.d != d:
-        raise ValueError(f"the SAE expects d_model={eng.d}, x has d={d}")
+    eng, xr, lead = encode_rows(sae, x, "refit_encode")
+    rows, d = xr.shape
     sup = None
     if support is not None:
         if tuple(support.shape[:-1]) != lead:
@@ -268,7 +185,6 @@ def refit_encode(sae, x, K: Optional[int] = None, support=None):
         sup = support.to(device=x.device, dtype=torch.int32).reshape(rows, K).contiguous()
     else:
         K = check_K(K, eng.variant, eng.n, eng.k)
-    xr = x.reshape(rows, d).contiguous()
     with torch.cuda.device(x.device):
         coef = torch.empty(rows, K, dtype=torch.float32, device=x.device)
         err = torch.empty(rows, K + 1, dtype=torch.float32, device=x.device)
@@ -289,31 +205,26 @@ def refit_encode(sae, x, K: Optional[int] = None, support=None):
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="FVU of an SAE at every per-frame latent budget with least-squares coefficients on the "
-                                             "encoder's own support, over a shard directory.")
-    add_pass_arguments(ap)
-    ap.add_argument("--K", type=int, default=None, help="slots per frame (default: a TopK SAE's k, min(n, 64) for L1; at most 128)")
-    ap.add_argument("--thresholds", default=",".join(str(t) for t in DEFAULT_THRESHOLDS), help="comma-separated shares of a frame's energy")
-    ap.add_argument("--frontier", default=None, help="a sparsity frontier (.npz of freud_amd.sparsity_frontier) over the same files: adds "
-                                                     "the coefficient gap to the summary")
-    ap.add_argument("--pursuit", default=None, help="a pursuit frontier (.npz of freud_amd.pursuit) over the same files: with --frontier, "
-                                                    "adds the support gap")
-    a = ap.parse_args(argv)
-    tau = [float(t) for t in a.thresholds.split(",") if t.strip()]
+    a, tau = parse_curve_cli(argv, "FVU of an SAE at every per-frame latent budget with least-squares coefficients on the encoder's own "
+                                   "support, over a shard directory.",
+                             "slots per frame (default: a TopK SAE's k, min(n, 64) for L1; at most 128)",
+                             [("--frontier", "a sparsity frontier (.npz of freud_amd.sparsity_frontier) over the same files: adds the "
+                                             "coefficient gap to the summary"),
+                              ("--pursuit", "a pursuit frontier (.npz of freud_amd.pursuit) over the same files: with --frontier, adds the "
+                                            "support gap")])
     out = refit_frontier(a.sae, a.data_path, a.layer_name, K=a.K, thresholds=tau, lengths=np.load(a.lengths) if a.lengths else None,
                          batch_files=a.batch_files)
     if a.out:
         out.save(a.out)
     summary = {"out": a.out, **out.summary()}
-    pick = lambda v: {str(k): float(v[k]) for k in sorted({k for k in (1, 2, 4, 8, 16, 32, 64, 128, len(v) - 1) if k < len(v)})}
     if a.frontier and a.pursuit:
         from .pursuit import PursuitFrontier
         dec = out.decompose(SparsityFrontier.from_npz(a.frontier), PursuitFrontier.load(a.pursuit))
-        summary["coefficient_gap"] = pick(dec["coefficient_gap"])
-        summary["support_gap"] = pick(dec["support_gap"])
+        summary["coefficient_gap"] = curve_marks(dec["coefficient_gap"])
+        summary["support_gap"] = curve_marks(dec["support_gap"])
     elif a.frontier:
         cmp_ = out.compare(SparsityFrontier.from_npz(a.frontier))
-        summary["coefficient_gap"] = pick(cmp_[:, 0] - cmp_[:, 1])
+        summary["coefficient_gap"] = curve_marks(cmp_[:, 0] - cmp_[:, 1])
     print(json.dumps(summary))
 
 

@@ -26,13 +26,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, run_pass_cli
+from .engine import FRONTIER_MAX_K as MAX_K, FRONTIER_MAX_TAU as MAX_TAU
+from .file_pass import FilePass, add_pass_arguments, is_raw, keep_rng, resolve_sae, run_pass_cli
 
-MAX_K, MAX_TAU = 256, 8                     # include/freud_sae.h: SAE_FRONTIER_MAX_K, SAE_FRONTIER_MAX_TAU
 DEFAULT_THRESHOLDS = (0.5, 0.2, 0.1, 0.05)
 DEFAULT_L1_K = 64
-_ARRAYS = ("thresholds", "sse", "sum_x", "sum_x_sq", "budget")
-_SCALARS = ("K", "n_frames", "rows_cut", "active_cut")
 
 
 def check_thresholds(thresholds) -> np.ndarray:
@@ -57,18 +55,17 @@ def check_K(K, variant: str, n: int, k: int) -> int:
     return K
 
 
-@dataclasses.dataclass
-class SparsityFrontier:
-    """The frontier of an SAE over a dataset (see the module docstring)."""
-    K: int
-    thresholds: np.ndarray      # float32 [n_tau]
-    n_frames: int
-    rows_cut: int
-    active_cut: int
-    sse: np.ndarray             # float64 [K + 1]
-    sum_x: np.ndarray           # float64 [d]
-    sum_x_sq: np.ndarray        # float64 [d]
-    budget: np.ndarray          # int64 [n_tau, K + 2]
+def curve_marks(v, lowest: int = 1) -> dict:
+    """{str(k): v[k]} at k = 0 (from `lowest` on), the powers of two and the last index of v: what the summaries print of a curve."""
+    last = len(v) - 1
+    return {str(k): float(v[k]) for k in sorted({0, 1, 2, 4, 8, 16, 32, 64, 128, 256, last}) if lowest <= k <= last}
+
+
+class FrontierCurve:
+    """What the three frontier dataclasses (SparsityFrontier, freud_amd.pursuit.PursuitFrontier, freud_amd.refit.RefitFrontier) share:
+    the arithmetic on K, thresholds, n_frames, sse, sum_x, sum_x_sq and budget, the .npz form and the reading of an engine block.  It
+    declares no field; _PASS names the engine's layout function and pass method, _NAME the object in error texts."""
+    _PASS = _NAME = "frontier"
 
     @property
     def d(self) -> int:
@@ -121,10 +118,6 @@ class SparsityFrontier:
             return 0
         return int(np.searchsorted(np.cumsum(h), q * total, side="left"))
 
-    def cut_fraction(self) -> float:
-        """The share of the counted frames that have active latents beyond slot K."""
-        return self.rows_cut / self.n_frames if self.n_frames else 0.0
-
     def compare_pca(self, cov) -> np.ndarray:
         """float64 [K + 1, 2]: (fvu(k), cov.pca_fvu(k)) -- k latents per frame against the best rank-k linear code (freud_amd.input_pca's
         InputCovariance; ranks above d stay at its last entry)."""
@@ -133,31 +126,154 @@ class SparsityFrontier:
         pca = np.asarray(cov.fvu_curve(), dtype=np.float64)
         return np.stack([self.fvu_curve(), pca[np.minimum(np.arange(self.K + 1), self.d)]], axis=1)
 
-    def summary(self) -> dict:
-        fvu = self.fvu_curve()
-        marks = sorted({0, 1, 2, 4, 8, 16, 32, 64, 128, 256, self.K} & set(range(self.K + 1)))
-        return {"n_frames": int(self.n_frames), "K": int(self.K), "d": self.d, "rows_cut": int(self.rows_cut),
-                "active_cut": int(self.active_cut), "cut_fraction": self.cut_fraction(),
-                "fvu": {str(k): float(fvu[k]) for k in marks},
-                "median_budget": {format(float(t), ".6g"): self.frame_budget_quantile(float(t), 0.5) for t in self.thresholds}}
+    def _same_frames(self, other, what: str) -> None:
+        if int(other.n_frames) != int(self.n_frames):
+            raise ValueError(f"the {what} counted {other.n_frames} frames, the {self._NAME} {self.n_frames}")
+        if int(other.d) != self.d:
+            raise ValueError(f"the {what} has d={other.d}, the {self._NAME} d={self.d}")
 
-    def to_npz(self, path: str) -> None:
-        np.savez(path, **{k: np.int64(getattr(self, k)) for k in _SCALARS}, **{k: getattr(self, k) for k in _ARRAYS})
+    def compare(self, frontier: "SparsityFrontier") -> np.ndarray:
+        """float64 [min(K, frontier.K) + 1, 2]: (encoder FVU, this curve's FVU) at every budget, both over THIS object's denominator.
+        The frontier must cover the same frames of the same d."""
+        self._same_frames(frontier, "frontier")
+        m = min(self.K, int(frontier.K)) + 1
+        tv = self.total_variance()
+        if not tv > 0:
+            return np.full((m, 2), np.nan)
+        return np.stack([np.asarray(frontier.sse, np.float64)[:m] / tv, self.sse[:m] / tv], axis=1)
+
+    def _fvu_marks(self) -> dict:
+        return curve_marks(self.fvu_curve(), 0)
+
+    def _median_budgets(self) -> dict:
+        return {format(float(t), ".6g"): self.frame_budget_quantile(float(t), 0.5) for t in self.thresholds}
+
+    # -- the .npz form, by the dataclass's own fields: the int fields as int64, then the float fields as float64, then the arrays
+    def save(self, path: str) -> None:
+        kinds = _field_kinds(self)
+        np.savez(path, **{k: np.int64(getattr(self, k)) for k, t in kinds.items() if t is int},
+                 **{k: np.float64(getattr(self, k)) for k, t in kinds.items() if t is float},
+                 **{k: getattr(self, k) for k, t in kinds.items() if t is None})
 
     @classmethod
-    def from_npz(cls, path: str) -> "SparsityFrontier":
+    def load(cls, path: str):
         z = np.load(path)
-        return cls(**{k: int(z[k]) for k in _SCALARS}, **{k: z[k] for k in _ARRAYS})
+        return cls(**{k: z[k] if t is None else t(z[k]) for k, t in _field_kinds(cls).items()})
+
+    to_npz = save
+    from_npz = load
+
+    # -- an engine block (uint8 bytes) by its layout: a scalar field from its one element, budget as [n_tau, K + 2]
+    @classmethod
+    def _layout(cls, n_tau: int, K: int, d: int, n: int) -> dict:
+        from . import engine as E
+        return getattr(E, cls._PASS + "_layout")(n_tau, K, d, n)
+
+    @classmethod
+    def _from_layout(cls, block: np.ndarray, layout: dict, K: int, thresholds):
+        from .engine import unpack_block
+        a = unpack_block(block, layout)
+        vals = {k: a[k] if t is None else t(a[k][0]) for k, t in _field_kinds(cls).items() if k in a}
+        vals["budget"] = a["budget"].reshape(len(thresholds), K + 2)
+        return cls(K=int(K), thresholds=np.asarray(thresholds, np.float32).copy(), **vals)
+
+
+def _field_kinds(cls) -> dict:
+    """name -> int, float or None (an array) for every field of a frontier dataclass, in declaration order."""
+    scalar = {"int": int, int: int, "float": float, float: float}
+    return {f.name: scalar.get(f.type) for f in dataclasses.fields(cls)}
+
+
+@dataclasses.dataclass
+class SparsityFrontier(FrontierCurve):
+    """The frontier of an SAE over a dataset (see the module docstring)."""
+    K: int
+    thresholds: np.ndarray      # float32 [n_tau]
+    n_frames: int
+    rows_cut: int
+    active_cut: int
+    sse: np.ndarray             # float64 [K + 1]
+    sum_x: np.ndarray           # float64 [d]
+    sum_x_sq: np.ndarray        # float64 [d]
+    budget: np.ndarray          # int64 [n_tau, K + 2]
+
+    def cut_fraction(self) -> float:
+        """The share of the counted frames that have active latents beyond slot K."""
+        return self.rows_cut / self.n_frames if self.n_frames else 0.0
+
+    def summary(self) -> dict:
+        return {"n_frames": int(self.n_frames), "K": int(self.K), "d": self.d, "rows_cut": int(self.rows_cut),
+                "active_cut": int(self.active_cut), "cut_fraction": self.cut_fraction(), "fvu": self._fvu_marks(),
+                "median_budget": self._median_budgets()}
+
+    @classmethod
+    def _layout(cls, n_tau: int, K: int, d: int, n: int = 0) -> dict:
+        from .engine import frontier_layout
+        return frontier_layout(n_tau, K, d)
 
     @classmethod
     def from_block(cls, block: np.ndarray, K: int, thresholds: np.ndarray, d: int) -> "SparsityFrontier":
         """The arrays of an sae_frontier_files block (uint8 bytes, engine.frontier_layout)."""
-        from .engine import frontier_layout, unpack_block
-        n_tau = int(len(thresholds))
-        a = unpack_block(block, frontier_layout(n_tau, K, d))
-        return cls(K=int(K), thresholds=np.asarray(thresholds, np.float32).copy(), n_frames=int(a["n_frames"][0]),
-                   rows_cut=int(a["rows_cut"][0]), active_cut=int(a["active_cut"][0]), sse=a["sse"], sum_x=a["sum_x"],
-                   sum_x_sq=a["sum_x_sq"], budget=a["budget"].reshape(n_tau, K + 2))
+        return cls._from_layout(block, cls._layout(len(thresholds), K, d), K, thresholds)
+
+
+def _run_frontier_pass(cls, check_K, max_k: int, sae, data_path: str, layer_name: str, *, what: str, lacks: str, K, thresholds, lengths,
+                       subset_size, batch_files):
+    """The driver of sparsity_frontier(), pursuit.pursuit_frontier() and refit.refit_frontier(): one pass of SaeEngine.<cls._PASS>_files
+    over the files into one zeroed block, read back once as a cls."""
+    import torch
+
+    if is_raw(sae):
+        raise ValueError(f"a {what} needs an SAE (raw activations have no {lacks})")
+    tau = check_thresholds(thresholds)
+    if K is not None and not 1 <= int(K) <= max_k:
+        raise ValueError(f"K={K} outside [1, {max_k}]")
+    if all(hasattr(sae, a) for a in ("variant", "n", "k")):             # an engine: its limits are known before any loading
+        check_K(K, sae.variant, sae.n, sae.k)
+    fp = FilePass(sae, data_path, layer_name, what=what, lengths=lengths, subset_size=subset_size, batch_files=batch_files)
+    K = check_K(K, fp.eng.variant, fp.eng.n, fp.eng.k)
+    layout = cls._layout(tau.size, K, fp.eng.d, fp.eng.n)
+    run = getattr(fp.eng, cls._PASS + "_files")
+    with torch.cuda.device(fp.device):
+        block = torch.zeros(layout["bytes"], dtype=torch.uint8, device=fp.device)
+        for x, _file0, _nb, lb in fp:
+            run(x, K, tau, block, lb)
+        host = block.cpu().numpy()                                      # the one read-back
+    out = cls._from_layout(host, layout, K, tau)
+    fp.check_counted(out.n_frames)
+    return out
+
+
+def encode_rows(sae, x, who: str):
+    """The front half of pursuit.pursuit_encode() and refit.refit_encode(): -> (the engine of sae, x as contiguous rows [rows, d], the
+    leading shape of x)."""
+    model, eng = resolve_sae(sae)
+    if model is None and eng is None:
+        raise ValueError(f"{who} needs an SAE")
+    if not (hasattr(x, "is_cuda") and x.is_cuda and x.dim() >= 1):
+        raise ValueError("x must be a CUDA tensor [..., d]")
+    lead, d = tuple(x.shape[:-1]), int(x.shape[-1])
+    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    if rows < 1:
+        raise ValueError("x holds no rows")
+    if eng is None:
+        eng = model._ensure(-(-rows // 256) * 256)
+    if eng.d != d:
+        raise ValueError(f"the SAE expects d_model={eng.d}, x has d={d}")
+    return eng, x.reshape(rows, d).contiguous(), lead
+
+
+def parse_curve_cli(argv, description: str, k_help: str, npz_options=()):
+    """The command line of the three frontier tools: the pass arguments, --K, --thresholds and the tool's own .npz options (flag,
+    help).  -> (the parsed arguments, the thresholds as floats)."""
+    ap = argparse.ArgumentParser(description=description)
+    add_pass_arguments(ap)
+    ap.add_argument("--K", type=int, default=None, help=k_help)
+    ap.add_argument("--thresholds", default=",".join(str(t) for t in DEFAULT_THRESHOLDS), help="comma-separated shares of a frame's energy")
+    for flag, text in npz_options:
+        ap.add_argument(flag, default=None, help=text)
+    a = ap.parse_args(argv)
+    return a, [float(t) for t in a.thresholds.split(",") if t.strip()]
 
 
 @keep_rng
@@ -167,36 +283,14 @@ def sparsity_frontier(sae, data_path: str, layer_name: str, *, K: Optional[int] 
     """The sparsity frontier of `sae` (a checkpoint path, a freud_amd.models SAE or a SaeEngine; bf16 contexts) over the files of a
     shard directory, in one pass.  K: slots per frame (default: a TopK SAE's k, min(n, 64) for L1; at most 256); thresholds: up to 8
     shares of a frame's energy, each inside (0, 1); batch_files: files per engine call."""
-    import torch
-    from . import engine as E
-
-    if is_raw(sae):
-        raise ValueError("a sparsity frontier needs an SAE (raw activations have no latents to budget)")
-    tau = check_thresholds(thresholds)
-    if K is not None and not 1 <= int(K) <= MAX_K:
-        raise ValueError(f"K={K} outside [1, {MAX_K}]")
-    if all(hasattr(sae, a) for a in ("variant", "n", "k")):             # an engine: its limits are known before any loading
-        check_K(K, sae.variant, sae.n, sae.k)
-    fp = FilePass(sae, data_path, layer_name, what="sparsity frontier", lengths=lengths, subset_size=subset_size, batch_files=batch_files)
-    K = check_K(K, fp.eng.variant, fp.eng.n, fp.eng.k)
-    d = fp.eng.d
-    with torch.cuda.device(fp.device):
-        block = torch.zeros(E.frontier_layout(tau.size, K, d)["bytes"], dtype=torch.uint8, device=fp.device)
-        for x, _file0, _nb, lb in fp:
-            fp.eng.frontier_files(x, K, tau, block, lb)
-        host = block.cpu().numpy()                                      # the one read-back
-    out = SparsityFrontier.from_block(host, K, tau, d)
-    fp.check_counted(out.n_frames)
-    return out
+    return _run_frontier_pass(SparsityFrontier, check_K, MAX_K, sae, data_path, layer_name, what="sparsity frontier",
+                              lacks="latents to budget", K=K, thresholds=thresholds, lengths=lengths, subset_size=subset_size,
+                              batch_files=batch_files)
 
 
 def main(argv=None) -> None:
-    ap = argparse.ArgumentParser(description="FVU of an SAE at every per-frame latent budget, and the frames' budgets, over a shard directory.")
-    add_pass_arguments(ap)
-    ap.add_argument("--K", type=int, default=None, help="slots per frame (default: a TopK SAE's k, min(n, 64) for L1)")
-    ap.add_argument("--thresholds", default=",".join(str(t) for t in DEFAULT_THRESHOLDS), help="comma-separated shares of a frame's energy")
-    a = ap.parse_args(argv)
-    tau = [float(t) for t in a.thresholds.split(",") if t.strip()]
+    a, tau = parse_curve_cli(argv, "FVU of an SAE at every per-frame latent budget, and the frames' budgets, over a shard directory.",
+                             "slots per frame (default: a TopK SAE's k, min(n, 64) for L1)")
     run_pass_cli(a, lambda lengths: sparsity_frontier(a.sae, a.data_path, a.layer_name, K=a.K, thresholds=tau, lengths=lengths,
                                                       batch_files=a.batch_files))
 

@@ -65,10 +65,11 @@ def run_op(eng, op, inp):
     elif name == "coact":
         outs = [zeros((N, N), torch.int32)]
         eng.coact_files(x, outs[0], L)
-    elif name == "frontier":
+    elif name in ("frontier", "pursuit", "refit"):          # (one family: each embeds the same fold pieces in a scratch of its own)
         tau = [0.5, 0.9]
-        outs = [zeros(E.frontier_layout(len(tau), K_TOP, D)["bytes"], torch.uint8)]
-        eng.frontier_files(x, K_TOP, tau, outs[0], L)
+        layout = E.frontier_layout(len(tau), K_TOP, D) if name == "frontier" else getattr(E, name + "_layout")(len(tau), K_TOP, D, N)
+        outs = [zeros(layout["bytes"], torch.uint8)]
+        getattr(eng, name + "_files")(x, K_TOP, tau, outs[0], L)
     elif name == "manip":
         outs = [zeros(F * T * D, torch.float32), zeros(2 * F * T * D, torch.float32), zeros(2 * F * T, torch.float32)]
         eng.manipulate_files(x, [3, 170], [E.MANIP_OPS["scale"], E.MANIP_OPS["set"]], [[2.0, 0.5], [0.0, 1.0]], *outs)
@@ -96,11 +97,13 @@ def train_and_eval(eng, inp):
 
 
 # The scratch grows (statistics -> labels, 3 classes), serves a pass that needs less (reconstruction), grows (200 classes: a larger
-# label pack), serves less again (co-activation), grows (the frontier's slots), serves the smallest user (manipulation), then -- after
-# one training step and one evaluation -- histograms over more files than any call before, the two-area resampling pass (L1) and the
-# statistics again.
-SEQUENCE = [("stats", 5), ("labels", 5, 3), ("recon", 5), ("labels", 6, 200), ("coact", 4), ("frontier", 7), ("manip", 3), "train",
-            ("hist", 9), ("resample", 6), ("labels", 9, 3), ("stats", 8), ("recon", 9), ("frontier", 9)]
+# label pack), serves less again (co-activation), grows (the frontier's slots), is carved by the frontier's two relatives (the
+# pursuit's residuals in front of the fold pieces, the refit's curves behind them), serves the smallest user (manipulation), then --
+# after one training step and one evaluation -- histograms over more files than any call before, the two-area resampling pass (L1),
+# the statistics again and the three frontier passes one after another in the other order.
+SEQUENCE = [("stats", 5), ("labels", 5, 3), ("recon", 5), ("labels", 6, 200), ("coact", 4), ("frontier", 7), ("pursuit", 5), ("refit", 7),
+            ("manip", 3), "train", ("hist", 9), ("resample", 6), ("labels", 9, 3), ("stats", 8), ("recon", 9), ("refit", 9), ("pursuit", 9),
+            ("frontier", 9)]
 
 
 @pytest.mark.parametrize("variant", ["l1", "topk"])

@@ -5,7 +5,7 @@ residual rebuilt from (trace_idx, trace_val) -- against which every pick, stop, 
 there from the kernel's roundings.  No row is exempt from those; only the comparison with the float64 rule's own picks is restricted
 to the rows the rule decides, and at least 95 % of the counted rows must be decided before anything is compared.
 
-Models are the frontier tests' (tests/test_sparsity_frontier_gpu.py): L1 with +-1/16 columns at d = 256, TopK tied unit rows with a
+Models are the frontier tests' (tests/frontier_cases.py): L1 with +-1/16 columns at d = 256, TopK tied unit rows with a
 random b_dec, frames from planted() with nplant = K.  Files of T = 37 frames, 5 files in batches of 2 (74, 74 and 37 rows) unless a
 test says otherwise.
 
@@ -35,25 +35,11 @@ from freud_amd.config import TopKAutoEncoderConfig
 from freud_amd.loader import write_shards
 from freud_amd.models import TopKAutoEncoder
 from tests import pursuit_reference as R
-from tests.test_sparsity_frontier_gpu import collect, counted_rows, frontier, l1_model, topk_model
+from tests.frontier_cases import F, T, collect, counted_rows, frontier, l1_model, planted, topk_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-F, T = 5, 37
 TAUS = (0.5, 0.2, 0.1, 0.05)
-
-
-def planted(w_op, b, seed, files=F, rows_per_file=T, nplant=6, sigma=0.044):
-    """The frontier tests' planted(): b + nplant decoder rows with amplitudes 8 * 0.6^i (+-10 %) + a little noise, for any T."""
-    g = np.random.default_rng(seed)
-    n, d = w_op.shape
-    bb = np.zeros(d) if b is None else b
-    x = np.tile(bb, (files * rows_per_file, 1)) + sigma * g.normal(size=(files * rows_per_file, d))
-    for r in range(files * rows_per_file):
-        js = g.permutation(n)[:nplant]
-        a = 8 * 0.6 ** np.arange(nplant) * (1 + 0.1 * g.uniform(-1, 1, nplant))
-        x[r] += a @ w_op[js]
-    return x.astype(np.float32).reshape(files, rows_per_file, d)
 
 
 def pursue(sae, x, K, taus, batch, lengths=None, trace=True):

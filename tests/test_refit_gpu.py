@@ -7,7 +7,7 @@ Three references, each for what it can say:
 * refit_chol.h's rf_row_serial, compiled for the host and fed the engine's OWN G, c and e_0: everything after the MFMA to the bit.
 
 Files of T = 37 frames, 5 files, batches of 2 (74, 74 and 37 rows: a ragged last batch).  The model builders are those of
-tests/test_sparsity_frontier_gpu.py (copied).  L1: d = 256, +-1/16 columns, n = 512.  TopK: d = 128, n = 512, k = 64 on planted()
+tests/frontier_cases.py.  L1: d = 256, +-1/16 columns, n = 512.  TopK: d = 128, n = 512, k = 64 on planted()
 frames; one case each at d_p = 384 and 768.  K = 1, 17, 31 / 32 / 33 (the MFMA tile edge), 64, 65 (a lane's second row), 128 (L1)."""
 import ctypes as C
 import os
@@ -20,80 +20,18 @@ from freud_amd import engine as E
 from freud_amd import pursuit as PU
 from freud_amd import refit as RF
 from freud_amd import sparsity_frontier as SF
-from freud_amd.config import L1AutoEncoderConfig, TopKAutoEncoderConfig
-from freud_amd.models import L1AutoEncoder, TopKAutoEncoder
 from tests import frontier_reference as FR
 from tests import refit_reference as R
+from tests.frontier_cases import F, T, collect, counted_rows, data, frontier, l1_model, planted, topk_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-F, T = 5, 37
 TAUS = (0.5, 0.1)
 
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
     return R.build_serial(tmp_path_factory.mktemp("rf"), ROOT)
-
-
-def l1_model(n, seed, bias, d=256):
-    g = np.random.default_rng(seed)
-    W = np.where(g.random((d, n)) < 0.5, np.float32(-1 / 16), np.float32(1 / 16)).astype(np.float32)
-    sae = L1AutoEncoder(d, L1AutoEncoderConfig(n_dict_components=n), max_rows=1500)
-    b = np.broadcast_to(np.asarray(bias, np.float32), (n,)).copy()
-    sae.load_state_dict({"decoder.weight": torch.from_numpy(W), "encoder_bias": torch.from_numpy(b)})
-    return sae, np.ascontiguousarray(W.T), None
-
-
-def topk_model(d, n, k, seed, bias=None):
-    """A tied dictionary: unit decoder rows (a seeded Linear's, normalised), the encoder their copy, a random b_dec."""
-    torch.manual_seed(seed)
-    W = torch.nn.Linear(d, n).weight.data.clone()
-    W /= W.norm(dim=1, keepdim=True) + 1e-7
-    b_dec = torch.randn(d, generator=torch.Generator().manual_seed(seed + 1)) * 0.3
-    sae = TopKAutoEncoder(d, TopKAutoEncoderConfig(n_dict_components=n, k=k), max_rows=1500)
-    sae.load_state_dict({"W_dec": W.clone(), "b_dec": b_dec, "encoder.weight": W.clone(),
-                         "encoder.bias": torch.full((n,), float(0.0 if bias is None else bias))})
-    return sae, W.to(torch.bfloat16).float().numpy(), b_dec.numpy()
-
-
-def planted(w_op, b, seed, files=F, nplant=6, sigma=0.044):
-    g = np.random.default_rng(seed)
-    n, d = w_op.shape
-    x = np.tile(b, (files * T, 1)) + sigma * g.normal(size=(files * T, d))
-    for r in range(files * T):
-        js = g.permutation(n)[:nplant]
-        a = 8 * 0.6 ** np.arange(nplant) * (1 + 0.1 * g.uniform(-1, 1, nplant))
-        x[r] += a @ w_op[js]
-    return x.astype(np.float32).reshape(files, T, d)
-
-
-def data(d, seed, files=F):
-    return np.random.default_rng(seed).normal(0, 1, (files, T, d)).astype(np.float32)
-
-
-def collect(sae, x, K, batch):
-    Fn, Tn, _ = x.shape
-    eng = sae._ensure(batch * Tn)
-    vals = torch.empty(Fn, Tn, K, dtype=torch.float32, device="cuda")
-    idx = torch.empty(Fn, Tn, K, dtype=torch.int64, device="cuda")
-    stats = torch.zeros(8, dtype=torch.int64, device="cuda")
-    for f0 in range(0, Fn, batch):
-        eng.collect_files(x[f0:f0 + batch].contiguous(), K, vals[f0:f0 + batch], idx[f0:f0 + batch], stats)
-    torch.cuda.synchronize()
-    return vals.cpu().numpy().reshape(Fn * Tn, K), idx.cpu().numpy().reshape(Fn * Tn, K)
-
-
-def frontier(sae, x, K, taus, batch, lengths=None):
-    Fn, Tn, d = x.shape
-    eng = sae._ensure(batch * Tn)
-    tau = SF.check_thresholds(taus)
-    block = torch.zeros(E.frontier_layout(tau.size, K, d)["bytes"], dtype=torch.uint8, device="cuda")
-    lens = torch.from_numpy(np.asarray(lengths, np.int32)).cuda() if lengths is not None else None
-    for f0 in range(0, Fn, batch):
-        eng.frontier_files(x[f0:f0 + batch].contiguous(), K, tau, block, lens[f0:f0 + batch] if lens is not None else None)
-    torch.cuda.synchronize()
-    return SF.SparsityFrontier.from_block(block.cpu().numpy(), K, tau, d)
 
 
 def refit(sae, x, K, taus, batch, lengths=None, support=None, gram=True):
@@ -119,12 +57,6 @@ def refit(sae, x, K, taus, batch, lengths=None, support=None, gram=True):
     return RF.RefitFrontier.from_block(host, K, tau, d, eng.n), host.tobytes(), {k: v.cpu().numpy() for k, v in tr.items()}
 
 
-def counted_rows(Fn, Tn, lengths):
-    if lengths is None:
-        return np.ones(Fn * Tn, bool)
-    return (np.arange(Tn)[None, :] < np.minimum(np.asarray(lengths), Tn)[:, None]).reshape(-1)
-
-
 def check(prog, tmp_path, sae, w_op, b, x, K, batch=2, taus=TAUS, lengths=None, support=None, ctx=""):
     """One run against the three references.  support: None (the encoder's slots) or int [F * T, K]."""
     Fn, Tn, d = x.shape
@@ -134,7 +66,7 @@ def check(prog, tmp_path, sae, w_op, b, x, K, batch=2, taus=TAUS, lengths=None, 
     xf = xd.float().cpu().numpy().reshape(Fn * Tn, d)
     keep = counted_rows(Fn, Tn, lengths)
     if support is None:
-        vals, idx = collect(sae, xd, K, batch)
+        vals, idx, _ = collect(sae, xd, K, batch)
         active = vals != 0
     else:
         idx = np.asarray(support, np.int64).reshape(Fn * Tn, K)
@@ -237,7 +169,7 @@ def test_l1(prog, tmp_path, K):
     x = data(256, 100 + K)
     rf, _, _, aux = check(prog, tmp_path, sae, w_op, b, x, K, ctx=f"l1 K={K}")
     # least-squares optimality against the encoder's own curve on the same batches
-    fr = frontier(sae, torch.from_numpy(x).cuda(), K, TAUS, 2)
+    fr, _ = frontier(sae, torch.from_numpy(x).cuda(), K, TAUS, 2)
     ref = FR.reference(aux["vals"], aux["idx"], w_op, aux["xf"], b)
     slack = aux["B"].sum(0) + ref.sse_bound() + 72 * R.U * fr.sse
     print(f"l1 K={K}: refit / encoder sse at K = {rf.sse[K] / fr.sse[K]:.4f}")
@@ -250,7 +182,7 @@ def test_topk(prog, tmp_path, K):
     sae, w_op, b = topk_model(128, 512, 64, seed=31)
     x = planted(w_op, b, 131)
     rf, _, _, aux = check(prog, tmp_path, sae, w_op, b, x, K, ctx=f"topk K={K}")
-    fr = frontier(sae, torch.from_numpy(x).cuda(), K, TAUS, 2)
+    fr, _ = frontier(sae, torch.from_numpy(x).cuda(), K, TAUS, 2)
     ref = FR.reference(aux["vals"], aux["idx"], w_op, aux["xf"], b)
     assert (rf.sse <= fr.sse + aux["B"].sum(0) + ref.sse_bound() + 72 * R.U * fr.sse).all() and rf.sse[0] == fr.sse[0]
 
