@@ -26,6 +26,7 @@
 #include "bwd_fused.h"
 #include "fwd_fused.h"
 #include "fwd_fused2.h"
+#include "fwd_split.h"
 #include "topk_kernels.h"
 #include "topk_sparse.h"
 #include "topk_aux.h"
@@ -389,7 +390,7 @@ static int l1_create(sae_ctx* c, int64_t Mp) {
   // generic three-GEMM path (used by the tests to cover both)
   c->use_fused_bwd = (c->d_p == BF_D) && cfg->force_generic != 1 && !c->fp8;
   c->use_fused_fwd = (c->d_p == FF_D) && cfg->force_generic != 1 && !c->fp8;
-  if (const char* fv = getenv("FREUD_FWD")) c->fwd_variant = atoi(fv) == 1 ? 1 : 2;
+  if (const char* fv = getenv("FREUD_FWD")) c->fwd_variant = atoi(fv) == 1 ? 1 : (atoi(fv) == 2 ? 2 : 3);
   c->bwd_splits = fused_bwd_splits(c->n_p / BF_BN, (int)(Mp / BF_BM), c->n_p);
   // column-tile ranges (sae_dist_set_overlap, up to 4): a range of ntiles / r tiles is split into more row ranges
   c->bwd_range_splits = c->bwd_splits;
@@ -1400,22 +1401,22 @@ static int l1_prepare(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t
 // One fused d = 384 forward over all rows: the full workgroups (all 128 rows < M) run the mask-free instantiation `full`, a ragged
 // last workgroup the padded one `ragged`
 using FwdFusedKernel = void (*)(FwdFusedArgs);
-static int launch_fwd_fused_pair(FwdFusedKernel full, FwdFusedKernel ragged, FwdFusedArgs a, int64_t M, int64_t Mp, hipStream_t s) {
+static int launch_fwd_fused_pair(FwdFusedKernel full, FwdFusedKernel ragged, int threads, FwdFusedArgs a, int64_t M, int64_t Mp, hipStream_t s) {
   const int full_wgs = (int)(M / FF_BM), all_wgs = (int)(Mp / FF_BM);
   if (full_wgs > 0) {
     LDS_ATTR(full, 160 * 1024, g_device);     // opt in to > 64 KiB dynamic LDS once per instantiation and device
     a.block_offset = 0;
-    hipLaunchKernelGGL(full, dim3(full_wgs), dim3(256), FF_LDS_BYTES, s, a);
+    hipLaunchKernelGGL(full, dim3(full_wgs), dim3(threads), FF_LDS_BYTES, s, a);
   }
   if (all_wgs > full_wgs) {
     LDS_ATTR(ragged, 160 * 1024, g_device);
     a.block_offset = full_wgs;
-    hipLaunchKernelGGL(ragged, dim3(all_wgs - full_wgs), dim3(256), FF_LDS_BYTES, s, a);
+    hipLaunchKernelGGL(ragged, dim3(all_wgs - full_wgs), dim3(threads), FF_LDS_BYTES, s, a);
   }
   return SAE_OK;
 }
 
-// c = relu(x W + b), x_hat = c W^T, residual and dx_hat in one kernel (fwd_fused2.h; FREUD_FWD=1: fwd_fused.h)
+// c = relu(x W + b), x_hat = c W^T, residual and dx_hat in one kernel (fwd_split.h; FREUD_FWD=2: fwd_fused2.h, FREUD_FWD=1: fwd_fused.h)
 template <typename T>
 static int l1_forward_fused(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipStream_t s) {
   FwdFusedArgs a{};
@@ -1426,7 +1427,12 @@ static int l1_forward_fused(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipSt
   const bool stamp = c->cfg.debug_flags == 65 && M >= FF_BM;
   if (stamp) a.stamps = reinterpret_cast<unsigned long long*>(c->dpre);
   FwdFusedKernel full, ragged;
-  if (c->fwd_variant == 2) {               // the second decomposition (fwd_fused2.h)
+  int threads = 256;
+  if (c->fwd_variant == 3 && !stamp) {     // encoder and decoder waves, two per SIMD (fwd_split.h); the stamps exist in variant 2 only
+    full = fwd_split_d384_kernel<T, false>;
+    ragged = fwd_split_d384_kernel<T, true>;
+    threads = FS_THREADS;
+  } else if (c->fwd_variant >= 2) {        // the second decomposition (fwd_fused2.h)
     full = stamp ? fwd_fused2_d384_kernel<T, false, true> : fwd_fused2_d384_kernel<T, false>;
     ragged = fwd_fused2_d384_kernel<T, true>;
   } else {
@@ -1434,7 +1440,7 @@ static int l1_forward_fused(sae_ctx* c, const T* x, int64_t M, int64_t Mp, hipSt
     ragged = fwd_fused_d384_kernel<T, true, false>;
   }
   ev_begin(c, KID_FWD_FUSED, s);
-  const int rc = launch_fwd_fused_pair(full, ragged, a, M, Mp, s);
+  const int rc = launch_fwd_fused_pair(full, ragged, threads, a, M, Mp, s);
   if (rc) return rc;
   ev_end(c, KID_FWD_FUSED, s);
   HIP_TRY(hipGetLastError());

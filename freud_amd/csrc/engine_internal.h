@@ -198,7 +198,8 @@ struct sae_ctx {
   unsigned char *x8 = nullptr, *c8 = nullptr, *W8 = nullptr, *W8t = nullptr;
   float *scal8 = nullptr, *x8_part = nullptr;
   bool use_fused_fwd = false;
-  int fwd_variant = 2;          // fused forward: 2 = fwd_fused2.h (decoder split along d), 1 = fwd_fused.h (FREUD_FWD=1: A/B, stamps)
+  int fwd_variant = 3;          // fused forward: 3 = fwd_split.h (fwd_fused2's products on encoder and decoder waves, two per SIMD),
+                                // 2 = fwd_fused2.h (FREUD_FWD=2: A/B; the stamping diagnostic runs it), 1 = fwd_fused.h (FREUD_FWD=1: A/B, stamps)
   bf16_t *xb = nullptr, *c = nullptr, *dxh = nullptr, *dpre = nullptr;
   float *slab = nullptr, *db_part = nullptr, *l1_part = nullptr, *sq_part = nullptr, *scal = nullptr;
   double* gn_part = nullptr;
