@@ -83,6 +83,8 @@ class CollectReport:
 
 def check_out_folder(data_path: str, out_folder: str, layer_name: str, layout: str, overwrite: bool) -> None:
     """The refusals of a collection; no file is touched."""
+    from .loader import require_directory
+    require_directory(data_path)                              # (the guard below compares the two folders)
     if os.path.realpath(out_folder) == os.path.realpath(data_path):
         raise ValueError(f"out_folder {out_folder!r} is the shard directory itself: its {layer_name}_metadata.json would be replaced")
     p = store_paths(out_folder, layer_name)

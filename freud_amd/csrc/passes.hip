@@ -29,6 +29,7 @@
 #include "input_stats.h"
 #include "input_cov_plan.h"
 #include "input_cov.h"
+#include "resident.h"
 
 // ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
 static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
@@ -1762,6 +1763,54 @@ extern "C" int sae_input_cov(const void* x, int64_t n_files, int64_t rows_per_fi
   });
   if (rc) return rc;
   hipLaunchKernelGGL(icv_fold_kernel, dim3((unsigned)p.tiles, ICV_TILE * ICV_TILE / 256), dim3(256), 0, s, (const double*)part, p, (int)d, out);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- the HBM-resident activation store (resident.h): the one-time fp32 -> bf16 conversion of uploaded rows and the gather of a
+// batch's files out of the store
+extern "C" int64_t sae_store_piece_bytes(void) { return RS_PIECE_BYTES; }
+
+extern "C" int sae_store_convert(const float* src, void* dst, int64_t n_elems, void* stream) {
+  const char* const fn = "sae_store_convert";
+  if (!src || !dst) return fail(SAE_ERR_INVALID, "%s: null argument", fn);
+  if (n_elems < 0) return fail(SAE_ERR_INVALID, "%s: n_elems=%lld is negative", fn, (long long)n_elems);
+  if (misaligned(src, 4) || misaligned(dst, 2)) return fail(SAE_ERR_INVALID, "%s: src must be 4-byte aligned and dst 2-byte aligned", fn);
+  if (n_elems == 0) return SAE_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (!misaligned(src, 16) && !misaligned(dst, 16))
+    hipLaunchKernelGGL(store_convert_kernel<true>, dim3(grid_for(std::max<int64_t>(n_elems >> 3, 1), 8192)), dim3(256), 0, s, src, (uint16_t*)dst, n_elems);
+  else
+    hipLaunchKernelGGL(store_convert_kernel<false>, dim3(grid_for(n_elems, 8192)), dim3(256), 0, s, src, (uint16_t*)dst, n_elems);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_store_gather(const void* store, int64_t n_files, int64_t row_bytes, const int32_t* idx, int64_t nb, void* out,
+                                int64_t out_stride_bytes, uint32_t* err, void* stream) {
+  const char* const fn = "sae_store_gather";
+  if (!store || !idx || !out || !err) return fail(SAE_ERR_INVALID, "%s: null argument", fn);
+  if (n_files < 1 || n_files > 0x7FFFFFFFll) return fail(SAE_ERR_INVALID, "%s: n_files=%lld outside [1, 2^31 - 1]", fn, (long long)n_files);
+  if (row_bytes < 1 || nb < 0) return fail(SAE_ERR_INVALID, "%s: row_bytes=%lld, nb=%lld", fn, (long long)row_bytes, (long long)nb);
+  if (out_stride_bytes < row_bytes)
+    return fail(SAE_ERR_INVALID, "%s: out_stride_bytes=%lld < row_bytes=%lld", fn, (long long)out_stride_bytes, (long long)row_bytes);
+  if (misaligned(idx, 4) || misaligned(err, 4)) return fail(SAE_ERR_INVALID, "%s: idx and err must be 4-byte aligned", fn);
+  const int width = rs_copy_width((uint64_t)reinterpret_cast<uintptr_t>(store) | (uint64_t)reinterpret_cast<uintptr_t>(out) | (uint64_t)row_bytes |
+                                  (uint64_t)out_stride_bytes);
+  if (!width) return fail(SAE_ERR_INVALID, "%s: the store, the destination, row_bytes and out_stride_bytes must be multiples of 2 bytes", fn);
+  const int64_t pieces = rs_pieces(row_bytes);
+  if (nb > 0x7FFFFFFFll / pieces) return fail(SAE_ERR_INVALID, "%s: nb=%lld rows of %lld pieces exceed 2^31 - 1 workgroups", fn, (long long)nb, (long long)pieces);
+  if (nb == 0) return SAE_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)(nb * pieces));
+  const char* const src = (const char*)store;
+  char* const dst = (char*)out;
+  if (width == 16)
+    hipLaunchKernelGGL(store_gather_kernel<rs_u32x4>, grid, dim3(RS_THREADS), 0, s, src, n_files, row_bytes, idx, pieces, dst, out_stride_bytes, err);
+  else if (width == 4)
+    hipLaunchKernelGGL(store_gather_kernel<uint32_t>, grid, dim3(RS_THREADS), 0, s, src, n_files, row_bytes, idx, pieces, dst, out_stride_bytes, err);
+  else
+    hipLaunchKernelGGL(store_gather_kernel<uint16_t>, grid, dim3(RS_THREADS), 0, s, src, n_files, row_bytes, idx, pieces, dst, out_stride_bytes, err);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

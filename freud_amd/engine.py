@@ -151,6 +151,9 @@ _SIGNATURES = {
     "sae_findex_fill": (C.c_int, [_vp, _vp, _i64, C.c_int, C.c_int, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp,
                                   _vp]),
     "sae_findex_verify": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "sae_store_piece_bytes": (_i64, []),
+    "sae_store_convert": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "sae_store_gather": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "sae_profile": (C.c_int, [_vp, C.c_int]),
     "sae_profile_period": (C.c_int, [_vp, C.c_int]),
     "sae_kernel_times": (C.c_int, [_vp, _fptr, C.POINTER(_i32), C.c_int]),
@@ -1243,6 +1246,38 @@ def dict_sim_keys(packed_a, n_a: int, packed_b, n_b: int, d: int, row0: int, n_r
     out = _dev("keys", keys, "int64", max(int(n_rows), 0) * int(n_b), at_least=True)
     _check(load().sae_dict_sim_keys(pa, int(n_a), pb, int(n_b), int(d), int(row0), int(n_rows), int(bool(self_mode)), out,
                                     _stream_ptr(stream)))
+
+
+def store_piece_bytes() -> int:
+    """Bytes of a row that one workgroup of store_gather copies (include/freud_sae.h, sae_store_piece_bytes)."""
+    return int(load().sae_store_piece_bytes())
+
+
+def store_convert(src, dst, stream=None) -> None:
+    """dst (bfloat16 CUDA, contiguous) = src (float32 CUDA, contiguous, as many elements) by the loader's conversion rule
+    (include/freud_sae.h, sae_store_convert)."""
+    n = int(src.numel())
+    _check(load().sae_store_convert(_dev("src", src, "float32", n), _dev("dst", dst, ("bfloat16", "int16"), n), n, _stream_ptr(stream)))
+
+
+def store_gather(store, idx, out, err, stream=None) -> None:
+    """out[j] = store[idx[j]] for j < len(idx) (include/freud_sae.h, sae_store_gather): store [n_files, row] a contiguous CUDA tensor,
+    idx a contiguous int32 CUDA vector, out [>= len(idx), row] a CUDA tensor of the store's dtype whose rows are contiguous (its row
+    stride may exceed the row), err one int32 on the device -- incremented per index outside the store, never cleared here."""
+    import torch
+    if not (store.is_cuda and store.dim() == 2 and store.is_contiguous() and store.shape[0] >= 1 and store.shape[1] >= 1):
+        raise EngineError("store must be a contiguous CUDA tensor [n_files, row] with n_files, row >= 1")
+    nb = int(idx.numel())
+    if not (idx.is_cuda and idx.dtype == torch.int32 and idx.dim() == 1 and idx.is_contiguous()):
+        raise EngineError("idx must be a contiguous int32 CUDA vector")
+    row = int(store.shape[1])
+    if not (out.is_cuda and out.dtype == store.dtype and out.dim() == 2 and out.shape[0] >= nb and out.shape[1] == row
+            and (out.stride(1) == 1 or row == 1) and (out.stride(0) >= row or out.shape[0] <= 1)):
+        raise EngineError(f"out must be a {store.dtype} CUDA tensor [>= {nb}, {row}] with contiguous rows")
+    es = store.element_size()
+    stride = int(out.stride(0)) if out.shape[0] > 1 else row
+    _check(load().sae_store_gather(C.c_void_p(store.data_ptr()), int(store.shape[0]), row * es, C.c_void_p(idx.data_ptr()), nb,
+                                   C.c_void_p(out.data_ptr()), stride * es, _dev("err", err, "int32", 1), _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:

@@ -159,7 +159,8 @@ def top_activations(sae, data_path: str, layer_name: str, feature_idx: int, n_fi
                     min_val: Optional[float], absolute_magnitude: bool, return_max_per_file: bool, lengths=None):
     """activations.py:61-132 with the reference's return shape: ([(audio_file, trimmed series, value, time)], max_per_file or None).
     The series are re-encoded for the winning files only."""
-    from .loader import MemoryMappedActivationsDataset
+    from .loader import MemoryMappedActivationsDataset, require_directory
+    require_directory(data_path)                # (the winners' series are read from the files below)
     model, eng = resolve_sae(sae)
     atlas = search_features(model if model is not None else eng, data_path, layer_name, n_files, absolute_magnitude=absolute_magnitude,
                             min_val=min_val, max_val=max_val, lengths=lengths,

@@ -80,7 +80,9 @@ def keep_rng(fn):
 class FilePass:
     """The set-up of one pass, then its batches.  `sae`: see resolve_sae (None: raw mode, no engine); `what` is the noun of the
     error messages ("feature search", "feature statistics").  `max_frames`: a pass over more than this many frames (files x T) is
-    refused.  Every check that needs no device comes before the one that does.
+    refused.  Every check that needs no device comes before the one that does.  `data_path`: the shard directory, or a
+    freud_amd.resident.ResidentActivations of it in the shards' own dtype -- then the batches are zero-copy slices of the store and
+    nothing crosses the host link.
 
     Attributes: model, eng (None in raw mode), device, T, d, n_total, n_frames (the frames that count: the trimmed lengths, or
     files x T), batch_files, filenames.  Iterating yields
@@ -93,8 +95,21 @@ class FilePass:
 
         if batch_files is not None and int(batch_files) < 1:
             raise ValueError(f"batch_files={batch_files} must be >= 1")
-        ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
-        n_total = len(ds)
+        from .resident import ResidentActivations
+        store = data_path if isinstance(data_path, ResidentActivations) else None
+        if store is not None:
+            # a resident store in place of the directory: its first subset_size files, as zero-copy slices (__iter__)
+            if store.layer_name != layer_name:
+                raise ValueError(f"the store holds layer {store.layer_name!r}, the {what} asks for {layer_name!r}")
+            if not store.native:
+                raise ValueError(f"the {what} reads the shards' own values: the store holds them converted to {store.data.dtype}")
+            if subset_size is not None and not 0 <= int(subset_size) <= len(store):
+                raise ValueError(f"subset_size={subset_size} outside the store's {len(store)} files")
+            ds = store.dataset
+            n_total = len(store) if subset_size is None else int(subset_size)
+        else:
+            ds = MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
+            n_total = len(ds)
         if n_total == 0:
             raise ValueError(f"{data_path}: no files")
         T, d = int(ds.tensor_shape[-2]), int(ds.tensor_shape[-1])
@@ -134,7 +149,10 @@ class FilePass:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.model, self.eng, self.device = model, eng, dev
         self.T, self.d, self.n_total, self.batch_files = T, d, n_total, B
-        self.filenames = list(ds.metadata["filenames"])
+        self.filenames = list(ds.metadata["filenames"])[:n_total]
+        if store is not None and store.device.index != (dev.index if dev.index is not None else torch.cuda.current_device()):
+            raise ValueError(f"the store lives on {store.device}, the {what} runs on {dev}")
+        self._store = store
         self._loader_args = (data_path, layer_name, subset_size)
 
     def check_counted(self, counted: int) -> None:
@@ -148,6 +166,12 @@ class FilePass:
 
         data_path, layer_name, subset_size = self._loader_args
         lens_dev = torch.from_numpy(self._lens).to(self.device) if self._lens is not None else None
+        if self._store is not None:
+            for file0 in range(0, self.n_total, self.batch_files):
+                nb = min(self.batch_files, self.n_total - file0)
+                yield (self._store.data[file0:file0 + nb].view(nb, self.T, self.d), file0, nb,
+                       lens_dev[file0:file0 + nb] if lens_dev is not None else None)
+            return
         # (native delivery whatever FREUD_LOADER_DELIVER says, no shuffle: raw mode sees x unrounded, an SAE what encode() of the
         # shard rows sees)
         loader = MemoryMappedActivationDataLoader(data_path, layer_name, self.batch_files, subset_size=subset_size,

@@ -74,11 +74,18 @@ def _mem_available_bytes() -> int:
     return 16 << 30
 
 
+def require_directory(data_path) -> None:
+    """What reads the shards' files itself takes the directory's path, not a resident store of it (freud_amd/resident.py)."""
+    if not isinstance(data_path, (str, os.PathLike)):
+        raise TypeError(f"data_path must be the path of a shard directory here, got {type(data_path).__name__}")
+
+
 class MemoryMappedActivationsDataset:
     """dataset/activations.py:116-174 (tensor-type shards only; 'indexed' SAE-feature shards are
     not consumed by training)."""
 
     def __init__(self, data_path: str, layer_name: str, subset_size: Optional[int] = None):
+        require_directory(data_path)
         self.data_path, self.layer_name = data_path, layer_name
         self.metadata_file = os.path.join(data_path, f"{layer_name}_metadata.json")
         with open(self.metadata_file, "r") as f:

@@ -75,8 +75,9 @@ def resample_dead_latents(sae, data_path: str, layer_name: str, *, files: int = 
     RNG is left as it was."""
     import torch
     from . import engine as E
-    from .loader import MemoryMappedActivationsDataset
+    from .loader import MemoryMappedActivationsDataset, require_directory
 
+    require_directory(data_path)                # (the chosen frames are read from the files below)
     if is_raw(sae) or isinstance(sae, str):
         raise ValueError("resampling rewrites a live SAE: pass a freud_amd.models L1 SAE or an L1 SaeEngine (for a checkpoint, the "
                          "command line reads one and writes one)")

@@ -274,6 +274,22 @@ def _dist_env():
 # ------------------------------------------------------------------------------------------------
 # train()
 # ------------------------------------------------------------------------------------------------
+def _resident_loader(rd: dict, streaming, data_path: str, layer_name: str, batch_size: int, dl_max_workers: int, dl_kwargs: dict, device,
+                     rank: int, world: int, is_main: bool):
+    """The train loader of "resident_data" (freud_amd/resident.py) in place of `streaming`, or `streaming` itself where the store does
+    not fit and the key says "on_overflow": "stream".  The upload leaves the global RNG as it found it."""
+    from freud_amd.resident import ResidentActivationDataLoader, ResidentOverflow
+    try:
+        return ResidentActivationDataLoader(data_path, layer_name, batch_size, dl_max_workers, None, dl_kwargs, device=device, rank=rank,
+                                            world_size=world, deliver_dtype=rd["dtype"], max_gb=rd["max_gb"])
+    except ResidentOverflow as e:
+        if rd["on_overflow"] != "stream":
+            raise
+        if is_main:
+            print(f"resident_data: {e}; streaming the shards instead")
+        return streaming
+
+
 def parse_init_b_dec(init_b_dec, autoencoder_variant: str) -> Optional[dict]:
     """The optional train() key "init_b_dec" -> None or {"method", "files", "iterations"}; ValueError for a form it does not take.
     Needs no device."""
@@ -300,7 +316,7 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
           val_every: int, start_checkpoint: Optional[str], whisper_config: dict, optimizer: str, scheduler: str,
           scheduler_params: dict, from_disk: bool, autoencoder_variant: str, autoencoder_config: dict, *,
           eval_precision: Optional[str] = None, resample: Optional[dict] = None, decoder_constraint: Optional[bool] = None,
-          init_b_dec=None, engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
+          init_b_dec=None, resident_data=None, engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
     """Same keyword arguments as the reference's train() (train_sae.py:297-320).  One OPTIONAL key beyond them: "eval_precision":
     "fp32" makes validate() -- and with it the choice of bestval.pth -- compute what the reference's validate() computes on
     device='cpu' (no autocast: fp32 end to end, train_sae.py:162-166); "bf16" (default; also FREUD_EVAL_PRECISION) keeps the training
@@ -316,7 +332,13 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
     {"method": ..., "files": F, "iterations": I} (TopK only; F defaults to 256, I to 32): b_dec starts at that statistic of the first F
     training files in file order (freud_amd/input_stats.py) instead of at zero; the other initial parameters, the loader's shuffles
     and the global RNG are what they are without the key, every rank computes the same bytes, and with start_checkpoint the key is
-    recorded and the checkpoint's b_dec stands.  A config file without
+    recorded and the checkpoint's b_dec stands.  And "resident_data": true | {"dtype": "native" | "bfloat16", "max_gb": G,
+    "on_overflow": "error" | "stream"} (freud_amd/resident.py): the training shards are uploaded to HBM once and every batch is drawn
+    from them on the device -- the same batches, bit for bit, as the streaming loader delivers, so the run's checkpoints are the
+    streaming run's.  dtype defaults to what FREUD_LOADER_DELIVER (else native) would deliver; a store that does not fit max_gb GiB
+    (default: the free device memory less a reserve) is an error, or with "stream" one log line and the ordinary loader.  With several
+    ranks each holds the whole store and draws its slice of the permutation.  Validation, "resample" and "init_b_dec" keep streaming:
+    their inputs must be the shards' native values and they read a few files once.  A config file without
     these keys is a reference config file and trains bit for bit as before.  The two trailing keyword-only arguments are test hooks
     and are never present in a config file."""
     eval_precision = eval_precision or os.environ.get("FREUD_EVAL_PRECISION") or "bf16"
@@ -340,6 +362,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         if not TopKAutoEncoderConfig.from_dict(autoencoder_config).normalize_decoder:
             raise ValueError("\"decoder_constraint\" keeps the decoder rows at unit norm: autoencoder_config.normalize_decoder is false")
     ib = parse_init_b_dec(init_b_dec, autoencoder_variant)
+    from freud_amd.resident import parse_resident_data
+    rd = parse_resident_data(resident_data)
     device = torch.device(device)
     rank, local_rank, world = _dist_env()
     # FREUD_FORCE_DIST=1 (test hook, like bench.py --force-dist): take the data-parallel code path - process group,
@@ -379,6 +403,9 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
     train_loader, feat_dim, dset_len = init_dataloader(from_disk, train_folder, whisper_config["model"], None,
                                                        whisper_config["layer_name"], device, batch_size, dl_max_workers,
                                                        None, dl_kwargs, rank=rank, world_size=world)
+    if rd is not None:
+        train_loader = _resident_loader(rd, train_loader, train_folder, whisper_config["layer_name"], batch_size, dl_max_workers,
+                                        dl_kwargs, device, rank, world, is_main=rank == 0)
     hparam_dict = {
         "autoencoder_variant": autoencoder_variant, "autoencoder_config": autoencoder_config, "lr": lr,
         "weight_decay": weight_decay, "steps": steps, "clip_thresh": clip_thresh, "batch_size": batch_size,
@@ -391,6 +418,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         hparam_dict["decoder_constraint"] = True
     if ib is not None:
         hparam_dict["init_b_dec"] = init_b_dec if isinstance(init_b_dec, str) else dict(init_b_dec)
+    if rd is not None:
+        hparam_dict["resident_data"] = True if resident_data is True else dict(resident_data)
     assert autoencoder_variant in ["l1", "topk"], \
         f"Invalid autoencoder variant: {autoencoder_variant}, must be 'l1' or 'topk'"
     if optimizer not in ("radam", "adam"):

@@ -1144,6 +1144,27 @@ int sae_input_cov_plan(int64_t n_files, int64_t rows_per_file, int64_t d, int64_
 int sae_input_cov(const void* x_dev, int64_t n_files, int64_t rows_per_file, int64_t d, int x_dtype, const int32_t* lengths_dev,
                   const double* center_dev, double* out_dev, void* workspace_dev, int64_t workspace_bytes, void* stream);
 
+/* ---- The HBM-resident activation store (freud_amd/resident.py): a shard directory uploaded once as one device array
+ * store [n_files][row_bytes], and every batch drawn from it on the device instead of over the host link.
+ *
+ * sae_store_convert: dst_dev[i] = bf16(src_dev[i]) for i < n_elems, by the rule of the loader's host conversion
+ *   (freud_amd/csrc/bf16_guard.h; freud_amd/csrc/host_convert.c): round to nearest even; a NaN stays a quiet NaN
+ *   ((u >> 16) | 0x40); a value that is not -1.0 but would round to 0xBF80 goes to 0xBF81 or 0xBF7F, because exactly -1.0 is the
+ *   reference's mask value.  src 4-byte and dst 2-byte aligned; both 16-byte aligned take the vector form.  n_elems >= 0.
+ * sae_store_gather: out_dev[j] = store_dev[idx_dev[j]] for j < nb, rows of row_bytes bytes, row j of the destination at
+ *   out_dev + j * out_stride_bytes (out_stride_bytes >= row_bytes; the bytes between rows are left as they are).  A byte copy: it
+ *   serves stores of any element type.  The store, the destination, row_bytes and out_stride_bytes must be multiples of 2 bytes;
+ *   multiples of 16 take the 16-byte form, of 4 the 4-byte form.  One workgroup copies one piece of sae_store_piece_bytes() bytes
+ *   of one row; nb * ceil(row_bytes / piece) <= 2^31 - 1.  An index outside [0, n_files) is clamped into it -- nothing outside the
+ *   store is ever read -- and *err_dev (uint32, never cleared by the call) is incremented once per such batch row: the caller
+ *   validates its index lists on the host and reads the word as the second line.
+ * Both need no context, run on the current device, are asynchronous on `stream` and return SAE_ERR_INVALID for an argument outside
+ * the above before anything is enqueued. */
+int64_t sae_store_piece_bytes(void);
+int sae_store_convert(const float* src_dev, void* dst_dev, int64_t n_elems, void* stream);
+int sae_store_gather(const void* store_dev, int64_t n_files, int64_t row_bytes, const int32_t* idx_dev, int64_t nb, void* out_dev,
+                     int64_t out_stride_bytes, uint32_t* err_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order; 14 = the multi-TopK pass's d (decoder output) [M][d] of the last training forward, as
