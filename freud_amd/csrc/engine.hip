@@ -2666,6 +2666,18 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
     if (rc_d) return rc_d;
   }
   const int64_t M = c->last_M;
+  if (which == 15) {   // Wt [n_p][d_p], the bf16 weights as the L1 kernels read them, widened: [n][d]
+    if (c->topk) return fail(SAE_ERR_INVALID, "debug tensor 15: not an L1 context");
+    if (cap < (int64_t)c->n * c->d) return fail(SAE_ERR_INVALID, "capacity too small");
+    std::vector<uint16_t> tmp((size_t)c->n * c->d_p);
+    HIP_TRY(hipMemcpy(tmp.data(), c->Wt, tmp.size() * 2, hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < c->n; ++j)
+      for (int i = 0; i < c->d; ++i) {
+        uint32_t u = (uint32_t)tmp[(size_t)j * c->d_p + i] << 16;
+        memcpy(&out[j * c->d + i], &u, 4);
+      }
+    return SAE_OK;
+  }
   if (which == 0 || which == 1 || which == 14) {   // 14 = dm_b, the multi-TopK pass's d (decoder output) of the last training forward
     const int cols = which == 0 ? c->n : c->d, ld = which == 0 ? c->n_p : c->d_p;
     if (cap < M * cols) return fail(SAE_ERR_INVALID, "capacity too small");
@@ -2766,6 +2778,27 @@ extern "C" int sae_debug_read(sae_ctx* c, int which, float* out, int64_t cap) {
     return rc;
   }
   return fail(SAE_ERR_INVALID, "unknown debug tensor %d", which);
+}
+
+// what dw_plan and bwd_fused_args decide for a batch of M rows (launches nothing)
+extern "C" int sae_l1_backward_plan(sae_ctx* c, int64_t M, int32_t out[8]) {
+  if (!c || !out) return fail(SAE_ERR_INVALID, "null argument");
+  if (c->topk || c->fp8) return fail(SAE_ERR_INVALID, "sae_l1_backward_plan: not a bf16 L1 context");
+  if (M < 1 || M > c->cfg.max_rows) return fail(SAE_ERR_INVALID, "sae_l1_backward_plan: M outside [1, max_rows]");
+  const int64_t Mp = round_up(M, c->row_pad);
+  const DwPlan p = dw_plan(c, Mp);
+  const bool fused = p.form == DW_FUSED || p.form == DW_FUSED_RANGES;
+  BwdFusedArgs a{};
+  if (fused) a = bwd_fused_args(c, p, M, Mp, false);
+  out[0] = (int32_t)p.form;
+  out[1] = p.splits;
+  out[2] = p.balanced ? 1 : 0;
+  out[3] = a.bal_m;
+  out[4] = a.bal_q;
+  out[5] = !fused ? 0 : p.balanced ? c->bal_grid : a.ntiles * a.splits;
+  out[6] = (int32_t)(Mp / 32);
+  out[7] = c->n_p / 128;
+  return SAE_OK;
 }
 
 extern "C" int sae_latent_buffer(sae_ctx* c, void** dev_ptr, int64_t* row_stride) {

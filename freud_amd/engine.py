@@ -113,6 +113,7 @@ _SIGNATURES = {
     "sae_read_metrics": (C.c_int, [_vp, _fptr, _vp]),
     "sae_latent_colmax": (C.c_int, [_vp, _fptr, _i64, _vp]),
     "sae_debug_read": (C.c_int, [_vp, C.c_int, _fptr, _i64]),
+    "sae_l1_backward_plan": (C.c_int, [_vp, _i64, C.POINTER(_i32)]),
     "sae_search_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp]),
     "sae_search_raw_files": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "sae_search_merge": (C.c_int, [_vp, _vp, _i64, _i64, _i64, C.c_int, C.c_int, _dbl, _dbl, _vp, _vp, _vp]),
@@ -923,6 +924,13 @@ class SaeEngine:
         out = np.empty(count, dtype=np.float32)
         _check(self._lib.sae_debug_read(self._ctx, which, out.ctypes.data_as(C.POINTER(C.c_float)), count))
         return out
+
+    def l1_backward_plan(self, M: int) -> dict:
+        """L1, bf16 contexts: how the weight gradient of a batch of M rows would be launched (nothing runs)."""
+        out = (_i32 * 8)()
+        _check(self._lib.sae_l1_backward_plan(self._ctx, int(M), out))
+        keys = ("form", "splits", "balanced", "bal_m", "bal_q", "grid", "steps", "ntiles")
+        return {k: int(v) for k, v in zip(keys, out)}
 
     def profile(self, level: int, period: Optional[int] = None) -> None:
         """level 1 brackets the dominant kernel with HIP events on every `period`-th step (default 8)."""

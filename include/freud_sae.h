@@ -1169,8 +1169,15 @@ int sae_store_gather(const void* store_dev, int64_t n_files, int64_t row_bytes, 
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order; 14 = the multi-TopK pass's d (decoder output) [M][d] of the last training forward, as
  * the sparse backward reads it (bf16 values; SAE_ERR_INVALID unless the context is TopK with multi_topk, SAE_ERR_STATE after an fp32
- * evaluation, like 1).  Synchronising.  Not part of the hot path. */
+ * evaluation, like 1); 15 = the L1 weights as the kernels read them, bf16 Wt[n_p][d_p] widened to [n][d] (SAE_ERR_INVALID for a
+ * TopK context).  Synchronising.  Not part of the hot path. */
 int sae_debug_read(sae_ctx* ctx, int which, float* out_host, int64_t capacity_floats);
+
+/* Test / inspection hook: the launch plan of the L1 weight gradient for a batch of M rows (1 <= M <= max_rows), nothing is launched.
+ * out_host = {form (0 = fused d = 384, 1 = fused in column ranges, 2 .. 6 = the GEMM forms), splits (row ranges / split-K slabs),
+ * balanced (0 / 1), bal_m (quanta per workgroup), bal_q (32-row steps per quantum), grid (workgroups of the fused backward, 0 for the
+ * GEMM forms), M_p / 32, n_p / 128}; bal_m and bal_q are 0 unless balanced.  SAE_ERR_INVALID for TopK and fp8 contexts. */
+int sae_l1_backward_plan(sae_ctx* ctx, int64_t M, int32_t out_host[8]);
 
 /* Timing hooks for bench.py / profiling.  level 0 = off, 1 = bracket only the dominant kernel of
  * every step with HIP events on the launch stream, 2 = bracket every kernel (diagnostic).
