@@ -30,6 +30,7 @@
 #include "input_cov_plan.h"
 #include "input_cov.h"
 #include "resident.h"
+#include "frame_gather.h"
 
 // ---- feature search (search.h; the reference's top_activations, utils/activations.py:61-132, for every latent at once)
 static int search_launch_colreduce(const void* x, int x_dtype, int64_t ld, int ncols, int Trows, int64_t n_files, const int* lengths,
@@ -1811,6 +1812,51 @@ extern "C" int sae_store_gather(const void* store, int64_t n_files, int64_t row_
     hipLaunchKernelGGL(store_gather_kernel<uint32_t>, grid, dim3(RS_THREADS), 0, s, src, n_files, row_bytes, idx, pieces, dst, out_stride_bytes, err);
   else
     hipLaunchKernelGGL(store_gather_kernel<uint16_t>, grid, dim3(RS_THREADS), 0, s, src, n_files, row_bytes, idx, pieces, dst, out_stride_bytes, err);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- frame batches (frame_gather.h): rows of the destination = the frames that a run of positions of the epoch's permutation holds
+extern "C" int sae_store_gather_frames(const void* store, int64_t n_files, int64_t rows_per_file, int64_t frame_bytes, const int64_t* prefix,
+                                       int64_t n_frames, uint64_t key, int64_t pos0, int64_t pos_stride, int64_t rows, void* out,
+                                       int64_t out_stride_bytes, int64_t* ordinals_out, uint32_t* err, void* stream) {
+  const char* const fn = "sae_store_gather_frames";
+  if (!store || (!out && rows != 0) || !err) return fail(SAE_ERR_INVALID, "%s: null argument", fn);
+  if (n_files < 1 || n_files > 0x7FFFFFFFll || rows_per_file < 1 || rows_per_file > 0x7FFFFFFFll)
+    return fail(SAE_ERR_INVALID, "%s: n_files=%lld, rows_per_file=%lld outside [1, 2^31 - 1]", fn, (long long)n_files, (long long)rows_per_file);
+  if (frame_bytes < 1 || frame_bytes > 0x7FFFFFFFll) return fail(SAE_ERR_INVALID, "%s: frame_bytes=%lld outside [1, 2^31 - 1]", fn, (long long)frame_bytes);
+  if (n_frames < 1 || n_frames > n_files * rows_per_file)
+    return fail(SAE_ERR_INVALID, "%s: n_frames=%lld outside [1, n_files * rows_per_file = %lld]", fn, (long long)n_frames,
+                (long long)(n_files * rows_per_file));
+  if (rows < 0 || rows > n_frames || (rows > 0 && (pos0 < 0 || pos0 >= n_frames || pos_stride < 1)))
+    return fail(SAE_ERR_INVALID, "%s: rows=%lld, pos0=%lld, pos_stride=%lld with %lld frames", fn, (long long)rows, (long long)pos0,
+                (long long)pos_stride, (long long)n_frames);
+  if (rows > 1 && (rows - 1) > (n_frames - 1 - pos0) / pos_stride)       // pos0 + (rows - 1) * pos_stride >= n_frames, without the product
+    return fail(SAE_ERR_INVALID, "%s: the last position pos0 + (rows - 1) * pos_stride leaves the %lld frames", fn, (long long)n_frames);
+  if (out_stride_bytes < frame_bytes)
+    return fail(SAE_ERR_INVALID, "%s: out_stride_bytes=%lld < frame_bytes=%lld", fn, (long long)out_stride_bytes, (long long)frame_bytes);
+  if (misaligned(err, 4) || misaligned(prefix, 8) || misaligned(ordinals_out, 8))
+    return fail(SAE_ERR_INVALID, "%s: err must be 4-byte, prefix and ordinals_out 8-byte aligned", fn);
+  const int width = rs_copy_width((uint64_t)reinterpret_cast<uintptr_t>(store) | (uint64_t)reinterpret_cast<uintptr_t>(out) | (uint64_t)frame_bytes |
+                                  (uint64_t)out_stride_bytes);
+  if (!width) return fail(SAE_ERR_INVALID, "%s: the store, the destination, frame_bytes and out_stride_bytes must be multiples of 2 bytes", fn);
+  const fp_plan plan = fp_plan_of(frame_bytes, width, rows);
+  if (plan.blocks > 0x7FFFFFFFll) return fail(SAE_ERR_INVALID, "%s: %lld workgroups exceed 2^31 - 1", fn, (long long)plan.blocks);
+  if (rows == 0) return SAE_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)plan.blocks);
+  const char* const src = (const char*)store;
+  char* const dst = (char*)out;
+  const uint64_t N = (uint64_t)n_frames, p0 = (uint64_t)pos0, ps = (uint64_t)pos_stride;
+  if (width == 16)
+    hipLaunchKernelGGL(frame_gather_kernel<rs_u32x4>, grid, dim3(FP_THREADS), 0, s, src, prefix, n_files, rows_per_file, frame_bytes, N, key, p0, ps,
+                       rows, plan, dst, out_stride_bytes, ordinals_out, err);
+  else if (width == 4)
+    hipLaunchKernelGGL(frame_gather_kernel<uint32_t>, grid, dim3(FP_THREADS), 0, s, src, prefix, n_files, rows_per_file, frame_bytes, N, key, p0, ps,
+                       rows, plan, dst, out_stride_bytes, ordinals_out, err);
+  else
+    hipLaunchKernelGGL(frame_gather_kernel<uint16_t>, grid, dim3(FP_THREADS), 0, s, src, prefix, n_files, rows_per_file, frame_bytes, N, key, p0, ps,
+                       rows, plan, dst, out_stride_bytes, ordinals_out, err);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

@@ -155,6 +155,7 @@ _SIGNATURES = {
     "sae_store_piece_bytes": (_i64, []),
     "sae_store_convert": (C.c_int, [_vp, _vp, _i64, _vp]),
     "sae_store_gather": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "sae_store_gather_frames": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, C.c_uint64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
     "sae_profile": (C.c_int, [_vp, C.c_int]),
     "sae_profile_period": (C.c_int, [_vp, C.c_int]),
     "sae_kernel_times": (C.c_int, [_vp, _fptr, C.POINTER(_i32), C.c_int]),
@@ -1286,6 +1287,31 @@ def store_gather(store, idx, out, err, stream=None) -> None:
     stride = int(out.stride(0)) if out.shape[0] > 1 else row
     _check(load().sae_store_gather(C.c_void_p(store.data_ptr()), int(store.shape[0]), row * es, C.c_void_p(idx.data_ptr()), nb,
                                    C.c_void_p(out.data_ptr()), stride * es, _dev("err", err, "int32", 1), _stream_ptr(stream)))
+
+
+def store_gather_frames(store, T: int, prefix, n_frames: int, key: int, pos0: int, pos_stride: int, out, err, ordinals=None,
+                        stream=None) -> None:
+    """out[j] = the frame that position pos0 + j * pos_stride of the epoch `key` holds, for j < out.shape[0] (include/freud_sae.h,
+    sae_store_gather_frames): store [n_files, T * d] a contiguous CUDA tensor, prefix None (untrimmed) or a contiguous int64 CUDA
+    vector [n_files + 1] (the exclusive prefix sum of the trimmed lengths), n_frames the counted frames, key any integer (taken mod
+    2^64), out [rows, d] a CUDA tensor of the store's dtype whose rows are contiguous (its row stride may exceed d), err one int32 on
+    the device -- incremented per frame a malformed prefix placed outside the store, never cleared here --, ordinals None or a
+    contiguous int64 CUDA vector [rows] that receives every row's index into store.view(n_files * T, d)."""
+    T = int(T)
+    if not (store.is_cuda and store.dim() == 2 and store.is_contiguous() and store.shape[0] >= 1 and T >= 1 and store.shape[1] >= T
+            and store.shape[1] % T == 0):
+        raise EngineError("store must be a contiguous CUDA tensor [n_files, T * d] with n_files, T, d >= 1")
+    n_files, d = int(store.shape[0]), int(store.shape[1]) // T
+    if not (out.is_cuda and out.dtype == store.dtype and out.dim() == 2 and out.shape[1] == d and (out.stride(1) == 1 or d == 1)
+            and (out.stride(0) >= d or out.shape[0] <= 1)):
+        raise EngineError(f"out must be a {store.dtype} CUDA tensor [rows, {d}] with contiguous rows")
+    rows = int(out.shape[0])
+    es = store.element_size()
+    stride = int(out.stride(0)) if rows > 1 else d
+    _check(load().sae_store_gather_frames(C.c_void_p(store.data_ptr()), n_files, T, d * es, _dev("prefix", prefix, "int64", n_files + 1, optional=True),
+                                          int(n_frames), int(key) & (2 ** 64 - 1), int(pos0), int(pos_stride), rows, C.c_void_p(out.data_ptr()),
+                                          stride * es, _dev("ordinals", ordinals, "int64", rows, optional=True), _dev("err", err, "int32", 1),
+                                          _stream_ptr(stream)))
 
 
 def search_file_values(file_keys, aux, n_files: int, ncols: int, flags: int, latents, file0: int, out, stream=None) -> None:

@@ -10,6 +10,9 @@ many times over.  For them
 * ResidentActivationDataLoader is MemoryMappedActivationDataLoader with the batches assembled by one gather kernel per batch
   (sae_store_gather) instead of copies over the link: the same epoch_batches() -- so the same RNG draws, rank slices, drop_last and
   skip_next -- the same (x [B, T, d], filenames) batches bit for bit, into a ring of `depth` device buffers;
+* ResidentFrameDataLoader draws FRAMES instead of files: an epoch is a keyed permutation of every counted frame, evaluated inside
+  the gather kernel (sae_store_gather_frames; csrc/frame_perm.h), a batch is the next batch_size * T of them, and with lengths the
+  padding of every file is left out -- the train() key "frame_batches" (parse_frame_batches);
 * FilePass (file_pass.py) takes a native store in place of the directory and yields zero-copy slices of it.
 
 An index list is validated on the host (check_indices) before it is uploaded; the kernel clamps and counts all the same, and the
@@ -176,7 +179,6 @@ class ResidentActivationDataLoader(MemoryMappedActivationDataLoader):
         self._err = None
 
     def __iter__(self):
-        import torch
         from . import engine
         batches = self.epoch_batches()
         if self.skip_next:
@@ -184,10 +186,33 @@ class ResidentActivationDataLoader(MemoryMappedActivationDataLoader):
             self.skip_next = 0
         if not batches:
             return
-        store, dev, depth = self.store, self.device, self.depth
+        import torch
+        store = self.store
         T, d = int(store.tensor_shape[-2]), int(store.tensor_shape[-1])
         names = store.filenames
         flat = check_indices(batches, len(store))        # the check; the kernel's clamp and count are the second line
+
+        def jobs(dev):
+            idx_dev = torch.from_numpy(flat).to(dev)     # the epoch's indices: one upload
+            at = 0
+            for idxs in batches:
+                nb, idx = len(idxs), idx_dev[at:at + len(idxs)]
+                at += nb
+                yield (lambda buf, err, stream, idx=idx: engine.store_gather(store.data, idx, buf, err, stream=stream),
+                       lambda buf, nb=nb, idxs=idxs: (buf[:nb].view(nb, T, d), [names[i] for i in idxs]))
+
+        yield from self._ring_epoch(jobs, lambda bad: f"{bad} batch rows of this epoch asked for files outside the store's [0, {len(store)}): "
+                                                      "they were clamped into it, the batches are not the epoch's")
+
+    def _ring_epoch(self, jobs, complaint):
+        """One epoch through the ring of `depth` buffers [batch_size, T * d].  jobs(dev) -- called once, after the ring exists and
+        before the first gather, on the compute stream -- yields per batch (launch(buffer, err, stream), deliver(buffer) -> what
+        the loader yields).  With overlap the launches run on the side stream, ordered against the compute stream by events both
+        ways: a buffer is not overwritten before the compute stream has passed its last reader, and not read before its gather
+        landed.  The error word is read once, after the last batch; a count is complaint(count) as a RuntimeError."""
+        import torch
+        store, dev, depth = self.store, self.device, self.depth
+        T, d = int(store.tensor_shape[-2]), int(store.tensor_shape[-1])
         shared = not self._ring_busy
         new_ring = lambda: ([torch.empty((self.batch_size, T * d), dtype=store.data.dtype, device=dev) for _ in range(depth)], [None] * depth)
         if shared:
@@ -201,24 +226,24 @@ class ResidentActivationDataLoader(MemoryMappedActivationDataLoader):
             if self.overlap and self._stream is None:
                 self._stream = torch.cuda.Stream(device=dev)
             err, side = self._err, self._stream if self.overlap else None
-            idx_dev = torch.from_numpy(flat).to(dev)     # the epoch's indices: one upload
+            todo = jobs(dev)
+            first = next(todo)                           # (the generator's setup -- the uploads -- runs here)
             if side is not None:
                 uploaded = torch.cuda.Event()
                 uploaded.record(torch.cuda.current_stream(dev))
                 side.wait_event(uploaded)
-            at = 0
-            for bi, idxs in enumerate(batches):
-                slot, nb = bi % depth, len(idxs)
+            import itertools
+            for bi, (launch, deliver) in enumerate(itertools.chain([first], todo)):
+                slot = bi % depth
                 compute = torch.cuda.current_stream(dev)
                 if side is not None and consumed[slot] is not None:
                     side.wait_event(consumed[slot])
-                engine.store_gather(store.data, idx_dev[at:at + nb], ring[slot], err, stream=side if side is not None else compute)
+                launch(ring[slot], err, side if side is not None else compute)
                 if side is not None:
                     landed = torch.cuda.Event()
                     landed.record(side)
                     compute.wait_event(landed)
-                at += nb
-                yield ring[slot][:nb].view(nb, T, d), [names[i] for i in idxs]
+                yield deliver(ring[slot])
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(dev))
                 consumed[slot] = ev
@@ -227,8 +252,114 @@ class ResidentActivationDataLoader(MemoryMappedActivationDataLoader):
             bad = int(err.item())                        # once per epoch
             if bad:
                 err.zero_()
-                raise RuntimeError(f"{bad} batch rows of this epoch asked for files outside the store's [0, {len(store)}): "
-                                   "they were clamped into it, the batches are not the epoch's")
+                raise RuntimeError(complaint(bad))
         finally:
             if shared:
                 self._ring_busy = False
+
+
+def parse_frame_batches(spec, resident: Optional[dict] = None) -> Optional[dict]:
+    """The optional train() key "frame_batches" -> None (absent or false) or {"lengths": None | path}; `resident` is what
+    parse_resident_data made of the config's "resident_data".  ValueError for a form it does not take, for the key without a
+    resident store and for a store that may fall back to streaming.  Needs no device."""
+    if spec is None or spec is False:
+        return None
+    if spec is True:
+        spec = {}
+    if not isinstance(spec, dict) or set(spec) - {"lengths"}:
+        raise ValueError(f"\"frame_batches\" is true, false or an object of lengths; got {spec!r}")
+    lengths = spec.get("lengths")
+    if lengths is not None and not isinstance(lengths, (str, os.PathLike)):
+        raise ValueError(f"\"frame_batches\": lengths is the path of a .npy file of frames per file; got {lengths!r}")
+    if resident is None:
+        raise ValueError("\"frame_batches\" draws its frames from the resident store: the config needs \"resident_data\" too")
+    if resident["on_overflow"] == "stream":
+        raise ValueError("\"frame_batches\" with \"resident_data\": {\"on_overflow\": \"stream\"}: the streaming loader has no frame "
+                         "batches to fall back to")
+    return {"lengths": None if lengths is None else os.fspath(lengths)}
+
+
+def load_frame_lengths(path: str, data_path: str, layer_name: str) -> np.ndarray:
+    """The lengths file of "frame_batches" (.npy, int frames per file in file order) held to the shard directory by
+    file_pass.check_lengths; every failure is a ValueError that names the key.  Needs no device."""
+    from .file_pass import check_lengths
+    try:
+        raw = np.load(path, allow_pickle=False)
+    except Exception as e:          # noqa: BLE001 -- whatever numpy makes of a file that is no array
+        raise ValueError(f"\"frame_batches\": lengths file {path!r} does not load: {e}") from e
+    ds = MemoryMappedActivationsDataset(data_path, layer_name)
+    try:
+        return check_lengths(raw, len(ds), int(ds.tensor_shape[-2]))
+    except ValueError as e:
+        raise ValueError(f"\"frame_batches\": lengths file {path!r}: {e}") from e
+
+
+class ResidentFrameDataLoader(ResidentActivationDataLoader):
+    """Frame batches over a resident store: an epoch is a pseudo-random permutation of every COUNTED frame of the dataset and a batch
+    is the next batch_size * T of them -- all T frames of every file, or with lengths (frames per file, in file order; what
+    file_pass.check_lengths takes) only each file's first lengths[f], so that padding never reaches a batch.  The permutation is
+    computed, not stored: position p of the epoch holds frame fp_permute(key, N, p) (freud_amd/csrc/frame_perm.h), evaluated inside
+    the gather kernel (sae_store_gather_frames), one call per batch.
+
+    Iteration yields (x [batch_size, T, d], []): the shape the engine, max_rows and set_topk_options(..., T) expect, and no
+    filenames, because the frames of a batch share none.  The T axis carries no meaning here -- TopK's x.mean(0) is then a mean over
+    batch_size unrelated frames per slot.  len(loader) = (N // world_size) // (batch_size * T) batches; the frames beyond the last
+    full batch are not seen in that epoch, and they are other frames in the next one, since the key changes.  An epoch without a
+    single batch is a ValueError here.  Rank r of W reads the positions r, r + W, ...: with the same seed and RNG history every rank
+    draws the same key and the ranks' frames are disjoint.
+
+    __iter__ makes exactly one draw from torch's global RNG -- the epoch's key, kept as epoch_key -- so train()'s resume works
+    unchanged: skip_next = s starts at batch s of the same permutation and reads nothing of the batches before it.  The ring, the
+    overlap switch, the event ordering and the once-per-epoch error word are ResidentActivationDataLoader's.  data_path may be a
+    ResidentActivations (of either dtype).  Needs a GPU."""
+
+    def __init__(self, data_path, layer_name: str, batch_size: int, dl_max_workers: int = 0, subset_size: Optional[int] = None, *,
+                 lengths=None, device="cuda", rank: int = 0, world_size: int = 1, depth: int = 3, deliver_dtype: Optional[str] = None,
+                 max_gb: Optional[float] = None, overlap: bool = DEFAULT_OVERLAP):
+        from .file_pass import check_lengths
+        if not (isinstance(batch_size, int) and batch_size >= 1 and 0 <= rank < world_size):
+            raise ValueError(f"batch_size={batch_size!r}, rank={rank!r}, world_size={world_size!r}")
+        ds = data_path.dataset if isinstance(data_path, ResidentActivations) else MemoryMappedActivationsDataset(data_path, layer_name, subset_size)
+        n_files, T = len(ds), int(ds.tensor_shape[-2])
+        trimmed = check_lengths(lengths, n_files, T)       # (before any device work)
+        N = n_files * T if trimmed is None else int(trimmed.astype(np.int64).sum())
+        R = batch_size * T
+        if (N // world_size) // R < 1:
+            raise ValueError(f"an epoch holds no batch: N = {N} counted frames over world_size = {world_size} ranks are fewer than one "
+                             f"batch of R = batch_size * T = {R} frames")
+        super().__init__(data_path, layer_name, batch_size, dl_max_workers, subset_size, {"shuffle": True, "drop_last": True}, device=device,
+                         rank=rank, world_size=world_size, depth=depth, deliver_dtype=deliver_dtype, max_gb=max_gb, overlap=overlap)
+        self.n_frames, self.rows_per_batch, self.lengths = N, R, trimmed
+        self.epoch_key = None
+        self._prefix = None
+        if trimmed is not None:
+            import torch
+            prefix = np.concatenate([[0], np.cumsum(trimmed.astype(np.int64))]).astype(np.int64)
+            self._prefix = torch.from_numpy(prefix).to(self.device)     # once per loader
+
+    def __len__(self) -> int:
+        return (self.n_frames // self.world_size) // self.rows_per_batch
+
+    def epoch_batches(self):
+        raise TypeError("a frame loader's batches hold frames, not files: there is no list of file indices")
+
+    def __iter__(self):
+        import torch
+        from . import engine
+        key = int(torch.empty((), dtype=torch.int64).random_().item())      # the epoch's key: the one draw
+        self.epoch_key = key
+        first, self.skip_next = self.skip_next, 0
+        n = len(self)
+        if first >= n:
+            return
+        store, R, W, rank, N, prefix = self.store, self.rows_per_batch, self.world_size, self.rank, self.n_frames, self._prefix
+        T, d, B = int(store.tensor_shape[-2]), int(store.tensor_shape[-1]), self.batch_size
+
+        def jobs(_dev):
+            for b in range(first, n):
+                yield (lambda buf, err, stream, b=b: engine.store_gather_frames(store.data, T, prefix, N, key, b * R * W + rank, W,
+                                                                                buf.view(B * T, d), err, stream=stream),
+                       lambda buf: (buf.view(B, T, d), []))
+
+        yield from self._ring_epoch(jobs, lambda bad: f"{bad} frames of this epoch lay outside the store by the length prefix: they were "
+                                                      "clamped into it, the batches are not the epoch's")

@@ -275,10 +275,14 @@ def _dist_env():
 # train()
 # ------------------------------------------------------------------------------------------------
 def _resident_loader(rd: dict, streaming, data_path: str, layer_name: str, batch_size: int, dl_max_workers: int, dl_kwargs: dict, device,
-                     rank: int, world: int, is_main: bool):
+                     rank: int, world: int, is_main: bool, frames: Optional[dict] = None):
     """The train loader of "resident_data" (freud_amd/resident.py) in place of `streaming`, or `streaming` itself where the store does
-    not fit and the key says "on_overflow": "stream".  The upload leaves the global RNG as it found it."""
-    from freud_amd.resident import ResidentActivationDataLoader, ResidentOverflow
+    not fit and the key says "on_overflow": "stream".  The upload leaves the global RNG as it found it.  frames ({"lengths": None |
+    array}): the frame loader of "frame_batches" over the same store; it has no fall-back."""
+    from freud_amd.resident import ResidentActivationDataLoader, ResidentFrameDataLoader, ResidentOverflow
+    if frames is not None:
+        return ResidentFrameDataLoader(data_path, layer_name, batch_size, dl_max_workers, None, lengths=frames["lengths"], device=device,
+                                       rank=rank, world_size=world, deliver_dtype=rd["dtype"], max_gb=rd["max_gb"])
     try:
         return ResidentActivationDataLoader(data_path, layer_name, batch_size, dl_max_workers, None, dl_kwargs, device=device, rank=rank,
                                             world_size=world, deliver_dtype=rd["dtype"], max_gb=rd["max_gb"])
@@ -316,7 +320,7 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
           val_every: int, start_checkpoint: Optional[str], whisper_config: dict, optimizer: str, scheduler: str,
           scheduler_params: dict, from_disk: bool, autoencoder_variant: str, autoencoder_config: dict, *,
           eval_precision: Optional[str] = None, resample: Optional[dict] = None, decoder_constraint: Optional[bool] = None,
-          init_b_dec=None, resident_data=None, engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
+          init_b_dec=None, resident_data=None, frame_batches=None, engine_factory: Optional[Callable] = None, dist_backend: Optional[str] = None):
     """Same keyword arguments as the reference's train() (train_sae.py:297-320).  One OPTIONAL key beyond them: "eval_precision":
     "fp32" makes validate() -- and with it the choice of bestval.pth -- compute what the reference's validate() computes on
     device='cpu' (no autocast: fp32 end to end, train_sae.py:162-166); "bf16" (default; also FREUD_EVAL_PRECISION) keeps the training
@@ -338,7 +342,14 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
     streaming run's.  dtype defaults to what FREUD_LOADER_DELIVER (else native) would deliver; a store that does not fit max_gb GiB
     (default: the free device memory less a reserve) is an error, or with "stream" one log line and the ordinary loader.  With several
     ranks each holds the whole store and draws its slice of the permutation.  Validation, "resample" and "init_b_dec" keep streaming:
-    their inputs must be the shards' native values and they read a few files once.  A config file without
+    their inputs must be the shards' native values and they read a few files once.  And "frame_batches": true | {"lengths": "<path of
+    a .npy of int frames per file, in file order>"} (needs "resident_data", without "on_overflow": "stream"; ResidentFrameDataLoader
+    in freud_amd/resident.py): an epoch is a pseudo-random permutation of every counted frame of the training store -- every frame, or
+    with lengths only each file's first lengths[f], so that padding is never trained on -- and a batch is the next batch_size x T of
+    them, delivered in the usual [batch_size, T, d] shape (for TopK, x.mean(0) is then a mean over batch_size unrelated frames).  The
+    permutation is a keyed bijection evaluated inside the gather kernel; its key is the epoch's one draw from the global RNG, so
+    checkpoints resume mid-epoch as before, and a checkpoint whose hparams disagree with the config on this key is refused.  Ranks
+    draw the same key and read disjoint positions.  These batches are NOT the streaming run's.  A config file without
     these keys is a reference config file and trains bit for bit as before.  The two trailing keyword-only arguments are test hooks
     and are never present in a config file."""
     eval_precision = eval_precision or os.environ.get("FREUD_EVAL_PRECISION") or "bf16"
@@ -364,6 +375,10 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
     ib = parse_init_b_dec(init_b_dec, autoencoder_variant)
     from freud_amd.resident import parse_resident_data
     rd = parse_resident_data(resident_data)
+    from freud_amd.resident import load_frame_lengths, parse_frame_batches
+    fb = parse_frame_batches(frame_batches, rd)
+    if fb is not None:
+        fb = {"lengths": None if fb["lengths"] is None else load_frame_lengths(fb["lengths"], train_folder, whisper_config["layer_name"])}
     device = torch.device(device)
     rank, local_rank, world = _dist_env()
     # FREUD_FORCE_DIST=1 (test hook, like bench.py --force-dist): take the data-parallel code path - process group,
@@ -405,7 +420,7 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
                                                        None, dl_kwargs, rank=rank, world_size=world)
     if rd is not None:
         train_loader = _resident_loader(rd, train_loader, train_folder, whisper_config["layer_name"], batch_size, dl_max_workers,
-                                        dl_kwargs, device, rank, world, is_main=rank == 0)
+                                        dl_kwargs, device, rank, world, is_main=rank == 0, frames=fb)
     hparam_dict = {
         "autoencoder_variant": autoencoder_variant, "autoencoder_config": autoencoder_config, "lr": lr,
         "weight_decay": weight_decay, "steps": steps, "clip_thresh": clip_thresh, "batch_size": batch_size,
@@ -420,6 +435,8 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         hparam_dict["init_b_dec"] = init_b_dec if isinstance(init_b_dec, str) else dict(init_b_dec)
     if rd is not None:
         hparam_dict["resident_data"] = True if resident_data is True else dict(resident_data)
+    if fb is not None:
+        hparam_dict["frame_batches"] = True if frame_batches is True else dict(frame_batches)
     assert autoencoder_variant in ["l1", "topk"], \
         f"Invalid autoencoder variant: {autoencoder_variant}, must be 'l1' or 'topk'"
     if optimizer not in ("radam", "adam"):
@@ -510,6 +527,10 @@ def train(seed: int, train_folder: str, val_folder: str, device, run_dir: str, l
         if is_main:
             print(f"Checkpoint: {start_checkpoint}")
         load_checkpoint(state, start_checkpoint, device=device)
+        if state["hparams"].get("frame_batches") != hparam_dict.get("frame_batches"):
+            # the side file's epoch position counts batches of frames in one run and batches of files in the other
+            raise ValueError(f"\"frame_batches\": the checkpoint was trained with {state['hparams'].get('frame_batches')!r}, the config says "
+                             f"{hparam_dict.get('frame_batches')!r}: its position in the epoch would mean something else")
         if decoder_constraint:
             # re-applied after the parameters are in place.  A checkpoint of a constrained run holds rows the renorm already left, and
             # the renorm is not idempotent in fp32: keep them, so that the resumed run continues bit for bit.  Any other checkpoint

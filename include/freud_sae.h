@@ -1165,6 +1165,31 @@ int sae_store_convert(const float* src_dev, void* dst_dev, int64_t n_elems, void
 int sae_store_gather(const void* store_dev, int64_t n_files, int64_t row_bytes, const int32_t* idx_dev, int64_t nb, void* out_dev,
                      int64_t out_stride_bytes, uint32_t* err_dev, void* stream);
 
+/* ---- Frame batches (freud_amd/resident.py, ResidentFrameDataLoader; freud_amd/csrc/frame_perm.h, frame_gather.h): a batch of
+ * FRAMES of the resident store, drawn through a permutation that is evaluated in the kernel, not stored.
+ *
+ * The store is store_dev [n_files][rows_per_file][frame_bytes].  Its COUNTED frames are numbered g = 0 .. n_frames - 1 in file
+ * order: all rows_per_file frames of every file (prefix_dev NULL; n_frames = n_files * rows_per_file), or the first len[f] frames
+ * of file f (prefix_dev = int64 [n_files + 1], the exclusive prefix sum of the lengths, 1 <= len[f] <= rows_per_file,
+ * prefix_dev[n_files] = n_frames; device memory, 8-byte aligned).  An epoch is fp_permute(key, n_frames, .) of frame_perm.h, an
+ * exact bijection of [0, n_frames) for every key.
+ *
+ * sae_store_gather_frames: for j < rows, row j of the destination (out_dev + j * out_stride_bytes, out_stride_bytes >=
+ *   frame_bytes, the bytes between rows left as they are) = the frame_bytes of counted frame fp_permute(key, n_frames, pos0 +
+ *   j * pos_stride).  A byte copy: it serves stores of any element type.  ordinals_out_dev (NULL, or int64 [rows], 8-byte
+ *   aligned) receives the frame's row in the store's [n_files * rows_per_file, frame_bytes] view, file * rows_per_file + t -- the
+ *   counted ordinal itself when prefix_dev is NULL.  The store, the destination, frame_bytes and out_stride_bytes must be
+ *   multiples of 2 bytes; multiples of 16 take the 16-byte form, of 4 the 4-byte form.  SAE_ERR_INVALID before anything is enqueued
+ *   for: a null store, destination or error word; n_files, rows_per_file or frame_bytes outside [1, 2^31 - 1]; n_frames < 1 or
+ *   > n_files * rows_per_file; rows < 0; with rows > 0, pos0 outside [0, n_frames), pos_stride < 1 or pos0 + (rows - 1) *
+ *   pos_stride >= n_frames; out_stride_bytes < frame_bytes; addresses and sizes that admit no copy width.  rows == 0 succeeds and
+ *   launches nothing.  The prefix is read on the device and cannot be checked here: a frame that a malformed prefix places
+ *   outside the store is clamped into it -- nothing outside the store is ever read -- and *err_dev (uint32, never cleared by the
+ *   call) is incremented once per such row.  Needs no context, runs on the current device, asynchronous on `stream`. */
+int sae_store_gather_frames(const void* store_dev, int64_t n_files, int64_t rows_per_file, int64_t frame_bytes, const int64_t* prefix_dev,
+                            int64_t n_frames, uint64_t key, int64_t pos0, int64_t pos_stride, int64_t rows, void* out_dev,
+                            int64_t out_stride_bytes, int64_t* ordinals_out_dev, uint32_t* err_dev, void* stream);
+
 /* Test / inspection hook: copy an internal tensor of the last step to host as fp32, un-padded.
  * which: 0 = latent c [M][n]; 1 = x_hat-derived dx_hat [M][d]; 2 = raw gradients in reference
  * layouts, concatenated in parameter order; 14 = the multi-TopK pass's d (decoder output) [M][d] of the last training forward, as
