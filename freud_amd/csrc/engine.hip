@@ -78,7 +78,7 @@ static const char* kKernelNames[KID_COUNT] = {"prep_w", "prep_x", "enc_fwd_gemm"
                                               "manip_apply", "label_pack", "label_update", "hist", "recon_decode",
                                               "recon_resid", "recon_attr", "recon_attr_stream", "collect", "timing",
                                               "frontier_sort", "frontier_walk", "frontier_fold", "pursuit_gemm", "pursuit_step",
-                                              "pursuit_fold", "refit_sort", "refit_chol", "refit_fold"};
+                                              "pursuit_fold", "refit_sort", "refit_chol", "refit_fold", "cross_pack"};
 
 // fused d = 384 L1 path with the peer exchange: the batch statistics are exchanged inside finalize_losses_kernel (StatsPush)
 // (FREUD_DP_STATS=stream: the statistics leave the critical path instead -- a pass over x and their exchange on the communication stream

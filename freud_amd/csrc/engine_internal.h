@@ -140,6 +140,7 @@ enum KernelId {
   KID_REFIT_SORT,      // refit frontier (refit.h): the collect kernels into scratch, the refit kernel alone, the finish + dimension sums + fold
   KID_REFIT_CHOL,
   KID_REFIT_FOLD,
+  KID_CROSS_PACK,      // cross-activation (cross.h): the mask packs of sae_cross_mask_files (its update is context-free: no ring to record in)
   KID_COUNT
 };
 constexpr int EV_RING = 64;
@@ -151,7 +152,7 @@ struct EvRing {
 
 // What the last forward-like call left in the context: a bf16 forward (latent rows, metrics), an fp32 evaluation (metrics and the
 // per-feature maxima in e32_colmax, no bf16 latent rows), or a file pass (sae_search_files / sae_stats_files: nothing to read).
-enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER, LAST_PURSUIT, LAST_REFIT };
+enum LastCall { LAST_FWD_BF16 = 0, LAST_FWD_E32, LAST_SEARCH, LAST_STATS, LAST_COACT, LAST_LABELS, LAST_HIST, LAST_RECON, LAST_COLLECT, LAST_TIMING, LAST_RESAMPLE, LAST_FRONTIER, LAST_PURSUIT, LAST_REFIT, LAST_CROSS };
 
 // A file pass: the words of its entry point's messages, the flags it knows, the state it leaves (file_pass_end) and what the getters
 // of the last forward call that state when they refuse (no_forward_left).  sae_manipulate_files leaves the state of sae_eval.
@@ -174,8 +175,9 @@ static const FilePassKind kResamplePass = {"sae_resample_files", "resample in a 
 static const FilePassKind kFrontierPass = {"sae_frontier_files", "build the sparsity frontier in a bf16 context", "frontier", 0, LAST_FRONTIER, "a sparsity frontier pass"};
 static const FilePassKind kPursuitPass = {"sae_pursuit_files", "run the pursuit in a bf16 context", "pursuit", 0, LAST_PURSUIT, "a pursuit frontier pass"};
 static const FilePassKind kRefitPass = {"sae_refit_files", "run the refit in a bf16 context", "refit", 0, LAST_REFIT, "a refit frontier pass"};
+static const FilePassKind kCrossPass = {"sae_cross_mask_files", "pack the masks in a bf16 context", "cross-activation", 0, LAST_CROSS, "a cross-activation pass"};
 static const FilePassKind* const kFilePasses[] = {&kSearchPass, &kStatsPass, &kCoactPass, &kLabelPass, &kHistPass, &kReconPass, &kCollectPass,
-                                                  &kTimingPass, &kResamplePass, &kFrontierPass, &kPursuitPass, &kRefitPass};
+                                                  &kTimingPass, &kResamplePass, &kFrontierPass, &kPursuitPass, &kRefitPass, &kCrossPass};
 
 struct sae_ctx {
   // Every pointer field below that the context OWNS is allocated through `mem` (dev_mem.h; the last member, behind everything a step

@@ -15,6 +15,7 @@
 #include "stats.h"
 #include "coact.h"
 #include "labels.h"
+#include "cross.h"
 #include "hist.h"
 #include "timing.h"
 #include "collect.h"
@@ -461,6 +462,101 @@ extern "C" int sae_label_keys(const int32_t* counts, const int64_t* label_count,
     return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
   hipLaunchKernelGGL(label_keys_kernel, dim3((unsigned)((ncols + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
                      (hipStream_t)stream, counts, label_count, (int)n_classes, (int)n, measure, by_latent, row0, n_rows, keys);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+// ---- cross-activation (cross.h): the lag-aware masks of one batch of files into caller-owned memory, then -- without a context --
+// X += source x target^T of two such masks on label_update_kernel, and the keys of a block of rows of X in either orientation
+static_assert(SAE_CROSS_JACCARD == CX_JACCARD && SAE_CROSS_COND == CX_COND && SAE_CROSS_LIFT == CX_LIFT && SAE_CROSS_COUNT == CX_COUNT &&
+              SAE_CROSS_SOURCE == CX_SOURCE && SAE_CROSS_TARGET == CX_TARGET && SAE_CROSS_MAX_LAG == CX_MAX_LAG &&
+              SAE_CROSS_MAX_LAGS == CX_MAX_LAGS, "freud_sae.h and cross.h disagree");
+
+static bool cross_dims_ok(int64_t n, int64_t rows) { return n >= 1 && n <= CX_MAX_N && rows >= 1 && rows <= 65535ll * CO_BK; }
+static int64_t cross_rows_p(int64_t n) { return round_up(n + 1, CO_BM); }
+
+extern "C" int64_t sae_cross_mask_bytes(int64_t n_dict, int64_t rows) {
+  return cross_dims_ok(n_dict, rows) ? cross_rows_p(n_dict) * round_up(rows, CO_BK) : 0;
+}
+
+extern "C" int sae_cross_mask_files(sae_ctx* c, const void* x, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths,
+                                    int sides, const int32_t* lags_host, int n_lags, void* masks, int64_t masks_bytes, void* stream) {
+  int64_t M;
+  if (sides < 1 || sides > (CX_SOURCE | CX_TARGET)) return fail(SAE_ERR_INVALID, "sides=%d is not SAE_CROSS_SOURCE, SAE_CROSS_TARGET or both", sides);
+  const bool targets = (sides & CX_TARGET) != 0;
+  if (targets ? (n_lags < 1 || n_lags > CX_MAX_LAGS || !lags_host) : n_lags != 0)
+    return fail(SAE_ERR_INVALID, "n_lags=%d: target masks take 1 to %d lags, a source mask alone none", n_lags, CX_MAX_LAGS);
+  for (int a = 0; a < n_lags; ++a) {
+    if (lags_host[a] < 0 || lags_host[a] >= CX_MAX_LAG) return fail(SAE_ERR_INVALID, "lag %d outside [0, %d)", lags_host[a], CX_MAX_LAG);
+    for (int b = 0; b < a; ++b)
+      if (lags_host[a] == lags_host[b]) return fail(SAE_ERR_INVALID, "lag %d is given twice", lags_host[a]);
+  }
+  if (misaligned(masks, 16)) return fail(SAE_ERR_INVALID, "the masks must be 16-byte aligned");
+  if (int rc = file_pass_begin(kCrossPass, c, x, masks, n_files, rows_per_file, x_dtype, 0, &M)) return rc;
+  if (!cross_dims_ok(c->n, M)) return fail(SAE_ERR_INVALID, "n_dict=%d > 2^21 or %lld rows > %lld", c->n, (long long)M, 65535ll * CO_BK);
+  const int64_t Kp = round_up(M, CO_BK), one = cross_rows_p(c->n) * Kp;
+  const int n_masks = ((sides & CX_SOURCE) ? 1 : 0) + n_lags;
+  if (masks_bytes < n_masks * one)
+    return fail(SAE_ERR_INVALID, "masks_bytes=%lld < %d masks of %lld bytes", (long long)masks_bytes, n_masks, (long long)one);
+  hipStream_t s = (hipStream_t)stream;
+  const int Trows = (int)rows_per_file;
+  if (int rc = file_pass_encode(c, x, M, x_dtype, s)) return rc;
+
+  ev_begin(c, KID_CROSS_PACK, s);
+  hipError_t memset_zt = hipSuccess;
+  for (int m = 0; m < n_masks && memset_zt == hipSuccess; ++m) {
+    int8_t* zt = (int8_t*)masks + m * one;
+    const int lag = (sides & CX_SOURCE) ? (m == 0 ? 0 : lags_host[m - 1]) : lags_host[m];      // (the source mask: the target mask at lag 0)
+    if (c->topk) {                            // the selection scattered into the zeroed mask
+      memset_zt = hipMemsetAsync(zt, 0, (size_t)one, s);
+      if (memset_zt == hipSuccess)
+        hipLaunchKernelGGL(cross_pack_topk_kernel, dim3(grid_for(M * c->k, 4096)), dim3(256), 0, s, c->top_idx, (const unsigned short*)c->top_vals,
+                           c->k, M, Trows, lengths, c->n, lag, zt, Kp);
+    } else {
+      hipLaunchKernelGGL(cross_pack_l1_kernel, dim3((unsigned)(Kp / 64), (unsigned)(cross_rows_p(c->n) / 64)), dim3(256), 0, s,
+                         (const unsigned short*)c->c, (int64_t)c->n_p, c->n, M, Trows, lengths, lag, zt, Kp);
+    }
+  }
+  ev_end(c, KID_CROSS_PACK, s);             // (the bracket closes whatever the memset answered)
+  HIP_TRY(memset_zt);
+  HIP_TRY(hipGetLastError());
+  file_pass_end(kCrossPass, c);
+  return SAE_OK;
+}
+
+extern "C" int sae_cross_update(const void* mask_a, int64_t n_a, const void* mask_b, int64_t n_b, int64_t rows, int32_t* counts, void* stream) {
+  if (!mask_a || !mask_b || !counts) return fail(SAE_ERR_INVALID, "null argument");
+  if (!cross_dims_ok(n_a, rows) || !cross_dims_ok(n_b, rows))
+    return fail(SAE_ERR_INVALID, "n_a=%lld or n_b=%lld outside [1, 2^21], or rows=%lld outside [1, %lld]", (long long)n_a, (long long)n_b,
+                (long long)rows, 65535ll * CO_BK);
+  if (misaligned(mask_a, 16) || misaligned(mask_b, 16) || misaligned(counts, 4))
+    return fail(SAE_ERR_INVALID, "the masks must be 16-byte aligned and the count table 4-byte aligned");
+  const int64_t Kp = round_up(rows, CO_BK);
+  // the K split of coact.h's header over the rectangle's tiles
+  const int64_t ntr = cross_rows_p(n_a) / CO_BM, ntc = cross_rows_p(n_b) / CO_BM;
+  const KSplit ks = coact_ksplit(ntr * ntc, Kp);
+  const dim3 grid((unsigned)ntc, (unsigned)ntr, (unsigned)ks.ksplit);
+  hipStream_t s = (hipStream_t)stream;
+  const int8_t *za = (const int8_t*)mask_a, *zb = (const int8_t*)mask_b;
+  if (ks.ksplit > 1) hipLaunchKernelGGL(label_update_kernel<true>, grid, dim3(256), 0, s, za, zb, Kp, (int)n_a + 1, (int)n_b + 1, ks.per, counts);
+  else hipLaunchKernelGGL(label_update_kernel<false>, grid, dim3(256), 0, s, za, zb, Kp, (int)n_a + 1, (int)n_b + 1, ks.per, counts);
+  HIP_TRY(hipGetLastError());
+  return SAE_OK;
+}
+
+extern "C" int sae_cross_keys(const int32_t* counts, int64_t n_a, int64_t n_b, int measure, int by_b, int exclude_diagonal, int64_t row0,
+                              int64_t n_rows, uint64_t* keys, void* stream) {
+  if (!counts || !keys) return fail(SAE_ERR_INVALID, "null argument");
+  if (n_a < 1 || n_a > CX_MAX_N || n_b < 1 || n_b > CX_MAX_N) return fail(SAE_ERR_INVALID, "n_a=%lld or n_b=%lld outside [1, 2^21]", (long long)n_a, (long long)n_b);
+  if ((by_b != 0 && by_b != 1) || (exclude_diagonal != 0 && exclude_diagonal != 1))
+    return fail(SAE_ERR_INVALID, "by_b=%d and exclude_diagonal=%d must each be 0 or 1", by_b, exclude_diagonal);
+  const int64_t rows_all = by_b ? n_b : n_a, ncols = by_b ? n_a : n_b;
+  if (n_rows < 1 || row0 < 0 || row0 + n_rows > rows_all)
+    return fail(SAE_ERR_INVALID, "rows [%lld, %lld) are empty or outside [0, %lld)", (long long)row0, (long long)(row0 + n_rows), (long long)rows_all);
+  if (measure != SAE_CROSS_JACCARD && measure != SAE_CROSS_COND && measure != SAE_CROSS_LIFT && measure != SAE_CROSS_COUNT)
+    return fail(SAE_ERR_INVALID, "unknown measure %d", measure);
+  hipLaunchKernelGGL(cross_keys_kernel, dim3((unsigned)((ncols + 255) / 256), (unsigned)std::min<int64_t>(n_rows, 65535)), dim3(256), 0,
+                     (hipStream_t)stream, counts, (int)n_a, (int)n_b, measure, by_b, exclude_diagonal, row0, n_rows, keys);
   HIP_TRY(hipGetLastError());
   return SAE_OK;
 }

@@ -124,6 +124,10 @@ _SIGNATURES = {
     "sae_coact_neighbor_keys": (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp, _vp]),
     "sae_label_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "sae_label_keys": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, C.c_int, _i64, _i64, _vp, _vp]),
+    "sae_cross_mask_bytes": (_i64, [_i64, _i64]),
+    "sae_cross_mask_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, C.POINTER(_i32), C.c_int, _vp, _i64, _vp]),
+    "sae_cross_update": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "sae_cross_keys": (C.c_int, [_vp, _i64, _i64, C.c_int, C.c_int, C.c_int, _i64, _i64, _vp, _vp]),
     "sae_hist_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int,
                                  C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "sae_timing_files": (C.c_int, [_vp, _vp, _i64, _i64, C.c_int, _vp, C.c_int, C.c_int, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -206,6 +210,9 @@ COACT_MEASURES = {"jaccard": 0, "cond": 1, "count": 2}              # include/fr
 LABEL_MEASURES = {"f1": 0, "precision": 1, "recall": 2, "count": 3}  # include/freud_sae.h: SAE_LABEL_*
 LABEL_MAX_CLASSES = 4096                                            # include/freud_sae.h: SAE_LABEL_MAX_CLASSES
 LABEL_MAX_SLOTS = 16                                                # include/freud_sae.h: SAE_LABEL_MAX_SLOTS
+CROSS_MEASURES = {"jaccard": 0, "cond": 1, "lift": 2, "count": 3}   # include/freud_sae.h: SAE_CROSS_*
+CROSS_SOURCE, CROSS_TARGET = 1, 2                                   # include/freud_sae.h: SAE_CROSS_SOURCE / SAE_CROSS_TARGET
+CROSS_MAX_LAG, CROSS_MAX_LAGS = 32768, 8                            # include/freud_sae.h: SAE_CROSS_MAX_LAG / SAE_CROSS_MAX_LAGS
 HIST_MAX_REGULAR = 128                                              # freud_amd/csrc/hist_bins.h: octaves << sub_bits at most
 HIST_MAX_SEL = 64                                                   # include/freud_sae.h: SAE_HIST_MAX_SEL
 TIMING_ACTIVE, TIMING_SPAN, TIMING_RUNS, TIMING_FILES, TIMING_LONGEST, TIMING_CENSORED, TIMING_NTOTALS = range(7)   # include/freud_sae.h: SAE_TIMING_*
@@ -734,6 +741,19 @@ class SaeEngine:
         table, lc = _label_table(counts, label_count, n_classes, self.n)
         _check(self._lib.sae_label_files(self._ctx, xp, B, T, dt, lp, lab, n_slots, int(n_classes), 0, table, lc, _stream_ptr(stream)))
 
+    # -- cross-activation (include/freud_sae.h: sae_cross_mask_files; freud_amd/cross_activation.py) ---------------------------
+    def cross_mask_files(self, x, masks, sides: int, lags=(), lengths=None, stream=None) -> None:
+        """One encode of x [n_files, T, d] (CUDA), then its activity masks into masks (a contiguous int8 or uint8 CUDA tensor): the
+        source mask (sides & CROSS_SOURCE), then one target mask per lag (sides & CROSS_TARGET), each of
+        cross_mask_bytes(n_dict, n_files * T) bytes; lengths: int32 CUDA tensor [n_files] or None.  Asynchronous.  Afterwards the
+        last-forward getters fail until the next eval() / step()."""
+        x, xp, B, T, _d, dt, lp = _files_args(x, "cross_mask_files", lengths)
+        lags = [int(v) for v in lags]
+        m = _dev("masks", masks, ("int8", "uint8"), 0, at_least=True)
+        arr = (C.c_int32 * max(len(lags), 1))(*lags)
+        _check(self._lib.sae_cross_mask_files(self._ctx, xp, B, T, dt, lp, int(sides), arr if lags else None, len(lags), m,
+                                              int(masks.numel()), _stream_ptr(stream)))
+
     # -- activation histograms (include/freud_sae.h: sae_hist_files; freud_amd/activation_hist.py) ------------------------------
     def hist_files(self, x, spec, frame_hist, file_max_hist, n_frames, lengths=None, labels=None, n_classes: int = 0, sel_latents=None,
                    label_hist=None, label_count=None, stream=None) -> None:
@@ -1215,6 +1235,33 @@ def label_keys(counts, label_count, n_classes: int, n: int, measure: int, by_lat
     table, lc = _label_table(counts, label_count, n_classes, n)
     out = _dev("keys", keys, "int64", max(int(n_rows), 0) * (int(n_classes) if by_latent else n), at_least=True)
     _check(load().sae_label_keys(table, lc, int(n_classes), int(n), int(measure), int(by_latent), int(row0), int(n_rows), out,
+                                 _stream_ptr(stream)))
+
+
+def cross_mask_bytes(n: int, rows: int) -> int:
+    """Bytes of one activity mask of a dictionary of n latents over `rows` frames (include/freud_sae.h, sae_cross_mask_bytes)."""
+    b = int(load().sae_cross_mask_bytes(int(n), int(rows)))
+    if b <= 0:
+        raise EngineError(f"n={n} outside [1, 2^21] or rows={rows} outside [1, {65535 * 128}]")
+    return b
+
+
+def cross_update(mask_a, n_a: int, mask_b, n_b: int, rows: int, counts, stream=None) -> None:
+    """counts (contiguous int32 CUDA [n_a + 1, n_b + 1]) += mask_a x mask_b^T: a source mask of A and a target mask of B as
+    cross_mask_files wrote them for the same batch of `rows` frames (contiguous int8 / uint8 CUDA tensors of cross_mask_bytes)."""
+    a = _dev("mask_a", mask_a, ("int8", "uint8"), cross_mask_bytes(n_a, rows), at_least=True)
+    b = _dev("mask_b", mask_b, ("int8", "uint8"), cross_mask_bytes(n_b, rows), at_least=True)
+    table = _dev("counts", counts, "int32", (int(n_a) + 1) * (int(n_b) + 1))
+    _check(load().sae_cross_update(a, int(n_a), b, int(n_b), int(rows), table, _stream_ptr(stream)))
+
+
+def cross_keys(counts, n_a: int, n_b: int, measure: int, by_b: int, exclude_diagonal: int, row0: int, n_rows: int, keys, stream=None) -> None:
+    """keys (int64 holding uint64) = the keys of rows [row0, row0 + n_rows) of the cross-activation table counts [n_a + 1, n_b + 1]:
+    [n_rows, n_b] (by_b 0: a row is a latent of A) or [n_rows, n_a] (1: a row is a latent of B), for
+    file_top_features(keys, n_rows, columns, n_top, FILE_TOP_POSITIVE, ...); measure: a CROSS_MEASURES value."""
+    table = _dev("counts", counts, "int32", (int(n_a) + 1) * (int(n_b) + 1))
+    out = _dev("keys", keys, "int64", max(int(n_rows), 0) * int(n_a if by_b else n_b), at_least=True)
+    _check(load().sae_cross_keys(table, int(n_a), int(n_b), int(measure), int(by_b), int(exclude_diagonal), int(row0), int(n_rows), out,
                                  _stream_ptr(stream)))
 
 

@@ -514,6 +514,61 @@ enum { SAE_LABEL_F1 = 0, SAE_LABEL_PRECISION = 1, SAE_LABEL_RECALL = 2, SAE_LABE
 int sae_label_keys(const int32_t* counts_dev, const int64_t* label_count_dev, int64_t n_classes, int64_t n, int measure, int by_latent,
                    int64_t row0, int64_t n_rows, uint64_t* keys_dev, void* stream);
 
+/* ---- Cross-activation: how often latent i of dictionary A and latent j of dictionary B are active a fixed number of frames apart --
+ * two dictionaries compared as functions of the data (other layers, other widths, L1 against TopK), and what follows what in time.
+ *
+ * Semantics (freud_amd/csrc/cross.h states the rule once).  A (n_a latents) and B (n_b latents) see the same files; file f has len_f
+ * counted frames, exactly as in sae_stats_files; "active" is its rule.  For a lag l >= 0 the table X_l [(n_a + 1)][(n_b + 1)] (int32,
+ * row-major, caller-owned, zeroed before the first batch) holds
+ *     X_l[i][j]     = #{ (f, t) : t + l < len_f, A_i active at (f, t), B_j active at (f, t + l) }
+ *     X_l[i][n_b]   = fire_a_l[i] = #{ (f, t) : t + l < len_f, A_i active at (f, t) }
+ *     X_l[n_a][j]   = fire_b_l[j] = #{ (f, t) : t + l < len_f, B_j active at (f, t + l) }
+ *     X_l[n_a][n_b] = n_pairs_l   = sum_f max(len_f - l, 0)
+ * A pair of frames never crosses a file and an uncounted frame is on neither side.  A negative lag is the table of (B, A).  With
+ * A = B and l = 0 the interior is the table of sae_coact_files.  Counts are int32: THE CALLER GUARANTEES that at most 2^31 - 1 frames
+ * go into one table.
+ *
+ * A mask is int8 [n_dict + 1 rounded up to 128][rows rounded up to 128], latent-major, frames contiguous: sae_cross_mask_bytes bytes
+ * (0 for n_dict outside [1, 2^21] or rows outside [1, 65535 * 128]).  Row n_dict is the margin row.  The SOURCE mask holds at
+ * position (f, t) whether the latent is active on the counted frame (f, t), margin: (f, t) is counted.  The TARGET mask at lag l
+ * holds whether the latent is active at (f, t + l) and t + l < len_f, margin: t + l < len_f.  Every padding byte is zero.
+ *
+ * sae_cross_mask_files encodes one batch once, as sae_coact_files does, and writes into masks_dev, one after the other, the source
+ * mask (sides & SAE_CROSS_SOURCE) and the n_lags target masks in the order of lags_host (sides & SAE_CROSS_TARGET; a host array of
+ * 1 to SAE_CROSS_MAX_LAGS distinct lags in [0, SAE_CROSS_MAX_LAG); without the bit n_lags must be 0).  masks_dev: caller-owned,
+ * 16-byte aligned, masks_bytes >= the masks asked for, each of sae_cross_mask_bytes(n_dict, n_files * rows_per_file).
+ * n_files * rows_per_file <= max_rows; fp8 contexts: SAE_ERR_INVALID.  Null pointers, bad sides, lags or shapes and a short buffer
+ * fail before anything is enqueued.  Asynchronous on `stream`.  Training state is untouched; afterwards sae_latent_buffer,
+ * sae_topk_indices, sae_decode, sae_multi_topk_buffers, sae_latent_colmax and sae_read_metrics return SAE_ERR_STATE until the next
+ * sae_eval / step. */
+#define SAE_CROSS_MAX_LAG 32768
+#define SAE_CROSS_MAX_LAGS 8
+enum { SAE_CROSS_SOURCE = 1, SAE_CROSS_TARGET = 2 };
+int64_t sae_cross_mask_bytes(int64_t n_dict, int64_t rows);
+int sae_cross_mask_files(sae_ctx* ctx, const void* x_dev, int64_t n_files, int64_t rows_per_file, int x_dtype, const int32_t* lengths_dev,
+                         int sides, const int32_t* lags_host, int n_lags, void* masks_dev, int64_t masks_bytes, void* stream);
+
+/* counts_dev [(n_a + 1)][(n_b + 1)] += mask_a x mask_b^T for two masks of the same `rows` (a source mask of A, a target mask of B):
+ * one batch, one lag.  The i8 MFMA over the rectangle of 128 x 128 tiles, every tile computed; the K split of sae_coact_files
+ * (integer atomic adds when split, plain read-modify-write otherwise): two runs give bitwise identical tables.  Null pointers,
+ * dimensions outside those of sae_cross_mask_bytes, misaligned pointers (masks 16 bytes, table 4): SAE_ERR_INVALID.  Needs no
+ * context, runs on the current device, asynchronous on `stream`. */
+int sae_cross_update(const void* mask_a_dev, int64_t n_a, const void* mask_b_dev, int64_t n_b, int64_t rows, int32_t* counts_dev,
+                     void* stream);
+
+/* Keys of the rows [row0, row0 + n_rows) of a table X.  by_b = 0: the rows are latents of A, keys_dev [n_rows][n_b]; by_b = 1: the
+ * rows are latents of B, keys_dev [n_rows][n_a].  A key is ord(score) << 32 | X[i][j] (freud_amd/csrc/cross.h), 0 where X[i][j] == 0
+ * and, with exclude_diagonal = 1 (A and B are one dictionary and l = 0), where i == j.  score = one fixed fp64 expression converted
+ * once to fp32, the margins read from the table: SAE_CROSS_JACCARD X / (fire_a + fire_b - X); SAE_CROSS_COND X / fire_a (by_b = 0:
+ * P(B_j at t + l | A_i at t)) or X / fire_b (by_b = 1); SAE_CROSS_LIFT (X / fire_a) / (fire_b / n_pairs); SAE_CROSS_COUNT X.
+ * sae_file_top_features(keys_dev, n_rows, columns, n_top, SAE_FILE_TOP_POSITIVE, ...) then gives each row's partners in the order
+ * score descending, then the larger count, then the lower index.  Null pointers, n_a or n_b outside [1, 2^21], an empty or
+ * out-of-range row block, an unknown measure, orientation or flag: SAE_ERR_INVALID.  Needs no context, runs on the current device,
+ * asynchronous on `stream`, deterministic. */
+enum { SAE_CROSS_JACCARD = 0, SAE_CROSS_COND = 1, SAE_CROSS_LIFT = 2, SAE_CROSS_COUNT = 3 };
+int sae_cross_keys(const int32_t* counts_dev, int64_t n_a, int64_t n_b, int measure, int by_b, int exclude_diagonal, int64_t row0,
+                   int64_t n_rows, uint64_t* keys_dev, void* stream);
+
 /* ---- Activation histograms: how strongly every latent fires -- per latent the histogram of its value over the counted frames, the
  * histogram of every file's maximum (the reference GUI's "Histogram of Max Activation Values per File", for all latents at once)
  * and, for a few chosen latents, the frame histogram split by the frames' labels (the reference's plot_polysemantic.py).
